@@ -2,8 +2,16 @@
 """Headline benchmark: SLAM frames/sec of the per-frame hot path (MASt3R infer + match + TSDF fuse + GN
 solve) on a synthetic 512x384 RGB-D stream (BASELINE.json config 3), N GPUs of one node.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, pre-rolls, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, ...).
+`--full` adds what takes runs of its own: the `roofline` object (live HIP-event timing of the dominant GEMM inside the
+timed region, the same kernel alone, the HBM-bound kernels alone) and `cpu_baseline` (the oracle on the host cores;
+`--no-cpu-baseline` drops it).  `--dump-outputs DIR` writes what the timed loop computed, as of its last step, to
+DIR/<name>.npy (float32, rank 0): the last step's result (pose; mode / new-keyframe / relocalise flags), the last frame's
+pointmap and confidences, and every keyframe's pose once the backend has drained.  The global TSDF is left out: its
+budgeted re-fusion depends on the backend threads' timing, so it differs from run to run of the same build.
 
 The timed region is the PRODUCT loop: `SlamSystem.run()` (mast3r_slam/slam_system.py = the reference's main.py frontend
 loop + run_backend, one process) over frames of the procedural room, followed by the drain of its backend.
@@ -80,7 +88,11 @@ def parse():
                     help="loop-closure proposals: 'pose' = the pose-proximity stand-in (what a trained retrieval model would "
                          "return on this scene); 'asmk' = the product's RetrievalDatabase (mast3r_slam/retrieval_database.py) "
                          "with a random retrieval head and a random 64k x 1024 codebook on the random-weight encoder's tokens")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline object and the CPU baseline (off: only what the headline value needs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed loop computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline object")
     ap.add_argument("--host-frames", action="store_true",
                     help="PCIe-inclusive variant (DESIGN.md; never the headline value): the RGB frames wait in pinned host "
                          "memory and every run() call first uploads its frames on the tracking stream")
@@ -236,15 +248,35 @@ class Session:
             for k in range(self.pos, min(self.pos + n, len(self.frames))):
                 self.frames[k].img = self.host_imgs[k].to(self.dev, non_blocking=True)
                 self.host_imgs[k] = None
+        last = self.frames[self.pos + n - 1] if 0 < n and self.pos + n <= len(self.frames) else None
         if self.args.tracking_priority != 0:
             if not hasattr(self, "_trk_stream"):
                 self._trk_stream = torch.cuda.Stream(device=self.dev, priority=self.args.tracking_priority)
                 self._trk_stream.wait_stream(torch.cuda.current_stream(self.dev))
             with torch.cuda.stream(self._trk_stream):
-                self.system.run(self.frames, self.pos, self.pos + n, release=True)
+                res = self.system.run(self.frames, self.pos, self.pos + n, release=True)
         else:
-            self.system.run(self.frames, self.pos, self.pos + n, release=True)
+            res = self.system.run(self.frames, self.pos, self.pos + n, release=True)
+        if res:   # the last step's result (SlamSystem.step) and its frame, for --dump-outputs
+            self.last_result, self.last_frame = res[-1], last
         self.pos += n
+
+    def dump_outputs(self, dirname):
+        """What the timed loop computed, as of its last step, as DIR/<name>.npy (float32).  Call after drain()."""
+        os.makedirs(dirname, exist_ok=True)
+        out = {}
+        r = self.last_result
+        out["last_pose"] = r["pose"].float().cpu().numpy()                               # (1, 8) Sim3 [t, q(xyzw), s]
+        out["last_flags"] = np.array([r["mode"].value, r["new_kf"], r["try_reloc"]], dtype=np.float32)
+        f = self.last_frame
+        if f is not None and f.X_canon is not None:
+            out["last_pointmap"] = f.X_canon.float().cpu().numpy()                       # (H*W, 3)
+            out["last_confidence"] = f.C.float().cpu().numpy()                           # (H*W, 1)
+        kfs = self.system.keyframes
+        out["keyframe_poses"] = torch.cat([kfs[i].T_WC.data.float() for i in range(len(kfs))]).cpu().numpy()
+        for name, a in out.items():
+            np.save(os.path.join(dirname, name + ".npy"), a)
+        return sorted(out)
 
     def drain(self):
         self.system.drain()
@@ -643,7 +675,8 @@ def measure_replicas(args, rank, world, dev, L, mslam_hip, ranks_seen):
     # the look-ahead encoder's batch: calls do not cross the end of a run() segment, so a timed region shorter than the
     # batch sees ONE call of `steps` frames
     M, N, K = dominant_shape(min(max(B, ses.system.encoder_group), max(1, args.steps)))
-    mslam_hip.check(L.mslam_gemm_profile_begin(M, N, K, 8192), "gemm_profile_begin")
+    if args.full:   # roofline: HIP events around every launch of the dominant shape inside the timed region
+        mslam_hip.check(L.mslam_gemm_profile_begin(M, N, K, 8192), "gemm_profile_begin")
     prof = None
     if os.environ.get("BENCH_CPROFILE"):   # debug: where the frontend thread's host time goes
         import cProfile
@@ -661,16 +694,21 @@ def measure_replicas(args, rank, world, dev, L, mslam_hip, ranks_seen):
     ses.drain()                             # every queued keyframe task has been issued ...
     barrier(world)                          # ... and (device-wide synchronise inside) has finished
     elapsed = time.perf_counter() - t0
-    import ctypes
+    if args.full:
+        import ctypes
 
-    avg_us, min_us, nsamp = ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
-    mslam_hip.check(L.mslam_gemm_profile_end(ctypes.byref(avg_us), ctypes.byref(min_us), ctypes.byref(nsamp)),
-                    "gemm_profile_end")
+        avg_us, min_us, nsamp = ctypes.c_double(), ctypes.c_double(), ctypes.c_int()
+        mslam_hip.check(L.mslam_gemm_profile_end(ctypes.byref(avg_us), ctypes.byref(min_us), ctypes.byref(nsamp)),
+                        "gemm_profile_end")
     kf1, e1 = ses.graph()
     st1 = dict(ses.system.stats)
     st1["verdict_wait_s"] = ses.system.tracker.verdict_wait_s
-    iso_us = isolated_dominant_us(L, mslam_hip, M, N, K, dev) if not args.no_network else 0.0
-    hbm = hbm_kernel_probes(ses, dev)
+    if args.dump_outputs and rank == 0:
+        names = ses.dump_outputs(args.dump_outputs)
+        print(f"[bench] outputs of the last timed step -> {args.dump_outputs}: {', '.join(names)}", file=sys.stderr)
+    if args.full:
+        iso_us = isolated_dominant_us(L, mslam_hip, M, N, K, dev) if not args.no_network else 0.0
+        hbm = hbm_kernel_probes(ses, dev)
     enc_rows, dec_rows = ses.model.enc_rows - rows0[0], ses.model.dec_rows - rows0[1]
     if world > 1:
         import torch.distributed as dist
@@ -689,23 +727,6 @@ def measure_replicas(args, rank, world, dev, L, mslam_hip, ranks_seen):
             ph, ph0 = st1["backend_phase_s"], st0.get("backend_phase_s", {})
             print(f"[bench] backend phases, ms per keyframe task in the timed region ({new_kf} tasks, {kf0}->{kf1} keyframes): " +
                   ", ".join(f"{k} {1e3 * (v - ph0.get(k, 0.0)) / max(1, new_kf):.2f}" for k, v in ph.items()), file=sys.stderr)
-        # network FLOP actually launched inside the timed region (rows of every encoder / decoder+heads call)
-        gflop = 0.0 if args.no_network else enc_rows * ses.gf_enc + dec_rows * (GF_DEC + 2 * GF_HEAD)
-        dom_gflop = 2e-9 * M * N * K
-        dom_tflops = dom_gflop * 1e3 / avg_us.value if nsamp.value else 0.0
-        traffic = None
-        import glob
-
-        # PMC FETCH_SIZE (x2, gfx950) + WRITE_SIZE of the same launch, separate passes (tools/pmc_probe.sh): the committed
-        # record of THIS shape, newest round first
-        for tpath in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_dominant_kernel*.json")), reverse=True):
-            try:
-                tj = json.load(open(tpath))
-                if tj.get("shape") == [M, N, K] and tj.get("hbm_bytes_per_launch"):
-                    traffic = tj.get("hbm_bytes_per_launch")
-                    break
-            except Exception:
-                pass
         out = {
             "metric": "SLAM frames/sec (infer+match+TSDF+GN) @512x384", "value": fps, "unit": "frames/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
@@ -740,19 +761,37 @@ def measure_replicas(args, rank, world, dev, L, mslam_hip, ranks_seen):
                                  "frontend_enqueue_ms_per_step": 1e3 * (t_enqueued - t_wait) / args.steps,
                                  "frontend_wait_for_device_ms_per_step": 1e3 * t_wait / args.steps},
                        "parallelism": f"{world} independent session(s), one per GPU (replicas; {ranks_seen} rank(s) reported by the collective library)"},
-            "roofline": {"bound": "mfma", "achieved": dom_tflops, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                         "frac": dom_tflops / PEAK_BF16_TFLOPS, "traffic": traffic,
-                         "kernel": f"gemm_bf16_kernel, encoder fc1 {M}x{N}x{K} + GELU (largest share of the step)",
-                         "gflop_per_launch": dom_gflop, "us_per_launch_avg": avg_us.value, "us_per_launch_min": min_us.value,
-                         "launches_timed": nsamp.value,
-                         "us_per_launch_isolated": iso_us,
-                         "tflops_isolated": dom_gflop * 1e3 / iso_us if iso_us else 0.0,
-                         "method": "HIP events around every launch of this shape inside the timed region, on its launch stream "
-                                   "(mslam_gemm_profile_begin/end)",
-                         "network_tflops_over_timed_region": gflop / (1e3 * elapsed) if elapsed > 0 else 0.0,
-                         "network_gflop_per_step": gflop / args.steps,
-                         "hbm_bound_kernels": hbm},
         }
+    if rank == 0 and args.full:
+        # network FLOP actually launched inside the timed region (rows of every encoder / decoder+heads call)
+        gflop = 0.0 if args.no_network else enc_rows * ses.gf_enc + dec_rows * (GF_DEC + 2 * GF_HEAD)
+        dom_gflop = 2e-9 * M * N * K
+        dom_tflops = dom_gflop * 1e3 / avg_us.value if nsamp.value else 0.0
+        traffic = None
+        import glob
+
+        # PMC FETCH_SIZE (x2, gfx950) + WRITE_SIZE of the same launch, separate passes (tools/pmc_probe.sh): the committed
+        # record of THIS shape, newest round first
+        for tpath in sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_dominant_kernel*.json")), reverse=True):
+            try:
+                tj = json.load(open(tpath))
+                if tj.get("shape") == [M, N, K] and tj.get("hbm_bytes_per_launch"):
+                    traffic = tj.get("hbm_bytes_per_launch")
+                    break
+            except Exception:
+                pass
+        out["roofline"] = {"bound": "mfma", "achieved": dom_tflops, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                           "frac": dom_tflops / PEAK_BF16_TFLOPS, "traffic": traffic,
+                           "kernel": f"gemm_bf16_kernel, encoder fc1 {M}x{N}x{K} + GELU (largest share of the step)",
+                           "gflop_per_launch": dom_gflop, "us_per_launch_avg": avg_us.value, "us_per_launch_min": min_us.value,
+                           "launches_timed": nsamp.value,
+                           "us_per_launch_isolated": iso_us,
+                           "tflops_isolated": dom_gflop * 1e3 / iso_us if iso_us else 0.0,
+                           "method": "HIP events around every launch of this shape inside the timed region, on its launch stream "
+                                     "(mslam_gemm_profile_begin/end)",
+                           "network_tflops_over_timed_region": gflop / (1e3 * elapsed) if elapsed > 0 else 0.0,
+                           "network_gflop_per_step": gflop / args.steps,
+                           "hbm_bound_kernels": hbm}
         if not args.no_cpu_baseline and world == 1:   # the host baseline is reported on rank 0 at N = 1 only
             kfs_mean = max(2, (kf0 + kf1) // 2)
             edges_mean = max(1, (e0 + e1) // 2)

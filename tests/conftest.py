@@ -42,6 +42,33 @@ def golden_dir():
 
 
 @pytest.fixture(scope="session")
+def load_golden():
+    """load_golden(name) -> dict of the arrays of tests/golden/<name>.npz, or of its parts <name>_part1.npz, ... merged,
+    <key>.chunk<j> pieces joined along axis 0 (a fixture larger than 1 MiB is committed in parts:
+    tests/golden/make_golden.py::save_parts)."""
+    import numpy as np
+
+    def load(name):
+        one = os.path.join(GOLDEN, name + ".npz")
+        paths = [one] if os.path.exists(one) else sorted(
+            os.path.join(GOLDEN, f) for f in os.listdir(GOLDEN) if f.startswith(name + "_part") and f.endswith(".npz"))
+        assert paths, f"no golden fixture {name}"
+        out = {}
+        for p in paths:
+            with np.load(p) as z:
+                out.update({k: z[k] for k in z.files})
+        pieces = {}
+        for k in [k for k in out if ".chunk" in k]:
+            base, j = k.rsplit(".chunk", 1)
+            pieces.setdefault(base, []).append((int(j), out.pop(k)))
+        for base, cs in pieces.items():
+            out[base] = np.concatenate([c for _, c in sorted(cs, key=lambda t: t[0])])
+        return out
+
+    return load
+
+
+@pytest.fixture(scope="session")
 def device():
     import torch
 

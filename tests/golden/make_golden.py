@@ -4,7 +4,7 @@ box; only these small .npz data files do.  Usage:
 
     PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py [section ...]
 
-Sections: prep  tracker  tsdf_global  tsdf_refine  network  resize  geometry  quality  frame  factor_graph  track_logic  utils_wrappers  refine_block  refine_schedule  retrieval_quantize  retrieval_asmk  evaluate  dataloader
+Sections: prep  tracker  tsdf_global  tsdf_refine  network  resize  geometry  quality  frame  factor_graph  track_logic  utils_wrappers  refine_block  refine_schedule  retrieval_quantize  retrieval_asmk  evaluate  dataloader  asmk_direct
 Every fixture records numpy/torch versions (the global TSDF arithmetic depends on NumPy's
 promotion rules: the container has NumPy 2.x (NEP 50), the reference pins numpy==1.26.4).
 """
@@ -30,6 +30,41 @@ def load_by_path(name, path):
 
 def meta():
     return dict(numpy_version=np.__version__, torch_version=torch.__version__)
+
+
+def save_parts(name, arrays):
+    """np.savez_compressed as HERE/<name>.npz or, when that would exceed 1 MiB, as <name>_part1.npz, <name>_part2.npz, ...:
+    arrays above 512 KiB are cut along axis 0 into <key>.chunk<j> pieces, which are spread over the parts by size
+    (tests/conftest.py::load_golden merges the parts and joins the pieces)."""
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    for old in [f for f in os.listdir(HERE) if f == f"{name}.npz" or (f.startswith(f"{name}_part") and f.endswith(".npz"))]:
+        os.remove(os.path.join(HERE, old))
+    one = os.path.join(HERE, f"{name}.npz")
+    np.savez_compressed(one, **arrays)
+    if os.path.getsize(one) < 1 << 20:
+        return [one]
+    os.remove(one)
+    pieces = {}
+    for k, v in arrays.items():
+        n = -(-v.nbytes // (512 << 10))
+        if n > 1 and v.ndim and v.shape[0] >= n:
+            pieces.update({f"{k}.chunk{j}": c for j, c in enumerate(np.array_split(v, n))})
+        else:
+            pieces[k] = v
+    for n in range(2, 16):
+        groups, load = [{} for _ in range(n)], [0] * n
+        for k in sorted(pieces, key=lambda k: -pieces[k].nbytes):
+            i = load.index(min(load))
+            groups[i][k] = pieces[k]
+            load[i] += pieces[k].nbytes
+        paths = [os.path.join(HERE, f"{name}_part{i + 1}.npz") for i in range(n)]
+        for p, g in zip(paths, groups):
+            np.savez_compressed(p, **g)
+        if all(os.path.getsize(p) < 1 << 20 for p in paths):
+            return paths
+        for p in paths:
+            os.remove(p)
+    raise RuntimeError(f"{name}: does not fit 15 parts of 1 MiB")
 
 
 def section_prep():
@@ -236,7 +271,7 @@ def section_network():
     for h, r in ((1, r1), (2, r2)):
         for k in ("pts3d", "conf", "desc", "desc_conf"):
             out[f"head{h}_{k}"] = r[k].numpy()
-    np.savez_compressed(os.path.join(HERE, "mast3r_small.npz"), **out, **meta())
+    save_parts("mast3r_small", dict(**out, **meta()))
     print("mast3r_small.npz", {k: getattr(v, "shape", None) for k, v in out.items()})
 
 
@@ -339,7 +374,7 @@ def section_resize():
         out[f"{name}_uimg"] = res["unnormalized_img"]
         out[f"{name}_img_sum"] = np.float64(res["img"].double().sum().item())
         out[f"{name}_tf"] = np.array(tf, np.float64)
-    np.savez_compressed(os.path.join(HERE, "resize_img.npz"), **out, **meta())
+    save_parts("resize_img", dict(**out, **meta()))
     print("resize:", {k: v.shape for k, v in out.items() if k.endswith("_uimg")})
 
 
@@ -1118,7 +1153,7 @@ def section_refine_schedule():
         out[f"trace_{i}"] = np.array(t, np.int64).reshape(-1, 2)
     out["trace_n"] = np.array(len(trace))
     print("refine_schedule", {k: (v.tolist() if v.size < 24 else v.shape) for k, v in out.items() if k.startswith(("trace", "select_single_0", "fallback_ok", "fallback_n", "fallback_fail", "fallback5_n", "fallback5_0_p"))})
-    np.savez_compressed(os.path.join(HERE, "refine_schedule.npz"), **out, **meta())
+    save_parts("refine_schedule", dict(**out, **meta()))
 
 
 SECTIONS["refine_schedule"] = section_refine_schedule
@@ -1291,7 +1326,23 @@ def section_retrieval_asmk():
     np.savez_compressed(os.path.join(HERE, "asmk_hamming.npz"), **kat, **meta())
 
 
+def section_asmk_direct():
+    """The reference's compiled hamming extension (oracle/_ref/asmk_ext, oracle/Makefile `ref`) on two seeded 1024-d
+    descriptor sets: packed words of both and their packed Hamming distance matrix."""
+    sys.path.insert(0, os.path.join(ROOT, "oracle", "_ref", "asmk_ext"))
+    import hamming
+
+    r = np.random.default_rng(9)
+    a = (r.random((40, 1024)) - 0.5).astype(np.float32)
+    b = (r.random((60, 1024)) - 0.5).astype(np.float32)
+    pa, pb = hamming.binarize_and_pack_2D(a), hamming.binarize_and_pack_2D(b)
+    np.savez_compressed(os.path.join(HERE, "asmk_hamming_direct.npz"), a=a, b=b, pack_a=pa, pack_b=pb,
+                        cdist=hamming.hamming_cdist_packed(pa, pb), **meta())
+    print("asmk_hamming_direct.npz", pa.shape, pb.shape)
+
+
 SECTIONS["retrieval_asmk"] = section_retrieval_asmk
+SECTIONS["asmk_direct"] = section_asmk_direct
 SECTIONS["utils_wrappers"] = section_utils_wrappers
 SECTIONS["track_logic"] = section_track_logic
 SECTIONS["factor_graph"] = section_factor_graph

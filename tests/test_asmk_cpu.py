@@ -70,19 +70,11 @@ def test_update_sequence(gold):
     np.testing.assert_array_equal(db.ivf.norm_factor, gold["norm_factor"])
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(os.path.dirname(GOLD), "..", "oracle", "_ref", "asmk_ext")),
-                    reason="oracle/_ref/asmk_ext (the reference's hamming extension, make -C oracle ref) not built")
 def test_oracle_against_the_built_reference_extension_directly():
-    import sys
-
-    sys.path.insert(0, os.path.join(os.path.dirname(GOLD), "..", "oracle", "_ref", "asmk_ext"))
-    try:
-        import hamming
-    finally:
-        sys.path.pop(0)
-    r = np.random.default_rng(9)
-    a = (r.random((40, 1024)) - 0.5).astype(np.float32)
-    b = (r.random((60, 1024)) - 0.5).astype(np.float32)
-    pa, pb = hamming.binarize_and_pack_2D(a), hamming.binarize_and_pack_2D(b)
-    np.testing.assert_array_equal(asmk_py.binarize_and_pack_2D(a), pa)
-    np.testing.assert_array_equal(asmk_py.hamming_cdist_packed(pa, pb), hamming.hamming_cdist_packed(pa, pb))
+    """The reference's compiled hamming extension at full descriptor width (1024-d), as recorded by make_golden.py
+    section asmk_direct."""
+    k = np.load(os.path.join(GOLD, "asmk_hamming_direct.npz"))
+    pa, pb = k["pack_a"], k["pack_b"]
+    np.testing.assert_array_equal(asmk_py.binarize_and_pack_2D(k["a"]), pa)
+    np.testing.assert_array_equal(asmk_py.binarize_and_pack_2D(k["b"]), pb)
+    np.testing.assert_array_equal(asmk_py.hamming_cdist_packed(pa, pb), k["cdist"])

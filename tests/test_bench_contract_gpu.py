@@ -1,6 +1,7 @@
 """bench.py's output contract on a short run (a child process, as the driver starts it): ONE JSON line on stdout with the
-keys the driver reads, the roofline object measured live (launches of the dominant shape were timed inside the region),
-the per-kernel HBM entries, and the cpu_baseline object when it is not switched off."""
+keys the driver reads; under --full also the roofline object measured live (launches of the dominant shape were timed
+inside the region), the per-kernel HBM entries, and the cpu_baseline object when it is not switched off.  A plain run
+carries only the headline figures and writes the loop's outputs with --dump-outputs."""
 import json
 import os
 import subprocess
@@ -15,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_line(device):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "8", "--warmup", "4", "--preroll", "40",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+                        "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -34,6 +35,34 @@ def test_bench_line(device):
     st = d["config"]["stats"]
     assert st["relocalised"] == 0 and st["keyframes"] >= 2 and st["encoder_rows"] >= 8
     assert "cpu_baseline" not in d                                                              # switched off above
+
+
+def test_plain_bench_line_and_dumped_outputs(device, tmp_path):
+    """The plain run (no --full) prints the headline figures only and, with --dump-outputs, writes what the timed loop
+    computed in its last step as float .npy files, 64 MB at most."""
+    import numpy as np
+
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    dump = str(tmp_path / "outputs")
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2",
+                        "--preroll", "40", "--dump-outputs", dump], capture_output=True, text=True, timeout=600, env=env,
+                       cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["metric"].startswith("SLAM frames/sec") and d["unit"] == "frames/s" and d["higher_is_better"] is True
+    assert d["n_gpus"] == 1 and d["steps"] == 6 and d["warmup"] == 2 and d["dtype"] == "bf16"
+    assert d["value"] > 0 and abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 1e-6
+    assert "roofline" not in d and "cpu_baseline" not in d                                     # --full only
+    got = {f[:-4]: np.load(os.path.join(dump, f)) for f in os.listdir(dump)}
+    assert set(got) == {"last_pose", "last_flags", "last_pointmap", "last_confidence", "keyframe_poses"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert got["last_pose"].shape == (1, 8) and np.isfinite(got["last_pose"]).all()
+    assert got["last_flags"][0] == 1                                                            # Mode.TRACKING
+    assert got["last_pointmap"].shape == (384 * 512, 3) and got["last_confidence"].shape == (384 * 512, 1)
+    assert got["keyframe_poses"].shape == (d["config"]["stats"]["keyframes"], 8) and np.isfinite(got["keyframe_poses"]).all()
 
 
 def _check_two_rank_line(p):

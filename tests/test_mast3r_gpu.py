@@ -1,6 +1,6 @@
 """GPU parity tests (-m gpu) for the MASt3R forward (csrc/gemm.hip, attention.hip, mast3r.hip) through the
 C ABI, against the torch-fp32 oracle (oracle/mast3r_ref.py, itself pinned to the reference model classes
-by tests/golden/mast3r_small.npz) and against that fixture directly.
+by tests/golden/mast3r_small_part*.npz) and against that fixture directly.
 
 Stated tolerances (bf16 MFMA operands, fp32 accumulate):
   encoder / decoder tokens   rel-L2 <= 2e-2
@@ -42,8 +42,8 @@ def _model(cfg, seed, device):
     return sd, Mast3rHIP(sd, hip_cfg, device=device)
 
 
-def test_small_model_matches_reference_fixture(device, golden_dir):
-    fx = np.load(os.path.join(golden_dir, "mast3r_small.npz"))
+def test_small_model_matches_reference_fixture(device, load_golden):
+    fx = load_golden("mast3r_small")
     c = fx["cfg"]
     cfg = R.Mast3rConfig(enc_dim=int(c[0]), enc_depth=int(c[1]), enc_heads=int(c[2]), dec_dim=int(c[3]),
                          dec_depth=int(c[4]), dec_heads=int(c[5]))

@@ -1,7 +1,6 @@
 """CPU test (-m "not gpu"): the torch-functional MASt3R oracle (oracle/mast3r_ref.py) against outputs
-of the reference's own AsymmetricMASt3R classes (tests/golden/mast3r_small.npz: reduced width/depth,
+of the reference's own AsymmetricMASt3R classes (tests/golden/mast3r_small_part*.npz: reduced width/depth,
 weights = init_state_dict(seed) on both sides, so only inputs/outputs are stored)."""
-import os
 
 import numpy as np
 import pytest
@@ -11,8 +10,8 @@ from oracle import mast3r_ref as R
 
 
 @pytest.fixture(scope="module")
-def fx(golden_dir):
-    return np.load(os.path.join(golden_dir, "mast3r_small.npz"))
+def fx(load_golden):
+    return load_golden("mast3r_small")
 
 
 def test_forward_matches_reference_model(fx):

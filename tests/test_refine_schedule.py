@@ -1,7 +1,6 @@
 """TSDFRefiner block selection, clustering and sliding-window scheduling (tsdf_refine.py:246-601) against
-tests/golden/refine_schedule.npz, recorded from the reference class itself (tests/golden/make_golden.py
+tests/golden/refine_schedule_part*.npz, recorded from the reference class itself (tests/golden/make_golden.py
 refine_schedule).  Host logic only: runs without a GPU."""
-import os
 
 import numpy as np
 import pytest
@@ -9,8 +8,8 @@ import torch
 
 
 @pytest.fixture(scope="module")
-def fx(golden_dir):
-    return np.load(os.path.join(golden_dir, "refine_schedule.npz"))
+def fx(load_golden):
+    return load_golden("refine_schedule")
 
 
 BASE = dict(enabled=True, window_size=5, voxel_size=0.02, trunc_dist=0.08, max_grid_dim=64, roi_size=0.4, ray_samples=64,
