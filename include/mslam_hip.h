@@ -227,6 +227,27 @@ int mslam_tsdf_pose_step_lookup(const double* lookup, const float* points, const
                                 double damping, int update_pose, double* H_out, double* b_out, int* used_out,
                                 void* workspace, size_t workspace_bytes, void* stream);
 
+/* Triangle mesh of the volume (marching cubes; no counterpart in the reference, DESIGN.md "Mesh extraction").  The table
+ * is only read.  Sequence, all on one stream:
+ *   mslam_tsdf_mesh_keys     sort_keys i64[capacity]: packed key of every voxel with weight >= min_weight, INT64_MAX
+ *                            elsewhere; the caller sorts them ascending (values + their slot indices `order`);
+ *   mslam_tsdf_mesh_count    counts i32[2][capacity]: vertices owned / triangles of the cube at each sorted position;
+ *                            the caller forms their exclusive scans vbase, fbase (i64) and the totals V, F;
+ *   mslam_tsdf_mesh_emit     vertices f32[V,3], normals f32[V,3], faces i32[F,3] in canonical order.
+ * workspace >= mslam_tsdf_mesh_workspace_bytes(capacity), kept between count and emit. */
+size_t mslam_tsdf_mesh_workspace_bytes(uint64_t capacity);
+int mslam_tsdf_mesh_keys(void* table, uint64_t capacity, double min_weight, int64_t* sort_keys, void* stream);
+int mslam_tsdf_mesh_count(void* table, uint64_t capacity, double min_weight, double level, const int64_t* sorted_keys,
+                          const int64_t* order, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int mslam_tsdf_mesh_emit(void* table, uint64_t capacity, double voxel_size, double min_weight, double level,
+                         const int64_t* sorted_keys, const int64_t* order, const int64_t* vbase, const int64_t* fbase,
+                         void* workspace, size_t workspace_bytes, float* vertices, float* normals, int32_t* faces,
+                         int64_t n_vertices, int64_t n_faces, void* stream);
+/* Inserts n distinct voxels keys i64[n,3], tsdf f64[n], weight f64[n] into an initialised table as averaged voxels;
+ * a full table or a key outside the 21-bit range sets the header's overflow flag (as integrate does). */
+int mslam_tsdf_load(void* table, uint64_t capacity, const int64_t* keys, const double* tsdf, const double* weight,
+                    int n, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * MASt3R two-view forward.  Replaces the three model methods the SLAM front/back-end call
  * (mast3r_slam/mast3r_utils.py:34-40,57-64,74): model._encode_image, model._decoder,

@@ -103,6 +103,44 @@ def save_ply(filename, points, colors):
     _write_ply(filename, pcd)
 
 
+def save_mesh(filename, vertices, faces, normals=None):
+    """Triangle mesh as binary little-endian PLY: `element vertex` (x, y, z [, nx, ny, nz] float) and `element face`
+    (`property list uchar int vertex_indices`).  Arrays may be numpy or device tensors."""
+    def host(a, dtype):
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        return a.astype(dtype).reshape(-1, 3)
+
+    v = host(vertices, np.float32)
+    f = host(faces, np.int32)
+    cols = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if normals is not None:
+        cols += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    vert = np.empty(len(v), dtype=cols)
+    vert["x"], vert["y"], vert["z"] = v.T
+    if normals is not None:
+        n = host(normals, np.float32)
+        vert["nx"], vert["ny"], vert["nz"] = n.T
+    face = np.empty(len(f), dtype=[("n", "u1"), ("i", "<i4", (3,))])
+    face["n"], face["i"] = 3, f
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"]
+    header += [f"property float {name}" for name, _ in cols]
+    header += [f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
+    with open(filename, "wb") as fh:
+        fh.write(("\n".join(header) + "\n").encode("ascii"))
+        fh.write(vert.tobytes())
+        fh.write(face.tobytes())
+
+
+def save_tsdf_mesh(savedir, filename, source, min_weight=None, level=0.0):
+    """The global TSDF's triangle mesh (marching cubes) as PLY with normals, beside save_reconstruction's point cloud.
+    `source`: a SlamSystem, a TSDFGlobalManager or a TSDFVolume.  Returns (V, F)."""
+    savedir = pathlib.Path(savedir)
+    savedir.mkdir(exist_ok=True, parents=True)
+    v, n, f = source.extract_mesh(min_weight=min_weight, level=level)
+    save_mesh(savedir / filename, v, f, normals=n)
+    return int(v.shape[0]), int(f.shape[0])
+
+
 def _resize_grid(g, H, W, mode):
     """cv2.resize(g, (W, H), INTER_NEAREST | INTER_LINEAR) for a 2-D float32 grid: nearest takes src = floor(dst * scale),
     linear samples at (dst + 0.5) * scale - 0.5 with the border replicated."""

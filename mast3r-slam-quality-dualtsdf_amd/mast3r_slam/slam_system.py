@@ -355,6 +355,15 @@ class SlamSystem:
             with self._critical("main"):
                 self._apply_commits(wait=True)
 
+    def extract_mesh(self, min_weight=None, level=0.0):
+        """Triangle mesh of the global TSDF at this point of the run: (vertices f32[V,3], normals f32[V,3], faces i32[F,3])
+        device tensors (TSDFVolume.extract_mesh).  Drains the backend first, so every fusion it has issued is ordered
+        before the read."""
+        if self.tsdf_manager is None:
+            raise RuntimeError("SlamSystem.extract_mesh: the global TSDF is disabled (tsdf_global.enabled = False)")
+        self.drain()
+        return self.tsdf_manager.extract_mesh(min_weight=min_weight, level=level)
+
     def _adopt_backend_tensors(self):
         """Relocalisation (main.py:28-71) edits and solves the factor graph on the TRACKING stream, but its tensors were
         allocated and last written on the backend stream: the tracking stream first waits for everything the (now idle)

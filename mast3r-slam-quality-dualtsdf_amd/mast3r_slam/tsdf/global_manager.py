@@ -139,6 +139,11 @@ class TSDFGlobalManager:
         if self.enabled:
             self.volume.maintain()   # samples dropped by the last solve are reported here
 
+    def extract_mesh(self, min_weight=None, level=0.0):
+        """Triangle mesh of the global volume: (vertices f32[V,3], normals f32[V,3], faces i32[F,3]) device tensors
+        (TSDFVolume.extract_mesh)."""
+        return self.volume.extract_mesh(min_weight=min_weight, level=level)
+
     def on_after_backend_solve(self, factor_graph):
         """global_manager.py:213-226, followed by the pass the reference's two threads would make."""
         self.execute(self.plan(factor_graph))

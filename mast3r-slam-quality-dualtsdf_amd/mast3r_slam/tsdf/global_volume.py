@@ -225,7 +225,82 @@ class TSDFVolume:
         o = np.lexsort((keys[:, 2], keys[:, 1], keys[:, 0]))
         return keys[o], t[o], w[o]
 
+    # ------------------------------------------------------------------
+    def load_voxels(self, keys, tsdf, weight):
+        """Inserts distinct voxels keys i64[n,3], tsdf f64[n], weight f64[n] as averaged voxels (a table that was built
+        elsewhere, e.g. the union of voxel shards).  Local to this table; raises when the table overflowed."""
+        k = self._dev(keys, torch.int64).reshape(-1, 3)
+        t = self._dev(tsdf, torch.float64).reshape(-1)
+        w = self._dev(weight, torch.float64).reshape(-1)
+        n = k.shape[0]
+        if t.shape[0] != n or w.shape[0] != n:
+            raise ValueError("load_voxels: keys, tsdf and weight must have the same length")
+        if n == 0:
+            return
+        _m.check(_m.lib().mslam_tsdf_load(_m.ptr(self._table), self.capacity, _m.ptr(k), _m.ptr(t), _m.ptr(w), n,
+                                          _m.stream_ptr()), "tsdf_load")
+        h = self._header()
+        if h[1]:
+            raise RuntimeError(f"TSDFVolume.load_voxels: table overflow (code {int(h[1])}, {n} voxels into "
+                               f"{self.capacity} slots)")
+
+    def extract_mesh(self, min_weight=None, level=0.0):
+        """Marching cubes over the fused volume -> (vertices f32[V,3], normals f32[V,3], faces i32[F,3]) device tensors in
+        canonical order (DESIGN.md "Mesh extraction").  Corners are voxel centres with weight >= min_weight (default
+        self.min_weight), inside = tsdf < level, normals point to free space, faces are counter-clockwise seen from
+        there.  The table is only read.  One host read (the output sizes).  Sharded volumes: cubes span owners, so the
+        union of the shards (voxels(), collective) is meshed on every rank."""
+        mw = self.min_weight if min_weight is None else float(min_weight)
+        if self.num_shards > 1:
+            keys, t, w = self.voxels()
+            return mesh_from_voxels(keys, t, w, self.voxel_size, mw, level, device=self.device)
+        return _extract(self._table, self.capacity, self.voxel_size, mw, float(level), self.device)
+
     def stats(self):
         """global_volume.py:136-140."""
         keys, t, w = self.voxels()
         return {"valid_voxels": int((w >= self.min_weight).sum()), "total_voxels": int(len(w))}
+
+
+def _extract(table, capacity, voxel_size, min_weight, level, device):
+    L = _m.lib()
+    stream = _m.stream_ptr()
+    sk = torch.empty(capacity, dtype=torch.int64, device=device)
+    _m.check(L.mslam_tsdf_mesh_keys(_m.ptr(table), capacity, min_weight, _m.ptr(sk), stream), "tsdf_mesh_keys")
+    sk, order = torch.sort(sk)       # packed-key order = lexicographic (x, y, z): the canonical voxel order
+    order = order.contiguous()
+    wsb = L.mslam_tsdf_mesh_workspace_bytes(capacity)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=device)
+    counts = torch.empty((2, capacity), dtype=torch.int32, device=device)
+    _m.check(L.mslam_tsdf_mesh_count(_m.ptr(table), capacity, min_weight, level, _m.ptr(sk), _m.ptr(order),
+                                     _m.ptr(counts), _m.ptr(ws), wsb, stream), "tsdf_mesh_count")
+    # one device-wide scan over both rows (a scan along dim 1 of the (2, capacity) tensor runs one block per row here:
+    # 50x slower): the face row then carries V in front of every entry
+    incl = torch.cumsum(counts.view(-1), dim=0).view(2, capacity)
+    V, VF = (int(x) for x in incl[:, -1].cpu())
+    F = VF - V
+    verts = torch.empty((V, 3), dtype=torch.float32, device=device)
+    normals = torch.empty((V, 3), dtype=torch.float32, device=device)
+    faces = torch.empty((F, 3), dtype=torch.int32, device=device)
+    if V == 0 and F == 0:
+        return verts, normals, faces
+    if V >= 1 << 31:
+        raise RuntimeError(f"extract_mesh: {V} vertices exceed the int32 face indices")
+    base = incl - counts
+    base[1] -= incl[0, -1]
+    _m.check(L.mslam_tsdf_mesh_emit(_m.ptr(table), capacity, float(voxel_size), min_weight, level, _m.ptr(sk),
+                                    _m.ptr(order), _m.ptr(base[0]), _m.ptr(base[1]), _m.ptr(ws), wsb, _m.ptr(verts),
+                                    _m.ptr(normals), _m.ptr(faces), V, F, stream), "tsdf_mesh_emit")
+    return verts, normals, faces
+
+
+def mesh_from_voxels(keys, tsdf, weight, voxel_size, min_weight, level=0.0, device="cuda"):
+    """Mesh of a voxel set given as arrays (keys i64[n,3] distinct, tsdf f64[n], weight f64[n]; numpy or device): loads
+    a temporary table of at least 2n slots and extracts from it (TSDFVolume.extract_mesh semantics)."""
+    n = int(len(keys))
+    cap = 1024
+    while cap < 2 * n:
+        cap *= 2
+    vol = TSDFVolume(voxel_size, 1.0, min_weight=min_weight, capacity=cap, device=device)
+    vol.load_voxels(keys, tsdf, weight)
+    return vol.extract_mesh(min_weight=min_weight, level=level)

@@ -72,6 +72,10 @@ _SIGNATURES = {
     "mslam_tsdf_query_lookup": [_c_vp, _c_int, _c_double, _c_double, _c_vp, _c_vp, _c_vp, _c_vp],
     "mslam_tsdf_pose_step_lookup": [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_int] + [_c_double] * 4 + [_c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_size, _c_vp],
     "mslam_tsdf_pose_step": [_c_vp, ctypes.c_uint64, _c_vp, _c_vp, _c_int, _c_vp, _c_int] + [_c_double] * 4 + [_c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_size, _c_vp],
+    "mslam_tsdf_mesh_keys": [_c_vp, ctypes.c_uint64, _c_double, _c_vp, _c_vp],
+    "mslam_tsdf_mesh_count": [_c_vp, ctypes.c_uint64, _c_double, _c_double] + [_c_vp] * 4 + [_c_size, _c_vp],
+    "mslam_tsdf_mesh_emit": [_c_vp, ctypes.c_uint64] + [_c_double] * 3 + [_c_vp] * 5 + [_c_size] + [_c_vp] * 3 + [_c_i64, _c_i64, _c_vp],
+    "mslam_tsdf_load": [_c_vp, ctypes.c_uint64, _c_vp, _c_vp, _c_vp, _c_int, _c_vp],
 }
 _RESTYPES = {
     "mslam_last_error": ctypes.c_char_p,
@@ -82,6 +86,7 @@ _RESTYPES = {
     "mslam_track_prepare_workspace_bytes": ctypes.c_size_t,
     "mslam_mast3r_workspace_bytes": ctypes.c_size_t,
     "mslam_tsdf_integrate_workspace_bytes": ctypes.c_size_t,
+    "mslam_tsdf_mesh_workspace_bytes": ctypes.c_size_t,
 }
 
 _lib = None
@@ -121,6 +126,8 @@ def lib() -> ctypes.CDLL:
         handle.mslam_tsdf_table_bytes.restype = ctypes.c_size_t
         handle.mslam_tsdf_integrate_workspace_bytes.argtypes = [_c_int, _c_double, _c_double, _c_double]
         handle.mslam_tsdf_integrate_workspace_bytes.restype = ctypes.c_size_t
+        handle.mslam_tsdf_mesh_workspace_bytes.argtypes = [ctypes.c_uint64]
+        handle.mslam_tsdf_mesh_workspace_bytes.restype = ctypes.c_size_t
         _lib = handle
     return _lib
 
