@@ -248,6 +248,24 @@ int mslam_tsdf_mesh_emit(void* table, uint64_t capacity, double voxel_size, doub
 int mslam_tsdf_load(void* table, uint64_t capacity, const int64_t* keys, const double* tsdf, const double* weight,
                     int n, void* stream);
 
+/* Depth / normal view of the volume by ray casting (no counterpart in the reference, DESIGN.md "View rendering").  The
+ * table is only read.  Sequence, on one stream:
+ *   mslam_tsdf_render_blocks  fills the workspace with the set of 8^3-voxel blocks that hold a voxel with weight >=
+ *                             min_weight (what the march may not jump over); once per table state and min_weight;
+ *   mslam_tsdf_render         one ray per pixel: rays f32[h*w,3] unit, camera frame, moved with pose8 (Sim3 [t,q,s] f32);
+ *                             samples at near + k * step (world units) up to far; range f32[h*w] = distance along the
+ *                             unit ray in camera units (world range / s; 0 on a miss), normal f32[h*w,3] world frame
+ *                             towards free space (0 on a miss), hit u8[h*w].  skip = 0: brute-force march; != 0: jumps
+ *                             over unmarked blocks, same output bit for bit.  h, w only shape the 8x8-pixel wave tiles.
+ * workspace >= mslam_tsdf_render_workspace_bytes(capacity). */
+size_t mslam_tsdf_render_workspace_bytes(uint64_t capacity);
+int mslam_tsdf_render_blocks(void* table, uint64_t capacity, double min_weight, void* workspace, size_t workspace_bytes,
+                             void* stream);
+int mslam_tsdf_render(void* table, uint64_t capacity, const float* rays, int h, int w, const float* pose8,
+                      double voxel_size, double min_weight, double level, double near, double far, double step, int skip,
+                      const void* workspace, size_t workspace_bytes, float* range, float* normal, uint8_t* hit,
+                      void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * MASt3R two-view forward.  Replaces the three model methods the SLAM front/back-end call
  * (mast3r_slam/mast3r_utils.py:34-40,57-64,74): model._encode_image, model._decoder,

@@ -141,6 +141,37 @@ def save_tsdf_mesh(savedir, filename, source, min_weight=None, level=0.0):
     return int(v.shape[0]), int(f.shape[0])
 
 
+def save_depth_view(savedir, filename, range_or_depth, normals, hit, pose=None):
+    """A rendered view (TSDFVolume.render) as two images beside `filename`'s stem: `<stem>_depth.png`, 16-bit grey,
+    the given range or depth in millimetres (rounded, clipped to 65535; 0 = miss), and `<stem>_normal.png`, 8-bit RGB of
+    0.5 * (n_cam + 1) (0 on a miss).  `normals` are camera-frame, or world-frame (as render returns them) together with
+    the view's `pose` (8,) [t, q, s], whose rotation is then undone.  Arrays may be numpy or device tensors.  Returns the
+    two paths."""
+    from PIL import Image
+
+    def host(a):
+        return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+
+    savedir = pathlib.Path(savedir)
+    savedir.mkdir(exist_ok=True, parents=True)
+    stem = pathlib.Path(filename).stem
+    m = host(hit).astype(bool)
+    d = np.where(m, host(range_or_depth).astype(np.float64), 0.0)
+    mm = np.clip(np.rint(d * 1000.0), 0, 65535).astype(np.uint16)
+    n = host(normals).astype(np.float64)
+    if pose is not None:          # n_cam = R^T n_world: rotate with the conjugate quaternion
+        q = host(getattr(pose, "data", pose)).astype(np.float64).reshape(8)[3:7]
+        qv, qw = -q[:3], q[3]
+        u = 2.0 * np.cross(qv, n)
+        n = n + qw * u + np.cross(qv, u)
+    n = np.where(m[..., None], 0.5 * (n + 1.0), 0.0)
+    rgb = np.clip(np.rint(n * 255.0), 0, 255).astype(np.uint8)
+    depth_path, normal_path = savedir / f"{stem}_depth.png", savedir / f"{stem}_normal.png"
+    Image.fromarray(mm).save(depth_path)          # uint16 array -> mode I;16
+    Image.fromarray(rgb).save(normal_path)
+    return depth_path, normal_path
+
+
 def _resize_grid(g, H, W, mode):
     """cv2.resize(g, (W, H), INTER_NEAREST | INTER_LINEAR) for a 2-D float32 grid: nearest takes src = floor(dst * scale),
     linear samples at (dst + 0.5) * scale - 0.5 with the border replicated."""

@@ -364,6 +364,29 @@ class SlamSystem:
         self.drain()
         return self.tsdf_manager.extract_mesh(min_weight=min_weight, level=level)
 
+    def render_view(self, pose=None, rays=None, K=None, hw=None, **kw):
+        """Depth / normal view of the global TSDF at this point of the run: (range f32[h,w], normals f32[h,w,3],
+        hit bool[h,w]) device tensors (TSDFVolume.render; `kw`: near, far, min_weight, level, step, skip).  Drains the
+        backend first, like extract_mesh.  `pose=None`: the newest keyframe's pose.  Without `rays` and `K` the view uses
+        the system's intrinsics when it is calibrated and otherwise the newest keyframe's canonical pointmap normalised
+        to unit length - the ray model of an uncalibrated camera - so the view lies pixel for pixel over that keyframe."""
+        if self.tsdf_manager is None:
+            raise RuntimeError("SlamSystem.render_view: the global TSDF is disabled (tsdf_global.enabled = False)")
+        self.drain()
+        kf = self.keyframes.last_keyframe()
+        if kf is None and (pose is None or (rays is None and K is None)):
+            raise RuntimeError("SlamSystem.render_view: no keyframe yet; give pose and rays (or K with hw)")
+        if pose is None:
+            pose = kf.T_WC.data
+        if rays is None and K is None:
+            h, w = (int(x) for x in kf.img_shape.reshape(-1)[:2].tolist())
+            if config["use_calib"] and self.K is not None:
+                K, hw = self.K, (h, w)
+            else:
+                X = kf.X_canon.detach().reshape(h, w, 3).float()
+                rays = X / X.norm(dim=-1, keepdim=True).clamp_min(1.0e-12)
+        return self.tsdf_manager.render(pose, rays=rays, K=K, hw=hw, **kw)
+
     def _adopt_backend_tensors(self):
         """Relocalisation (main.py:28-71) edits and solves the factor graph on the TRACKING stream, but its tensors were
         allocated and last written on the backend stream: the tracking stream first waits for everything the (now idle)

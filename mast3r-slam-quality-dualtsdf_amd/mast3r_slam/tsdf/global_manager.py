@@ -144,6 +144,11 @@ class TSDFGlobalManager:
         (TSDFVolume.extract_mesh)."""
         return self.volume.extract_mesh(min_weight=min_weight, level=level)
 
+    def render(self, pose, rays=None, K=None, hw=None, **kw):
+        """Depth / normal view of the global volume from `pose`: (range f32[h,w], normals f32[h,w,3], hit bool[h,w])
+        device tensors (TSDFVolume.render)."""
+        return self.volume.render(pose, rays=rays, K=K, hw=hw, **kw)
+
     def on_after_backend_solve(self, factor_graph):
         """global_manager.py:213-226, followed by the pass the reference's two threads would make."""
         self.execute(self.plan(factor_graph))

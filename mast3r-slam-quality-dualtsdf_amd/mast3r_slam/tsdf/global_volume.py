@@ -256,6 +256,26 @@ class TSDFVolume:
             return mesh_from_voxels(keys, t, w, self.voxel_size, mw, level, device=self.device)
         return _extract(self._table, self.capacity, self.voxel_size, mw, float(level), self.device)
 
+    def render(self, pose, rays=None, K=None, hw=None, near=0.05, far=10.0, min_weight=None, level=0.0, step=None,
+               skip=True):
+        """Ray cast of the fused volume from a camera -> (range f32[h,w], normals f32[h,w,3], hit bool[h,w]) device
+        tensors (DESIGN.md "View rendering").  `pose`: Sim3 (8,) [t, q, s], world from camera.  Either `rays` f32[h,w,3],
+        unit, camera frame (the project's ray model for an uncalibrated camera), or a pinhole `K` (3,3) with `hw` =
+        (h, w).  `range` is the distance along the unit ray in camera units (range * rays = the camera-frame pointmap;
+        0 on a miss); normals are in the world frame and point to free space.  Samples every `step` (default half a
+        voxel) between `near` and `far`, world units; a hit is the first crossing from >= level to < level between two
+        valid samples.  `skip=False` marches through empty space sample by sample (same output, for checks and timing).
+        The table is only read.  Sharded volumes: samples span owners, so the union of the shards (voxels(), collective)
+        is rendered on every rank."""
+        mw = self.min_weight if min_weight is None else float(min_weight)
+        pose, rays, step = _render_args(pose, rays, K, hw, near, far, step, self.voxel_size, self.device)
+        if self.num_shards > 1:
+            keys, t, w = self.voxels()
+            return render_from_voxels(keys, t, w, self.voxel_size, mw, pose, rays, near=near, far=far, level=level,
+                                      step=step, skip=skip, device=self.device)
+        return _render(self._table, self.capacity, self.voxel_size, mw, float(level), pose, rays, float(near),
+                       float(far), step, bool(skip), self.device)
+
     def stats(self):
         """global_volume.py:136-140."""
         keys, t, w = self.voxels()
@@ -292,6 +312,80 @@ def _extract(table, capacity, voxel_size, min_weight, level, device):
                                     _m.ptr(order), _m.ptr(base[0]), _m.ptr(base[1]), _m.ptr(ws), wsb, _m.ptr(verts),
                                     _m.ptr(normals), _m.ptr(faces), V, F, stream), "tsdf_mesh_emit")
     return verts, normals, faces
+
+
+def pinhole_rays(K, hw, device="cuda"):
+    """Unit camera-frame rays f32[h,w,3] of a pinhole camera: ((u - cx) / fx, (v - cy) / fy, 1) normalised, pixel
+    centres at integer (u, v) (synthetic.pixel_rays)."""
+    h, w = (int(x) for x in hw)
+    K = torch.as_tensor(K).detach().to(device="cpu", dtype=torch.float64).reshape(3, 3)
+    u = torch.arange(w, dtype=torch.float64).view(1, w).expand(h, w)
+    v = torch.arange(h, dtype=torch.float64).view(h, 1).expand(h, w)
+    r = torch.stack(((u - K[0, 2]) / K[0, 0], (v - K[1, 2]) / K[1, 1], torch.ones(h, w, dtype=torch.float64)), -1)
+    return (r / r.norm(dim=-1, keepdim=True)).to(device=device, dtype=torch.float32).contiguous()
+
+
+def _render_args(pose, rays, K, hw, near, far, step, voxel_size, device):
+    """Checked (pose f32[8], rays f32[h,w,3], step) on `device`."""
+    if isinstance(pose, np.ndarray):
+        pose = torch.from_numpy(np.ascontiguousarray(pose))
+    pose = getattr(pose, "data", pose)        # a lietorch Sim3 carries its (1,8) tensor in .data
+    pose = torch.as_tensor(pose)
+    if pose.numel() != 8:
+        raise ValueError(f"render: pose must hold 8 values [t, q, s], got shape {tuple(pose.shape)}")
+    pose = pose.detach().to(device=device, dtype=torch.float32).reshape(8).contiguous()
+    if (rays is None) == (K is None):
+        raise ValueError("render: give either rays (h,w,3) or K with hw")
+    if rays is None:
+        if hw is None or len(hw) != 2 or min(int(x) for x in hw) < 1:
+            raise ValueError("render: K needs hw = (h, w)")
+        if tuple(torch.as_tensor(K).shape) != (3, 3):
+            raise ValueError("render: K must be (3,3)")
+        rays = pinhole_rays(K, hw, device)
+    else:
+        if isinstance(rays, np.ndarray):
+            rays = torch.from_numpy(np.ascontiguousarray(rays))
+        if rays.dim() != 3 or rays.shape[-1] != 3 or rays.shape[0] < 1 or rays.shape[1] < 1:
+            raise ValueError(f"render: rays must be (h,w,3), got {tuple(rays.shape)}")
+        if hw is not None and tuple(int(x) for x in hw) != tuple(rays.shape[:2]):
+            raise ValueError("render: hw does not match rays")
+        rays = rays.detach().to(device=device, dtype=torch.float32).contiguous()
+    step = 0.5 * float(voxel_size) if step is None else float(step)
+    if not step > 0.0:
+        raise ValueError("render: step must be positive")
+    if not float(far) > float(near) or not np.isfinite(float(far) - float(near)):
+        raise ValueError("render: far must be greater than near")
+    return pose, rays, step
+
+
+def _render(table, capacity, voxel_size, min_weight, level, pose, rays, near, far, step, skip, device):
+    L = _m.lib()
+    stream = _m.stream_ptr()
+    h, w = int(rays.shape[0]), int(rays.shape[1])
+    wsb = L.mslam_tsdf_render_workspace_bytes(capacity)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=device)
+    _m.check(L.mslam_tsdf_render_blocks(_m.ptr(table), capacity, min_weight, _m.ptr(ws), wsb, stream),
+             "tsdf_render_blocks")
+    rng = torch.empty((h, w), dtype=torch.float32, device=device)
+    nrm = torch.empty((h, w, 3), dtype=torch.float32, device=device)
+    hit = torch.empty((h, w), dtype=torch.uint8, device=device)
+    _m.check(L.mslam_tsdf_render(_m.ptr(table), capacity, _m.ptr(rays), h, w, _m.ptr(pose), float(voxel_size),
+                                 min_weight, level, near, far, step, int(skip), _m.ptr(ws), wsb, _m.ptr(rng),
+                                 _m.ptr(nrm), _m.ptr(hit), stream), "tsdf_render")
+    return rng, nrm, hit.bool()
+
+
+def render_from_voxels(keys, tsdf, weight, voxel_size, min_weight, pose, rays, near=0.05, far=10.0, level=0.0,
+                       step=None, skip=True, device="cuda"):
+    """View of a voxel set given as arrays (keys i64[n,3] distinct, tsdf f64[n], weight f64[n]; numpy or device): loads
+    a temporary table of at least 2n slots and renders from it (TSDFVolume.render semantics)."""
+    n = int(len(keys))
+    cap = 1024
+    while cap < 2 * n:
+        cap *= 2
+    vol = TSDFVolume(voxel_size, 1.0, min_weight=min_weight, capacity=cap, device=device)
+    vol.load_voxels(keys, tsdf, weight)
+    return vol.render(pose, rays=rays, near=near, far=far, min_weight=min_weight, level=level, step=step, skip=skip)
 
 
 def mesh_from_voxels(keys, tsdf, weight, voxel_size, min_weight, level=0.0, device="cuda"):

@@ -76,6 +76,8 @@ _SIGNATURES = {
     "mslam_tsdf_mesh_count": [_c_vp, ctypes.c_uint64, _c_double, _c_double] + [_c_vp] * 4 + [_c_size, _c_vp],
     "mslam_tsdf_mesh_emit": [_c_vp, ctypes.c_uint64] + [_c_double] * 3 + [_c_vp] * 5 + [_c_size] + [_c_vp] * 3 + [_c_i64, _c_i64, _c_vp],
     "mslam_tsdf_load": [_c_vp, ctypes.c_uint64, _c_vp, _c_vp, _c_vp, _c_int, _c_vp],
+    "mslam_tsdf_render_blocks": [_c_vp, ctypes.c_uint64, _c_double, _c_vp, _c_size, _c_vp],
+    "mslam_tsdf_render": [_c_vp, ctypes.c_uint64, _c_vp, _c_int, _c_int, _c_vp] + [_c_double] * 6 + [_c_int, _c_vp, _c_size] + [_c_vp] * 4,
 }
 _RESTYPES = {
     "mslam_last_error": ctypes.c_char_p,
@@ -87,6 +89,7 @@ _RESTYPES = {
     "mslam_mast3r_workspace_bytes": ctypes.c_size_t,
     "mslam_tsdf_integrate_workspace_bytes": ctypes.c_size_t,
     "mslam_tsdf_mesh_workspace_bytes": ctypes.c_size_t,
+    "mslam_tsdf_render_workspace_bytes": ctypes.c_size_t,
 }
 
 _lib = None
@@ -128,6 +131,8 @@ def lib() -> ctypes.CDLL:
         handle.mslam_tsdf_integrate_workspace_bytes.restype = ctypes.c_size_t
         handle.mslam_tsdf_mesh_workspace_bytes.argtypes = [ctypes.c_uint64]
         handle.mslam_tsdf_mesh_workspace_bytes.restype = ctypes.c_size_t
+        handle.mslam_tsdf_render_workspace_bytes.argtypes = [ctypes.c_uint64]
+        handle.mslam_tsdf_render_workspace_bytes.restype = ctypes.c_size_t
         _lib = handle
     return _lib
 
