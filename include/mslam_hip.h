@@ -11,6 +11,12 @@
  *
  * Each declaration cites the reference interface it replaces (paths relative to the reference
  * repository root).  The Python binding a maintainer adds is shown in INTEGRATION.md.
+ *
+ * This header is also READ AT RUN TIME by mslam_hip.py, which takes every ctypes signature from it (there is no second
+ * copy to keep in step).  So it holds plain C declarations only, one per `;`: `<ret> mslam_<name>(<params>);` with <ret>
+ * one of int, size_t, const char*; a by-value parameter is named and of type int, float, double, size_t, long long,
+ * int64_t, uint64_t or uint32_t; any parameter with a `*` is passed as an address.  Anything else (another scalar type, a
+ * by-value struct, a function pointer, a typedef, a multi-line macro) makes the binding refuse to load.
  */
 #ifndef MSLAM_HIP_H
 #define MSLAM_HIP_H

@@ -5,99 +5,88 @@ library is missing, or a tensor is not resident on a HIP device, the call raises
 """
 import ctypes
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MSLAM_LIB", os.path.join(_HERE, "libmslam_hip.so"))   # MSLAM_LIB: measurement builds (tools/probes)
 
-_c_int = ctypes.c_int
-_c_float = ctypes.c_float
-_c_vp = ctypes.c_void_p
-_c_i64 = ctypes.c_int64
-_c_double = ctypes.c_double
-_c_size = ctypes.c_size_t
+_HEADER_PATH = os.path.normpath(os.path.join(_HERE, "..", "include", "mslam_hip.h"))
 
-# name -> argtypes (restype is always int unless listed in _RESTYPES)
-_SIGNATURES = {
-    "mslam_abi_version": [],
-    "mslam_device_check": [],
-    "mslam_iter_proj": [_c_vp] * 5 + [_c_int] * 5 + [_c_float, _c_float, _c_vp],
-    "mslam_refine_matches": [_c_vp] * 4 + [_c_int] * 7 + [_c_vp],
-    "mslam_prep_iter_proj": [_c_vp] * 6 + [_c_int] * 3 + [_c_vp],
-    "mslam_match_occlusion": [_c_vp] * 5 + [_c_int] * 3 + [_c_float, _c_vp],
-    "mslam_pixel_to_lin": [_c_vp] * 2 + [_c_int] * 3 + [_c_vp],
-    "mslam_gauss_newton_rays": [_c_vp] * 8 + [_c_int] * 3 + [_c_float] * 4 + [_c_int, _c_float, _c_vp, _c_vp, _c_size, _c_vp],
-    "mslam_gauss_newton_calib": [_c_vp] * 9 + [_c_int] * 6 + [_c_float] * 5 + [_c_int, _c_float, _c_vp, _c_vp, _c_size, _c_vp],
-    "mslam_gauss_newton_points": [_c_vp] * 8 + [_c_int] * 3 + [_c_float] * 3 + [_c_int, _c_float, _c_vp, _c_vp, _c_size, _c_vp],
-    "mslam_gn_begin": [_c_vp] * 2 + [_c_int] * 3 + [_c_vp, _c_size, _c_vp],
-    "mslam_gn_compact": [_c_vp] * 5 + [_c_int] * 5 + [_c_float] * 2 + [_c_vp, _c_size, _c_vp],
-    "mslam_gn_compact_at": [_c_vp] * 5 + [_c_int] * 7 + [_c_float] * 2 + [_c_vp, _c_size, _c_vp],
-    "mslam_gn_accumulate": [_c_int] + [_c_vp] * 2 + [_c_int] * 5 + [_c_float] * 2 + [_c_int] * 3 + [_c_float] + [_c_vp] * 3 + [_c_size, _c_vp],
-    "mslam_gn_solve_retract": [_c_vp] * 2 + [_c_int] * 3 + [_c_vp, _c_vp, _c_float, _c_vp, _c_size, _c_vp],
-    "mslam_gn_status": [_c_vp] + [_c_int] * 3 + [_c_vp, _c_size, _c_vp],
-    "mslam_sim3_act": [_c_vp] * 3 + [_c_int, ctypes.c_longlong, _c_int, _c_vp],
-    "mslam_sim3_op": [_c_int] + [_c_vp] * 3 + [_c_int] * 3 + [_c_vp],
-    "mslam_mast3r_create": [_c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_vp],
-    "mslam_mast3r_destroy": [_c_vp],
-    "mslam_mast3r_encode": [_c_vp, _c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp, _c_size, _c_vp],
-    "mslam_mast3r_decode": [_c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int] + [_c_vp] * 10 + [_c_vp, _c_size, _c_vp],
-    "mslam_gemm_bf16": [_c_vp] * 5 + [_c_int] * 5 + [_c_vp],
-    "mslam_gemm_tile_override": [_c_int] * 4,
-    "mslam_gemm_profile_begin": [_c_int] * 4,
-    "mslam_gemm_profile_end": [_c_vp] * 3,
-    "mslam_conv2d_nhwc_bf16": [_c_vp] * 5 + [_c_int] * 9 + [_c_vp],
-    "mslam_attention_bf16": [_c_vp] * 4 + [_c_int] * 4 + [_c_vp],
-    "mslam_layernorm_f32": [_c_vp] * 5 + [_c_int, _c_int, _c_float, _c_vp],
-    "mslam_track_pose": [_c_int] + [_c_vp] * 6 + [_c_int, _c_vp, _c_int, _c_int] + [_c_float] * 3 + [_c_int, _c_float, _c_int, _c_int, _c_float, _c_float, _c_vp, _c_vp, _c_size, _c_vp],
-    "mslam_track_prepare": [_c_vp] * 5 + [_c_float, _c_vp, _c_float, _c_float, _c_float, _c_int] + [_c_vp] * 8 + [_c_size, _c_vp],
-    "mslam_track_verdict": [_c_vp, _c_vp, _c_int, _c_vp, _c_vp],
-    "mslam_track_fuse": [_c_vp] * 6 + [_c_int] + [_c_vp] * 4,
-    "mslam_tsdf_local_build": [_c_vp] * 5 + [_c_int] * 4 + [_c_double, _c_double, _c_float, _c_vp, _c_vp, _c_vp, _c_size, _c_vp],
-    "mslam_tsdf_local_raycast": [_c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_float, _c_vp, _c_vp, _c_vp],
-    "mslam_quality_reduce_grid": [_c_vp] * 3 + [_c_int] * 4 + [_c_double, _c_double, _c_vp, _c_vp],
-    "mslam_quality_classify": [_c_vp] * 3 + [_c_int] + [_c_float] * 3 + [_c_vp] * 3,
-    "mslam_tsdf_table_init": [_c_vp, _c_size, ctypes.c_uint64, _c_vp],
-    "mslam_tsdf_integrate": [_c_vp, ctypes.c_uint64, _c_vp, _c_vp, _c_vp, _c_int] + [_c_double] * 4 + [_c_int, _c_int, _c_vp, _c_size, _c_vp],
-    "mslam_room_pair": [_c_vp, _c_vp] + [_c_int] * 4 + [_c_double] * 5 + [_c_vp] * 10 + [_c_vp],
-    "mslam_remap_bilinear_u8": [_c_vp, _c_int, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_vp],
-    "mslam_gemm_f64": [_c_vp, _c_int, _c_vp, _c_int, _c_int, _c_vp, _c_vp, _c_vp, _c_int, _c_int, _c_int, _c_vp],
-    "mslam_asmk_aggregate": [_c_vp] * 5 + [_c_int] * 5 + [_c_vp],
-    "mslam_asmk_search": [_c_vp] * 3 + [_c_int] + [_c_vp] * 2 + [_c_int] * 2 + [_c_float] * 2 + [_c_vp, _c_vp],
-    "mslam_tsdf_rehash": [_c_vp, ctypes.c_uint64, _c_vp, ctypes.c_uint64, _c_vp],
-    "mslam_tsdf_header": [_c_vp, ctypes.c_uint64, _c_vp, _c_vp],
-    "mslam_tsdf_dump": [_c_vp, ctypes.c_uint64, _c_vp, _c_vp, _c_vp, ctypes.c_uint32, _c_vp],
-    "mslam_tsdf_query": [_c_vp, ctypes.c_uint64, _c_vp, _c_int, _c_double, _c_double, _c_vp, _c_vp, _c_vp, _c_vp],
-    "mslam_tsdf_lookup7": [_c_vp, ctypes.c_uint64, _c_vp, _c_int, _c_vp, _c_double, _c_vp, _c_vp],
-    "mslam_tsdf_query_lookup": [_c_vp, _c_int, _c_double, _c_double, _c_vp, _c_vp, _c_vp, _c_vp],
-    "mslam_tsdf_pose_step_lookup": [_c_vp, _c_vp, _c_vp, _c_int, _c_vp, _c_int] + [_c_double] * 4 + [_c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_size, _c_vp],
-    "mslam_tsdf_pose_step": [_c_vp, ctypes.c_uint64, _c_vp, _c_vp, _c_int, _c_vp, _c_int] + [_c_double] * 4 + [_c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_size, _c_vp],
-    "mslam_tsdf_mesh_keys": [_c_vp, ctypes.c_uint64, _c_double, _c_vp, _c_vp],
-    "mslam_tsdf_mesh_count": [_c_vp, ctypes.c_uint64, _c_double, _c_double] + [_c_vp] * 4 + [_c_size, _c_vp],
-    "mslam_tsdf_mesh_emit": [_c_vp, ctypes.c_uint64] + [_c_double] * 3 + [_c_vp] * 5 + [_c_size] + [_c_vp] * 3 + [_c_i64, _c_i64, _c_vp],
-    "mslam_tsdf_load": [_c_vp, ctypes.c_uint64, _c_vp, _c_vp, _c_vp, _c_int, _c_vp],
-    "mslam_tsdf_render_blocks": [_c_vp, ctypes.c_uint64, _c_double, _c_vp, _c_size, _c_vp],
-    "mslam_tsdf_render": [_c_vp, ctypes.c_uint64, _c_vp, _c_int, _c_int, _c_vp] + [_c_double] * 6 + [_c_int, _c_vp, _c_size] + [_c_vp] * 4,
+# by-value parameter types the header may use; any parameter with a `*` is passed as an address
+_SCALARS = {
+    "int": ctypes.c_int,
+    "float": ctypes.c_float,
+    "double": ctypes.c_double,
+    "size_t": ctypes.c_size_t,
+    "long long": ctypes.c_longlong,
+    "int64_t": ctypes.c_int64,
+    "uint64_t": ctypes.c_uint64,
+    "uint32_t": ctypes.c_uint32,
 }
-_RESTYPES = {
-    "mslam_last_error": ctypes.c_char_p,
-    "mslam_gn_workspace_bytes": ctypes.c_size_t,
-    "mslam_tsdf_table_bytes": ctypes.c_size_t,
-    "mslam_tsdf_local_workspace_bytes": ctypes.c_size_t,
-    "mslam_track_workspace_bytes": ctypes.c_size_t,
-    "mslam_track_prepare_workspace_bytes": ctypes.c_size_t,
-    "mslam_mast3r_workspace_bytes": ctypes.c_size_t,
-    "mslam_tsdf_integrate_workspace_bytes": ctypes.c_size_t,
-    "mslam_tsdf_mesh_workspace_bytes": ctypes.c_size_t,
-    "mslam_tsdf_render_workspace_bytes": ctypes.c_size_t,
-}
+_RETURNS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p}
 
-_lib = None
+
+def _argtype(fn: str, param: str):
+    if "*" in param and "(" not in param:   # any data pointer; a function pointer falls through and is refused
+        return ctypes.c_void_p
+    words = [w for w in param.split() if w != "const"]
+    ctype = _SCALARS.get(" ".join(words[:-1]))   # the last word is the parameter's name
+    if ctype is None or not re.fullmatch(r"\w+", words[-1]):   # `float v[3]` is a pointer in C: write it as one
+        raise ValueError(f"{fn}: unsupported parameter '{param}'")
+    return ctype
+
+
+def parse_header(text: str) -> dict:
+    """{name: (restype, [argtypes])} of every `<ret> mslam_<name>(<params>);` in the header text.
+
+    Anything outside the closed type maps above raises ValueError: a default would load, run and hand
+    the callee garbage."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{', ";", text).replace("}", ";")   # the header's only braces are the C++ guard's
+    out = {}
+    for stmt in text.split(";"):
+        stmt = " ".join(stmt.split())
+        if not stmt:
+            continue
+        m = re.fullmatch(r"([\w *]+?) ?\b(mslam_\w+) ?\((.*)\)", stmt)
+        if m is None:
+            raise ValueError(f"not a plain declaration of an mslam_ function: '{stmt}'")
+        ret, fn, params = m.group(1).replace(" *", "*"), m.group(2), m.group(3).strip()
+        restype = _RETURNS.get(ret)
+        if restype is None:
+            raise ValueError(f"{fn}: unsupported return type '{ret}'")
+        plist = [] if params in ("", "void") else [q.strip() for q in params.split(",")]
+        out[fn] = (restype, [_argtype(fn, q) for q in plist])
+    return out
+
+
+_signatures = None
+
+
+def _header_signatures() -> dict:
+    """parse_header() of include/mslam_hip.h, read once."""
+    global _signatures
+    if _signatures is None:
+        if not os.path.exists(_HEADER_PATH):
+            raise RuntimeError(
+                f"{_HEADER_PATH} not found: the binding reads every signature from the header that "
+                "libmslam_hip.so is built against. There is no hand-written copy to fall back to."
+            )
+        with open(_HEADER_PATH) as f:
+            _signatures = parse_header(f.read())
+    return _signatures
 
 
 def exported_symbols():
     """Every symbol include/mslam_hip.h declares (used by the CPU-side ABI test)."""
-    return sorted(list(_SIGNATURES) + list(_RESTYPES))
+    return sorted(_header_signatures())
+
+
+_lib = None
 
 
 def lib() -> ctypes.CDLL:
@@ -109,30 +98,10 @@ def lib() -> ctypes.CDLL:
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback for this path."
             )
         handle = ctypes.CDLL(LIB_PATH)
-        for name, argtypes in _SIGNATURES.items():
+        for name, (restype, argtypes) in _header_signatures().items():
             fn = getattr(handle, name)
             fn.argtypes = argtypes
-            fn.restype = ctypes.c_int
-        handle.mslam_last_error.argtypes = []
-        handle.mslam_last_error.restype = ctypes.c_char_p
-        handle.mslam_gn_workspace_bytes.argtypes = [_c_int] * 4
-        handle.mslam_gn_workspace_bytes.restype = ctypes.c_size_t
-        handle.mslam_mast3r_workspace_bytes.argtypes = [_c_vp, _c_int, _c_int, _c_int]
-        handle.mslam_mast3r_workspace_bytes.restype = ctypes.c_size_t
-        handle.mslam_track_workspace_bytes.argtypes = [_c_int]
-        handle.mslam_track_workspace_bytes.restype = ctypes.c_size_t
-        handle.mslam_track_prepare_workspace_bytes.argtypes = [_c_int]
-        handle.mslam_track_prepare_workspace_bytes.restype = ctypes.c_size_t
-        handle.mslam_tsdf_local_workspace_bytes.argtypes = [_c_int]
-        handle.mslam_tsdf_local_workspace_bytes.restype = ctypes.c_size_t
-        handle.mslam_tsdf_table_bytes.argtypes = [ctypes.c_uint64]
-        handle.mslam_tsdf_table_bytes.restype = ctypes.c_size_t
-        handle.mslam_tsdf_integrate_workspace_bytes.argtypes = [_c_int, _c_double, _c_double, _c_double]
-        handle.mslam_tsdf_integrate_workspace_bytes.restype = ctypes.c_size_t
-        handle.mslam_tsdf_mesh_workspace_bytes.argtypes = [ctypes.c_uint64]
-        handle.mslam_tsdf_mesh_workspace_bytes.restype = ctypes.c_size_t
-        handle.mslam_tsdf_render_workspace_bytes.argtypes = [ctypes.c_uint64]
-        handle.mslam_tsdf_render_workspace_bytes.restype = ctypes.c_size_t
+            fn.restype = restype
         _lib = handle
     return _lib
 
