@@ -272,8 +272,38 @@ int mslam_tsdf_render(void* table, uint64_t capacity, const float* rays, int h, 
                       const void* workspace, size_t workspace_bytes, float* range, float* normal, uint8_t* hit,
                       void* stream);
 
+/* Colour of the volume (no counterpart in the reference, DESIGN.md "Colour").  `color` is a second caller-owned device
+ * buffer of mslam_tsdf_color_bytes(capacity) bytes, addressed by the slot index of `table`: four u64 words per slot,
+ * sum_w (units of 2^-20), sum_w * r8, sum_w * g8, sum_w * b8 with 8-bit colours.  The sums are integers: the fused
+ * colour is bit-identical for any order of arrival, capacity and shard count.
+ *   mslam_tsdf_integrate_color  after mslam_tsdf_integrate of the same points (so the voxels exist): walks the same
+ *                               samples with the same weights, rgb f32[n,3] in [0,1]; a sample whose voxel is not in
+ *                               this table is skipped.  The table is only read.
+ *   mslam_tsdf_color_rehash     after mslam_tsdf_rehash: every old slot finds its key in the new table and moves its words.
+ *   mslam_tsdf_color_dump       sums u64[n,4] of the voxels keys i64[n,3] (zeros for a voxel that is not in the table).
+ *   mslam_tsdf_color_load       counterpart of mslam_tsdf_load (call it after that): stores sums u64[n,4] at keys i64[n,3].
+ *   mslam_tsdf_color_sample     trilinear colour at world points f32[n,3] on the lattice of the mesh and the views
+ *                               (g = p / vs - 0.5, corner c = dx + 2 dy + 4 dz, a + f (b - a) along x, y, z in f64); a
+ *                               corner without colour contributes the default colour; out_rgb f32[n,3], out_count
+ *                               u8[n] = coloured corners.  image_w > 0: the points are image rows of image_w pixels
+ *                               (shapes the 8x8-pixel wave tiles only), 0: a plain list. */
+size_t mslam_tsdf_color_bytes(uint64_t capacity);
+int mslam_tsdf_color_init(void* color, size_t color_bytes, uint64_t capacity, void* stream);
+int mslam_tsdf_integrate_color(void* table, uint64_t capacity, void* color, const float* points_world,
+                               const double* conf, const float* rgb, const float* cam_origin, int n_points,
+                               double voxel_size, double trunc, double step_scale, void* stream);
+int mslam_tsdf_color_rehash(void* old_table, uint64_t old_capacity, const void* old_color, void* new_table,
+                            uint64_t new_capacity, void* new_color, void* stream);
+int mslam_tsdf_color_dump(void* table, uint64_t capacity, const void* color, const int64_t* keys, int n, uint64_t* sums,
+                          void* stream);
+int mslam_tsdf_color_load(void* table, uint64_t capacity, void* color, const int64_t* keys, const uint64_t* sums, int n,
+                          void* stream);
+int mslam_tsdf_color_sample(void* table, uint64_t capacity, const void* color, const float* points, int n, int image_w,
+                            double voxel_size, double default_r, double default_g, double default_b, float* out_rgb,
+                            uint8_t* out_count, void* stream);
+
 /* ------------------------------------------------------------------------------------------
- * MASt3R two-view forward.  Replaces the three model methods the SLAM front/back-end call
+ * MASt3R two-view forward. Replaces the three model methods the SLAM front/back-end call
  * (mast3r_slam/mast3r_utils.py:34-40,57-64,74): model._encode_image, model._decoder,
  * model._downstream_head (thirdparty/mast3r/dust3r/dust3r/model.py:127-139,171-196;
  * mast3r/catmlp_dpt_head.py:71-96).  bf16 MFMA operands, fp32 accumulate / residual / softmax.

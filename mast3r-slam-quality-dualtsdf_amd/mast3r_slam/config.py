@@ -37,6 +37,7 @@ _BASE = {
         "enabled": False, "voxel_size": 0.03, "trunc_dist": 0.12, "max_weight": 100.0,
         "min_tsdf_weight": 1.0e-3, "max_points_per_kf": 40000, "min_confidence": 0.05,
         "samples_per_kf": 2000, "lambda": 0.15, "max_iterations": 3, "pre_icp_iters": 2, "damping": 1.0e-4,
+        "color": False,     # fuse the keyframes' uimg into the volume: coloured meshes and views (DESIGN.md "Colour")
     },
 }
 

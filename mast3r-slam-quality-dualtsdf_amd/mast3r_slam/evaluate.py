@@ -103,9 +103,10 @@ def save_ply(filename, points, colors):
     _write_ply(filename, pcd)
 
 
-def save_mesh(filename, vertices, faces, normals=None):
-    """Triangle mesh as binary little-endian PLY: `element vertex` (x, y, z [, nx, ny, nz] float) and `element face`
-    (`property list uchar int vertex_indices`).  Arrays may be numpy or device tensors."""
+def save_mesh(filename, vertices, faces, normals=None, colors=None):
+    """Triangle mesh as binary little-endian PLY: `element vertex` (x, y, z [, nx, ny, nz] float [, red, green, blue]
+    uchar = rint(255 c) of `colors` in [0, 1]) and `element face` (`property list uchar int vertex_indices`).  Arrays may
+    be numpy or device tensors."""
     def host(a, dtype):
         a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
         return a.astype(dtype).reshape(-1, 3)
@@ -115,15 +116,24 @@ def save_mesh(filename, vertices, faces, normals=None):
     cols = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
     if normals is not None:
         cols += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    n_float = len(cols)
+    if colors is not None:
+        cols += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
     vert = np.empty(len(v), dtype=cols)
     vert["x"], vert["y"], vert["z"] = v.T
     if normals is not None:
         n = host(normals, np.float32)
         vert["nx"], vert["ny"], vert["nz"] = n.T
+    if colors is not None:
+        c = np.clip(np.rint(255.0 * host(colors, np.float64)), 0, 255).astype(np.uint8)
+        if len(c) != len(v):
+            raise ValueError(f"save_mesh: {len(c)} colours for {len(v)} vertices")
+        vert["red"], vert["green"], vert["blue"] = c.T
     face = np.empty(len(f), dtype=[("n", "u1"), ("i", "<i4", (3,))])
     face["n"], face["i"] = 3, f
     header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}"]
-    header += [f"property float {name}" for name, _ in cols]
+    header += [f"property float {name}" for name, _ in cols[:n_float]]
+    header += [f"property uchar {name}" for name, _ in cols[n_float:]]
     header += [f"element face {len(f)}", "property list uchar int vertex_indices", "end_header"]
     with open(filename, "wb") as fh:
         fh.write(("\n".join(header) + "\n").encode("ascii"))
@@ -131,14 +141,39 @@ def save_mesh(filename, vertices, faces, normals=None):
         fh.write(face.tobytes())
 
 
-def save_tsdf_mesh(savedir, filename, source, min_weight=None, level=0.0):
+def save_tsdf_mesh(savedir, filename, source, min_weight=None, level=0.0, colors=False):
     """The global TSDF's triangle mesh (marching cubes) as PLY with normals, beside save_reconstruction's point cloud.
-    `source`: a SlamSystem, a TSDFGlobalManager or a TSDFVolume.  Returns (V, F)."""
+    `source`: a SlamSystem, a TSDFGlobalManager or a TSDFVolume.  `colors=True` (a volume with tsdf_global.color): the
+    vertices carry the fused colour as red / green / blue.  Returns (V, F)."""
     savedir = pathlib.Path(savedir)
     savedir.mkdir(exist_ok=True, parents=True)
-    v, n, f = source.extract_mesh(min_weight=min_weight, level=level)
-    save_mesh(savedir / filename, v, f, normals=n)
+    if colors:
+        v, n, f, c = source.extract_mesh(min_weight=min_weight, level=level, colors=True)
+        save_mesh(savedir / filename, v, f, normals=n, colors=c)
+    else:
+        v, n, f = source.extract_mesh(min_weight=min_weight, level=level)
+        save_mesh(savedir / filename, v, f, normals=n)
     return int(v.shape[0]), int(f.shape[0])
+
+
+def save_color_view(savedir, filename, rgb, hit):
+    """A rendered colour view (TSDFVolume.render(colors=True)[3], in [0, 1]) as 8-bit RGB PNG, rint(255 c), black on a
+    miss.  Arrays may be numpy or device tensors.  Returns the path."""
+    from PIL import Image
+
+    def host(a):
+        return a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+
+    savedir = pathlib.Path(savedir)
+    savedir.mkdir(exist_ok=True, parents=True)
+    m = host(hit).astype(bool)
+    c = host(rgb).astype(np.float64)
+    if c.shape != m.shape + (3,):
+        raise ValueError(f"save_color_view: rgb {c.shape} does not match hit {m.shape}")
+    img = np.where(m[..., None], np.clip(np.rint(255.0 * c), 0, 255), 0).astype(np.uint8)
+    path = savedir / filename
+    Image.fromarray(img).save(path)
+    return path
 
 
 def save_depth_view(savedir, filename, range_or_depth, normals, hit, pose=None):

@@ -355,18 +355,19 @@ class SlamSystem:
             with self._critical("main"):
                 self._apply_commits(wait=True)
 
-    def extract_mesh(self, min_weight=None, level=0.0):
+    def extract_mesh(self, min_weight=None, level=0.0, colors=False, **kw):
         """Triangle mesh of the global TSDF at this point of the run: (vertices f32[V,3], normals f32[V,3], faces i32[F,3])
         device tensors (TSDFVolume.extract_mesh).  Drains the backend first, so every fusion it has issued is ordered
-        before the read."""
+        before the read.  `colors=True` (tsdf_global.color on): vertex colours f32[V,3] as a fourth tensor."""
         if self.tsdf_manager is None:
             raise RuntimeError("SlamSystem.extract_mesh: the global TSDF is disabled (tsdf_global.enabled = False)")
         self.drain()
-        return self.tsdf_manager.extract_mesh(min_weight=min_weight, level=level)
+        return self.tsdf_manager.extract_mesh(min_weight=min_weight, level=level, colors=colors, **kw)
 
     def render_view(self, pose=None, rays=None, K=None, hw=None, **kw):
         """Depth / normal view of the global TSDF at this point of the run: (range f32[h,w], normals f32[h,w,3],
-        hit bool[h,w]) device tensors (TSDFVolume.render; `kw`: near, far, min_weight, level, step, skip).  Drains the
+        hit bool[h,w]) device tensors (TSDFVolume.render; `kw`: near, far, min_weight, level, step, skip, and - with
+        tsdf_global.color on - colors=True for the colour image f32[h,w,3] as a fourth tensor).  Drains the
         backend first, like extract_mesh.  `pose=None`: the newest keyframe's pose.  Without `rays` and `K` the view uses
         the system's intrinsics when it is calibrated and otherwise the newest keyframe's canonical pointmap normalised
         to unit length - the ray model of an uncalibrated camera - so the view lies pixel for pixel over that keyframe."""

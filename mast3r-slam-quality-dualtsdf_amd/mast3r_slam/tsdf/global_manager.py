@@ -18,6 +18,21 @@ from lietorch_hip import Sim3
 from mast3r_slam.config import config
 
 
+def gather_uimg(uimg, choice, map_hw):
+    """Colours f32[n,3] of the pointmap pixels `choice` (linear indices, device) from the keyframe image `uimg`
+    ((h,w,3) f32 in [0, 1], host or device).  create_frame subsamples uimg when dataset.img_downsample > 1, so it can be
+    smaller than the pointmap: a pixel is then looked up through its row and column scaled to uimg's shape.  `map_hw`:
+    the pointmap's (H, W), python ints or a device tensor (no host read either way)."""
+    img = uimg.to(device=choice.device, dtype=torch.float32)
+    uh, uw = int(img.shape[0]), int(img.shape[1])
+    H, W = map_hw[0], map_hw[1]
+    row = torch.div(choice, W, rounding_mode="floor")
+    col = choice - row * W
+    ur = torch.div(row * uh, H, rounding_mode="floor").clamp(0, uh - 1)
+    uc = torch.div(col * uw, W, rounding_mode="floor").clamp(0, uw - 1)
+    return img.reshape(-1, 3)[ur * uw + uc].contiguous()
+
+
 class TSDFGlobalIntegrator:
     def __init__(self, volume, keyframes, cfg, optimizer):
         """global_manager.py:19-41."""
@@ -56,7 +71,9 @@ class TSDFGlobalIntegrator:
         self._process_dirty_queue()
 
     def snapshot(self, idx):
-        """The copies _integrate_single takes under the keyframes lock (global_manager.py:82-88): X, C, T_WC."""
+        """The copies _integrate_single takes under the keyframes lock (global_manager.py:82-88): X, C, T_WC - and, when
+        the volume fuses colour, the keyframe's image `uimg` (host, (H,W,3) f32 in [0, 1]) and the pointmap's (H, W)
+        (device) as further members."""
         if idx >= len(self.keyframes):
             return None
         frame = self.keyframes[idx]
@@ -64,7 +81,12 @@ class TSDFGlobalIntegrator:
             cur = torch.cuda.current_stream(frame.X_canon.device)   # below are still queued on this one
             for t in (frame.X_canon, frame.C, frame.T_WC.data):
                 t.record_stream(cur)
-        return (frame.X_canon.detach().clone(), frame.C.detach().clone(), frame.T_WC.data.clone())
+        snap = (frame.X_canon.detach().clone(), frame.C.detach().clone(), frame.T_WC.data.clone())
+        if self.volume.color:
+            if frame.uimg is None:
+                raise ValueError(f"tsdf_global.color: keyframe {idx} has no uimg to take colours from")
+            snap += (frame.uimg.detach().clone(), frame.img_true_shape.detach().reshape(-1)[:2].clone())
+        return snap
 
     def _integrate_single(self, idx):
         """global_manager.py:81-106: random subset (<= max_points_per_kf) of the points with C > min_confidence,
@@ -75,7 +97,7 @@ class TSDFGlobalIntegrator:
     def _integrate_snapshot(self, snap):
         if snap is None:
             return
-        X_canon, C, T_data = snap
+        X_canon, C, T_data = snap[:3]
         points = X_canon.reshape(-1, 3)
         conf = C.reshape(-1)
         valid_idx = torch.nonzero(conf > self.min_conf).view(-1)
@@ -86,7 +108,10 @@ class TSDFGlobalIntegrator:
         pose = Sim3(T_data)
         pts_world = pose.act(points[choice].contiguous())
         cam_origin = pose.act(torch.zeros(1, 3, device=points.device, dtype=points.dtype)).squeeze(0)
-        self.volume.integrate(pts_world, conf[choice].double(), cam_origin, return_fused=False)
+        colors = None
+        if len(snap) > 3:
+            colors = gather_uimg(snap[3], choice, snap[4])
+        self.volume.integrate(pts_world, conf[choice].double(), cam_origin, return_fused=False, colors=colors)
 
     def _integrate_new_keyframes(self):
         """global_manager.py:64-69."""
@@ -109,6 +134,10 @@ class TSDFGlobalManager:
         from .tsdf_optimizer import TSDFPoseOptimizer
 
         self.enabled = bool(cfg.get("enabled", False))
+        color = bool(cfg.get("color", False))
+        if color and channel is not None:
+            raise ValueError("TSDFGlobalManager: tsdf_global.color is not supported with a channel-driven voxel shard "
+                             "(the fuse op carries no colours); use one table or the SPMD form (shard_id / group)")
         self.keyframes = keyframes
         self.cfg = cfg
         self.volume = TSDFVolume(voxel_size=cfg.get("voxel_size", 0.03), truncation=cfg.get("trunc_dist", 0.12),
@@ -116,7 +145,7 @@ class TSDFGlobalManager:
                                  capacity=int(cfg.get("hash_capacity", 1 << 22)), device=device,
                                  shard_id=channel.rank if channel is not None else shard_id,
                                  num_shards=channel.world if channel is not None else num_shards, group=group,
-                                 channel=channel)
+                                 channel=channel, color=color)
         self.optimizer = TSDFPoseOptimizer(self.volume, keyframes, cfg, use_calib, device)
         self.integrator = TSDFGlobalIntegrator(self.volume, keyframes, cfg, self.optimizer)
         self.reintegrate_budget = int(cfg.get("sync_reintegrate_per_solve", 4))
@@ -139,14 +168,16 @@ class TSDFGlobalManager:
         if self.enabled:
             self.volume.maintain()   # samples dropped by the last solve are reported here
 
-    def extract_mesh(self, min_weight=None, level=0.0):
+    def extract_mesh(self, min_weight=None, level=0.0, colors=False, **kw):
         """Triangle mesh of the global volume: (vertices f32[V,3], normals f32[V,3], faces i32[F,3]) device tensors
-        (TSDFVolume.extract_mesh)."""
-        return self.volume.extract_mesh(min_weight=min_weight, level=level)
+        (TSDFVolume.extract_mesh); `colors=True`: vertex colours f32[V,3] as a fourth tensor."""
+        if not colors and not kw:
+            return self.volume.extract_mesh(min_weight=min_weight, level=level)
+        return self.volume.extract_mesh(min_weight=min_weight, level=level, colors=colors, **kw)
 
     def render(self, pose, rays=None, K=None, hw=None, **kw):
         """Depth / normal view of the global volume from `pose`: (range f32[h,w], normals f32[h,w,3], hit bool[h,w])
-        device tensors (TSDFVolume.render)."""
+        device tensors (TSDFVolume.render); `colors=True` in `kw`: the colour image f32[h,w,3] as a fourth tensor."""
         return self.volume.render(pose, rays=rays, K=K, hw=hw, **kw)
 
     def on_after_backend_solve(self, factor_graph):
@@ -195,7 +226,7 @@ class TSDFGlobalManager:
         todo = []
         for kind, i, snap in plan["todo"]:
             if snap is not None and i in row:
-                snap = (snap[0], snap[1], pose_data[row[i]].reshape(1, 8).clone())
+                snap = (snap[0], snap[1], pose_data[row[i]].reshape(1, 8).clone()) + tuple(snap[3:])
             todo.append((kind, i, snap))
         plan["todo"] = todo
 

@@ -32,7 +32,7 @@ def voxel_shard(keys, num_shards):
 
 class TSDFVolume:
     def __init__(self, voxel_size, truncation, max_weight=100.0, min_weight=1.0e-3, capacity=1 << 22,
-                 device="cuda", shard_id=0, num_shards=1, group=None, channel=None):
+                 device="cuda", shard_id=0, num_shards=1, group=None, channel=None, color=False):
         self.voxel_size = float(voxel_size)
         self.truncation = float(truncation)
         self.max_weight = float(max_weight)
@@ -54,6 +54,13 @@ class TSDFVolume:
         self._table = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         self._ws = None
         _m.check(L.mslam_tsdf_table_init(_m.ptr(self._table), nbytes, self.capacity, _m.stream_ptr()), "tsdf_table_init")
+        # Colour (DESIGN.md "Colour"): a second buffer addressed by the table's slot index, four integer sums per slot.
+        # Off: nothing is allocated and nothing below touches it.
+        self.color = bool(color)
+        if self.color and channel is not None:
+            raise ValueError("TSDFVolume: color=True is not supported with a channel-driven shard (the fuse op carries "
+                             "no colours); use the SPMD form (group=) or one table")
+        self._color = self._new_color(self.capacity) if self.color else None
 
     @property
     def _driver(self):
@@ -79,6 +86,13 @@ class TSDFVolume:
         if self._ws is None or self._ws.numel() < nbytes:
             self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
         return self._ws
+
+    def _new_color(self, capacity):
+        L = _m.lib()
+        nbytes = L.mslam_tsdf_color_bytes(capacity)
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        _m.check(L.mslam_tsdf_color_init(_m.ptr(buf), nbytes, capacity, _m.stream_ptr()), "tsdf_color_init")
+        return buf
 
     def _header(self):
         out = (np.zeros(8, np.uint32))
@@ -109,6 +123,11 @@ class TSDFVolume:
             _m.check(L.mslam_tsdf_table_init(_m.ptr(new), nbytes, new_cap, _m.stream_ptr()), "tsdf_table_init")
             _m.check(L.mslam_tsdf_rehash(_m.ptr(self._table), self.capacity, _m.ptr(new), new_cap, _m.stream_ptr()),
                      "tsdf_rehash")
+            if self.color:
+                new_color = self._new_color(new_cap)
+                _m.check(L.mslam_tsdf_color_rehash(_m.ptr(self._table), self.capacity, _m.ptr(self._color), _m.ptr(new),
+                                                   new_cap, _m.ptr(new_color), _m.stream_ptr()), "tsdf_color_rehash")
+                self._color = new_color
             self._table, self.capacity = new, new_cap
             h = self._header()
             if h[1]:
@@ -116,11 +135,21 @@ class TSDFVolume:
         return int(h[0]), self.capacity
 
     # ------------------------------------------------------------------
-    def integrate(self, points_world, confidences, cam_origin, step_scale=0.5, return_fused=True):
+    def integrate(self, points_world, confidences, cam_origin, step_scale=0.5, return_fused=True, colors=None):
         """global_volume.py:35-72.  Returns the number of fused points (needs one stream sync; pass
-        return_fused=False inside a pipeline to stay asynchronous)."""
+        return_fused=False inside a pipeline to stay asynchronous).  `colors` f32[n,3] in [0, 1] (needs color=True):
+        the points' colours are fused into the voxels the same samples touch, after the TSDF integrate and on the same
+        stream; the TSDF itself is the same with and without them."""
         pts = self._dev(points_world, torch.float32).reshape(-1, 3)
         n = pts.shape[0]
+        rgb = None
+        if colors is not None:
+            if not self.color:
+                raise ValueError("TSDFVolume.integrate: colors= needs a volume built with color=True")
+            rgb = self._dev(colors, torch.float32)
+            if rgb.dim() < 1 or rgb.shape[-1] != 3 or rgb.numel() != 3 * n:
+                raise ValueError(f"TSDFVolume.integrate: colors must be ({n},3), got {tuple(rgb.shape)}")
+            rgb = rgb.reshape(-1, 3)
         if n == 0:
             return 0
         conf = self._dev(confidences, torch.float64).reshape(-1)
@@ -140,6 +169,11 @@ class TSDFVolume:
             self.truncation, self.max_weight, float(step_scale), self.shard_id, self.num_shards, _m.ptr(ws),
             ws.numel(), _m.stream_ptr())
         _m.check(rc, "tsdf_integrate")
+        if rgb is not None:
+            rc = L.mslam_tsdf_integrate_color(_m.ptr(self._table), self.capacity, _m.ptr(self._color), _m.ptr(pts),
+                                              _m.ptr(conf), _m.ptr(rgb), _m.ptr(org), n, self.voxel_size,
+                                              self.truncation, float(step_scale), _m.stream_ptr())
+            _m.check(rc, "tsdf_integrate_color")
         if not return_fused:
             return None
         h = self._header()
@@ -225,16 +259,80 @@ class TSDFVolume:
         o = np.lexsort((keys[:, 2], keys[:, 1], keys[:, 0]))
         return keys[o], t[o], w[o]
 
+    def voxel_color_sums(self):
+        """(keys i64[n,3], sums u64[n,4]) in voxels()'s order: the integer colour sums (sum_w in units of 2^-20, sum_w *
+        r8, sum_w * g8, sum_w * b8) of every voxel.  Sharded + collective: the union over the shards, on every rank."""
+        if not self.color:
+            raise ValueError("TSDFVolume: this volume was built with color=False")
+        if self._collective:
+            import torch.distributed as dist
+
+            mine = self._local_color_sums()
+            parts = [None] * dist.get_world_size(self.group)
+            dist.all_gather_object(parts, mine, group=self.group)
+            keys = np.concatenate([p[0] for p in parts]); sums = np.concatenate([p[1] for p in parts])
+            o = np.lexsort((keys[:, 2], keys[:, 1], keys[:, 0]))
+            return keys[o], sums[o]
+        return self._local_color_sums()
+
+    def _local_color_sums(self):
+        keys = self._local_voxels()[0]
+        n = len(keys)
+        sums = torch.zeros((n, 4), dtype=torch.int64, device=self.device)     # the u64 words, bit for bit
+        k = self._dev(keys, torch.int64).reshape(-1, 3)
+        _m.check(_m.lib().mslam_tsdf_color_dump(_m.ptr(self._table), self.capacity, _m.ptr(self._color), _m.ptr(k), n,
+                                                _m.ptr(sums), _m.stream_ptr()), "tsdf_color_dump")
+        return keys, sums.cpu().numpy().view(np.uint64)
+
+    def voxel_colors(self):
+        """(keys i64[n,3], rgb f64[n,3] in [0, 1], sum_w u64[n]) in voxels()'s order: c = sum_wc / (255 sum_w), zero
+        where sum_w == 0 (a voxel that was loaded or fused without colours)."""
+        keys, sums = self.voxel_color_sums()
+        sw = sums[:, 0]
+        den = 255.0 * np.where(sw > 0, sw, 1).astype(np.float64)
+        return keys, sums[:, 1:].astype(np.float64) / den[:, None], sw
+
+    def sample_color(self, points, default_color=(0.5, 0.5, 0.5)):
+        """Trilinear colour at world points (...,3) -> (rgb f32[...,3], count u8[...]) device tensors, on the lattice of
+        the mesh and the views; a corner voxel without colour contributes `default_color`, `count` is the number of
+        coloured corners.  The table is only read.  Sharded volumes: the union of the shards is sampled (collective)."""
+        if not self.color:
+            raise ValueError("TSDFVolume.sample_color needs a volume built with color=True")
+        pts = self._dev(points, torch.float32)
+        if pts.dim() < 1 or pts.shape[-1] != 3:
+            raise ValueError(f"sample_color: points must be (...,3), got {tuple(pts.shape)}")
+        if self.num_shards > 1:
+            return self._union().sample_color(pts, default_color)
+        image_w = int(pts.shape[1]) if pts.dim() == 3 else 0
+        return _sample_color(self._table, self.capacity, self._color, pts, image_w, self.voxel_size, default_color)
+
+    def _union(self):
+        """A one-table copy of a sharded volume (with its colours), for the operations whose samples span owners."""
+        keys, t, w = self.voxels()
+        return _loaded(keys, t, w, self.voxel_size, self.min_weight, self.device,
+                       self.voxel_color_sums()[1] if self.color else None)
+
     # ------------------------------------------------------------------
-    def load_voxels(self, keys, tsdf, weight):
+    def load_voxels(self, keys, tsdf, weight, colors=None):
         """Inserts distinct voxels keys i64[n,3], tsdf f64[n], weight f64[n] as averaged voxels (a table that was built
-        elsewhere, e.g. the union of voxel shards).  Local to this table; raises when the table overflowed."""
+        elsewhere, e.g. the union of voxel shards).  Local to this table; raises when the table overflowed.  `colors`
+        u64[n,4] (needs color=True): the voxels' colour sums as voxel_color_sums() returns them."""
         k = self._dev(keys, torch.int64).reshape(-1, 3)
         t = self._dev(tsdf, torch.float64).reshape(-1)
         w = self._dev(weight, torch.float64).reshape(-1)
         n = k.shape[0]
         if t.shape[0] != n or w.shape[0] != n:
             raise ValueError("load_voxels: keys, tsdf and weight must have the same length")
+        c = None
+        if colors is not None:
+            if not self.color:
+                raise ValueError("TSDFVolume.load_voxels: colors= needs a volume built with color=True")
+            if isinstance(colors, np.ndarray):
+                colors = torch.from_numpy(np.ascontiguousarray(colors).view(np.int64) if colors.dtype == np.uint64
+                                          else np.ascontiguousarray(colors))
+            c = colors.to(device=self.device, dtype=torch.int64).contiguous()
+            if c.numel() != 4 * n:
+                raise ValueError(f"load_voxels: colors must be ({n},4), got {tuple(c.shape)}")
         if n == 0:
             return
         _m.check(_m.lib().mslam_tsdf_load(_m.ptr(self._table), self.capacity, _m.ptr(k), _m.ptr(t), _m.ptr(w), n,
@@ -243,21 +341,33 @@ class TSDFVolume:
         if h[1]:
             raise RuntimeError(f"TSDFVolume.load_voxels: table overflow (code {int(h[1])}, {n} voxels into "
                                f"{self.capacity} slots)")
+        if c is not None:
+            _m.check(_m.lib().mslam_tsdf_color_load(_m.ptr(self._table), self.capacity, _m.ptr(self._color), _m.ptr(k),
+                                                    _m.ptr(c), n, _m.stream_ptr()), "tsdf_color_load")
 
-    def extract_mesh(self, min_weight=None, level=0.0):
+    def extract_mesh(self, min_weight=None, level=0.0, colors=False, default_color=(0.5, 0.5, 0.5)):
         """Marching cubes over the fused volume -> (vertices f32[V,3], normals f32[V,3], faces i32[F,3]) device tensors in
         canonical order (DESIGN.md "Mesh extraction").  Corners are voxel centres with weight >= min_weight (default
         self.min_weight), inside = tsdf < level, normals point to free space, faces are counter-clockwise seen from
         there.  The table is only read.  One host read (the output sizes).  Sharded volumes: cubes span owners, so the
-        union of the shards (voxels(), collective) is meshed on every rank."""
+        union of the shards (voxels(), collective) is meshed on every rank.  `colors=True` (needs color=True): a fourth
+        tensor f32[V,3] in [0, 1], the colour sampled at each f32 vertex position (sample_color)."""
         mw = self.min_weight if min_weight is None else float(min_weight)
+        if colors and not self.color:
+            raise ValueError("TSDFVolume.extract_mesh: colors=True needs a volume built with color=True")
         if self.num_shards > 1:
+            if colors:
+                return self._union().extract_mesh(min_weight=mw, level=level, colors=True, default_color=default_color)
             keys, t, w = self.voxels()
             return mesh_from_voxels(keys, t, w, self.voxel_size, mw, level, device=self.device)
-        return _extract(self._table, self.capacity, self.voxel_size, mw, float(level), self.device)
+        mesh = _extract(self._table, self.capacity, self.voxel_size, mw, float(level), self.device)
+        if not colors:
+            return mesh
+        return mesh + (_sample_color(self._table, self.capacity, self._color, mesh[0], 0, self.voxel_size,
+                                     default_color)[0],)
 
     def render(self, pose, rays=None, K=None, hw=None, near=0.05, far=10.0, min_weight=None, level=0.0, step=None,
-               skip=True):
+               skip=True, colors=False, default_color=(0.5, 0.5, 0.5)):
         """Ray cast of the fused volume from a camera -> (range f32[h,w], normals f32[h,w,3], hit bool[h,w]) device
         tensors (DESIGN.md "View rendering").  `pose`: Sim3 (8,) [t, q, s], world from camera.  Either `rays` f32[h,w,3],
         unit, camera frame (the project's ray model for an uncalibrated camera), or a pinhole `K` (3,3) with `hw` =
@@ -266,15 +376,29 @@ class TSDFVolume:
         voxel) between `near` and `far`, world units; a hit is the first crossing from >= level to < level between two
         valid samples.  `skip=False` marches through empty space sample by sample (same output, for checks and timing).
         The table is only read.  Sharded volumes: samples span owners, so the union of the shards (voxels(), collective)
-        is rendered on every rank."""
+        is rendered on every rank.  `colors=True` (needs color=True): a fourth tensor f32[h,w,3] in [0, 1], the colour
+        sampled (sample_color) at the hit point recomputed from the f32 range output, o + (double)range * s * d; zero on
+        a miss.  The march does not change."""
         mw = self.min_weight if min_weight is None else float(min_weight)
+        if colors and not self.color:
+            raise ValueError("TSDFVolume.render: colors=True needs a volume built with color=True")
         pose, rays, step = _render_args(pose, rays, K, hw, near, far, step, self.voxel_size, self.device)
         if self.num_shards > 1:
+            if colors:
+                return self._union().render(pose, rays=rays, near=near, far=far, min_weight=mw, level=level, step=step,
+                                            skip=skip, colors=True, default_color=default_color)
             keys, t, w = self.voxels()
             return render_from_voxels(keys, t, w, self.voxel_size, mw, pose, rays, near=near, far=far, level=level,
                                       step=step, skip=skip, device=self.device)
-        return _render(self._table, self.capacity, self.voxel_size, mw, float(level), pose, rays, float(near),
+        view = _render(self._table, self.capacity, self.voxel_size, mw, float(level), pose, rays, float(near),
                        float(far), step, bool(skip), self.device)
+        if not colors:
+            return view
+        rng, _, hit = view
+        pts = hit_points(pose, rays, rng)
+        rgb = _sample_color(self._table, self.capacity, self._color, pts, int(pts.shape[1]), self.voxel_size,
+                            default_color)[0]
+        return view + (rgb * hit.unsqueeze(-1),)
 
     def stats(self):
         """global_volume.py:136-140."""
@@ -312,6 +436,37 @@ def _extract(table, capacity, voxel_size, min_weight, level, device):
                                     _m.ptr(order), _m.ptr(base[0]), _m.ptr(base[1]), _m.ptr(ws), wsb, _m.ptr(verts),
                                     _m.ptr(normals), _m.ptr(faces), V, F, stream), "tsdf_mesh_emit")
     return verts, normals, faces
+
+
+def _sample_color(table, capacity, color, pts, image_w, voxel_size, default_color):
+    dc = [float(x) for x in default_color]
+    if len(dc) != 3:
+        raise ValueError("default_color must hold 3 values")
+    shape = tuple(pts.shape[:-1])
+    pts = pts.reshape(-1, 3).contiguous()
+    n = pts.shape[0]
+    if n >= 1 << 31:
+        raise ValueError("sample_color: too many points")
+    rgb = torch.empty((n, 3), dtype=torch.float32, device=pts.device)
+    cnt = torch.empty(n, dtype=torch.uint8, device=pts.device)
+    _m.check(_m.lib().mslam_tsdf_color_sample(_m.ptr(table), capacity, _m.ptr(color), _m.ptr(pts), n, image_w,
+                                              float(voxel_size), dc[0], dc[1], dc[2], _m.ptr(rgb), _m.ptr(cnt),
+                                              _m.stream_ptr()), "tsdf_color_sample")
+    return rgb.reshape(shape + (3,)), cnt.reshape(shape)
+
+
+def hit_points(pose, rays, rng):
+    """World points f32[h,w,3] of a view's range image: o + (double)range * s * d in f64, d the ray directions as the
+    render kernel forms them (r + w u + q x u, u = 2 q x r, on the f32 pose and rays), rounded to f32 once."""
+    p = pose.double()
+    q, r = p[3:7], rays.double()
+    u0 = 2.0 * (q[1] * r[..., 2] - q[2] * r[..., 1])
+    u1 = 2.0 * (q[2] * r[..., 0] - q[0] * r[..., 2])
+    u2 = 2.0 * (q[0] * r[..., 1] - q[1] * r[..., 0])
+    d = torch.stack(((r[..., 0] + q[3] * u0) + (q[1] * u2 - q[2] * u1),
+                     (r[..., 1] + q[3] * u1) + (q[2] * u0 - q[0] * u2),
+                     (r[..., 2] + q[3] * u2) + (q[0] * u1 - q[1] * u0)), -1)
+    return (p[:3] + (rng.double() * p[7]).unsqueeze(-1) * d).float().contiguous()
 
 
 def pinhole_rays(K, hw, device="cuda"):
@@ -375,26 +530,31 @@ def _render(table, capacity, voxel_size, min_weight, level, pose, rays, near, fa
     return rng, nrm, hit.bool()
 
 
+def _loaded(keys, tsdf, weight, voxel_size, min_weight, device, colors=None):
+    """A temporary table of at least 2n slots that holds the given voxels (and their colour sums)."""
+    n = int(len(keys))
+    cap = 1024
+    while cap < 2 * n:
+        cap *= 2
+    vol = TSDFVolume(voxel_size, 1.0, min_weight=min_weight, capacity=cap, device=device, color=colors is not None)
+    vol.load_voxels(keys, tsdf, weight, colors=colors)
+    return vol
+
+
 def render_from_voxels(keys, tsdf, weight, voxel_size, min_weight, pose, rays, near=0.05, far=10.0, level=0.0,
-                       step=None, skip=True, device="cuda"):
+                       step=None, skip=True, device="cuda", colors=None, default_color=(0.5, 0.5, 0.5)):
     """View of a voxel set given as arrays (keys i64[n,3] distinct, tsdf f64[n], weight f64[n]; numpy or device): loads
-    a temporary table of at least 2n slots and renders from it (TSDFVolume.render semantics)."""
-    n = int(len(keys))
-    cap = 1024
-    while cap < 2 * n:
-        cap *= 2
-    vol = TSDFVolume(voxel_size, 1.0, min_weight=min_weight, capacity=cap, device=device)
-    vol.load_voxels(keys, tsdf, weight)
-    return vol.render(pose, rays=rays, near=near, far=far, min_weight=min_weight, level=level, step=step, skip=skip)
+    a temporary table of at least 2n slots and renders from it (TSDFVolume.render semantics).  `colors` u64[n,4]: the
+    voxels' colour sums (voxel_color_sums()); the view then carries the colour image as a fourth tensor."""
+    vol = _loaded(keys, tsdf, weight, voxel_size, min_weight, device, colors)
+    return vol.render(pose, rays=rays, near=near, far=far, min_weight=min_weight, level=level, step=step, skip=skip,
+                      colors=colors is not None, default_color=default_color)
 
 
-def mesh_from_voxels(keys, tsdf, weight, voxel_size, min_weight, level=0.0, device="cuda"):
+def mesh_from_voxels(keys, tsdf, weight, voxel_size, min_weight, level=0.0, device="cuda", colors=None,
+                     default_color=(0.5, 0.5, 0.5)):
     """Mesh of a voxel set given as arrays (keys i64[n,3] distinct, tsdf f64[n], weight f64[n]; numpy or device): loads
-    a temporary table of at least 2n slots and extracts from it (TSDFVolume.extract_mesh semantics)."""
-    n = int(len(keys))
-    cap = 1024
-    while cap < 2 * n:
-        cap *= 2
-    vol = TSDFVolume(voxel_size, 1.0, min_weight=min_weight, capacity=cap, device=device)
-    vol.load_voxels(keys, tsdf, weight)
-    return vol.extract_mesh(min_weight=min_weight, level=level)
+    a temporary table of at least 2n slots and extracts from it (TSDFVolume.extract_mesh semantics).  `colors`
+    u64[n,4]: the voxels' colour sums (voxel_color_sums()); the mesh then carries vertex colours as a fourth tensor."""
+    vol = _loaded(keys, tsdf, weight, voxel_size, min_weight, device, colors)
+    return vol.extract_mesh(min_weight=min_weight, level=level, colors=colors is not None, default_color=default_color)
