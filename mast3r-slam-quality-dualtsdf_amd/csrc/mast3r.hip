@@ -12,8 +12,6 @@
 // 24x32 token grid), DPT feature maps NHWC bf16.  The 1x1 out_conv of each fusion block is applied
 // BEFORE the bilinear x2 upsample (both are linear and commute; 4x fewer FLOPs).
 #include <stdlib.h>
-#include <map>
-#include <mutex>
 #include <vector>
 #include "common.h"
 #include "gemm.h"
@@ -68,104 +66,73 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const TIN* __restrict__ 
   }
 }
 
-// Vectorised form for D == NV * 256 (the 1024 / 768 wide streams of the real model): one wave per row,
-// 16-byte loads, gamma/beta fetched before the reductions so their latency overlaps them.
+// Shared body of the vectorised LayerNorms for D == NV * 256 (the 1024 / 768 wide streams of the real model): one
+// wave per row, 16-byte accesses, lane l holds float4 l + 64 * c of the row.
+typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
+
+// the row and its statistics
+template <int NV>
+__device__ __forceinline__ void ln_load_stats(const float* xrow, int lane, float4 (&v)[NV], float& mean, float& rstd,
+                                              float eps) {
+  constexpr int D = NV * 256;
+  const float4* xr = reinterpret_cast<const float4*>(xrow);
+#pragma unroll
+  for (int c = 0; c < NV; c++) v[c] = xr[lane + 64 * c];
+  float s = 0.0f;
+#pragma unroll
+  for (int c = 0; c < NV; c++) s += (v[c].x + v[c].y) + (v[c].z + v[c].w);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  mean = s / (float)D;
+  float q = 0.0f;
+#pragma unroll
+  for (int c = 0; c < NV; c++) {
+    const float dx = v[c].x - mean, dy = v[c].y - mean, dz = v[c].z - mean, dw = v[c].w - mean;
+    q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) q += __shfl_xor(q, off, 64);
+  rstd = rsqrtf(q / (float)D + eps);
+}
+
+__device__ __forceinline__ float4 ln_affine(const float4& v, float mean, float rstd, const float4& w, const float4& b) {
+  float4 y;
+  y.x = (v.x - mean) * rstd * w.x + b.x;
+  y.y = (v.y - mean) * rstd * w.y + b.y;
+  y.z = (v.z - mean) * rstd * w.z + b.z;
+  y.w = (v.w - mean) * rstd * w.w + b.w;
+  return y;
+}
+
+// float4 `idx` of a bf16 output row
+__device__ __forceinline__ void ln_store_bf16(bf16* out_row, int idx, const float4& y) {
+  bf16x4 o;
+  o[0] = (bf16)y.x; o[1] = (bf16)y.y; o[2] = (bf16)y.z; o[3] = (bf16)y.w;
+  reinterpret_cast<bf16x4*>(out_row)[idx] = o;
+}
+
+// gamma/beta are fetched before the reductions in program order, so the compiler may overlap their latency with them
 template <int NV>
 __global__ __launch_bounds__(256) void layernorm_vec_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                             const float* __restrict__ b, bf16* __restrict__ out_bf,
                                                             float* __restrict__ out_f, int rows, float eps) {
   constexpr int D = NV * 256;
-  typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= rows) return;
-  const float4* xr = reinterpret_cast<const float4*>(x + (size_t)row * D);
   float4 v[NV], wv[NV], bv[NV];
-#pragma unroll
-  for (int c = 0; c < NV; c++) v[c] = xr[lane + 64 * c];
+  float mean, rstd;
 #pragma unroll
   for (int c = 0; c < NV; c++) {
     wv[c] = reinterpret_cast<const float4*>(w)[lane + 64 * c];
     bv[c] = reinterpret_cast<const float4*>(b)[lane + 64 * c];
   }
-  float s = 0.0f;
-#pragma unroll
-  for (int c = 0; c < NV; c++) s += (v[c].x + v[c].y) + (v[c].z + v[c].w);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-  const float mean = s / (float)D;
-  float q = 0.0f;
+  ln_load_stats<NV>(x + (size_t)row * D, lane, v, mean, rstd, eps);
 #pragma unroll
   for (int c = 0; c < NV; c++) {
-    const float dx = v[c].x - mean, dy = v[c].y - mean, dz = v[c].z - mean, dw = v[c].w - mean;
-    q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) q += __shfl_xor(q, off, 64);
-  const float rstd = rsqrtf(q / (float)D + eps);
-#pragma unroll
-  for (int c = 0; c < NV; c++) {
-    float4 y;
-    y.x = (v[c].x - mean) * rstd * wv[c].x + bv[c].x;
-    y.y = (v[c].y - mean) * rstd * wv[c].y + bv[c].y;
-    y.z = (v[c].z - mean) * rstd * wv[c].z + bv[c].z;
-    y.w = (v[c].w - mean) * rstd * wv[c].w + bv[c].w;
-    if (out_bf) {
-      bf16x4 o;
-      o[0] = (bf16)y.x; o[1] = (bf16)y.y; o[2] = (bf16)y.z; o[3] = (bf16)y.w;
-      reinterpret_cast<bf16x4*>(out_bf + (size_t)row * D)[lane + 64 * c] = o;
-    }
+    const float4 y = ln_affine(v[c], mean, rstd, wv[c], bv[c]);
+    if (out_bf) ln_store_bf16(out_bf + (size_t)row * D, lane + 64 * c, y);
     if (out_f) reinterpret_cast<float4*>(out_f + (size_t)row * D)[lane + 64 * c] = y;
-  }
-}
-
-// Two LayerNorms of the SAME rows with different affine parameters (decoder: norm_y of one side and norm1
-// of the other both normalise the previous layer's tokens): statistics once, two bf16 outputs.
-template <int NV>
-__global__ __launch_bounds__(256) void layernorm_dual_vec_kernel(const float* __restrict__ x, const float* __restrict__ w1,
-                                                                 const float* __restrict__ b1, bf16* __restrict__ out1,
-                                                                 const float* __restrict__ w2, const float* __restrict__ b2,
-                                                                 bf16* __restrict__ out2, int rows, float eps) {
-  constexpr int D = NV * 256;
-  typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  if (row >= rows) return;
-  const float4* xr = reinterpret_cast<const float4*>(x + (size_t)row * D);
-  float4 v[NV];
-#pragma unroll
-  for (int c = 0; c < NV; c++) v[c] = xr[lane + 64 * c];
-  float s = 0.0f;
-#pragma unroll
-  for (int c = 0; c < NV; c++) s += (v[c].x + v[c].y) + (v[c].z + v[c].w);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-  const float mean = s / (float)D;
-  float q = 0.0f;
-#pragma unroll
-  for (int c = 0; c < NV; c++) {
-    const float dx = v[c].x - mean, dy = v[c].y - mean, dz = v[c].z - mean, dw = v[c].w - mean;
-    q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) q += __shfl_xor(q, off, 64);
-  const float rstd = rsqrtf(q / (float)D + eps);
-#pragma unroll
-  for (int k = 0; k < 2; k++) {
-    const float* w = k ? w2 : w1;
-    const float* b = k ? b2 : b1;
-    bf16* out = k ? out2 : out1;
-#pragma unroll
-    for (int c = 0; c < NV; c++) {
-      const float4 wv = reinterpret_cast<const float4*>(w)[lane + 64 * c];
-      const float4 bv = reinterpret_cast<const float4*>(b)[lane + 64 * c];
-      bf16x4 o;
-      o[0] = (bf16)((v[c].x - mean) * rstd * wv.x + bv.x);
-      o[1] = (bf16)((v[c].y - mean) * rstd * wv.y + bv.y);
-      o[2] = (bf16)((v[c].z - mean) * rstd * wv.z + bv.z);
-      o[3] = (bf16)((v[c].w - mean) * rstd * wv.w + bv.w);
-      reinterpret_cast<bf16x4*>(out + (size_t)row * D)[lane + 64 * c] = o;
-    }
   }
 }
 
@@ -179,30 +146,13 @@ __global__ __launch_bounds__(256) void layernorm_group_vec_kernel(const float* _
                                                                   LnSet mem0, LnSet mem1, bf16* __restrict__ out_self,
                                                                   bf16* __restrict__ out_mem, int M, float eps) {
   constexpr int D = NV * 256;
-  typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= 2 * M) return;
   const int side = row >= M;
-  const float4* xr = reinterpret_cast<const float4*>(x + (size_t)row * D);
   float4 v[NV];
-#pragma unroll
-  for (int c = 0; c < NV; c++) v[c] = xr[lane + 64 * c];
-  float s = 0.0f;
-#pragma unroll
-  for (int c = 0; c < NV; c++) s += (v[c].x + v[c].y) + (v[c].z + v[c].w);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-  const float mean = s / (float)D;
-  float q = 0.0f;
-#pragma unroll
-  for (int c = 0; c < NV; c++) {
-    const float dx = v[c].x - mean, dy = v[c].y - mean, dz = v[c].z - mean, dw = v[c].w - mean;
-    q += (dx * dx + dy * dy) + (dz * dz + dw * dw);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) q += __shfl_xor(q, off, 64);
-  const float rstd = rsqrtf(q / (float)D + eps);
+  float mean, rstd;
+  ln_load_stats<NV>(x + (size_t)row * D, lane, v, mean, rstd, eps);
 #pragma unroll
   for (int k = 0; k < (CROSS ? 2 : 1); k++) {
     // k = 0: this side's own norm, same row; k = 1: the other side's norm_y, written to the other side's memory block
@@ -212,12 +162,7 @@ __global__ __launch_bounds__(256) void layernorm_group_vec_kernel(const float* _
     for (int c = 0; c < NV; c++) {
       const float4 wv = reinterpret_cast<const float4*>(ps.w)[lane + 64 * c];
       const float4 bv = reinterpret_cast<const float4*>(ps.b)[lane + 64 * c];
-      bf16x4 o;
-      o[0] = (bf16)((v[c].x - mean) * rstd * wv.x + bv.x);
-      o[1] = (bf16)((v[c].y - mean) * rstd * wv.y + bv.y);
-      o[2] = (bf16)((v[c].z - mean) * rstd * wv.z + bv.z);
-      o[3] = (bf16)((v[c].w - mean) * rstd * wv.w + bv.w);
-      reinterpret_cast<bf16x4*>(out)[lane + 64 * c] = o;
+      ln_store_bf16(out, lane + 64 * c, ln_affine(v[c], mean, rstd, wv, bv));
     }
   }
 }
@@ -234,7 +179,6 @@ __global__ void cast_f32_bf16_kernel(const float* __restrict__ x, bf16* __restri
   const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   if (i + 3 < n) {
     const float4 v = *reinterpret_cast<const float4*>(x + i);
-    typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
     bf16x4 o;
     o[0] = (bf16)v.x; o[1] = (bf16)v.y; o[2] = (bf16)v.z; o[3] = (bf16)v.w;
     *reinterpret_cast<bf16x4*>(y + i) = o;
@@ -449,46 +393,8 @@ struct Mast3rModel {
   float* rope_sin = nullptr;
   int rope_len = 0;
   int hooks[4];
-  // Second queue of a decode call (decoder side 2 / head 2 run beside side 1 / head 1) with its fork/join
-  // events.  One per CALLER stream, created on first use: decode calls issued on different streams (the
-  // frontend and the backend of the SLAM system run concurrently) never share a queue or an event.
-  struct Fork {
-    hipStream_t side = nullptr;
-    std::vector<hipEvent_t> events;
-    size_t ev_next = 0;
-  };
   unsigned* pf_sink = nullptr;           // 4 scratch bytes behind the RoPE tables (gemm.h: pf_sink)
   bool prefetch = true;                  // MSLAM_PREFETCH=0: no weight prefetch blocks
-  // The two heads (and, when the decoder is not grouped, its two sides) of a decode call on two queues.  Pays with the
-  // call ALONE on the chip (round 1: 7.3 vs 9.5 ms for four frames); inside the loop the other streams fill the chip and
-  // one queue measures +4 % frames/s at 60-120 keyframes, neutral at 64 (profiles/r03_decoder_grouping_ab.log): off by
-  // default since round 3 (MSLAM_TWO_STREAMS=1 turns it on; results do not depend on it)
-  bool two_streams = false;
-  int fork_max_rows = 1 << 30;           // MSLAM_FORK_MAX_M: calls with more token rows per side stay on one queue
-  bool dec_grouped = true;               // both decoder sides per launch (MSLAM_DEC_GROUPED=0: one queue per side)
-  // ... up to this many token rows per side (MSLAM_GROUP_MAX_M), two queues above.  Round 1 / 2 measured the switch-over
-  // at 1 024 rows with the stage ALONE on the chip (two queues hide each other's launch bubbles: 7.3 vs 7.8 ms for a decode
-  // of four frames); inside the loop, where the other streams keep the chip busy anyway, what counts is the work a launch
-  // costs, and one launch over both sides does the same FLOP in ~20 % less GEMM time (6144x768x768 16 us against
-  // 2 x 10 us, ...): always grouped measures +4-5 % frames/s end to end (profiles/r03_decoder_grouping_ab.log)
-  int group_max_rows = 1 << 30;
-  mutable std::mutex fork_mu;
-  mutable std::map<hipStream_t, Fork*> forks;
-  Fork* fork_for(hipStream_t caller, int& rc) const {
-    std::lock_guard<std::mutex> lock(fork_mu);
-    auto it = forks.find(caller);
-    if (it != forks.end()) return it->second;
-    Fork* f = new Fork();
-    rc = check_hip(hipStreamCreateWithFlags(&f->side, hipStreamNonBlocking), "side stream");
-    for (int k = 0; k < 64 && !rc; k++) {
-      hipEvent_t ev;
-      rc = check_hip(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "event");
-      if (!rc) f->events.push_back(ev);
-    }
-    if (rc) { delete f; return nullptr; }
-    forks[caller] = f;
-    return f;
-  }
 };
 
 struct PtrFeed {
@@ -521,10 +427,12 @@ struct PtrFeed {
 // bump allocator over the caller's workspace; in dry mode only measures
 struct Arena {
   char* base; size_t off = 0, cap; bool dry; bool overflow = false;
+  size_t peak = 0;   // high-water mark of off: callers may rewind off to reuse a region
   template <typename T> T* get(size_t n) {
     const size_t bytes = (n * sizeof(T) + 255) / 256 * 256;
     T* p = dry ? nullptr : reinterpret_cast<T*>(base + off);
     off += bytes;
+    if (off > peak) peak = off;
     if (!dry && off > cap) { overflow = true; return reinterpret_cast<T*>(base); }
     return p;
   }
@@ -535,8 +443,6 @@ struct Ctx {
   Arena ar;
   hipStream_t s;
   int rc = MSLAM_OK;
-  Mast3rModel::Fork* fk = nullptr;
-  int side = 0;   // which queue of the call c.s currently is
   bool dry() const { return ar.dry; }
   void fail(int r) { if (rc == MSLAM_OK) rc = r; }
 };
@@ -574,24 +480,16 @@ static GemmArgs dense_args(const bf16* A, int M, const Lin& l) {
   return g;
 }
 
+// Both sides of a decoder layer in ONE launch: side 1 has its own matrix and bias and lives a_gstride elements /
+// out_gbytes bytes behind side 0 in A / the output.
+static void group2(GemmArgs& g, const Lin& l1, size_t a_gstride, size_t out_gbytes) {
+  g.groups = 2; g.W1 = l1.W; g.bias1 = l1.b; g.a_gstride = a_gstride; g.out_gbytes = out_gbytes;
+}
+
 static void layernorm(Ctx& c, const float* x, const Norm& n, int rows, bf16* out_bf, float* out_f) {
   if (c.dry() || c.rc) return;
   launch_layernorm(x, n.w, n.b, out_bf, out_f, rows, n.d, 1e-6f, c.s);
   dbg(c, "layernorm", rows, n.d);
-}
-
-static void layernorm2(Ctx& c, const float* x, const Norm& n1, bf16* out1, const Norm& n2, bf16* out2, int rows) {
-  if (c.dry() || c.rc) return;
-  const dim3 grid((rows + 3) / 4), block(256);
-  if (n1.d == 768 && n2.d == 768)
-    hipLaunchKernelGGL(layernorm_dual_vec_kernel<3>, grid, block, 0, c.s, x, n1.w, n1.b, out1, n2.w, n2.b, out2, rows, 1e-6f);
-  else if (n1.d == 1024 && n2.d == 1024)
-    hipLaunchKernelGGL(layernorm_dual_vec_kernel<4>, grid, block, 0, c.s, x, n1.w, n1.b, out1, n2.w, n2.b, out2, rows, 1e-6f);
-  else {
-    launch_layernorm(x, n1.w, n1.b, out1, nullptr, rows, n1.d, 1e-6f, c.s);
-    launch_layernorm(x, n2.w, n2.b, out2, nullptr, rows, n2.d, 1e-6f, c.s);
-  }
-  dbg(c, "layernorm2", rows, n1.d);
 }
 
 static void cast_bf16(Ctx& c, const float* x, bf16* y, size_t n) {
@@ -602,13 +500,19 @@ static void cast_bf16(Ctx& c, const float* x, bf16* y, size_t n) {
 
 struct AttnBufs { bf16 *q, *k, *vt, *o; };
 
+// Attention projection with the RoPE / head-split epilogue.  With l1 (decoder): both sides in one launch, side 1 at
+// rows [M, 2M) of A and behind side 0's M / ntok images in q/k/vt.
 static void attn_project(Ctx& c, const bf16* A, int M, const Lin& l, int sec_base, int heads, int ntok, int kv_ntok,
-                         int tok_w, const AttnBufs& ab, const Pf& pf = Pf()) {
+                         int tok_w, const AttnBufs& ab, const Pf& pf = Pf(), const Lin* l1 = nullptr) {
   GemmArgs g = dense_args(A, M, l);
   set_pf(c, g, pf);
   g.epi = EPI_ATTN; g.sec_base = sec_base; g.sec_dim = heads * 64; g.heads = heads; g.ntok = ntok; g.kv_ntok = kv_ntok;
   g.tok_w = tok_w; g.q_out = ab.q; g.k_out = ab.k; g.vt_out = ab.vt; g.rope_cos = c.m->rope_cos;
   g.rope_sin = c.m->rope_sin; g.q_scale = 0.125f;  // head_dim 64 ** -0.5
+  if (l1) {
+    group2(g, *l1, (size_t)M * l.in, 0);
+    g.qkv_gstride = (size_t)(M / ntok) * heads * 64 * (sec_base == 0 ? ntok : kv_ntok);
+  }
   run_gemm(c, g);
 }
 
@@ -619,17 +523,24 @@ static void attention(Ctx& c, const AttnBufs& ab, int B, int heads, int nq, int 
 }
 
 // x (f32 residual stream, [M,D]) += Linear(A) (+bias)
-static void linear_residual(Ctx& c, const bf16* A, int M, const Lin& l, float* x, const Pf& pf = Pf()) {
+static void linear_residual(Ctx& c, const bf16* A, int M, const Lin& l, float* x, const Pf& pf = Pf(),
+                            const Lin* l1 = nullptr) {
   GemmArgs g = dense_args(A, M, l);
   set_pf(c, g, pf);
   g.res1 = x; g.res1_kind = KIND_F32; g.out = x; g.out_kind = KIND_F32;
+  if (l1) {
+    group2(g, *l1, (size_t)M * l.in, (size_t)M * l.out * sizeof(float));
+    g.res1_gbytes = g.out_gbytes;
+  }
   run_gemm(c, g);
 }
 
-static void linear_bf16(Ctx& c, const bf16* A, int M, const Lin& l, bf16* out, int act, const Pf& pf = Pf()) {
+static void linear_bf16(Ctx& c, const bf16* A, int M, const Lin& l, bf16* out, int act, const Pf& pf = Pf(),
+                        const Lin* l1 = nullptr) {
   GemmArgs g = dense_args(A, M, l);
   set_pf(c, g, pf);
   g.out = out; g.out_kind = KIND_BF16; g.act = act;
+  if (l1) group2(g, *l1, (size_t)M * l.in, (size_t)M * l.out * sizeof(bf16));
   run_gemm(c, g);
 }
 
@@ -803,37 +714,8 @@ static void run_head(Ctx& c, const Head& hd, const bf16* const toks[4], int B, i
   }
 }
 
-static void dec_block(Ctx& c, const DecBlock& b, const DecBlock* nb, float* x, const bf16* yn, int B, int N, int Nk, int nw,
-                      int nw_k, BlockScratch& s) {
-  const Mast3rModel& m = *c.m;
-  const int M = B * N, Mk = B * Nk;
-  // s.h already holds norm1(x): computed together with the other side's norm_y (layernorm2 in decode())
-  attn_project(c, s.h, M, b.qkv, 0, m.dec_heads, N, N, nw, s.ab, Pf{nb ? &nb->qkv : nullptr});
-  attention(c, s.ab, B, m.dec_heads, N, N);
-  linear_residual(c, s.ab.o, M, b.proj, x, Pf{nb ? &nb->proj : nullptr});
-  layernorm(c, x, b.n2, M, s.h, nullptr);
-  attn_project(c, s.h, M, b.pq, 0, m.dec_heads, N, Nk, nw, s.ab, Pf{nb ? &nb->pq : nullptr});
-  attn_project(c, yn, Mk, b.pkv, 1, m.dec_heads, N, Nk, nw_k, s.ab, Pf{nb ? &nb->pkv : nullptr});   // [projk; projv] stacked
-  attention(c, s.ab, B, m.dec_heads, N, Nk);
-  linear_residual(c, s.ab.o, M, b.cproj, x, Pf{nb ? &nb->cproj : nullptr});
-  mlp_residual(c, x, M, b.n3, b.fc1, b.fc2, s, Pf{nb ? &nb->fc1 : nullptr}, Pf{nb ? &nb->fc2 : nullptr});
-}
-
-// feat1/feat2 f32 [B*N, E]; outputs for both sides; dec_last (optional) f32 [2][B*N, Dd]
-// fork/join between the caller's stream and the model's side stream (no-ops in the sizing pass)
-static void stream_wait(Ctx& c, hipStream_t waiter, hipStream_t on) {
-  if (c.dry() || c.rc) return;
-  hipEvent_t ev = c.fk->events[c.fk->ev_next++ % c.fk->events.size()];
-  c.fail(check_hip(hipEventRecord(ev, on), "hipEventRecord"));
-  c.fail(check_hip(hipStreamWaitEvent(waiter, ev, 0), "hipStreamWaitEvent"));
-}
-
 // ---- grouped decoder layers: both sides of a layer in ONE launch per operation --------------------
 // Activations of side s live at rows [s*M, (s+1)*M) of every buffer (x, h, u, q/k/vt/o, yn).
-static void group2(GemmArgs& g, const Lin& l1, size_t a_gstride, size_t out_gbytes) {
-  g.groups = 2; g.W1 = l1.W; g.bias1 = l1.b; g.a_gstride = a_gstride; g.out_gbytes = out_gbytes;
-}
-
 static void g_layernorm(Ctx& c, const float* x, const Norm& n0, const Norm& n1, int M, bf16* out) {
   if (c.dry() || c.rc) return;
   const LnSet s0{n0.w, n0.b}, s1{n1.w, n1.b};
@@ -865,146 +747,62 @@ static void g_layernorm_cross(Ctx& c, const float* x, const DecBlock& b0, const 
   dbg(c, "g_layernorm_cross", M, D);
 }
 
-static void g_attn_project(Ctx& c, const bf16* A, int M, const Lin& l0, const Lin& l1, int sec_base, int heads, int B,
-                           int ntok, int kv_ntok, int tok_w, const AttnBufs& ab, const Pf& pf = Pf()) {
-  GemmArgs g = dense_args(A, M, l0);
-  set_pf(c, g, pf);
-  g.epi = EPI_ATTN; g.sec_base = sec_base; g.sec_dim = heads * 64; g.heads = heads; g.ntok = ntok; g.kv_ntok = kv_ntok;
-  g.tok_w = tok_w; g.q_out = ab.q; g.k_out = ab.k; g.vt_out = ab.vt; g.rope_cos = c.m->rope_cos;
-  g.rope_sin = c.m->rope_sin; g.q_scale = 0.125f;
-  group2(g, l1, (size_t)M * l0.in, 0);
-  g.qkv_gstride = (size_t)B * heads * 64 * (sec_base == 0 ? ntok : kv_ntok);
-  run_gemm(c, g);
-}
-
-static void g_linear_residual(Ctx& c, const bf16* A, int M, const Lin& l0, const Lin& l1, float* x, const Pf& pf = Pf()) {
-  GemmArgs g = dense_args(A, M, l0);
-  set_pf(c, g, pf);
-  g.res1 = x; g.res1_kind = KIND_F32; g.out = x; g.out_kind = KIND_F32;
-  group2(g, l1, (size_t)M * l0.in, (size_t)M * l0.out * sizeof(float));
-  g.res1_gbytes = g.out_gbytes;
-  run_gemm(c, g);
-}
-
-static void g_linear_bf16(Ctx& c, const bf16* A, int M, const Lin& l0, const Lin& l1, bf16* out, int act,
-                          const Pf& pf = Pf()) {
-  GemmArgs g = dense_args(A, M, l0);
-  set_pf(c, g, pf);
-  g.out = out; g.out_kind = KIND_BF16; g.act = act;
-  group2(g, l1, (size_t)M * l0.in, (size_t)M * l0.out * sizeof(bf16));
-  run_gemm(c, g);
-}
-
 // one decoder layer for both sides; x [2M, Dd] f32; scratch s sized for 2M rows
 static void dec_layer_grouped(Ctx& c, const DecBlock& b0, const DecBlock& b1, const DecBlock* n0, const DecBlock* n1,
                               float* x, bf16* yn, int B, int N, int nw, BlockScratch& s) {
   const Mast3rModel& m = *c.m;
   const int M = B * N;
-#define MSLAM_PF(field) (n0 ? Pf{&n0->field, &n1->field} : Pf{})   /* the next layer's matrices of both sides */
+  // each GEMM streams the next layer's matrices of both sides
+  const auto pf = [&](Lin DecBlock::*f) { return n0 ? Pf{&(n0->*f), &(n1->*f)} : Pf{}; };
   g_layernorm_cross(c, x, b0, b1, M, s.h, yn);
-  g_attn_project(c, s.h, M, b0.qkv, b1.qkv, 0, m.dec_heads, B, N, N, nw, s.ab, MSLAM_PF(qkv));
+  attn_project(c, s.h, M, b0.qkv, 0, m.dec_heads, N, N, nw, s.ab, pf(&DecBlock::qkv), &b1.qkv);
   attention(c, s.ab, 2 * B, m.dec_heads, N, N);
-  g_linear_residual(c, s.ab.o, M, b0.proj, b1.proj, x, MSLAM_PF(proj));
+  linear_residual(c, s.ab.o, M, b0.proj, x, pf(&DecBlock::proj), &b1.proj);
   g_layernorm(c, x, b0.n2, b1.n2, M, s.h);
-  g_attn_project(c, s.h, M, b0.pq, b1.pq, 0, m.dec_heads, B, N, N, nw, s.ab, MSLAM_PF(pq));
-  g_attn_project(c, yn, M, b0.pkv, b1.pkv, 1, m.dec_heads, B, N, N, nw, s.ab, MSLAM_PF(pkv));
+  attn_project(c, s.h, M, b0.pq, 0, m.dec_heads, N, N, nw, s.ab, pf(&DecBlock::pq), &b1.pq);
+  attn_project(c, yn, M, b0.pkv, 1, m.dec_heads, N, N, nw, s.ab, pf(&DecBlock::pkv), &b1.pkv);   // [projk; projv] stacked
   attention(c, s.ab, 2 * B, m.dec_heads, N, N);
-  g_linear_residual(c, s.ab.o, M, b0.cproj, b1.cproj, x, MSLAM_PF(cproj));
+  linear_residual(c, s.ab.o, M, b0.cproj, x, pf(&DecBlock::cproj), &b1.cproj);
   g_layernorm(c, x, b0.n3, b1.n3, M, s.h);
-  g_linear_bf16(c, s.h, M, b0.fc1, b1.fc1, s.u, ACT_GELU, MSLAM_PF(fc1));
-  g_linear_residual(c, s.u, M, b0.fc2, b1.fc2, x, MSLAM_PF(fc2));
-#undef MSLAM_PF
+  linear_bf16(c, s.h, M, b0.fc1, s.u, ACT_GELU, pf(&DecBlock::fc1), &b1.fc1);
+  linear_residual(c, s.u, M, b0.fc2, x, pf(&DecBlock::fc2), &b1.fc2);
 }
 
 // feat1/feat2 f32 [B*N, E]; outputs for both sides; dec_last (optional) f32 [2][B*N, Dd].
 // The two sides of a decoder layer are independent (both read the PREVIOUS layer's outputs,
-// dust3r/model.py:178-183) and at one image per side neither fills 256 CUs, so side 1 runs on the
-// caller's stream and side 2 on the model's side stream, joined once per layer; the two heads likewise.
+// dust3r/model.py:178-183), so every per-side buffer is one allocation with side s at rows [s*M, (s+1)*M) and each
+// operation of a layer is ONE launch over both.  Everything runs on the caller's stream, the two heads one after
+// the other in the same scratch.
 static void decode(Ctx& c, const float* feat1, const float* feat2, int B, int H, int W, const HeadOut out[2],
                    float* dec_last1, float* dec_last2) {
   const Mast3rModel& m = *c.m;
   const int nh = H / m.P, nw = W / m.P, N = nh * nw, M = B * N;
-  const float* feat[2] = {feat1, feat2};
   float* dec_last[2] = {dec_last1, dec_last2};
-  if (!c.dry() && m.two_streams && !c.rc && M <= m.fork_max_rows) {
-    int frc = MSLAM_OK;
-    c.fk = m.fork_for(c.s, frc);
-    c.fail(frc);
-  }
-  hipStream_t sA = c.s, sB = c.fk ? c.fk->side : c.s;
-  hipStream_t st[2] = {sA, sB};
-  // every per-side buffer is one allocation with side s at rows [s*M, (s+1)*M)
   const size_t ME = (size_t)M * m.E, MD = (size_t)M * m.Dd;
   bf16* fb_all = c.ar.get<bf16>(2 * ME);
   float* x_all = c.ar.get<float>(2 * MD);
   bf16* yn_all = c.ar.get<bf16>(2 * MD);
   bf16* tok_all[4] = {fb_all, c.ar.get<bf16>(2 * MD), c.ar.get<bf16>(2 * MD), c.ar.get<bf16>(2 * MD)};
   BlockScratch bs_all = block_scratch(c, 2 * M, m.Dd);
-  bf16* fb[2];
-  float* x[2];
-  bf16* yn[2];
-  bf16* tok[2][4];
-  BlockScratch bs[2];
-  for (int s = 0; s < 2; s++) {
-    fb[s] = c.dry() ? nullptr : fb_all + s * ME;
-    x[s] = c.dry() ? nullptr : x_all + s * MD;
-    yn[s] = c.dry() ? nullptr : yn_all + s * MD;
-    tok[s][0] = fb[s];
-    for (int k = 1; k < 4; k++) tok[s][k] = c.dry() ? nullptr : tok_all[k] + s * MD;
-    bs[s] = bs_all;
-    if (!c.dry()) {
-      bs[s].h += s * MD; bs[s].u += s * 4 * MD;
-      bs[s].ab.q += s * MD; bs[s].ab.k += s * MD; bs[s].ab.vt += s * MD; bs[s].ab.o += s * MD;
-    }
-  }
-  // grouping pays while one side alone does not fill the chip (measured: 3.42 -> 3.29 ms at one image per side,
-  // 7.7 -> 8.1 ms at four)
-  if (m.dec_grouped && M <= m.group_max_rows) {
-    // ---- both sides per launch, one queue (heads fork below) ----------------------------------------
-    cast_bf16(c, feat[0], fb[0], ME);
-    cast_bf16(c, feat[1], fb[1], ME);
-    linear_f32(c, fb_all, 2 * M, m.dec_embed, x_all);          // decoder_embed is shared by the two sides
-    for (int l = 0; l < m.dec_depth; l++) {
-      const bool more = l + 1 < m.dec_depth;
-      dec_layer_grouped(c, m.dec[0][l], m.dec[1][l], more ? &m.dec[0][l + 1] : nullptr, more ? &m.dec[1][l + 1] : nullptr,
-                        x_all, yn_all, B, N, nw, bs_all);
-      for (int k = 1; k < 3; k++)
-        if (l + 1 == m.hooks[k]) cast_bf16(c, x_all, tok_all[k], 2 * MD);
-    }
-    if (sB != sA) stream_wait(c, sB, sA);  // fork for the heads
-  } else {
-  if (sB != sA) stream_wait(c, sB, sA);  // fork: side stream starts after everything already queued
-  for (int s = 0; s < 2; s++) {
-    c.s = st[s]; c.side = s;
-    cast_bf16(c, feat[s], fb[s], (size_t)M * m.E);
-    linear_f32(c, fb[s], M, m.dec_embed, x[s]);
-  }
+  cast_bf16(c, feat1, fb_all, ME);
+  cast_bf16(c, feat2, c.dry() ? nullptr : fb_all + ME, ME);
+  linear_f32(c, fb_all, 2 * M, m.dec_embed, x_all);          // decoder_embed is shared by the two sides
   for (int l = 0; l < m.dec_depth; l++) {
-    c.s = sA; c.side = 0;
-    if (sB != sA) stream_wait(c, sA, sB);                     // x[1] of the previous layer is final
-    layernorm2(c, x[1], m.dec[0][l].ny, yn[0], m.dec[1][l].n1, bs[1].h, M);   // memory for side 1 = norm_y(f2); side 2's norm1
-    layernorm2(c, x[0], m.dec[1][l].ny, yn[1], m.dec[0][l].n1, bs[0].h, M);   // memory for side 2 = norm_y(f1); side 1's norm1
-    if (sB != sA) stream_wait(c, sB, sA);                     // memories ready; x[0] final for side 2's reads
-    for (int s = 0; s < 2; s++) {
-      c.s = st[s]; c.side = s;
-      dec_block(c, m.dec[s][l], l + 1 < m.dec_depth ? &m.dec[s][l + 1] : nullptr, x[s], yn[s], B, N, N, nw, nw, bs[s]);
-      for (int k = 1; k < 3; k++)
-        if (l + 1 == m.hooks[k]) cast_bf16(c, x[s], tok[s][k], (size_t)M * m.Dd);
-    }
+    const bool more = l + 1 < m.dec_depth;
+    dec_layer_grouped(c, m.dec[0][l], m.dec[1][l], more ? &m.dec[0][l + 1] : nullptr, more ? &m.dec[1][l + 1] : nullptr,
+                      x_all, yn_all, B, N, nw, bs_all);
+    for (int k = 1; k < 3; k++)
+      if (l + 1 == m.hooks[k]) cast_bf16(c, x_all, tok_all[k], 2 * MD);
   }
-  }
+  // stream order lets head 2 start in the scratch head 1 has finished with
   const size_t mark = c.ar.off;
-  size_t end = mark;
   for (int s = 0; s < 2; s++) {
-    c.s = st[s]; c.side = s;
-    layernorm(c, x[s], m.dec_norm, M, tok[s][3], dec_last[s]);
-    // each head gets its own scratch region when the two run concurrently
-    c.ar.off = (sB != sA || c.dry()) ? end : mark;
-    run_head(c, m.head[s], tok[s], B, H, W, out[s]);
-    end = c.ar.off;
+    bf16* tok[4];   // (the sizing pass has no pointers to offset)
+    for (int k = 0; k < 4; k++) tok[k] = c.dry() ? nullptr : tok_all[k] + s * (k ? MD : ME);
+    layernorm(c, c.dry() ? nullptr : x_all + s * MD, m.dec_norm, M, tok[3], dec_last[s]);
+    c.ar.off = mark;
+    run_head(c, m.head[s], tok, B, H, W, out[s]);
   }
-  c.s = sA; c.side = 0;
-  if (sB != sA) stream_wait(c, sA, sB);  // join
 }
 
 }  // namespace mslam
@@ -1092,12 +890,7 @@ extern "C" int mslam_mast3r_create(void** handle_out, const int* cfg9, void* con
   if (!rc) rc = check_hip(hipMemcpyAsync(m->rope_cos, hc.data(), hc.size() * 4, hipMemcpyHostToDevice, (hipStream_t)stream), "rope copy");
   if (!rc) rc = check_hip(hipMemcpyAsync(m->rope_sin, hs.data(), hs.size() * 4, hipMemcpyHostToDevice, (hipStream_t)stream), "rope copy");
   if (!rc) rc = check_hip(hipStreamSynchronize((hipStream_t)stream), "rope sync");
-  if (const char* e = getenv("MSLAM_TWO_STREAMS")) m->two_streams = atoi(e) != 0;
-  if (getenv("MSLAM_SINGLE_STREAM")) m->two_streams = false;
-  if (const char* e = getenv("MSLAM_FORK_MAX_M")) m->fork_max_rows = atoi(e);
   if (const char* e = getenv("MSLAM_PREFETCH")) m->prefetch = atoi(e) != 0;
-  if (const char* e = getenv("MSLAM_DEC_GROUPED")) m->dec_grouped = atoi(e) != 0;
-  if (const char* e = getenv("MSLAM_GROUP_MAX_M")) m->group_max_rows = atoi(e);
   if (rc) { delete m; return rc; }
   *handle_out = m;
   return MSLAM_OK;
@@ -1108,11 +901,6 @@ extern "C" int mslam_mast3r_destroy(void* handle) {
   if (!m) return MSLAM_OK;
   if (m->rope_cos) (void)hipFree(m->rope_cos);
   if (m->rope_sin) (void)hipFree(m->rope_sin);
-  for (auto& kv : m->forks) {
-    for (hipEvent_t ev : kv.second->events) (void)hipEventDestroy(ev);
-    (void)hipStreamDestroy(kv.second->side);
-    delete kv.second;
-  }
   delete m;
   return MSLAM_OK;
 }
@@ -1133,11 +921,10 @@ extern "C" size_t mslam_mast3r_workspace_bytes(void* handle, int batch, int H, i
   if (!m || check_shape(m, batch, H, W, "mast3r_workspace_bytes")) return 0;
   Ctx c{m, Arena{nullptr, 0, 0, true}, nullptr};
   encode(c, nullptr, batch, H, W, nullptr);
-  const size_t enc = c.ar.off;
   c.ar.off = 0;
   HeadOut out[2] = {};
   decode(c, nullptr, nullptr, batch, H, W, out, nullptr, nullptr);
-  return (enc > c.ar.off ? enc : c.ar.off) + 4096;
+  return c.ar.peak + 4096;
 }
 
 extern "C" int mslam_mast3r_encode(void* handle, const float* img, int batch, int H, int W, float* feat_out,
@@ -1149,7 +936,7 @@ extern "C" int mslam_mast3r_encode(void* handle, const float* img, int batch, in
   MSLAM_REQUIRE(workspace_bytes >= mslam_mast3r_workspace_bytes(handle, batch, H, W), "mast3r_encode: workspace too small");
   Ctx c{m, Arena{(char*)workspace, 0, workspace_bytes, false}, (hipStream_t)stream};
   encode(c, img, batch, H, W, feat_out);
-  MSLAM_REQUIRE(!c.ar.overflow, "mast3r_encode: workspace arena overflow (%zu > %zu)", c.ar.off, c.ar.cap);
+  MSLAM_REQUIRE(!c.ar.overflow, "mast3r_encode: workspace arena overflow (%zu > %zu)", c.ar.peak, c.ar.cap);
   if (c.rc) return c.rc;
   return check_hip(hipGetLastError(), "mast3r_encode launch");
 }
@@ -1166,7 +953,7 @@ extern "C" int mslam_mast3r_decode(void* handle, const float* feat1, const float
   Ctx c{m, Arena{(char*)workspace, 0, workspace_bytes, false}, (hipStream_t)stream};
   HeadOut out[2] = {{X1, C1, D1, Q1}, {X2, C2, D2, Q2}};
   decode(c, feat1, feat2, batch, H, W, out, dec_last1, dec_last2);
-  MSLAM_REQUIRE(!c.ar.overflow, "mast3r_decode: workspace arena overflow (%zu > %zu)", c.ar.off, c.ar.cap);
+  MSLAM_REQUIRE(!c.ar.overflow, "mast3r_decode: workspace arena overflow (%zu > %zu)", c.ar.peak, c.ar.cap);
   if (c.rc) return c.rc;
   return check_hip(hipGetLastError(), "mast3r_decode launch");
 }

@@ -171,7 +171,7 @@ def test_frame_group_matches_per_frame(device):
 
 
 def test_graph_replay_matches_eager(device):
-    """use_graphs=True replays captured HIP graphs (two-stream decoder included); results are bit-identical
+    """use_graphs=True replays captured HIP graphs (a decode call is one queue: no parallel branches); results are bit-identical
     to the eager launches and stay valid after later calls (fresh output tensors)."""
     from mast3r_slam.mast3r_model import Mast3rConfig, Mast3rHIP
 
@@ -197,7 +197,7 @@ def test_graph_replay_matches_eager(device):
 
 def test_concurrent_calls_from_two_threads(device):
     """The SLAM frontend and backend call the model at the same time from different host threads and streams
-    (bench.py): every (call kind, stream) has its own arena and fork context, so concurrent results are
+    (bench.py): every (call kind, stream) has its own arena and a call stays on its stream, so concurrent results are
     bit-identical to the same calls issued one after the other."""
     import threading
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""One batch call on one queue vs the same frames as k concurrent sub-batches on k streams (each with its own arena and
-decoder fork): does inter-launch concurrency beat intra-launch batching at a frame group of 4 / 8?"""
+"""One batch call on one queue vs the same frames as k concurrent sub-batches on k streams (each with its own
+arena): does inter-launch concurrency beat intra-launch batching at a frame group of 4 / 8?"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "mast3r-slam-quality-dualtsdf_amd")]
