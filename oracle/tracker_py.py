@@ -3,9 +3,11 @@
   act_Sim3 / point_to_ray_dist / project_calib                        /root/reference/mast3r_slam/geometry.py:17-104
   huber / check_convergence                                           /root/reference/mast3r_slam/nonlinear_optimizer.py:5-33
 written in the reference's own form (explicit (n,4,7) Jacobians, A^T A, Cholesky solve, retr), float32
-tensors / python-float scalars like the torch code.  The single-step normal equations are pinned by
-tests/golden/tracker_formulae.npz (built from the reference's geometry.py); lietorch's retr is the
-oracle's Sim3 restatement (lietorch itself is absent: parity unpinned for the group ops)."""
+tensors / python-float scalars like the torch code.  Its single step is pinned through tests/tracker_ref.py, the float64
+statement of the same step: tests/test_tracker_ref_cpu.py holds that one to tests/golden/tracker_formulae.npz (built
+from the reference's geometry.py) and to finite differences of the cost, and measures this module's float32 step
+against it.  lietorch's retr is the oracle's Sim3 restatement (lietorch itself is absent: parity unpinned for the
+group ops)."""
 import math
 
 import numpy as np
@@ -76,8 +78,9 @@ def check_convergence(rel_thr, dn_thr, old_cost, new_cost, delta):
     return rel_dec < rel_thr or float(np.linalg.norm(delta)) < dn_thr
 
 
-def track(use_calib, Xf_g, Xk, T_WCf, T_WCk, Qk, valid, cfg, K=None, img_size=None):
-    """Xf_g = frame points already gathered by idx_f2k (tracker.py:206).  Returns (T_WCf, T_CkCf, iters)."""
+def track(use_calib, Xf_g, Xk, T_WCf, T_WCk, Qk, valid, cfg, K=None, img_size=None, trace=None):
+    """Xf_g = frame points already gathered by idx_f2k (tracker.py:206).  Returns (T_WCf, T_CkCf, iters).
+    trace: a list that receives (tau f32[7], cost) of every iteration."""
     sa, sb = (cfg["sigma_pixel"], cfg["sigma_depth"]) if use_calib else (cfg["sigma_ray"], cfg["sigma_dist"])
     na = 2 if use_calib else 3
     sq = (valid.reshape(-1, 1) * np.sqrt(Qk.reshape(-1, 1))).astype(np.float32)
@@ -107,6 +110,8 @@ def track(use_calib, Xf_g, Xk, T_WCf, T_WCk, Qk, valid, cfg, K=None, img_size=No
             r = rd_k - rd_f
             J = -(drd @ dP)
         tau, cost = solve(si.astype(np.float32), r.astype(np.float32), J.astype(np.float32), cfg["huber"])
+        if trace is not None:
+            trace.append((tau[0].copy(), cost))
         T = oracle.sim3_retr(tau, T)[0]
         if check_convergence(cfg["rel_error"], cfg["delta_norm"], old, cost, tau):
             break
