@@ -254,6 +254,31 @@ int mslam_tsdf_mesh_emit(void* table, uint64_t capacity, double voxel_size, doub
 int mslam_tsdf_load(void* table, uint64_t capacity, const int64_t* keys, const double* tsdf, const double* weight,
                     int n, void* stream);
 
+/* Connected components of a welded triangle mesh and the filter that drops whole components (no counterpart in the
+ * reference, DESIGN.md "Mesh components").  faces i32[F,3] hold vertex indices in [0, V); the caller checks that range
+ * (a face outside it is skipped, never followed).  Any welded mesh, not only the volume's.  Sequence, on one stream:
+ *   mslam_mesh_cc_label   root i32[V]: the smallest vertex index of each vertex's component (lock-free union-find in
+ *                         `root` itself; a parent is only ever replaced by a smaller value, so nothing can spin); exact
+ *                         and bit-identical for any scheduling.  A vertex no face uses is its own component.
+ *   mslam_mesh_cc_count   faces_at_root i32[V], verts_at_root i32[V] (either may be NULL): faces (by their first vertex)
+ *                         and vertices of the component, at the root's index, zero elsewhere.  aggregate != 0: a run of
+ *                         neighbouring lanes with one root adds once; 0: one atomic per element.  Same output.
+ *   mslam_mesh_cc_select  keep_vertex i32[V], keep_face i32[F] <- keep_root u8[V] looked up at each element's root;
+ *                         the caller forms their exclusive scans vbase, fbase (i64) and the totals V', F';
+ *   mslam_mesh_cc_emit    kept vertices / normals / colours (colors and out_colors both NULL: none) f32[V',3] in their
+ *                         original order, kept faces i32[F',3] with remapped indices.
+ * No workspace: the union-find runs in `root`. */
+int mslam_mesh_cc_label(const int32_t* faces, int num_faces, int num_vertices, int32_t* root, void* stream);
+int mslam_mesh_cc_count(const int32_t* faces, int num_faces, int num_vertices, const int32_t* root,
+                        int32_t* faces_at_root, int32_t* verts_at_root, int aggregate, void* stream);
+int mslam_mesh_cc_select(const int32_t* faces, int num_faces, int num_vertices, const int32_t* root,
+                         const uint8_t* keep_root, int32_t* keep_vertex, int32_t* keep_face, void* stream);
+int mslam_mesh_cc_emit(const float* vertices, const float* normals, const float* colors, const int32_t* faces,
+                       int num_faces, int num_vertices, const int32_t* keep_vertex, const int32_t* keep_face,
+                       const int64_t* vbase, const int64_t* fbase, float* out_vertices, float* out_normals,
+                       float* out_colors, int32_t* out_faces, int64_t n_out_vertices, int64_t n_out_faces,
+                       void* stream);
+
 /* Depth / normal view of the volume by ray casting (no counterpart in the reference, DESIGN.md "View rendering").  The
  * table is only read.  Sequence, on one stream:
  *   mslam_tsdf_render_blocks  fills the workspace with the set of 8^3-voxel blocks that hold a voxel with weight >=

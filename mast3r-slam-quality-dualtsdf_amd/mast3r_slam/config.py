@@ -38,6 +38,7 @@ _BASE = {
         "min_tsdf_weight": 1.0e-3, "max_points_per_kf": 40000, "min_confidence": 0.05,
         "samples_per_kf": 2000, "lambda": 0.15, "max_iterations": 3, "pre_icp_iters": 2, "damping": 1.0e-4,
         "color": False,     # fuse the keyframes' uimg into the volume: coloured meshes and views (DESIGN.md "Colour")
+        "mesh_min_component_faces": 0,   # SlamSystem.extract_mesh drops smaller components (DESIGN.md "Mesh components")
     },
 }
 

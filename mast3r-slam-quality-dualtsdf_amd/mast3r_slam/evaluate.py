@@ -141,17 +141,22 @@ def save_mesh(filename, vertices, faces, normals=None, colors=None):
         fh.write(face.tobytes())
 
 
-def save_tsdf_mesh(savedir, filename, source, min_weight=None, level=0.0, colors=False):
+def save_tsdf_mesh(savedir, filename, source, min_weight=None, level=0.0, colors=False, min_component_faces=0,
+                   keep_largest=None):
     """The global TSDF's triangle mesh (marching cubes) as PLY with normals, beside save_reconstruction's point cloud.
     `source`: a SlamSystem, a TSDFGlobalManager or a TSDFVolume.  `colors=True` (a volume with tsdf_global.color): the
-    vertices carry the fused colour as red / green / blue.  Returns (V, F)."""
+    vertices carry the fused colour as red / green / blue.  `min_component_faces` > 0 / `keep_largest`: small connected
+    components are dropped first (DESIGN.md "Mesh components").  Returns (V, F)."""
     savedir = pathlib.Path(savedir)
     savedir.mkdir(exist_ok=True, parents=True)
+    kw = {}
+    if min_component_faces > 0 or keep_largest is not None:
+        kw = dict(min_component_faces=min_component_faces, keep_largest=keep_largest)
     if colors:
-        v, n, f, c = source.extract_mesh(min_weight=min_weight, level=level, colors=True)
+        v, n, f, c = source.extract_mesh(min_weight=min_weight, level=level, colors=True, **kw)
         save_mesh(savedir / filename, v, f, normals=n, colors=c)
     else:
-        v, n, f = source.extract_mesh(min_weight=min_weight, level=level)
+        v, n, f = source.extract_mesh(min_weight=min_weight, level=level, **kw)
         save_mesh(savedir / filename, v, f, normals=n)
     return int(v.shape[0]), int(f.shape[0])
 

@@ -355,14 +355,19 @@ class SlamSystem:
             with self._critical("main"):
                 self._apply_commits(wait=True)
 
-    def extract_mesh(self, min_weight=None, level=0.0, colors=False, **kw):
+    def extract_mesh(self, min_weight=None, level=0.0, colors=False, min_component_faces=None, keep_largest=None, **kw):
         """Triangle mesh of the global TSDF at this point of the run: (vertices f32[V,3], normals f32[V,3], faces i32[F,3])
         device tensors (TSDFVolume.extract_mesh).  Drains the backend first, so every fusion it has issued is ordered
-        before the read.  `colors=True` (tsdf_global.color on): vertex colours f32[V,3] as a fourth tensor."""
+        before the read.  `colors=True` (tsdf_global.color on): vertex colours f32[V,3] as a fourth tensor.
+        `min_component_faces` (default tsdf_global.mesh_min_component_faces, 0 = off) / `keep_largest`: drop small
+        connected components (DESIGN.md "Mesh components")."""
         if self.tsdf_manager is None:
             raise RuntimeError("SlamSystem.extract_mesh: the global TSDF is disabled (tsdf_global.enabled = False)")
+        if min_component_faces is None:
+            min_component_faces = int(self.tsdf_manager.cfg.get("mesh_min_component_faces", 0))
         self.drain()
-        return self.tsdf_manager.extract_mesh(min_weight=min_weight, level=level, colors=colors, **kw)
+        return self.tsdf_manager.extract_mesh(min_weight=min_weight, level=level, colors=colors,
+                                              min_component_faces=min_component_faces, keep_largest=keep_largest, **kw)
 
     def render_view(self, pose=None, rays=None, K=None, hw=None, **kw):
         """Depth / normal view of the global TSDF at this point of the run: (range f32[h,w], normals f32[h,w,3],

@@ -168,9 +168,12 @@ class TSDFGlobalManager:
         if self.enabled:
             self.volume.maintain()   # samples dropped by the last solve are reported here
 
-    def extract_mesh(self, min_weight=None, level=0.0, colors=False, **kw):
+    def extract_mesh(self, min_weight=None, level=0.0, colors=False, min_component_faces=0, keep_largest=None, **kw):
         """Triangle mesh of the global volume: (vertices f32[V,3], normals f32[V,3], faces i32[F,3]) device tensors
-        (TSDFVolume.extract_mesh); `colors=True`: vertex colours f32[V,3] as a fourth tensor."""
+        (TSDFVolume.extract_mesh); `colors=True`: vertex colours f32[V,3] as a fourth tensor.  `min_component_faces` /
+        `keep_largest`: drop small connected components (DESIGN.md "Mesh components"); off by default."""
+        if min_component_faces > 0 or keep_largest is not None:
+            kw = dict(kw, min_component_faces=min_component_faces, keep_largest=keep_largest)
         if not colors and not kw:
             return self.volume.extract_mesh(min_weight=min_weight, level=level)
         return self.volume.extract_mesh(min_weight=min_weight, level=level, colors=colors, **kw)

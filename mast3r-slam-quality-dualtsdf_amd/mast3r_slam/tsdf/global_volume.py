@@ -13,6 +13,8 @@ import torch
 
 import mslam_hip as _m
 
+from .mesh_ops import filter_mesh
+
 
 _KEY_BIAS = 1 << 20
 
@@ -345,26 +347,32 @@ class TSDFVolume:
             _m.check(_m.lib().mslam_tsdf_color_load(_m.ptr(self._table), self.capacity, _m.ptr(self._color), _m.ptr(k),
                                                     _m.ptr(c), n, _m.stream_ptr()), "tsdf_color_load")
 
-    def extract_mesh(self, min_weight=None, level=0.0, colors=False, default_color=(0.5, 0.5, 0.5)):
+    def extract_mesh(self, min_weight=None, level=0.0, colors=False, default_color=(0.5, 0.5, 0.5),
+                     min_component_faces=0, keep_largest=None):
         """Marching cubes over the fused volume -> (vertices f32[V,3], normals f32[V,3], faces i32[F,3]) device tensors in
         canonical order (DESIGN.md "Mesh extraction").  Corners are voxel centres with weight >= min_weight (default
         self.min_weight), inside = tsdf < level, normals point to free space, faces are counter-clockwise seen from
         there.  The table is only read.  One host read (the output sizes).  Sharded volumes: cubes span owners, so the
         union of the shards (voxels(), collective) is meshed on every rank.  `colors=True` (needs color=True): a fourth
-        tensor f32[V,3] in [0, 1], the colour sampled at each f32 vertex position (sample_color)."""
+        tensor f32[V,3] in [0, 1], the colour sampled at each f32 vertex position (sample_color).
+        `min_component_faces` > 0 / `keep_largest`=k: connected components with fewer faces / all but the k largest are
+        dropped after extraction and colour sampling (mesh_ops.filter_mesh, DESIGN.md "Mesh components"; one more host
+        read); the defaults leave the mesh as extracted."""
         mw = self.min_weight if min_weight is None else float(min_weight)
         if colors and not self.color:
             raise ValueError("TSDFVolume.extract_mesh: colors=True needs a volume built with color=True")
         if self.num_shards > 1:
             if colors:
-                return self._union().extract_mesh(min_weight=mw, level=level, colors=True, default_color=default_color)
+                return self._union().extract_mesh(min_weight=mw, level=level, colors=True, default_color=default_color,
+                                                  min_component_faces=min_component_faces, keep_largest=keep_largest)
             keys, t, w = self.voxels()
-            return mesh_from_voxels(keys, t, w, self.voxel_size, mw, level, device=self.device)
+            return mesh_from_voxels(keys, t, w, self.voxel_size, mw, level, device=self.device,
+                                    min_component_faces=min_component_faces, keep_largest=keep_largest)
         mesh = _extract(self._table, self.capacity, self.voxel_size, mw, float(level), self.device)
-        if not colors:
-            return mesh
-        return mesh + (_sample_color(self._table, self.capacity, self._color, mesh[0], 0, self.voxel_size,
-                                     default_color)[0],)
+        if colors:
+            mesh = mesh + (_sample_color(self._table, self.capacity, self._color, mesh[0], 0, self.voxel_size,
+                                         default_color)[0],)
+        return filter_mesh(mesh, min_component_faces, keep_largest, _validate=False)
 
     def render(self, pose, rays=None, K=None, hw=None, near=0.05, far=10.0, min_weight=None, level=0.0, step=None,
                skip=True, colors=False, default_color=(0.5, 0.5, 0.5)):
@@ -552,9 +560,11 @@ def render_from_voxels(keys, tsdf, weight, voxel_size, min_weight, pose, rays, n
 
 
 def mesh_from_voxels(keys, tsdf, weight, voxel_size, min_weight, level=0.0, device="cuda", colors=None,
-                     default_color=(0.5, 0.5, 0.5)):
+                     default_color=(0.5, 0.5, 0.5), min_component_faces=0, keep_largest=None):
     """Mesh of a voxel set given as arrays (keys i64[n,3] distinct, tsdf f64[n], weight f64[n]; numpy or device): loads
-    a temporary table of at least 2n slots and extracts from it (TSDFVolume.extract_mesh semantics).  `colors`
-    u64[n,4]: the voxels' colour sums (voxel_color_sums()); the mesh then carries vertex colours as a fourth tensor."""
+    a temporary table of at least 2n slots and extracts from it (TSDFVolume.extract_mesh semantics, its component filter
+    included).  `colors` u64[n,4]: the voxels' colour sums (voxel_color_sums()); the mesh then carries vertex colours as
+    a fourth tensor."""
     vol = _loaded(keys, tsdf, weight, voxel_size, min_weight, device, colors)
-    return vol.extract_mesh(min_weight=min_weight, level=level, colors=colors is not None, default_color=default_color)
+    return vol.extract_mesh(min_weight=min_weight, level=level, colors=colors is not None, default_color=default_color,
+                            min_component_faces=min_component_faces, keep_largest=keep_largest)
