@@ -279,6 +279,31 @@ int mslam_mesh_cc_emit(const float* vertices, const float* normals, const float*
                        float* out_colors, int32_t* out_faces, int64_t n_out_vertices, int64_t n_out_faces,
                        void* stream);
 
+/* Mesh quality: face areas, a surface sampler and the exact point-to-mesh distance (no counterpart in the reference,
+ * DESIGN.md "Mesh quality").  vertices f32[V,3], faces i32[F,3]; every index is checked against [0, V) before use.  A
+ * face is valid when its indices are in range and (b - a) x (c - a), in f64, is not exactly zero; an invalid face has
+ * area 0, is never sampled and is never the nearest face.  All arithmetic is f64 on the f32 inputs.
+ *   mslam_mesh_face_areas  area f64[F] = 0.5 |(b - a) x (c - a)|.
+ *   mslam_mesh_sample      cdf f64[F]: inclusive cumulative area (formed by the caller), total = cdf[F-1] > 0.  Sample i
+ *                          takes u = (i + 0.5) / n * total, the first face with cdf[f] > u (then back to the last valid
+ *                          face at or before it), and barycentrics from a stateless hash of (seed, i): points f32[n,3],
+ *                          face i32[n].  Stratified; the same bits on every call.
+ *   mslam_mesh_distance    dist2 f64[n], nearest i32[n]: the smallest squared distance from each point to a valid face
+ *                          (closest point by Voronoi regions) and the lowest index of a face that attains it; +inf and
+ *                          -1 without a valid face.  skip = 0: every face is scanned; 1: tiles of 128 faces whose box
+ *                          (written to the workspace first) lies beyond the current best are skipped, same output bit
+ *                          for bit; 2: as 1, and i32[4 * ceil(n / 256)] behind the boxes receives, per wave, the number
+ *                          of tiles it skipped (workspace_bytes must cover that too).  workspace >=
+ *                          mslam_mesh_distance_workspace_bytes(F) for skip = 1; unused for skip = 0. */
+int mslam_mesh_face_areas(const float* vertices, const int32_t* faces, int num_faces, int num_vertices, double* area,
+                          void* stream);
+int mslam_mesh_sample(const float* vertices, const int32_t* faces, int num_faces, int num_vertices, const double* cdf,
+                      double total, int n, uint64_t seed, float* points, int32_t* face, void* stream);
+size_t mslam_mesh_distance_workspace_bytes(int num_faces);
+int mslam_mesh_distance(const float* points, int n, const float* vertices, const int32_t* faces, int num_faces,
+                        int num_vertices, int skip, void* workspace, size_t workspace_bytes, double* dist2,
+                        int32_t* nearest, void* stream);
+
 /* Depth / normal view of the volume by ray casting (no counterpart in the reference, DESIGN.md "View rendering").  The
  * table is only read.  Sequence, on one stream:
  *   mslam_tsdf_render_blocks  fills the workspace with the set of 8^3-voxel blocks that hold a voxel with weight >=

@@ -141,6 +141,75 @@ def save_mesh(filename, vertices, faces, normals=None, colors=None):
         fh.write(face.tobytes())
 
 
+_PLY_SIZES = {"char": 1, "uchar": 1, "int8": 1, "uint8": 1, "short": 2, "ushort": 2, "int16": 2, "uint16": 2, "int": 4,
+              "uint": 4, "int32": 4, "uint32": 4, "float": 4, "float32": 4, "double": 8, "float64": 8}
+
+
+def load_mesh(filename):
+    """Reads a triangle mesh from the binary little-endian PLY that save_mesh writes -> (vertices f32[V,3], faces
+    i32[F,3]) numpy.  The vertex element needs float x, y, z; its other properties are skipped by their declared sizes.
+    The face element is one `property list uchar int|uint` of three indices per face.  ASCII or big-endian files, list
+    properties on vertices and faces that are no triangles raise ValueError."""
+    with open(filename, "rb") as fh:
+        data = fh.read()
+    end = data.find(b"end_header\n")
+    if not data.startswith(b"ply") or end < 0:
+        raise ValueError(f"load_mesh: {filename} is not a PLY file")
+    lines = data[:end].decode("ascii", "replace").split("\n")
+    body = end + len(b"end_header\n")
+    if not any(ln.split() == ["format", "binary_little_endian", "1.0"] for ln in lines):
+        raise ValueError(f"load_mesh: {filename} is not binary_little_endian 1.0 (ASCII and big-endian are not read)")
+    elements = []                                        # [name, count, [property words]]
+    for ln in lines:
+        w = ln.split()
+        if w[:1] == ["element"]:
+            elements.append([w[1], int(w[2]), []])
+        elif w[:1] == ["property"]:
+            if not elements:
+                raise ValueError("load_mesh: property before any element")
+            elements[-1][2].append(w[1:])
+    if [e[0] for e in elements[:2]] != ["vertex", "face"]:
+        raise ValueError("load_mesh: expected a vertex element followed by a face element")
+    (_, n_v, vprops), (_, n_f, fprops) = elements[:2]
+    fields = []
+    for w in vprops:
+        if w[0] == "list" or w[0] not in _PLY_SIZES:
+            raise ValueError(f"load_mesh: unsupported vertex property '{' '.join(w)}'")
+        is_xyz = w[1] in ("x", "y", "z")
+        if is_xyz and w[0] not in ("float", "float32"):
+            raise ValueError(f"load_mesh: vertex {w[1]} must be float, got {w[0]}")
+        fields.append((w[1], "<f4" if is_xyz else f"V{_PLY_SIZES[w[0]]}"))
+    if not {"x", "y", "z"} <= {name for name, _ in fields}:
+        raise ValueError("load_mesh: the vertex element has no float x, y, z")
+    if len(fprops) != 1 or fprops[0][:2] != ["list", "uchar"] or fprops[0][2] not in ("int", "uint", "int32", "uint32"):
+        raise ValueError("load_mesh: the face element must be one `property list uchar int|uint`")
+    vdt = np.dtype(fields)
+    fdt = np.dtype([("n", "u1"), ("i", "<u4" if fprops[0][2].startswith("u") else "<i4", (3,))])
+    if len(data) < body + n_v * vdt.itemsize:
+        raise ValueError("load_mesh: the file ends inside the vertex element")
+    vert = np.frombuffer(data, vdt, n_v, body)
+    body += n_v * vdt.itemsize
+    counts = np.frombuffer(data, "u1", len(data) - body, body)[::fdt.itemsize][:n_f]
+    if len(data) < body + n_f * fdt.itemsize or (counts != 3).any():
+        raise ValueError("load_mesh: only triangle faces are read")
+    face = np.frombuffer(data, fdt, n_f, body)
+    vertices = np.stack([vert["x"], vert["y"], vert["z"]], 1).astype(np.float32).reshape(-1, 3)
+    return vertices, face["i"].astype(np.int32).reshape(-1, 3)
+
+
+def save_mesh_metrics(savedir, filename, metrics):
+    """The dict of tsdf.compare_meshes / SlamSystem.evaluate_mesh as JSON with sorted keys.  Returns the path."""
+    import json
+
+    savedir = pathlib.Path(savedir)
+    savedir.mkdir(exist_ok=True, parents=True)
+    path = savedir / filename
+    with open(path, "w") as f:
+        json.dump(dict(metrics), f, indent=1, sort_keys=True)
+        f.write("\n")
+    return path
+
+
 def save_tsdf_mesh(savedir, filename, source, min_weight=None, level=0.0, colors=False, min_component_faces=0,
                    keep_largest=None):
     """The global TSDF's triangle mesh (marching cubes) as PLY with normals, beside save_reconstruction's point cloud.

@@ -369,6 +369,25 @@ class SlamSystem:
         return self.tsdf_manager.extract_mesh(min_weight=min_weight, level=level, colors=colors,
                                               min_component_faces=min_component_faces, keep_largest=keep_largest, **kw)
 
+    def evaluate_mesh(self, gt_vertices, gt_faces, n_samples=200_000, threshold=None, **extract_kw):
+        """Quality of the global TSDF's mesh at this point of the run against a ground-truth mesh (gt_vertices f32[V,3],
+        gt_faces i32[F,3]; numpy arrays or device tensors, in the map's frame): the dict of tsdf.compare_meshes,
+        accuracy / completion / precision / recall / fscore / chamfer (DESIGN.md "Mesh quality").  The mesh is
+        self.extract_mesh(**extract_kw), so the backend is drained first and the config's clean-up default applies.
+        `threshold` defaults to tsdf_global.mesh_eval_threshold."""
+        if self.tsdf_manager is None:
+            raise RuntimeError("SlamSystem.evaluate_mesh: the global TSDF is disabled (tsdf_global.enabled = False)")
+        from mast3r_slam.tsdf import compare_meshes
+
+        if threshold is None:
+            threshold = float(self.tsdf_manager.cfg.get("mesh_eval_threshold", 0.05))
+        mesh = self.extract_mesh(**extract_kw)
+        dev = mesh[0].device
+        gt_vertices = torch.as_tensor(gt_vertices, dtype=torch.float32).to(dev)
+        gt_faces = torch.as_tensor(gt_faces, dtype=torch.int32).to(dev)
+        return compare_meshes(mesh, (gt_vertices, gt_faces), n_samples=n_samples, threshold=threshold,
+                              _validate_pred=False)
+
     def render_view(self, pose=None, rays=None, K=None, hw=None, **kw):
         """Depth / normal view of the global TSDF at this point of the run: (range f32[h,w], normals f32[h,w,3],
         hit bool[h,w]) device tensors (TSDFVolume.render; `kw`: near, far, min_weight, level, step, skip, and - with

@@ -8,6 +8,17 @@ import numpy as np
 ROOM_HALF = np.array([3.0, 2.0, 1.5])  # 6 x 4 x 3 m box, camera inside
 
 
+def room_mesh():
+    """The room's surface as a triangle mesh -> (vertices f32[8,3], faces i32[12,3]): the corners of the ROOM_HALF box
+    (corner k has bit 0 / 1 / 2 of k set where x / y / z is positive) and two triangles per wall, counter-clockwise seen
+    from inside, so the face normals point into the room."""
+    k = np.arange(8)
+    sign = np.stack([(k >> d) & 1 for d in range(3)], 1) * 2.0 - 1.0
+    quads = [(0, 2, 6, 4), (1, 5, 7, 3), (0, 4, 5, 1), (2, 3, 7, 6), (0, 1, 3, 2), (4, 6, 7, 5)]       # -x +x -y +y -z +z
+    faces = [t for a, b, c, d in quads for t in ((a, b, c), (a, c, d))]
+    return (sign * ROOM_HALF).astype(np.float32), np.array(faces, np.int32)
+
+
 def intrinsics(h=384, w=512):
     s = w / 512.0
     return np.array([[400.0 * s, 0, w / 2.0], [0, 400.0 * s, h / 2.0], [0, 0, 1.0]], np.float32)

@@ -1,0 +1,139 @@
+"""Mesh quality on the device: face areas, an area-weighted stratified surface sampler, the exact distance from points
+to a triangle mesh, and the accuracy / completion / precision / recall / F-score / Chamfer figures between two meshes.
+
+No counterpart in the reference.  The kernels are csrc/mesh_distance.hip (DESIGN.md "Mesh quality"); the numpy
+statement of the same definitions is tests/meshdist_numpy.py.  A face is valid when its indices lie in [0, V) and its
+cross product is not exactly zero; an invalid face has area 0, is never sampled and is never the nearest face.  The two
+meshes of a comparison must be given in one frame: nothing here aligns them.
+"""
+import torch
+
+import mslam_hip as _m
+
+from .mesh_ops import _faces_arg
+
+_MASK64 = (1 << 64) - 1
+
+
+def _mesh_arg(vertices, faces, validate, what):
+    """(vertices f32[V,3], faces i32[F,3], V, F) contiguous device tensors; `validate`: the index range of the faces,
+    one reduction and one host read."""
+    if not torch.is_tensor(vertices):
+        raise TypeError(f"{what}: vertices must be a device tensor")
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError(f"{what}: vertices must be (V,3), got {tuple(vertices.shape)}")
+    _m.require_dtype(vertices, torch.float32, "vertices")
+    _m.ptr(vertices)                                        # a host tensor raises here: no CPU path exists
+    faces, V, F = _faces_arg(faces, vertices.shape[0], validate, what)
+    _m.ptr(faces)
+    if faces.device != vertices.device:
+        raise ValueError(f"{what}: vertices and faces are on different devices")
+    return vertices.contiguous(), faces, V, F
+
+
+def _areas(vertices, faces, V, F):
+    area = torch.empty(F, dtype=torch.float64, device=vertices.device)
+    _m.check(_m.lib().mslam_mesh_face_areas(_m.ptr(vertices), _m.ptr(faces), F, V, _m.ptr(area), _m.stream_ptr()),
+             "mesh_face_areas")
+    return area
+
+
+def face_areas(vertices, faces, _validate=True):
+    """area f64[F] = 0.5 |(b - a) x (c - a)| of the faces i32[F,3] over vertices f32[V,3] (device tensors), in f64."""
+    vertices, faces, V, F = _mesh_arg(vertices, faces, _validate, "face_areas")
+    return _areas(vertices, faces, V, F)
+
+
+def _sample(vertices, faces, V, F, n, seed, what):
+    """(points, face, total area as a Python float).  One host read: the total."""
+    n = int(n)
+    if n < 1 or n >= 1 << 31:
+        raise ValueError(f"{what}: n must be in [1, 2^31), got {n}")
+    dev = vertices.device
+    cdf = torch.cumsum(_areas(vertices, faces, V, F), 0) if F else torch.zeros(0, dtype=torch.float64, device=dev)
+    total = float(cdf[-1]) if F else 0.0
+    if not (total > 0.0 and total < float("inf")):
+        raise ValueError(f"{what}: the mesh has no area to sample (total area {total})")
+    points = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    face = torch.empty(n, dtype=torch.int32, device=dev)
+    _m.check(_m.lib().mslam_mesh_sample(_m.ptr(vertices), _m.ptr(faces), F, V, _m.ptr(cdf), total, n,
+                                        int(seed) & _MASK64, _m.ptr(points), _m.ptr(face), _m.stream_ptr()),
+             "mesh_sample")
+    return points, face, total
+
+
+def sample_mesh(vertices, faces, n, seed=0, _validate=True):
+    """n points on the mesh, area-weighted -> (points f32[n,3], face i32[n]) device tensors.  Stratified: sample i sits
+    at (i + 0.5) / n of the cumulative area, so every face gets its share of the samples to within one, in face order;
+    the place inside the face comes from a stateless hash of (seed, i).  The same inputs give the same bits.  Raises
+    ValueError when n < 1 or the mesh has no area."""
+    vertices, faces, V, F = _mesh_arg(vertices, faces, _validate, "sample_mesh")
+    return _sample(vertices, faces, V, F, n, seed, "sample_mesh")[:2]
+
+
+def _distance2(points, vertices, faces, V, F, skip):
+    n = int(points.shape[0])
+    dev = points.device
+    dist2 = torch.empty(n, dtype=torch.float64, device=dev)
+    nearest = torch.empty(n, dtype=torch.int32, device=dev)
+    L = _m.lib()
+    ws_bytes = int(L.mslam_mesh_distance_workspace_bytes(F)) if skip and F else 0
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    _m.check(L.mslam_mesh_distance(_m.ptr(points), n, _m.ptr(vertices), _m.ptr(faces), F, V, 1 if ws_bytes else 0,
+                                   _m.ptr(ws), ws_bytes, _m.ptr(dist2), _m.ptr(nearest), _m.stream_ptr()),
+             "mesh_distance")
+    return dist2, nearest
+
+
+def mesh_distance(points, vertices, faces, skip=True, _validate=True):
+    """Exact distance from points f32[n,3] to the mesh -> (distance f64[n], nearest i32[n]) device tensors: the distance
+    to the closest point of the closest valid face and the lowest index of a face at that distance; +inf and -1 when
+    the mesh has no valid face.  `skip`: tiles of faces whose bounding box lies beyond a point block's current best are
+    not scanned; the output is the same bit for bit (DESIGN.md "Mesh quality")."""
+    if not torch.is_tensor(points):
+        raise TypeError("mesh_distance: points must be a device tensor")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"mesh_distance: points must be (n,3), got {tuple(points.shape)}")
+    _m.require_dtype(points, torch.float32, "points")
+    _m.ptr(points)
+    if points.shape[0] >= 1 << 31:
+        raise ValueError("mesh_distance: too many points for the int32 index range")
+    vertices, faces, V, F = _mesh_arg(vertices, faces, _validate, "mesh_distance")
+    if points.device != vertices.device:
+        raise ValueError("mesh_distance: points and mesh are on different devices")
+    dist2, nearest = _distance2(points.contiguous(), vertices, faces, V, F, bool(skip))
+    return torch.sqrt(dist2), nearest
+
+
+def _pair(mesh, what):
+    mesh = tuple(mesh)
+    if len(mesh) == 2:
+        return mesh
+    if len(mesh) in (3, 4):                                  # extract_mesh: (vertices, normals, faces[, colors])
+        return mesh[0], mesh[2]
+    raise ValueError(f"compare_meshes: {what} must be (vertices, faces) or an extract_mesh tuple")
+
+
+def compare_meshes(pred, gt, n_samples=200_000, threshold=0.05, seed=0, skip=True, _validate_pred=True):
+    """Quality of the mesh `pred` against the ground truth `gt`, both (vertices f32[V,3], faces i32[F,3]) device tensors
+    or the tuples extract_mesh returns (normals and colours are ignored), in one frame.  n_samples points are drawn on
+    each (sample_mesh with `seed` on pred, `seed + 1` on gt) and measured against the other (mesh_distance).  Returns
+    Python numbers: accuracy / accuracy_median (pred samples to gt, mean and median), completion / completion_median
+    (gt samples to pred), precision / recall (share of pred / gt samples within `threshold`), fscore (their harmonic
+    mean, 0 when both are 0), chamfer = (accuracy + completion) / 2, n_samples, threshold, pred_area, gt_area.  The
+    means are f64 sums.  Host reads: the index range of each mesh, each total area, and the figures at the end."""
+    n = int(n_samples)
+    threshold = float(threshold)
+    pv, pf, pV, pF = _mesh_arg(*_pair(pred, "pred"), _validate_pred, "compare_meshes")
+    gv, gf, gV, gF = _mesh_arg(*_pair(gt, "gt"), True, "compare_meshes")
+    p_pts, _, p_area = _sample(pv, pf, pV, pF, n, seed, "compare_meshes (pred)")
+    g_pts, _, g_area = _sample(gv, gf, gV, gF, n, int(seed) + 1, "compare_meshes (gt)")
+    out = []
+    for pts, (v, f, V, F) in ((p_pts, (gv, gf, gV, gF)), (g_pts, (pv, pf, pV, pF))):
+        d = torch.sqrt(_distance2(pts, v, f, V, F, bool(skip))[0])
+        s = torch.sort(d)[0]
+        out += [d.sum() / n, 0.5 * (s[(n - 1) // 2] + s[n // 2]), (d <= threshold).sum().to(torch.float64) / n]
+    acc, acc_med, prec, comp, comp_med, rec = torch.stack(out).tolist()          # the one host read of the figures
+    return dict(accuracy=acc, accuracy_median=acc_med, completion=comp, completion_median=comp_med, precision=prec,
+                recall=rec, fscore=2.0 * prec * rec / (prec + rec) if prec + rec > 0.0 else 0.0,
+                chamfer=0.5 * (acc + comp), n_samples=n, threshold=threshold, pred_area=p_area, gt_area=g_area)
