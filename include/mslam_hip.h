@@ -304,6 +304,48 @@ int mslam_mesh_distance(const float* points, int n, const float* vertices, const
                         int num_vertices, int skip, void* workspace, size_t workspace_bytes, double* dist2,
                         int32_t* nearest, void* stream);
 
+/* Mesh alignment: the closed-form similarity between corresponding points and trimmed point-to-mesh ICP (no counterpart
+ * in the reference, DESIGN.md "Mesh alignment").  All arithmetic is f64 on the f32 inputs; every sum is reduced in a
+ * fixed order without atomics, so the same inputs give the same bits.
+ *   state      a device block of MSLAM_MESH_ALIGN_STATE_BYTES: f64[8] Sim3 [t(3), q(xyzw), s] in lietorch layout, then
+ *              an int32 status, MSLAM_MESH_ALIGN_OK or MSLAM_MESH_ALIGN_DEGENERATE (fewer than 3 pairs that count, no
+ *              spread among the source points, or no positive finite scale: the Sim3 is then left as it was).
+ *   log_row    f64[MSLAM_MESH_ALIGN_LOG_DOUBLES] on the device, written by every solve: the number of pairs that
+ *              count, their RMSE under the transform the pairs were formed with (+inf without a pair), the scale after
+ *              the solve, the status, then the 19 reduced sums about the origins (src[0]; T src[0] or dst[0]):
+ *              count, sum w, sum w p (3), sum w c (3), sum w p c^T (9, row-major), sum w |p|^2, sum w dist2.
+ *   workspace  mslam_mesh_align_workspace_bytes(n, F, count_skips): the target's tile boxes, one partial per block of
+ *              256 points, and with count_skips one int32 per wave, the tiles it did not scan (as skip = 2 of
+ *              mslam_mesh_distance), after them.  MSLAM_ENOMEM with the needed size in mslam_last_error when short.
+ *   mslam_mesh_align_init       state <- T0 (device f32[8], quaternion normalised in f64; NULL: the identity), and the
+ *                               boxes of the target mesh into the workspace, once per alignment.
+ *   mslam_mesh_align_step       one ICP iteration on the stream: moved f32[n,3] = (float)(s R src + t) in f64 rounded
+ *                               once; dist2 f64[n] / nearest i32[n] of `moved` against the mesh, bit for bit those of
+ *                               mslam_mesh_distance; `nearest` is read first as a warm start (any value is safe: -1, out
+ *                               of range and invalid faces are ignored) and overwritten; closest f64[n,3] (may be NULL)
+ *                               the closest point on the nearest face, NaN without one.  A pair counts when it has a
+ *                               face and dist2 <= trim^2 (trim >= 0 in target units, +inf keeps all).  Then the solve for
+ *                               the total transform src -> closest replaces the state (with_scale = 0: scale 1).
+ *                               n = 0 or F = 0: no pair, degenerate.
+ *   mslam_mesh_align_fit_pairs  the same solve for explicit pairs src f32[n,3] -> dst f32[n,3], weights f32[n] >= 0 or
+ *                               NULL (a pair of weight 0 does not count); the state is set to the identity first and
+ *                               the logged RMSE is that of dst - src.
+ *   mslam_mesh_align_read       device copies of the state: T64 f64[8], T32 f32[8], status i32[1]; each may be NULL. */
+#define MSLAM_MESH_ALIGN_STATE_BYTES 72
+#define MSLAM_MESH_ALIGN_LOG_DOUBLES 24
+#define MSLAM_MESH_ALIGN_OK 0
+#define MSLAM_MESH_ALIGN_DEGENERATE 1
+size_t mslam_mesh_align_workspace_bytes(int n, int num_faces, int count_skips);
+int mslam_mesh_align_init(const float* T0, const float* vertices, const int32_t* faces, int num_faces,
+                          int num_vertices, void* workspace, size_t workspace_bytes, void* state, void* stream);
+int mslam_mesh_align_step(const float* src, int n, const float* vertices, const int32_t* faces, int num_faces,
+                          int num_vertices, double trim, int with_scale, int count_skips, void* workspace,
+                          size_t workspace_bytes, void* state, int32_t* nearest, float* moved, double* dist2,
+                          double* closest, double* log_row, void* stream);
+int mslam_mesh_align_fit_pairs(const float* src, const float* dst, const float* weights, int n, int with_scale,
+                               void* workspace, size_t workspace_bytes, void* state, double* log_row, void* stream);
+int mslam_mesh_align_read(const void* state, double* T64, float* T32, int32_t* status, void* stream);
+
 /* Depth / normal view of the volume by ray casting (no counterpart in the reference, DESIGN.md "View rendering").  The
  * table is only read.  Sequence, on one stream:
  *   mslam_tsdf_render_blocks  fills the workspace with the set of 8^3-voxel blocks that hold a voxel with weight >=

@@ -197,6 +197,19 @@ def load_mesh(filename):
     return vertices, face["i"].astype(np.int32).reshape(-1, 3)
 
 
+def trajectory_ate(est_xyz, gt_xyz, with_scale=True, device="cuda:0"):
+    """Absolute trajectory error of the positions est_xyz (K x 3) against gt_xyz (K x 3), numpy arrays or tensors, after
+    the best similarity (tsdf.fit_sim3 on `device`; `with_scale=False`: the best rigid motion) -> (rmse, T): the root
+    mean square of |T(est_k) - gt_k| in f64 as a Python float and T as numpy f64[8] [t(3), q(xyzw), s]."""
+    from mast3r_slam.tsdf import fit_sim3, transform_mesh
+
+    est = torch.as_tensor(est_xyz, dtype=torch.float32).to(device).reshape(-1, 3)
+    gt = torch.as_tensor(gt_xyz, dtype=torch.float32).to(device).reshape(-1, 3)
+    T = fit_sim3(est, gt, with_scale=with_scale)[0]
+    r = transform_mesh(est.double(), T) - gt.double()
+    return float(torch.sqrt((r * r).sum(1).mean())), T.cpu().numpy()
+
+
 def save_mesh_metrics(savedir, filename, metrics):
     """The dict of tsdf.compare_meshes / SlamSystem.evaluate_mesh as JSON with sorted keys.  Returns the path."""
     import json

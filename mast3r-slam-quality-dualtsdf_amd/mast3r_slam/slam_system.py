@@ -369,24 +369,61 @@ class SlamSystem:
         return self.tsdf_manager.extract_mesh(min_weight=min_weight, level=level, colors=colors,
                                               min_component_faces=min_component_faces, keep_largest=keep_largest, **kw)
 
-    def evaluate_mesh(self, gt_vertices, gt_faces, n_samples=200_000, threshold=None, **extract_kw):
+    def align_trajectory(self, gt_positions):
+        """The Sim3 that moves the map's frame onto a ground truth's, from camera centres: tsdf.fit_sim3 of the keyframes'
+        centres (the translations of their T_WC, in keyframe order) onto gt_positions (K x 3, numpy or tensor, one row
+        per keyframe) -> f64[8] device tensor in lietorch layout.  An `init` for evaluate_mesh(align="icp").  Drains the
+        backend first, so the poses are the ones it has solved."""
+        from mast3r_slam.tsdf import fit_sim3
+
+        self.drain()
+        n = len(self.keyframes)
+        gt = torch.as_tensor(gt_positions, dtype=torch.float32).to(self.device).reshape(-1, 3)
+        if gt.shape[0] != n:
+            raise ValueError(f"SlamSystem.align_trajectory: {n} keyframes but {gt.shape[0]} ground-truth positions")
+        centres = [self.keyframes[i].T_WC.data.reshape(8)[:3] for i in range(n)]
+        est = torch.stack(centres).to(device=self.device, dtype=torch.float32) if n else gt.new_zeros((0, 3))
+        return fit_sim3(est, gt)[0]
+
+    def evaluate_mesh(self, gt_vertices, gt_faces, n_samples=200_000, threshold=None, align=None, init=None,
+                      gt_positions=None, align_kw=None, **extract_kw):
         """Quality of the global TSDF's mesh at this point of the run against a ground-truth mesh (gt_vertices f32[V,3],
-        gt_faces i32[F,3]; numpy arrays or device tensors, in the map's frame): the dict of tsdf.compare_meshes,
+        gt_faces i32[F,3]; numpy arrays or device tensors): the dict of tsdf.compare_meshes,
         accuracy / completion / precision / recall / fscore / chamfer (DESIGN.md "Mesh quality").  The mesh is
         self.extract_mesh(**extract_kw), so the backend is drained first and the config's clean-up default applies.
-        `threshold` defaults to tsdf_global.mesh_eval_threshold."""
+        `threshold` defaults to tsdf_global.mesh_eval_threshold.
+
+        `align=None`: the ground truth lies in the map's frame.  A Sim3 or "icp": compare_meshes(align=...) moves the
+        mesh into the ground truth's frame first (DESIGN.md "Mesh alignment"); `init` is where ICP starts - a Sim3, or
+        "trajectory" with `gt_positions` (K x 3, one row per keyframe) for self.align_trajectory(gt_positions);
+        `align_kw`: further arguments of tsdf.align_meshes."""
         if self.tsdf_manager is None:
             raise RuntimeError("SlamSystem.evaluate_mesh: the global TSDF is disabled (tsdf_global.enabled = False)")
         from mast3r_slam.tsdf import compare_meshes
 
         if threshold is None:
             threshold = float(self.tsdf_manager.cfg.get("mesh_eval_threshold", 0.05))
+        kw = {}
+        if align is not None:
+            kw["align"] = align
+            if isinstance(align, str):
+                kw["align_kw"] = dict(align_kw or {})
+                if isinstance(init, str):
+                    if init != "trajectory" or gt_positions is None:
+                        raise ValueError("SlamSystem.evaluate_mesh: init='trajectory' needs gt_positions")
+                    init = self.align_trajectory(gt_positions)
+                if init is not None:
+                    kw["align_kw"]["init"] = init
+            elif init is not None or align_kw:
+                raise ValueError("SlamSystem.evaluate_mesh: init and align_kw go with align='icp' only")
+        elif init is not None or align_kw:
+            raise ValueError("SlamSystem.evaluate_mesh: init and align_kw go with align='icp' only")
         mesh = self.extract_mesh(**extract_kw)
         dev = mesh[0].device
         gt_vertices = torch.as_tensor(gt_vertices, dtype=torch.float32).to(dev)
         gt_faces = torch.as_tensor(gt_faces, dtype=torch.int32).to(dev)
         return compare_meshes(mesh, (gt_vertices, gt_faces), n_samples=n_samples, threshold=threshold,
-                              _validate_pred=False)
+                              _validate_pred=False, **kw)
 
     def render_view(self, pose=None, rays=None, K=None, hw=None, **kw):
         """Depth / normal view of the global TSDF at this point of the run: (range f32[h,w], normals f32[h,w,3],

@@ -1,0 +1,177 @@
+"""Mesh alignment on the device: the closed-form similarity (Sim3) between corresponding points and trimmed
+point-to-mesh ICP, so that a monocular map - defined only up to a similarity - can be scored against a ground-truth mesh
+that lies in another frame.
+
+No counterpart in the reference.  The kernels are csrc/mesh_align.hip (DESIGN.md "Mesh alignment"); the numpy statement
+of the same definitions is tests/meshalign_numpy.py.  A Sim3 is lietorch's [t(3), q(xyzw), s] and acts as s R(q) p + t.
+"""
+import math
+
+import numpy as np
+import torch
+
+import mslam_hip as _m
+
+from .mesh_metrics import _mesh_arg, _pair, _sample
+
+STATE_BYTES = 72           # MSLAM_MESH_ALIGN_STATE_BYTES
+LOG_DOUBLES = 24           # MSLAM_MESH_ALIGN_LOG_DOUBLES
+OK, DEGENERATE = 0, 1      # MSLAM_MESH_ALIGN_OK / _DEGENERATE
+
+
+def _points_arg(x, name, what, device=None):
+    """f32[n,3] contiguous device tensor; numpy arrays and lists are moved to `device` (there is no CPU path)."""
+    if not torch.is_tensor(x):
+        if device is None:
+            raise TypeError(f"{what}: {name} must be a device tensor")
+        x = torch.as_tensor(np.asarray(x, np.float32)).to(device)
+    if x.dim() != 2 or x.shape[1] != 3:
+        raise ValueError(f"{what}: {name} must be (n,3), got {tuple(x.shape)}")
+    _m.require_dtype(x, torch.float32, name)
+    _m.ptr(x)
+    if x.shape[0] >= 1 << 31:
+        raise ValueError(f"{what}: too many points for the int32 index range")
+    return x.contiguous()
+
+
+def _sim3_arg(T, what, device, dtype):
+    """A Sim3 given as a tensor, array or sequence of 8 numbers (or a lietorch Sim3) -> tensor[8] on the device."""
+    T = getattr(T, "data", T)
+    T = T.detach().to(device=device, dtype=dtype) if torch.is_tensor(T) else torch.as_tensor(
+        np.asarray(T, np.float64), dtype=dtype, device=device)
+    if T.numel() != 8:
+        raise ValueError(f"{what}: a Sim3 is 8 numbers [t(3), q(xyzw), s], got shape {tuple(T.shape)}")
+    return T.reshape(8).contiguous()
+
+
+def _read_state(state):
+    """(T f64[8], T32 f32[8], status i32[1]) device tensors of a state block."""
+    dev = state.device
+    T64 = torch.empty(8, dtype=torch.float64, device=dev)
+    T32 = torch.empty(8, dtype=torch.float32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    _m.check(_m.lib().mslam_mesh_align_read(_m.ptr(state), _m.ptr(T64), _m.ptr(T32), _m.ptr(status), _m.stream_ptr()),
+             "mesh_align_read")
+    return T64, T32, status
+
+
+def fit_sim3(src, dst, weights=None, with_scale=True):
+    """The similarity that moves the points src f32[n,3] onto dst f32[n,3] (device tensors) in the weighted least-squares
+    sense (Umeyama; the rotation by Horn's quaternion method, always a proper rotation, defined for coplanar points)
+    -> (T f64[8], T32 f32[8]) device tensors in lietorch layout.  `weights` f32[n] >= 0, a pair of weight 0 does not
+    count; `with_scale=False` fixes the scale at 1.  Raises ValueError when the problem is degenerate: fewer than 3
+    pairs that count, no spread among the source points, or no positive scale.  One host read: the status."""
+    src = _points_arg(src, "src", "fit_sim3")
+    dst = _points_arg(dst, "dst", "fit_sim3")
+    if src.shape != dst.shape:
+        raise ValueError(f"fit_sim3: src {tuple(src.shape)} and dst {tuple(dst.shape)} differ in shape")
+    if src.device != dst.device:
+        raise ValueError("fit_sim3: src and dst are on different devices")
+    n, dev = int(src.shape[0]), src.device
+    if weights is not None:
+        if not torch.is_tensor(weights):
+            raise TypeError("fit_sim3: weights must be a device tensor")
+        if tuple(weights.shape) != (n,):
+            raise ValueError(f"fit_sim3: weights must be ({n},), got {tuple(weights.shape)}")
+        _m.require_dtype(weights, torch.float32, "weights")
+        _m.ptr(weights)
+        if weights.device != dev:
+            raise ValueError("fit_sim3: weights are on another device")
+        weights = weights.contiguous()
+    L = _m.lib()
+    ws_bytes = int(L.mslam_mesh_align_workspace_bytes(n, 0, 0))
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    state = torch.empty(STATE_BYTES, dtype=torch.uint8, device=dev)
+    log = torch.empty(LOG_DOUBLES, dtype=torch.float64, device=dev)
+    _m.check(L.mslam_mesh_align_fit_pairs(_m.ptr(src), _m.ptr(dst), _m.ptr(weights), n, 1 if with_scale else 0,
+                                          _m.ptr(ws), ws_bytes, _m.ptr(state), _m.ptr(log), _m.stream_ptr()),
+             "mesh_align_fit_pairs")
+    T64, T32, status = _read_state(state)
+    if int(status) != OK:
+        raise ValueError(f"fit_sim3: degenerate problem ({n} pairs): fewer than 3 pairs that count, no spread among "
+                         "the source points, or no positive scale")
+    return T64, T32
+
+
+def transform_mesh(vertices, T, normals=None):
+    """The vertices f32[V,3] moved by the Sim3 T (s R v + t, in f64, stored f32) and, when given, the normals rotated
+    (R n): torch ops on the vertices' device.  Returns the vertices, or (vertices, normals)."""
+    if not torch.is_tensor(vertices):
+        raise TypeError("transform_mesh: vertices must be a tensor")
+    if vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError(f"transform_mesh: vertices must be (V,3), got {tuple(vertices.shape)}")
+    T = _sim3_arg(T, "transform_mesh", vertices.device, torch.float64)
+    x, y, z, w = T[3:7] / torch.linalg.vector_norm(T[3:7])
+    R = torch.stack([1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - z * w), 2.0 * (x * z + y * w),
+                     2.0 * (x * y + z * w), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - x * w),
+                     2.0 * (x * z - y * w), 2.0 * (y * z + x * w), 1.0 - 2.0 * (x * x + y * y)]).reshape(3, 3)
+    moved = (T[7] * (vertices.to(torch.float64) @ R.T) + T[:3]).to(vertices.dtype)
+    if normals is None:
+        return moved
+    return moved, (normals.to(torch.float64) @ R.T).to(normals.dtype)
+
+
+def align_meshes(pred, gt, init=None, n_samples=20000, max_iters=50, trim=math.inf, with_scale=True, seed=0, tol=1e-6,
+                 check_every=5):
+    """Trimmed point-to-mesh ICP of the mesh `pred` onto the mesh `gt` (both (vertices f32[V,3], faces i32[F,3]) device
+    tensors or extract_mesh tuples): the Sim3 T with T(pred) ~ gt.
+
+    n_samples points are drawn on pred (sample_mesh with `seed`) once.  Every iteration moves them by the current T,
+    finds the exact closest point of gt for each (the culled scan of mesh_distance, warm-started from the last
+    iteration's faces; gt's tile boxes are built once), keeps the pairs within `trim` (in gt's units; +inf keeps all;
+    a sequence gives one value per iteration) and replaces T by the closed-form similarity of the original samples onto
+    their closest points (`with_scale=False`: scale 1).  Nothing is read back except the log, once every `check_every`
+    iterations; the loop stops when the RMSE of two successive iterations differs by at most `tol` relative, when an
+    iteration is degenerate (fewer than 3 pairs within `trim`), or after `max_iters`.
+
+    ICP is a LOCAL method: it needs `init` (a Sim3, default the identity) for anything beyond a modest offset.  On a
+    partial room, a numpy prototype recovered 8 degrees / 15 cm / scale 0.9 and failed at 15 degrees / 0.3 m / scale
+    0.8, where the samples slid along a wall.  SlamSystem.align_trajectory gives an `init` from camera centres.
+
+    Returns a dict: T (f64[8] device tensor), iterations (the steps run), converged, rmse and inliers (of the last
+    iteration: the pairs within trim under the T that iteration started from, and their RMSE), history (numpy
+    f64[iterations, 4]: inliers, rmse, scale after the solve, status)."""
+    what = "align_meshes"
+    max_iters, check_every = int(max_iters), int(check_every)
+    if max_iters < 1 or check_every < 1:
+        raise ValueError(f"{what}: max_iters and check_every must be >= 1, got {max_iters} and {check_every}")
+    if not float(tol) >= 0.0:
+        raise ValueError(f"{what}: tol must be >= 0, got {tol}")
+    trims = [float(t) for t in trim] if isinstance(trim, (list, tuple, np.ndarray)) else [float(trim)] * max_iters
+    if len(trims) != max_iters:
+        raise ValueError(f"{what}: a trim sequence needs one value per iteration ({max_iters}), got {len(trims)}")
+    if not all(t >= 0.0 for t in trims):
+        raise ValueError(f"{what}: trim must be >= 0 (+inf keeps every pair)")
+    pv, pf, pV, pF = _mesh_arg(*_pair(pred, "pred"), True, what)
+    gv, gf, gV, gF = _mesh_arg(*_pair(gt, "gt"), True, what)
+    if pv.device != gv.device:
+        raise ValueError(f"{what}: pred and gt are on different devices")
+    dev = pv.device
+    src = _sample(pv, pf, pV, pF, n_samples, seed, what)[0]
+    n = int(src.shape[0])
+    T0 = None if init is None else _sim3_arg(init, what, dev, torch.float32)
+    L, st = _m.lib(), _m.stream_ptr()
+    ws_bytes = int(L.mslam_mesh_align_workspace_bytes(n, gF, 0))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    state = torch.empty(STATE_BYTES, dtype=torch.uint8, device=dev)
+    log = torch.zeros((max_iters, LOG_DOUBLES), dtype=torch.float64, device=dev)
+    nearest = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    moved = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    dist2 = torch.empty(n, dtype=torch.float64, device=dev)
+    _m.check(L.mslam_mesh_align_init(_m.ptr(T0), _m.ptr(gv), _m.ptr(gf), gF, gV, _m.ptr(ws), ws_bytes, _m.ptr(state),
+                                     st), "mesh_align_init")
+    converged, hist, it = False, None, 0
+    for it in range(max_iters):
+        _m.check(L.mslam_mesh_align_step(_m.ptr(src), n, _m.ptr(gv), _m.ptr(gf), gF, gV, trims[it],
+                                         1 if with_scale else 0, 0, _m.ptr(ws), ws_bytes, _m.ptr(state),
+                                         _m.ptr(nearest), _m.ptr(moved), _m.ptr(dist2), 0, _m.ptr(log[it]), st),
+                 "mesh_align_step")
+        if (it + 1) % check_every == 0 or it + 1 == max_iters:
+            hist = log[:it + 1, :4].cpu().numpy()                      # the one host read of this stretch
+            if hist[it, 3] != OK:
+                break
+            if it >= 1 and abs(hist[it, 1] - hist[it - 1, 1]) <= float(tol) * hist[it - 1, 1]:
+                converged = True
+                break
+    return dict(T=_read_state(state)[0], iterations=it + 1, converged=converged, rmse=float(hist[it, 1]),
+                inliers=int(hist[it, 0]), history=hist)

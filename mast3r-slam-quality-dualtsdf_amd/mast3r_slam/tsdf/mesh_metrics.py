@@ -4,7 +4,8 @@ to a triangle mesh, and the accuracy / completion / precision / recall / F-score
 No counterpart in the reference.  The kernels are csrc/mesh_distance.hip (DESIGN.md "Mesh quality"); the numpy
 statement of the same definitions is tests/meshdist_numpy.py.  A face is valid when its indices lie in [0, V) and its
 cross product is not exactly zero; an invalid face has area 0, is never sampled and is never the nearest face.  The two
-meshes of a comparison must be given in one frame: nothing here aligns them.
+meshes of a comparison must lie in one frame; compare_meshes(align=...) moves the first into the second's frame first
+(mesh_align.py, DESIGN.md "Mesh alignment").
 """
 import torch
 
@@ -114,16 +115,41 @@ def _pair(mesh, what):
     raise ValueError(f"compare_meshes: {what} must be (vertices, faces) or an extract_mesh tuple")
 
 
-def compare_meshes(pred, gt, n_samples=200_000, threshold=0.05, seed=0, skip=True, _validate_pred=True):
+def compare_meshes(pred, gt, n_samples=200_000, threshold=0.05, seed=0, skip=True, _validate_pred=True, align=None,
+                   align_kw=None):
     """Quality of the mesh `pred` against the ground truth `gt`, both (vertices f32[V,3], faces i32[F,3]) device tensors
     or the tuples extract_mesh returns (normals and colours are ignored), in one frame.  n_samples points are drawn on
     each (sample_mesh with `seed` on pred, `seed + 1` on gt) and measured against the other (mesh_distance).  Returns
     Python numbers: accuracy / accuracy_median (pred samples to gt, mean and median), completion / completion_median
     (gt samples to pred), precision / recall (share of pred / gt samples within `threshold`), fscore (their harmonic
     mean, 0 when both are 0), chamfer = (accuracy + completion) / 2, n_samples, threshold, pred_area, gt_area.  The
-    means are f64 sums.  Host reads: the index range of each mesh, each total area, and the figures at the end."""
+    means are f64 sums.  Host reads: the index range of each mesh, each total area, and the figures at the end.
+
+    `align`: None - the meshes are taken as they are; a Sim3 ([t(3), q(xyzw), s], 8 numbers) - pred is moved by it first
+    (transform_mesh); "icp" - pred is moved by align_meshes(pred, gt, **align_kw) first (a local method: pass
+    align_kw=dict(init=...) for more than a modest offset).  With alignment the dict gains `alignment`: T (a list of 8
+    floats), rmse and iterations (None for a given Sim3)."""
     n = int(n_samples)
     threshold = float(threshold)
+    alignment = None
+    if align is not None:
+        from .mesh_align import _sim3_arg, align_meshes, transform_mesh
+
+        pvert, pfaces = _pair(pred, "pred")
+        if isinstance(align, str):
+            if align != "icp":
+                raise ValueError(f"compare_meshes: align must be None, a Sim3 or 'icp', got {align!r}")
+            res = align_meshes((pvert, pfaces), gt, **(align_kw or {}))
+            T, alignment = res["T"], dict(rmse=res["rmse"], iterations=res["iterations"])
+        else:
+            if align_kw:
+                raise ValueError("compare_meshes: align_kw goes with align='icp' only")
+            T, alignment = _sim3_arg(align, "compare_meshes", pvert.device, torch.float64), dict(rmse=None,
+                                                                                               iterations=None)
+        alignment["T"] = T.tolist()
+        pred = (transform_mesh(pvert, T), pfaces)
+    elif align_kw:
+        raise ValueError("compare_meshes: align_kw goes with align='icp' only")
     pv, pf, pV, pF = _mesh_arg(*_pair(pred, "pred"), _validate_pred, "compare_meshes")
     gv, gf, gV, gF = _mesh_arg(*_pair(gt, "gt"), True, "compare_meshes")
     p_pts, _, p_area = _sample(pv, pf, pV, pF, n, seed, "compare_meshes (pred)")
@@ -134,6 +160,9 @@ def compare_meshes(pred, gt, n_samples=200_000, threshold=0.05, seed=0, skip=Tru
         s = torch.sort(d)[0]
         out += [d.sum() / n, 0.5 * (s[(n - 1) // 2] + s[n // 2]), (d <= threshold).sum().to(torch.float64) / n]
     acc, acc_med, prec, comp, comp_med, rec = torch.stack(out).tolist()          # the one host read of the figures
-    return dict(accuracy=acc, accuracy_median=acc_med, completion=comp, completion_median=comp_med, precision=prec,
-                recall=rec, fscore=2.0 * prec * rec / (prec + rec) if prec + rec > 0.0 else 0.0,
-                chamfer=0.5 * (acc + comp), n_samples=n, threshold=threshold, pred_area=p_area, gt_area=g_area)
+    out = dict(accuracy=acc, accuracy_median=acc_med, completion=comp, completion_median=comp_med, precision=prec,
+               recall=rec, fscore=2.0 * prec * rec / (prec + rec) if prec + rec > 0.0 else 0.0,
+               chamfer=0.5 * (acc + comp), n_samples=n, threshold=threshold, pred_area=p_area, gt_area=g_area)
+    if alignment is not None:
+        out["alignment"] = alignment
+    return out
