@@ -279,6 +279,47 @@ int mslam_mesh_cc_emit(const float* vertices, const float* normals, const float*
                        float* out_colors, int32_t* out_faces, int64_t n_out_vertices, int64_t n_out_faces,
                        void* stream);
 
+/* Mesh simplification: vertices clustered on a uniform grid, each cluster's vertex placed by the plane quadrics of the
+ * faces that touch its cell (no counterpart in the reference, DESIGN.md "Mesh simplification").  vertices / normals /
+ * colors f32[V,3], faces i32[F,3]; every index read from memory is checked before it is followed and an element that
+ * fails is skipped.  All arithmetic is f64 on the f32 inputs, every sum runs in one fixed order, nothing is atomic: the
+ * same input gives the same bits.  Sequence, on one stream (C clusters, 3 F < 2^31, C F < 2^62):
+ *   mslam_mesh_simplify_keys   keys i64[V]: the packed cell floor(p / cell_size) of each vertex, 21 bits per axis biased
+ *                              by 2^20, x highest; INT64_MAX for a coordinate that is not finite or a cell outside
+ *                              [-2^20, 2^20).  The caller sorts them (stable) -> sorted_keys, vertex_order; numbers the
+ *                              distinct keys 0..C-1 -> cluster i32[V]; vertex_start i64[C+1]: the first sorted position
+ *                              of each cluster, V at the end.
+ *   mslam_mesh_simplify_faces  tri i32[F,3]: the face in cluster ids, rotated so that the smallest is first, -1 -1 -1
+ *                              unless the three differ.  packed != 0 (needs C^3 < 2^62): key_lo i64[F] = (t0 C + t1) C +
+ *                              t2, key_hi unused (may be NULL); 0: key_lo = t1 C + t2, key_hi = t0; INT64_MAX for a
+ *                              collapsed face.  pairs i64[3 F]: cluster * F + face, once per distinct cluster of a face
+ *                              whose indices are in range, INT64_MAX in the other slots.  The caller sorts the pairs ->
+ *                              sorted_pairs, pair_start i64[C+1] (the first pair with key >= cluster * F), and the triple
+ *                              keys -> face_order i64[F].
+ *   mslam_mesh_simplify_solve  per cluster c: x0 = the cell's centre; m = mean of (p - x0) over its vertices in ascending
+ *                              index; quadric != 0: A = sum w u u^T, b = sum w d u over its pairs' valid faces
+ *                              (mslam_mesh_face_areas' rule) in ascending index, u the unit normal, w the area, d = -u .
+ *                              (a - x0); x = m + sum over eigenpairs with lambda > 1e-3 lambda_max of e (e . (-b - A m)) /
+ *                              lambda, or m when lambda_max <= 0, some |x_j| > cell_size / 2 or x is not finite.
+ *                              out_vertices f32[C,3] = x0 + x; out_normals = the normalised sum of the normals (0 if
+ *                              the sum is 0); out_colors = the mean colour (colors and out_colors both NULL: none);
+ *                              out_fallback i32[C] (may be NULL) = 1 where x = m.
+ *   mslam_mesh_simplify_mark   sorted_tri i32[F,3] = tri in face_order (0 0 0 for a collapsed face); keep_face i32[F] = 1
+ *                              for a live face that differs from its predecessor; referenced i32[C] (zeroed by the
+ *                              caller) = 1 at every cluster of a kept face.
+ * The caller then scans the flags and calls mslam_mesh_cc_emit on (out_vertices, ..., sorted_tri). */
+int mslam_mesh_simplify_keys(const float* vertices, int num_vertices, double cell_size, int64_t* keys, void* stream);
+int mslam_mesh_simplify_faces(const int32_t* faces, int num_faces, int num_vertices, const int32_t* cluster,
+                              int num_clusters, int packed, int32_t* tri, int64_t* key_hi, int64_t* key_lo,
+                              int64_t* pairs, void* stream);
+int mslam_mesh_simplify_solve(const float* vertices, const float* normals, const float* colors, const int32_t* faces,
+                              int num_faces, int num_vertices, double cell_size, const int64_t* sorted_keys,
+                              const int64_t* vertex_order, const int64_t* vertex_start, const int64_t* sorted_pairs,
+                              const int64_t* pair_start, int num_clusters, int quadric, float* out_vertices,
+                              float* out_normals, float* out_colors, int32_t* out_fallback, void* stream);
+int mslam_mesh_simplify_mark(const int32_t* tri, const int64_t* face_order, int num_faces, int num_clusters,
+                             int32_t* sorted_tri, int32_t* keep_face, int32_t* referenced, void* stream);
+
 /* Mesh quality: face areas, a surface sampler and the exact point-to-mesh distance (no counterpart in the reference,
  * DESIGN.md "Mesh quality").  vertices f32[V,3], faces i32[F,3]; every index is checked against [0, V) before use.  A
  * face is valid when its indices are in range and (b - a) x (c - a), in f64, is not exactly zero; an invalid face has

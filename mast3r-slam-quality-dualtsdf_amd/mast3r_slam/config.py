@@ -39,6 +39,7 @@ _BASE = {
         "samples_per_kf": 2000, "lambda": 0.15, "max_iterations": 3, "pre_icp_iters": 2, "damping": 1.0e-4,
         "color": False,     # fuse the keyframes' uimg into the volume: coloured meshes and views (DESIGN.md "Colour")
         "mesh_min_component_faces": 0,   # SlamSystem.extract_mesh drops smaller components (DESIGN.md "Mesh components")
+        "mesh_simplify_voxels": 0.0,     # ... and simplifies on cells of this many voxels, 0 = off ("Mesh simplification")
         "mesh_eval_threshold": 0.05,     # SlamSystem.evaluate_mesh: precision / recall distance (DESIGN.md "Mesh quality")
     },
 }

@@ -224,16 +224,20 @@ def save_mesh_metrics(savedir, filename, metrics):
 
 
 def save_tsdf_mesh(savedir, filename, source, min_weight=None, level=0.0, colors=False, min_component_faces=0,
-                   keep_largest=None):
+                   keep_largest=None, simplify_cell=0.0, simplify_position="quadric"):
     """The global TSDF's triangle mesh (marching cubes) as PLY with normals, beside save_reconstruction's point cloud.
     `source`: a SlamSystem, a TSDFGlobalManager or a TSDFVolume.  `colors=True` (a volume with tsdf_global.color): the
     vertices carry the fused colour as red / green / blue.  `min_component_faces` > 0 / `keep_largest`: small connected
-    components are dropped first (DESIGN.md "Mesh components").  Returns (V, F)."""
+    components are dropped first (DESIGN.md "Mesh components").  `simplify_cell` > 0 (world units) /
+    `simplify_position`: the mesh is then simplified by vertex clustering (DESIGN.md "Mesh simplification").  Returns
+    (V, F)."""
     savedir = pathlib.Path(savedir)
     savedir.mkdir(exist_ok=True, parents=True)
     kw = {}
     if min_component_faces > 0 or keep_largest is not None:
         kw = dict(min_component_faces=min_component_faces, keep_largest=keep_largest)
+    if simplify_cell is not None and simplify_cell > 0:
+        kw = dict(kw, simplify_cell=simplify_cell, simplify_position=simplify_position)
     if colors:
         v, n, f, c = source.extract_mesh(min_weight=min_weight, level=level, colors=True, **kw)
         save_mesh(savedir / filename, v, f, normals=n, colors=c)

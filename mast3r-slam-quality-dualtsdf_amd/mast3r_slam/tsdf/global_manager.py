@@ -168,12 +168,17 @@ class TSDFGlobalManager:
         if self.enabled:
             self.volume.maintain()   # samples dropped by the last solve are reported here
 
-    def extract_mesh(self, min_weight=None, level=0.0, colors=False, min_component_faces=0, keep_largest=None, **kw):
+    def extract_mesh(self, min_weight=None, level=0.0, colors=False, min_component_faces=0, keep_largest=None,
+                     simplify_cell=0.0, simplify_position="quadric", **kw):
         """Triangle mesh of the global volume: (vertices f32[V,3], normals f32[V,3], faces i32[F,3]) device tensors
         (TSDFVolume.extract_mesh); `colors=True`: vertex colours f32[V,3] as a fourth tensor.  `min_component_faces` /
-        `keep_largest`: drop small connected components (DESIGN.md "Mesh components"); off by default."""
+        `keep_largest`: drop small connected components (DESIGN.md "Mesh components"); off by default.  `simplify_cell`
+        > 0 (world units) / `simplify_position`: simplify the result by vertex clustering (DESIGN.md "Mesh
+        simplification"); off by default."""
         if min_component_faces > 0 or keep_largest is not None:
             kw = dict(kw, min_component_faces=min_component_faces, keep_largest=keep_largest)
+        if simplify_cell is not None and simplify_cell > 0:
+            kw = dict(kw, simplify_cell=simplify_cell, simplify_position=simplify_position)
         if not colors and not kw:
             return self.volume.extract_mesh(min_weight=min_weight, level=level)
         return self.volume.extract_mesh(min_weight=min_weight, level=level, colors=colors, **kw)
