@@ -540,6 +540,58 @@ int mslam_attention_bf16(const void* Q, const void* K, const void* VT, void* O, 
 /* torch.nn.LayerNorm over the last dim (D <= 2048): x f32[rows,D] -> bf16 and/or f32 outputs. */
 int mslam_layernorm_f32(const float* x, const float* w, const float* b, void* out_bf16, float* out_f32,
                         int rows, int D, float eps, void* stream);
+/* The glue between those blocks.  Every entry below builds its launch with the very helper the forward uses (strides of
+ * a grouped launch, choice between two forms of a kernel), so a test of the entry is a test of the forward's launch. */
+/* HOST arrays cos, sin f32[len][16] <- cos / sin(p * 100^(-2i/32)), p < len, i < 16: the RoPE2D tables mslam_mast3r_create
+ * uploads (len 1024). */
+int mslam_rope_tables(float* cos_out, float* sin_out, int len);
+/* Attention projection: x = A[M,K] . W^T + bias, W [n_sections*heads*64, K] holding sections sec_base ... (0 q, 1 k, 2 v).
+ * q, k <- RoPE2D(x) (q also * q_scale) as bf16 [B,heads,ntok,64]; vt <- x transposed per head, bf16 [B,heads,64,kv_ntok];
+ * token n of an image sits at (n / tok_w, n % tok_w); rows are whole images of ntok (q) / kv_ntok (k, v) tokens, both
+ * divisible by 4.  W1 != NULL: a second problem (W1, bias1) on rows [M, 2M) of A, its outputs M*heads*64 elements behind
+ * the first one's.  rope_cos / rope_sin: DEVICE copies of mslam_rope_tables(rope_len).  Outputs of sections the launch does
+ * not hold are not touched (and may be NULL). */
+int mslam_gemm_attn_bf16(const void* A, const void* W0, const float* bias0, const void* W1, const float* bias1, void* q,
+                         void* k, void* vt, int M, int K, int n_sections, int sec_base, int heads, int ntok, int kv_ntok,
+                         int tok_w, const float* rope_cos, const float* rope_sin, int rope_len, float q_scale,
+                         void* stream);
+/* Both sides of a decoder layer in one launch: out[s] = act(A[s] . Ws^T + bias_s) (+ residual[s]), s = 0, 1, with A, the
+ * residual and out stacked as [2M, .].  out f32: optional f32 residual, which may be out itself (the residual stream);
+ * out bf16: no residual. */
+int mslam_gemm_grouped_bf16(const void* A, const void* W0, const float* bias0, const void* W1, const float* bias1,
+                            const float* residual_f32, void* out, int M, int N, int K, int act, int out_is_bf16,
+                            void* stream);
+/* ConvTranspose2d with kernel == stride s on NHWC bf16: W bf16 [Cout*s*s, Cin] with row co*s*s + i*s + j, bias f32 [Cout];
+ * out[b, y*s+i, x*s+j, co] bf16 [B, H*s, W*s, Cout].  Cin % 8 == 0. */
+int mslam_conv_transpose_nhwc_bf16(const void* in, const void* W, const float* bias, void* out_bf16, int B, int H, int Wd,
+                                   int Cin, int Cout, int s, void* stream);
+/* mslam_conv2d_nhwc_bf16 with two optional bf16 residuals, both added after act (the residual unit of the DPT fusion
+ * blocks: conv2(...) + x + the other path). */
+int mslam_conv2d_res2_nhwc_bf16(const void* in, const void* W, const float* bias, const void* residual1_bf16,
+                                const void* residual2_bf16, void* out_bf16, int B, int H, int Wd, int Cin, int Cout, int ks,
+                                int stride, int relu_in, int act, void* stream);
+/* LayerNorm of the two stacked decoder sides x f32 [2M, D], side s with its own affine pair: out_self[row] bf16 <-
+ * self_s(x[row]).  With the mem pairs (all of mem0_w ... out_mem non-NULL; all NULL otherwise) also the norm_y each side
+ * applies to the OTHER side's tokens: out_mem rows [0, M) <- mem0(x[M + r]), rows [M, 2M) <- mem1(x[r]). */
+int mslam_layernorm_group_bf16(const float* x, const float* self0_w, const float* self0_b, const float* self1_w,
+                               const float* self1_b, const float* mem0_w, const float* mem0_b, const float* mem1_w,
+                               const float* mem1_b, void* out_self, void* out_mem, int M, int D, float eps, void* stream);
+/* Bilinear x2, align_corners=True, NHWC bf16 [B,H,W,C] -> [B,2H,2W,C].  C % 8 == 0. */
+int mslam_upsample2x_nhwc_bf16(const void* in, void* out, int B, int H, int Wd, int C, void* stream);
+/* Tail of a head: l = w4[4,fc] . feat[pixel] + b4; X f32[B,H,W,3] <- l[0:3] * expm1(d)/d, d = |l[0:3]|; C <- 1 + exp(l[3]);
+ * local features lf f32 [B*(H/P)*(W/P), lf_ld], channel c of pixel (y, x) at [token][c*P*P + (y%P)*P + x%P]:
+ * D f32[B,H,W,desc_dim] <- unit vector of channels [0, desc_dim), Q <- exp(channel desc_dim).  feat bf16 [B,H,W,fc],
+ * fc % 8 == 0, desc_dim <= 31, P divides H and W.  force_generic != 0: the per-pixel form also where the patch form
+ * (P 16, fc 128, desc_dim 24) would run. */
+int mslam_head_post(const void* feat_bf16, int fc, const float* w4, const float* b4, const float* lf, int lf_ld,
+                    int desc_dim, int P, int B, int H, int Wd, float* X, float* C, float* D, float* Q, int force_generic,
+                    void* stream);
+/* img f32 [B,3,H,W] -> patches bf16 [B*(H/P)*(W/P), 3*P*P], column c*P*P + ky*P + kx (Conv2d weight order). */
+int mslam_patchify_bf16(const float* img, void* patches_bf16, int B, int H, int Wd, int P, void* stream);
+/* out bf16 [rows, ca+cb] <- cat(a [rows,ca], b [rows,cb]) along the columns. */
+int mslam_concat2_bf16(const void* a, int ca, const void* b, int cb, void* out, long long rows, void* stream);
+/* y bf16[n] <- x f32[n], round to nearest even. */
+int mslam_cast_f32_bf16(const float* x, void* y_bf16, long long n, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Local dense-block TSDF (camera-side half of the "dual TSDF"): replaces the python loops of

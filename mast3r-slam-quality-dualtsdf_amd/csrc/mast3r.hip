@@ -492,9 +492,13 @@ static void layernorm(Ctx& c, const float* x, const Norm& n, int rows, bf16* out
   dbg(c, "layernorm", rows, n.d);
 }
 
+static void launch_cast_bf16(const float* x, bf16* y, size_t n, hipStream_t s) {
+  hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3((unsigned)((n / 4 + 255) / 256 + 1)), dim3(256), 0, s, x, y, n);
+}
+
 static void cast_bf16(Ctx& c, const float* x, bf16* y, size_t n) {
   if (c.dry() || c.rc) return;
-  hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3((unsigned)((n / 4 + 255) / 256 + 1)), dim3(256), 0, c.s, x, y, n);
+  launch_cast_bf16(x, y, n, c.s);
   dbg(c, "cast", (int)n);
 }
 
@@ -502,17 +506,26 @@ struct AttnBufs { bf16 *q, *k, *vt, *o; };
 
 // Attention projection with the RoPE / head-split epilogue.  With l1 (decoder): both sides in one launch, side 1 at
 // rows [M, 2M) of A and behind side 0's M / ntok images in q/k/vt.
-static void attn_project(Ctx& c, const bf16* A, int M, const Lin& l, int sec_base, int heads, int ntok, int kv_ntok,
-                         int tok_w, const AttnBufs& ab, const Pf& pf = Pf(), const Lin* l1 = nullptr) {
+static GemmArgs attn_args(const bf16* A, int M, const Lin& l, int sec_base, int heads, int ntok, int kv_ntok, int tok_w,
+                          const AttnBufs& ab, const float* rope_cos, const float* rope_sin, float q_scale,
+                          const Lin* l1) {
   GemmArgs g = dense_args(A, M, l);
-  set_pf(c, g, pf);
   g.epi = EPI_ATTN; g.sec_base = sec_base; g.sec_dim = heads * 64; g.heads = heads; g.ntok = ntok; g.kv_ntok = kv_ntok;
-  g.tok_w = tok_w; g.q_out = ab.q; g.k_out = ab.k; g.vt_out = ab.vt; g.rope_cos = c.m->rope_cos;
-  g.rope_sin = c.m->rope_sin; g.q_scale = 0.125f;  // head_dim 64 ** -0.5
+  g.tok_w = tok_w; g.q_out = ab.q; g.k_out = ab.k; g.vt_out = ab.vt; g.rope_cos = rope_cos;
+  g.rope_sin = rope_sin; g.q_scale = q_scale;
   if (l1) {
     group2(g, *l1, (size_t)M * l.in, 0);
-    g.qkv_gstride = (size_t)(M / ntok) * heads * 64 * (sec_base == 0 ? ntok : kv_ntok);
+    // the M rows of a side are whole images of ntok (q) or kv_ntok (k, v) tokens: M * heads * 64 elements either way
+    g.qkv_gstride = (size_t)M * heads * 64;
   }
+  return g;
+}
+
+static void attn_project(Ctx& c, const bf16* A, int M, const Lin& l, int sec_base, int heads, int ntok, int kv_ntok,
+                         int tok_w, const AttnBufs& ab, const Pf& pf = Pf(), const Lin* l1 = nullptr) {
+  GemmArgs g = attn_args(A, M, l, sec_base, heads, ntok, kv_ntok, tok_w, ab, c.m->rope_cos, c.m->rope_sin,
+                         0.125f /* head_dim 64 ** -0.5 */, l1);
+  set_pf(c, g, pf);
   run_gemm(c, g);
 }
 
@@ -522,25 +535,37 @@ static void attention(Ctx& c, const AttnBufs& ab, int B, int heads, int nq, int 
   dbg(c, "attention", B * heads, nq, nk);
 }
 
-// x (f32 residual stream, [M,D]) += Linear(A) (+bias)
-static void linear_residual(Ctx& c, const bf16* A, int M, const Lin& l, float* x, const Pf& pf = Pf(),
-                            const Lin* l1 = nullptr) {
+// out f32 [M,D] = res (f32, may be out itself) + Linear(A) (+bias); with l1 both sides, side 1 M rows behind side 0
+static GemmArgs linear_residual_args(const bf16* A, int M, const Lin& l, const float* res, float* out, const Lin* l1) {
   GemmArgs g = dense_args(A, M, l);
-  set_pf(c, g, pf);
-  g.res1 = x; g.res1_kind = KIND_F32; g.out = x; g.out_kind = KIND_F32;
+  if (res) { g.res1 = res; g.res1_kind = KIND_F32; }
+  g.out = out; g.out_kind = KIND_F32;
   if (l1) {
     group2(g, *l1, (size_t)M * l.in, (size_t)M * l.out * sizeof(float));
     g.res1_gbytes = g.out_gbytes;
   }
+  return g;
+}
+
+static GemmArgs linear_bf16_args(const bf16* A, int M, const Lin& l, bf16* out, int act, const Lin* l1) {
+  GemmArgs g = dense_args(A, M, l);
+  g.out = out; g.out_kind = KIND_BF16; g.act = act;
+  if (l1) group2(g, *l1, (size_t)M * l.in, (size_t)M * l.out * sizeof(bf16));
+  return g;
+}
+
+// x (f32 residual stream, [M,D]) += Linear(A) (+bias)
+static void linear_residual(Ctx& c, const bf16* A, int M, const Lin& l, float* x, const Pf& pf = Pf(),
+                            const Lin* l1 = nullptr) {
+  GemmArgs g = linear_residual_args(A, M, l, x, x, l1);
+  set_pf(c, g, pf);
   run_gemm(c, g);
 }
 
 static void linear_bf16(Ctx& c, const bf16* A, int M, const Lin& l, bf16* out, int act, const Pf& pf = Pf(),
                         const Lin* l1 = nullptr) {
-  GemmArgs g = dense_args(A, M, l);
+  GemmArgs g = linear_bf16_args(A, M, l, out, act, l1);
   set_pf(c, g, pf);
-  g.out = out; g.out_kind = KIND_BF16; g.act = act;
-  if (l1) group2(g, *l1, (size_t)M * l.in, (size_t)M * l.out * sizeof(bf16));
   run_gemm(c, g);
 }
 
@@ -570,6 +595,11 @@ static void mlp_residual(Ctx& c, float* x, int M, const Norm& n, const Lin& fc1,
   linear_residual(c, s.u, M, fc2, x, pf2);
 }
 
+static void launch_patchify(const float* img, bf16* patches, int B, int H, int W, int P, hipStream_t s) {
+  const size_t total = (size_t)B * (H / P) * (W / P) * 3 * P * P;
+  hipLaunchKernelGGL(patchify_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, img, patches, B, H, W, P);
+}
+
 // feat_out f32 [B*N, E] (enc_norm output)
 static void encode(Ctx& c, const float* img, int B, int H, int W, float* feat_out) {
   const Mast3rModel& m = *c.m;
@@ -578,9 +608,7 @@ static void encode(Ctx& c, const float* img, int B, int H, int W, float* feat_ou
   float* x = c.ar.get<float>((size_t)M * m.E);
   BlockScratch s = block_scratch(c, M, m.E);
   if (!c.dry() && !c.rc) {
-    const size_t total = (size_t)M * KP;
-    hipLaunchKernelGGL(patchify_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c.s, img, patches, B, H, W,
-                       m.P);
+    launch_patchify(img, patches, B, H, W, m.P, c.s);
     dbg(c, "patchify", B, H, W);
   }
   linear_f32(c, patches, M, m.pe, x);
@@ -607,32 +635,47 @@ static GemmArgs conv_args(const bf16* in, int B, int H, int W, int C, const Lin&
   return g;
 }
 
+// output, activations and the (optional) bf16 residuals of a convolution described by conv_args
+static void conv_epilogue(GemmArgs& g, bf16* out, int a_relu, int act, const bf16* res1, const bf16* res2) {
+  g.out = out; g.a_relu = a_relu; g.act = act;
+  if (res1) { g.res1 = res1; g.res1_kind = KIND_BF16; }
+  if (res2) { g.res2 = res2; g.res2_kind = KIND_BF16; }
+}
+
 static bf16* conv(Ctx& c, const bf16* in, int B, int H, int W, int C, const Lin& l, int ks, int stride, int a_relu,
                   int act, const bf16* res1, const bf16* res2) {
   GemmArgs g = conv_args(in, B, H, W, C, l, ks, stride);
   bf16* out = c.ar.get<bf16>((size_t)g.M * l.out);
-  g.out = out; g.a_relu = a_relu; g.act = act;
-  if (res1) { g.res1 = res1; g.res1_kind = KIND_BF16; }
-  if (res2) { g.res2 = res2; g.res2_kind = KIND_BF16; }
+  conv_epilogue(g, out, a_relu, act, res1, res2);
   run_gemm(c, g);
   return out;
 }
 
-static bf16* conv_transpose(Ctx& c, const bf16* in, int B, int H, int W, int C, const Lin& l, int s, int cout) {
+// ConvTranspose2d with kernel == stride s: l.W [cout*s*s, C] (n = co*s*s + i*s + j), l.b [cout]; out NHWC [B, H*s, W*s, cout]
+static GemmArgs conv_transpose_args(const bf16* in, int B, int H, int W, int C, const Lin& l, int s, int cout, bf16* out) {
   GemmArgs g = {};
   g.A = in; g.W = l.W; g.M = B * H * W; g.N = cout * s * s; g.K = C; g.lda = C; g.bias = l.b;
   g.epi = EPI_CONVT; g.ct_s = s; g.ct_cout = cout; g.ct_h = H; g.ct_w = W; g.out_kind = KIND_BF16;
-  bf16* out = c.ar.get<bf16>((size_t)B * H * s * W * s * cout);
   g.out = out;
+  return g;
+}
+
+static bf16* conv_transpose(Ctx& c, const bf16* in, int B, int H, int W, int C, const Lin& l, int s, int cout) {
+  bf16* out = c.ar.get<bf16>((size_t)B * H * s * W * s * cout);
+  GemmArgs g = conv_transpose_args(in, B, H, W, C, l, s, cout, out);
   run_gemm(c, g);
   return out;
+}
+
+static void launch_upsample2x(const bf16* in, bf16* out, int B, int H, int W, int C, hipStream_t s) {
+  const size_t total = (size_t)B * 4 * H * W * (C / 8);
+  hipLaunchKernelGGL(upsample2x_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, in, out, B, H, W, C);
 }
 
 static bf16* upsample2x(Ctx& c, const bf16* in, int B, int H, int W, int C) {
   bf16* out = c.ar.get<bf16>((size_t)B * 4 * H * W * C);
   if (!c.dry() && !c.rc) {
-    const size_t total = (size_t)B * 4 * H * W * (C / 8);
-    hipLaunchKernelGGL(upsample2x_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c.s, in, out, B, H, W, C);
+    launch_upsample2x(in, out, B, H, W, C, c.s);
     dbg(c, "upsample2x", H, W, C);
   }
   return out;
@@ -655,6 +698,25 @@ static bf16* fusion(Ctx& c, const Fusion& f, const bf16* path, const bf16* layer
 }
 
 struct HeadOut { float *X, *C, *D, *Q; };
+
+static void launch_concat2(const bf16* a, int ca, const bf16* b, int cb, bf16* out, size_t rows, hipStream_t s) {
+  const size_t total = rows * (size_t)(ca + cb);
+  hipLaunchKernelGGL(concat2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a, ca, b, cb, out, rows);
+}
+
+// the patch kernel where the shape is the one it is built for, the per-pixel form everywhere else (or when asked for)
+static void launch_head_post(const bf16* feat, int fc, const float* w4, const float* b4, const float* lf, int lf_ld,
+                             int desc_dim, int P, int B, int H, int W, const HeadOut& out, bool force_generic,
+                             hipStream_t s) {
+  if (!force_generic && P == kHP && fc == 128 && desc_dim == 24) {
+    hipLaunchKernelGGL(head_post_kernel, dim3((unsigned)(B * (H / P) * (W / P))), dim3(256), 0, s, feat, fc, w4, b4, lf,
+                       lf_ld, desc_dim, B, H, W, out.X, out.C, out.D, out.Q);
+  } else {
+    const size_t npix = (size_t)B * H * W;
+    hipLaunchKernelGGL(head_post_generic_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, feat, fc, w4, b4,
+                       lf, lf_ld, desc_dim, P, B, H, W, out.X, out.C, out.D, out.Q);
+  }
+}
 
 // toks[4]: bf16 token tensors of hooks [0, 6, 9, 12]: [B*N, E], [B*N, Dd] x3
 static void run_head(Ctx& c, const Head& hd, const bf16* const toks[4], int B, int H, int W, const HeadOut& out) {
@@ -694,38 +756,47 @@ static void run_head(Ctx& c, const Head& hd, const bf16* const toks[4], int B, i
   bf16* hid = c.ar.get<bf16>((size_t)M * hd.fc1.out);
   float* lf = c.ar.get<float>((size_t)M * hd.fc2.out);
   if (!c.dry() && !c.rc) {
-    const size_t total = (size_t)M * idim;
-    hipLaunchKernelGGL(concat2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c.s, toks[0], m.E, toks[3],
-                       m.Dd, cat, (size_t)M);
+    launch_concat2(toks[0], m.E, toks[3], m.Dd, cat, (size_t)M, c.s);
     dbg(c, "concat2", M);
   }
   linear_bf16(c, cat, M, hd.fc1, hid, ACT_GELU);
   linear_f32(c, hid, M, hd.fc2, lf);
   if (!c.dry() && !c.rc) {
-    if (m.P == kHP && hd.h2.out == 128 && m.desc_dim == 24) {
-      hipLaunchKernelGGL(head_post_kernel, dim3((unsigned)(B * (H / m.P) * (W / m.P))), dim3(256), 0, c.s, h2, hd.h2.out,
-                         hd.h4w, hd.h4b, lf, hd.fc2.out, m.desc_dim, B, H, W, out.X, out.C, out.D, out.Q);
-    } else {
-      const size_t npix = (size_t)B * H * W;
-      hipLaunchKernelGGL(head_post_generic_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, c.s, h2, hd.h2.out,
-                         hd.h4w, hd.h4b, lf, hd.fc2.out, m.desc_dim, m.P, B, H, W, out.X, out.C, out.D, out.Q);
-    }
+    launch_head_post(h2, hd.h2.out, hd.h4w, hd.h4b, lf, hd.fc2.out, m.desc_dim, m.P, B, H, W, out, false, c.s);
     dbg(c, "head_post", B, H, W);
   }
 }
 
 // ---- grouped decoder layers: both sides of a layer in ONE launch per operation --------------------
 // Activations of side s live at rows [s*M, (s+1)*M) of every buffer (x, h, u, q/k/vt/o, yn).
+static void launch_layernorm_group(const float* x, int D, const LnSet& s0, const LnSet& s1, int M, bf16* out, float eps,
+                                   hipStream_t s) {
+  const dim3 grid((2 * M + 3) / 4), block(256);
+  if (D == 768) hipLaunchKernelGGL((layernorm_group_vec_kernel<3, false>), grid, block, 0, s, x, s0, s1, s0, s1, out, out, M, eps);
+  else if (D == 1024) hipLaunchKernelGGL((layernorm_group_vec_kernel<4, false>), grid, block, 0, s, x, s0, s1, s0, s1, out, out, M, eps);
+  else {
+    launch_layernorm(x, s0.w, s0.b, out, nullptr, M, D, eps, s);
+    launch_layernorm(x + (size_t)M * D, s1.w, s1.b, out + (size_t)M * D, nullptr, M, D, eps, s);
+  }
+}
+
+static void launch_layernorm_group_cross(const float* x, int D, const LnSet& self0, const LnSet& self1, const LnSet& mem0,
+                                         const LnSet& mem1, int M, bf16* h, bf16* yn, float eps, hipStream_t s) {
+  const dim3 grid((2 * M + 3) / 4), block(256);
+  if (D == 768) hipLaunchKernelGGL((layernorm_group_vec_kernel<3, true>), grid, block, 0, s, x, self0, self1, mem0, mem1, h, yn, M, eps);
+  else if (D == 1024) hipLaunchKernelGGL((layernorm_group_vec_kernel<4, true>), grid, block, 0, s, x, self0, self1, mem0, mem1, h, yn, M, eps);
+  else {
+    const size_t MD = (size_t)M * D;
+    launch_layernorm(x, self0.w, self0.b, h, nullptr, M, D, eps, s);
+    launch_layernorm(x + MD, self1.w, self1.b, h + MD, nullptr, M, D, eps, s);
+    launch_layernorm(x + MD, mem0.w, mem0.b, yn, nullptr, M, D, eps, s);        // memory of side 0 = side 1's tokens
+    launch_layernorm(x, mem1.w, mem1.b, yn + MD, nullptr, M, D, eps, s);
+  }
+}
+
 static void g_layernorm(Ctx& c, const float* x, const Norm& n0, const Norm& n1, int M, bf16* out) {
   if (c.dry() || c.rc) return;
-  const LnSet s0{n0.w, n0.b}, s1{n1.w, n1.b};
-  const dim3 grid((2 * M + 3) / 4), block(256);
-  if (n0.d == 768) hipLaunchKernelGGL((layernorm_group_vec_kernel<3, false>), grid, block, 0, c.s, x, s0, s1, s0, s1, out, out, M, 1e-6f);
-  else if (n0.d == 1024) hipLaunchKernelGGL((layernorm_group_vec_kernel<4, false>), grid, block, 0, c.s, x, s0, s1, s0, s1, out, out, M, 1e-6f);
-  else {
-    launch_layernorm(x, n0.w, n0.b, out, nullptr, M, n0.d, 1e-6f, c.s);
-    launch_layernorm(x + (size_t)M * n0.d, n1.w, n1.b, out + (size_t)M * n0.d, nullptr, M, n0.d, 1e-6f, c.s);
-  }
+  launch_layernorm_group(x, n0.d, LnSet{n0.w, n0.b}, LnSet{n1.w, n1.b}, M, out, 1e-6f, c.s);
   dbg(c, "g_layernorm", M, n0.d);
 }
 
@@ -733,17 +804,8 @@ static void g_layernorm(Ctx& c, const float* x, const Norm& n0, const Norm& n1, 
 static void g_layernorm_cross(Ctx& c, const float* x, const DecBlock& b0, const DecBlock& b1, int M, bf16* h, bf16* yn) {
   if (c.dry() || c.rc) return;
   const int D = b0.n1.d;
-  const dim3 grid((2 * M + 3) / 4), block(256);
-  const LnSet self0{b0.n1.w, b0.n1.b}, self1{b1.n1.w, b1.n1.b}, mem0{b0.ny.w, b0.ny.b}, mem1{b1.ny.w, b1.ny.b};
-  if (D == 768) hipLaunchKernelGGL((layernorm_group_vec_kernel<3, true>), grid, block, 0, c.s, x, self0, self1, mem0, mem1, h, yn, M, 1e-6f);
-  else if (D == 1024) hipLaunchKernelGGL((layernorm_group_vec_kernel<4, true>), grid, block, 0, c.s, x, self0, self1, mem0, mem1, h, yn, M, 1e-6f);
-  else {
-    const size_t MD = (size_t)M * D;
-    launch_layernorm(x, b0.n1.w, b0.n1.b, h, nullptr, M, D, 1e-6f, c.s);
-    launch_layernorm(x + MD, b1.n1.w, b1.n1.b, h + MD, nullptr, M, D, 1e-6f, c.s);
-    launch_layernorm(x + MD, b0.ny.w, b0.ny.b, yn, nullptr, M, D, 1e-6f, c.s);        // memory of side 0 = side 1's tokens
-    launch_layernorm(x, b1.ny.w, b1.ny.b, yn + MD, nullptr, M, D, 1e-6f, c.s);
-  }
+  launch_layernorm_group_cross(x, D, LnSet{b0.n1.w, b0.n1.b}, LnSet{b1.n1.w, b1.n1.b}, LnSet{b0.ny.w, b0.ny.b},
+                               LnSet{b1.ny.w, b1.ny.b}, M, h, yn, 1e-6f, c.s);
   dbg(c, "g_layernorm_cross", M, D);
 }
 
@@ -803,6 +865,17 @@ static void decode(Ctx& c, const float* feat1, const float* feat2, int B, int H,
     c.ar.off = mark;
     run_head(c, m.head[s], tok, B, H, W, out[s]);
   }
+}
+
+// RoPE2D tables (pos_embed.py:120-130) on the host: cos / sin [len][16] of p * inv_freq_i
+static void rope_tables(float* hc, float* hs, int len) {
+  for (int p = 0; p < len; p++)
+    for (int i = 0; i < 16; i++) {
+      const float inv_freq = 1.0f / powf(100.0f, (float)(2 * i) / 32.0f);
+      const float fr = (float)p * inv_freq;
+      hc[(size_t)p * 16 + i] = cosf(fr);
+      hs[(size_t)p * 16 + i] = sinf(fr);
+    }
 }
 
 }  // namespace mslam
@@ -877,13 +950,7 @@ extern "C" int mslam_mast3r_create(void** handle_out, const int* cfg9, void* con
   // RoPE2D tables (pos_embed.py:120-130): inv_freq_i = base^(-2i/32), i < 16; base fixed at 100
   m->rope_len = 1024;
   std::vector<float> hc((size_t)m->rope_len * 16), hs((size_t)m->rope_len * 16);
-  for (int p = 0; p < m->rope_len; p++)
-    for (int i = 0; i < 16; i++) {
-      const float inv_freq = 1.0f / powf(100.0f, (float)(2 * i) / 32.0f);
-      const float fr = (float)p * inv_freq;
-      hc[(size_t)p * 16 + i] = cosf(fr);
-      hs[(size_t)p * 16 + i] = sinf(fr);
-    }
+  rope_tables(hc.data(), hs.data(), m->rope_len);
   int rc = check_hip(hipMalloc(&m->rope_cos, hc.size() * 4 + 16), "rope hipMalloc");
   if (!rc) m->pf_sink = reinterpret_cast<unsigned*>(m->rope_cos + hc.size());
   if (!rc) rc = check_hip(hipMalloc(&m->rope_sin, hs.size() * 4), "rope hipMalloc");
@@ -1009,5 +1076,154 @@ extern "C" int mslam_layernorm_f32(const float* x, const float* w, const float* 
   MSLAM_REQUIRE(D <= 2048 && rows > 0, "layernorm: D=%d must be <= 2048", D);
   launch_layernorm(x, w, b, (bf16*)out_bf16, out_f32, rows, D, eps, (hipStream_t)stream);
   MSLAM_LAUNCH_CHECK("layernorm");
+  return MSLAM_OK;
+}
+
+// ---- the glue between those blocks, through the argument-building and dispatch code of the forward -------------
+extern "C" int mslam_rope_tables(float* cos_out, float* sin_out, int len) {
+  MSLAM_REQUIRE(cos_out && sin_out && len > 0, "rope_tables: bad arguments");
+  rope_tables(cos_out, sin_out, len);
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_gemm_attn_bf16(const void* A, const void* W0, const float* bias0, const void* W1,
+                                    const float* bias1, void* q, void* k, void* vt, int M, int K, int n_sections,
+                                    int sec_base, int heads, int ntok, int kv_ntok, int tok_w, const float* rope_cos,
+                                    const float* rope_sin, int rope_len, float q_scale, void* stream) {
+  MSLAM_REQUIRE(A && W0 && rope_cos && rope_sin, "gemm_attn: null pointer");
+  MSLAM_REQUIRE(M > 0 && K > 0 && heads > 0 && ntok > 0 && kv_ntok > 0 && tok_w > 0, "gemm_attn: empty problem");
+  MSLAM_REQUIRE(sec_base >= 0 && n_sections >= 1 && sec_base + n_sections <= 3,
+                "gemm_attn: sections [%d, %d) outside q, k, v", sec_base, sec_base + n_sections);
+  MSLAM_REQUIRE(ntok % 4 == 0 && kv_ntok % 4 == 0, "gemm_attn: token counts %d / %d must be divisible by 4", ntok, kv_ntok);
+  // the rows are whole images of ntok tokens for q and of kv_ntok tokens for k and v
+  MSLAM_REQUIRE(sec_base > 0 || M % ntok == 0, "gemm_attn: M=%d is not a multiple of ntok=%d", M, ntok);
+  MSLAM_REQUIRE(sec_base + n_sections <= 1 || M % kv_ntok == 0, "gemm_attn: M=%d is not a multiple of kv_ntok=%d", M, kv_ntok);
+  MSLAM_REQUIRE(sec_base > 0 || n_sections == 1 || ntok == kv_ntok, "gemm_attn: q with k/v in one launch needs ntok == kv_ntok");
+  MSLAM_REQUIRE(tok_w <= rope_len && (ntok - 1) / tok_w < rope_len && (kv_ntok - 1) / tok_w < rope_len,
+                "gemm_attn: token grid exceeds the RoPE table of %d positions", rope_len);
+  MSLAM_REQUIRE((sec_base > 0 || q) && (sec_base > 1 || sec_base + n_sections < 2 || k) && (sec_base + n_sections < 3 || vt),
+                "gemm_attn: null output of a section the launch produces");
+  MSLAM_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)vt) & 15) == 0, "gemm_attn: q, k, vt must be 16-byte aligned");
+  MSLAM_REQUIRE((size_t)M * heads * 64 < (1ull << 31), "gemm_attn: output larger than 2^31 elements");
+  Lin l0, l1;
+  l0.W = (const bf16*)W0; l0.b = bias0; l0.out = n_sections * heads * 64; l0.in = K;
+  l1 = l0; l1.W = (const bf16*)W1; l1.b = bias1;
+  const AttnBufs ab{(bf16*)q, (bf16*)k, (bf16*)vt, nullptr};
+  GemmArgs g = attn_args((const bf16*)A, M, l0, sec_base, heads, ntok, kv_ntok, tok_w, ab, rope_cos, rope_sin, q_scale,
+                         W1 ? &l1 : nullptr);
+  return launch_gemm(g, (hipStream_t)stream);
+}
+
+extern "C" int mslam_gemm_grouped_bf16(const void* A, const void* W0, const float* bias0, const void* W1,
+                                       const float* bias1, const float* residual_f32, void* out, int M, int N, int K,
+                                       int act, int out_is_bf16, void* stream) {
+  MSLAM_REQUIRE(A && W0 && W1 && out, "gemm_grouped: null pointer");
+  MSLAM_REQUIRE(!out_is_bf16 || !residual_f32, "gemm_grouped: the bf16 form has no residual");
+  Lin l0, l1;
+  l0.W = (const bf16*)W0; l0.b = bias0; l0.out = N; l0.in = K;
+  l1 = l0; l1.W = (const bf16*)W1; l1.b = bias1;
+  GemmArgs g = out_is_bf16 ? linear_bf16_args((const bf16*)A, M, l0, (bf16*)out, act, &l1)
+                           : linear_residual_args((const bf16*)A, M, l0, residual_f32, (float*)out, &l1);
+  g.act = act;
+  return launch_gemm(g, (hipStream_t)stream);
+}
+
+extern "C" int mslam_conv_transpose_nhwc_bf16(const void* in, const void* Wt, const float* bias, void* out_bf16, int B,
+                                              int H, int Wd, int Cin, int Cout, int s, void* stream) {
+  MSLAM_REQUIRE(in && Wt && out_bf16, "conv_transpose: null pointer");
+  MSLAM_REQUIRE(B > 0 && H > 0 && Wd > 0 && Cin > 0 && Cout > 0 && s > 0, "conv_transpose: empty problem");
+  MSLAM_REQUIRE(Cin % 8 == 0, "conv_transpose: Cin=%d must be a multiple of 8", Cin);
+  MSLAM_REQUIRE((size_t)B * H * s * Wd * s * Cout < (1ull << 31), "conv_transpose: output larger than 2^31 elements");
+  Lin l; l.W = (const bf16*)Wt; l.b = bias; l.out = Cout * s * s; l.in = Cin;
+  GemmArgs g = conv_transpose_args((const bf16*)in, B, H, Wd, Cin, l, s, Cout, (bf16*)out_bf16);
+  return launch_gemm(g, (hipStream_t)stream);
+}
+
+extern "C" int mslam_conv2d_res2_nhwc_bf16(const void* in, const void* Wt, const float* bias, const void* residual1_bf16,
+                                           const void* residual2_bf16, void* out_bf16, int B, int H, int Wd, int Cin,
+                                           int Cout, int ks, int stride, int relu_in, int act, void* stream) {
+  MSLAM_REQUIRE(in && Wt && out_bf16, "conv2d_res2: null pointer");
+  MSLAM_REQUIRE((ks == 1 || ks == 3) && (stride == 1 || stride == 2), "conv2d_res2: unsupported ks/stride");
+  MSLAM_REQUIRE(B > 0 && H > 0 && Wd > 0 && Cout > 0 && Cin > 0 && Cin % 8 == 0, "conv2d_res2: Cin=%d must be a positive multiple of 8", Cin);
+  Lin l; l.W = (const bf16*)Wt; l.b = bias; l.out = Cout; l.in = ks * ks * Cin;
+  GemmArgs g = conv_args((const bf16*)in, B, H, Wd, Cin, l, ks, stride);
+  conv_epilogue(g, (bf16*)out_bf16, relu_in, act, (const bf16*)residual1_bf16, (const bf16*)residual2_bf16);
+  return launch_gemm(g, (hipStream_t)stream);
+}
+
+extern "C" int mslam_layernorm_group_bf16(const float* x, const float* self0_w, const float* self0_b,
+                                          const float* self1_w, const float* self1_b, const float* mem0_w,
+                                          const float* mem0_b, const float* mem1_w, const float* mem1_b, void* out_self,
+                                          void* out_mem, int M, int D, float eps, void* stream) {
+  MSLAM_REQUIRE(x && self0_w && self0_b && self1_w && self1_b && out_self, "layernorm_group: null pointer");
+  MSLAM_REQUIRE(M > 0 && D > 0 && D <= 2048, "layernorm_group: M=%d, D=%d (D must be <= 2048)", M, D);
+  MSLAM_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)out_self & 7) == 0 && ((uintptr_t)out_mem & 7) == 0,
+                "layernorm_group: x must be 16-byte, the outputs 8-byte aligned");
+  const bool cross = mem0_w || mem0_b || mem1_w || mem1_b || out_mem;
+  const LnSet s0{self0_w, self0_b}, s1{self1_w, self1_b};
+  if (D == 768 || D == 1024) {   // the vector kernels fetch gamma / beta 16 bytes at a time
+    const uintptr_t p = (uintptr_t)self0_w | (uintptr_t)self0_b | (uintptr_t)self1_w | (uintptr_t)self1_b |
+                        (uintptr_t)mem0_w | (uintptr_t)mem0_b | (uintptr_t)mem1_w | (uintptr_t)mem1_b;
+    MSLAM_REQUIRE((p & 15) == 0, "layernorm_group: gamma / beta must be 16-byte aligned for D=%d", D);
+  }
+  if (cross) {
+    MSLAM_REQUIRE(mem0_w && mem0_b && mem1_w && mem1_b && out_mem, "layernorm_group: the cross form needs both norm_y sets and out_mem");
+    launch_layernorm_group_cross(x, D, s0, s1, LnSet{mem0_w, mem0_b}, LnSet{mem1_w, mem1_b}, M, (bf16*)out_self,
+                                 (bf16*)out_mem, eps, (hipStream_t)stream);
+  } else {
+    launch_layernorm_group(x, D, s0, s1, M, (bf16*)out_self, eps, (hipStream_t)stream);
+  }
+  MSLAM_LAUNCH_CHECK("layernorm_group");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_upsample2x_nhwc_bf16(const void* in, void* out, int B, int H, int Wd, int C, void* stream) {
+  MSLAM_REQUIRE(in && out, "upsample2x: null pointer");
+  MSLAM_REQUIRE(B > 0 && H > 0 && Wd > 0 && C > 0 && C % 8 == 0, "upsample2x: C=%d must be a positive multiple of 8", C);
+  MSLAM_REQUIRE((((uintptr_t)in | (uintptr_t)out) & 15) == 0, "upsample2x: in and out must be 16-byte aligned");
+  launch_upsample2x((const bf16*)in, (bf16*)out, B, H, Wd, C, (hipStream_t)stream);
+  MSLAM_LAUNCH_CHECK("upsample2x");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_head_post(const void* feat_bf16, int fc, const float* w4, const float* b4, const float* lf, int lf_ld,
+                               int desc_dim, int P, int B, int H, int Wd, float* X, float* C, float* D, float* Q,
+                               int force_generic, void* stream) {
+  MSLAM_REQUIRE(feat_bf16 && w4 && b4 && lf && X && C && D && Q, "head_post: null pointer");
+  MSLAM_REQUIRE(fc > 0 && fc % 8 == 0, "head_post: fc=%d must be a positive multiple of 8", fc);
+  MSLAM_REQUIRE(desc_dim >= 1 && desc_dim <= 31, "head_post: desc_dim=%d must be in [1, 31]", desc_dim);
+  MSLAM_REQUIRE(B > 0 && P > 0 && H >= P && Wd >= P && H % P == 0 && Wd % P == 0,
+                "head_post: image %dx%d must be a positive multiple of the patch size %d", H, Wd, P);
+  MSLAM_REQUIRE(lf_ld >= (desc_dim + 1) * P * P, "head_post: lf_ld=%d is below (desc_dim + 1) * P * P", lf_ld);
+  MSLAM_REQUIRE(((uintptr_t)feat_bf16 & 15) == 0 && (((uintptr_t)X | (uintptr_t)D) & 15) == 0,
+                "head_post: feat, X and D must be 16-byte aligned");
+  launch_head_post((const bf16*)feat_bf16, fc, w4, b4, lf, lf_ld, desc_dim, P, B, H, Wd, HeadOut{X, C, D, Q},
+                   force_generic != 0, (hipStream_t)stream);
+  MSLAM_LAUNCH_CHECK("head_post");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_patchify_bf16(const float* img, void* patches_bf16, int B, int H, int Wd, int P, void* stream) {
+  MSLAM_REQUIRE(img && patches_bf16, "patchify: null pointer");
+  MSLAM_REQUIRE(B > 0 && P > 0 && H >= P && Wd >= P && H % P == 0 && Wd % P == 0,
+                "patchify: image %dx%d must be a positive multiple of the patch size %d", H, Wd, P);
+  launch_patchify(img, (bf16*)patches_bf16, B, H, Wd, P, (hipStream_t)stream);
+  MSLAM_LAUNCH_CHECK("patchify");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_concat2_bf16(const void* a, int ca, const void* b, int cb, void* out, long long rows, void* stream) {
+  MSLAM_REQUIRE(a && b && out, "concat2: null pointer");
+  MSLAM_REQUIRE(ca > 0 && cb > 0 && rows > 0, "concat2: empty problem");
+  launch_concat2((const bf16*)a, ca, (const bf16*)b, cb, (bf16*)out, (size_t)rows, (hipStream_t)stream);
+  MSLAM_LAUNCH_CHECK("concat2");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_cast_f32_bf16(const float* x, void* y_bf16, long long n, void* stream) {
+  MSLAM_REQUIRE(x && y_bf16 && n > 0, "cast_f32_bf16: bad arguments");
+  MSLAM_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)y_bf16 & 7) == 0, "cast_f32_bf16: x must be 16-byte, y 8-byte aligned");
+  launch_cast_bf16(x, (bf16*)y_bf16, (size_t)n, (hipStream_t)stream);
+  MSLAM_LAUNCH_CHECK("cast_f32_bf16");
   return MSLAM_OK;
 }

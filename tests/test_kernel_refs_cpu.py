@@ -176,3 +176,281 @@ def test_guarded_buffer_sees_stray_writes_and_unwritten_elements():
         a.raw[a.g - 1] = 0            # last word in front
         with pytest.raises(AssertionError, match="guard of a"):
             R.check_guards({"a": a, "o": o}, [], "front")
+
+
+# ======================================================================================================================
+# References of the forward's glue (tests/test_forward_glue_gpu.py).  Each one: against an independent statement of the
+# operation, its bound against a correct fp32 emulation in the kernel's number formats (no more than about half of the
+# part of the bound that precedes the bf16 rounding; the whole bound with it), and against one named mutation each.
+# ======================================================================================================================
+def _inside(got, ref, bound):
+    return bool(((got.double() - ref).abs() <= bound).all())
+
+
+def _ratio(got, ref, bound):
+    err = (got.double() - ref).abs()
+    return float(torch.where(err > 0, err / bound.clamp_min(1e-300), torch.zeros_like(err)).max())
+
+
+def _rope_emulate(length):
+    """the table loop with correctly rounded fp32 functions (what a good libm's powf / cosf / sinf return in all but rare
+    cases): every operation evaluated in float64 and rounded to fp32 once"""
+    import math
+
+    inv_freq = np.array([np.float32(1.0) / np.float32(math.pow(100.0, float(np.float32(2 * i) / np.float32(32.0))))
+                         for i in range(16)], dtype=np.float32)
+    ang = (np.arange(length, dtype=np.float32)[:, None] * inv_freq[None]).astype(np.float32)
+    return (torch.from_numpy(np.cos(ang.astype(np.float64)).astype(np.float32)),
+            torch.from_numpy(np.sin(ang.astype(np.float64)).astype(np.float32)))
+
+
+def test_rope_tables_ref_and_bound():
+    c, s, bc, bs = R.rope_tables_ref(1024)
+    # independent statement: mpmath-free, the angle in float64 from the exact rational exponent
+    p = torch.arange(1024, dtype=torch.float64)[:, None]
+    ang = p * 100.0 ** (-torch.arange(16, dtype=torch.float64) / 16.0)[None]
+    assert float((c - ang.cos()).abs().max()) <= 1024 * 2.0 ** -23 and float((s - ang.sin()).abs().max()) <= 1024 * 2.0 ** -23
+    assert float(bs[0].max()) == 0.0 and float(bc.max()) < 3e-4
+    ec, es = _rope_emulate(1024)
+    assert _ratio(ec, c, bc) <= 0.5 and _ratio(es, s, bs) <= 0.5, (_ratio(ec, c, bc), _ratio(es, s, bs))
+    # mutations: base 10000 (the 1-D RoPE default), cos and sin exchanged
+    ang_m = p * 10000.0 ** (-torch.arange(16, dtype=torch.float64) / 16.0)[None]
+    assert not _inside(ang_m.cos(), c, bc)
+    assert not _inside(es, c, bc)
+
+
+def _attn_case(B, heads, gh, gw, K, seed):
+    g = torch.Generator().manual_seed(seed)
+    ntok, N = gh * gw, 3 * heads * 64
+    A, W, bias = R.rand_int(g, (B * ntok, K), 4), R.rand_int(g, (N, K), 4), R.rand_int(g, (N,), 64)
+    pre, mag = R.gemm_int_ref(A, W, bias, None, R.ACT_NONE)
+    assert mag < 2 ** 24
+    return pre, ntok
+
+
+def _attn_emulate(pre, B, heads, sec, ntok, tok_w, cos, sin, scale, swap_xy=False, flip=False):
+    """fp32 emulation of one RoPE section -> bf16 [B,heads,ntok,64]"""
+    x = pre.reshape(B, ntok, heads, 64).permute(0, 2, 1, 3).float()
+    n = torch.arange(ntok)
+    py, px = n // tok_w, n % tok_w
+    if swap_xy:
+        py, px = px, py
+    c32, s32 = cos.float(), sin.float()
+    out = torch.empty_like(x)
+    for h, pos in ((0, py), (1, px)):
+        a, b = x[..., 32 * h:32 * h + 16], x[..., 32 * h + 16:32 * h + 32]
+        c, s = c32[pos], s32[pos]
+        if flip:
+            s = -s
+        out[..., 32 * h:32 * h + 16] = (a * c - b * s) * scale
+        out[..., 32 * h + 16:32 * h + 32] = (b * c + a * s) * scale
+    return out
+
+
+def test_attn_project_ref_matches_oracle_rope2d_and_head_split():
+    """4 x 6 grid: the q and k of the reference against oracle.mast3r_ref.rope2d on the reference's own head split
+    (reshape(B, N, 3, heads, 64).transpose(1, 3)), v^T exact; then the bound: admits the fp32 emulation, rejects the
+    mutations."""
+    from oracle import mast3r_ref as O
+
+    B, heads, gh, gw = 2, 3, 4, 6
+    pre, ntok = _attn_case(B, heads, gh, gw, 64, 5)
+    cos, sin = (t.float().double() for t in R.rope_tables_ref(64)[:2])       # fp32 values, as the device's tables are
+    ref = R.attn_project_ref(pre, B, heads, 0, ntok, ntok, gw, cos, sin, 0.125)
+    qkv = pre.double().reshape(B, ntok, 3, heads, 64).transpose(1, 3)          # [B,heads,3,ntok,64]
+    pos = O.positions(B, gh, gw, "cpu")
+    for name, j, scale in (("q", 0, 0.125), ("k", 1, 1.0)):
+        want = O.rope2d(qkv[:, :, j], pos, 100.0) * scale
+        y, f32, bound = ref[name]
+        assert y.shape == want.shape
+        # rope2d forms its cos / sin in fp32: 2^-24 of |v| + |partner| per term
+        assert bool(((y - want).abs() <= 4e-7 * (qkv[:, :, j].abs().max() + 1)).all()), name
+    assert torch.equal(ref["vt"].double(), qkv[:, :, 2].transpose(-1, -2)) or \
+        torch.equal(ref["vt"], R.to_bf16_once(qkv[:, :, 2].transpose(-1, -2).contiguous()))
+    sd = heads * 64
+    for name, j, scale in (("q", 0, 0.125), ("k", 1, 1.0)):
+        y, f32, bound = ref[name]
+        sec = pre[:, j * sd:(j + 1) * sd]
+        emu = _attn_emulate(sec, B, heads, j, ntok, gw, cos, sin, scale)
+        assert _ratio(emu, y, f32) <= 0.5, (name, _ratio(emu, y, f32))
+        assert _inside(emu.to(torch.bfloat16), y, bound), name
+        assert not _inside(_attn_emulate(sec, B, heads, j, ntok, gw, cos, sin, scale, swap_xy=True).to(torch.bfloat16), y, bound)
+        assert not _inside(_attn_emulate(sec, B, heads, j, ntok, gw, cos, sin, scale, flip=True).to(torch.bfloat16), y, bound)
+    # q_scale applied to k
+    y, _, bound = ref["k"]
+    assert not _inside(_attn_emulate(pre[:, sd:2 * sd], B, heads, 1, ntok, gw, cos, sin, 0.125).to(torch.bfloat16), y, bound)
+    # V stored untransposed: the same bytes read as [B,heads,64,ntok] are not the reference
+    v_plain = R.to_bf16_once(pre[:, 2 * sd:].reshape(B, ntok, heads, 64).permute(0, 2, 1, 3).contiguous())
+    assert not torch.equal(v_plain.reshape(-1), ref["vt"].reshape(-1))
+    # side 1 using side 0's bias: another bias is outside the bound / not equal
+    g = torch.Generator().manual_seed(6)
+    other = R.attn_project_ref(pre + R.rand_int(g, (pre.shape[1],), 64), B, heads, 0, ntok, ntok, gw, cos, sin, 0.125)
+    assert not _inside(other["q"][0], ref["q"][0], ref["q"][2]) and not torch.equal(other["vt"], ref["vt"])
+
+
+def test_attn_project_ref_sections_and_kv_ntok():
+    """{k, v} with sec_base 1 and its own token count: the same numbers as sections 1, 2 of the joint call."""
+    B, heads = 2, 1
+    pre, ntok = _attn_case(B, heads, 4, 6, 64, 7)
+    cos, sin = (t.float().double() for t in R.rope_tables_ref(64)[:2])       # fp32 values, as the device's tables are
+    full = R.attn_project_ref(pre, B, heads, 0, ntok, ntok, 6, cos, sin, 0.125)
+    kv = R.attn_project_ref(pre[:, 64:], B, heads, 1, 32, ntok, 6, cos, sin, 0.125)
+    assert set(kv) == {"k", "vt"} and torch.equal(kv["k"][0], full["k"][0]) and torch.equal(kv["vt"], full["vt"])
+    q = R.attn_project_ref(pre[:, :64], B, heads, 0, ntok, 32, 6, cos, sin, 0.125)
+    assert set(q) == {"q"} and torch.equal(q["q"][0], full["q"][0])
+
+
+def test_layernorm_group_ref_blocks_and_mutations():
+    g = torch.Generator().manual_seed(8)
+    M, D, eps = 3, 192, 1e-6
+    x = torch.randn(2 * M, D, generator=g) * 3 + 0.5
+    sets = {k: (torch.rand(D, generator=g) + 0.5, torch.rand(D, generator=g) - 0.5) for k in ("self0", "self1", "mem0", "mem1")}
+    ys, bs, ym, bm = R.layernorm_group_ref(x, sets, M, eps, True)
+    ln = lambda rows, k: F.layer_norm(rows.double(), (D,), sets[k][0].double(), sets[k][1].double(), eps)
+    assert torch.allclose(ys, torch.cat([ln(x[:M], "self0"), ln(x[M:], "self1")]), rtol=0, atol=1e-12)
+    assert torch.allclose(ym, torch.cat([ln(x[M:], "mem0"), ln(x[:M], "mem1")]), rtol=0, atol=1e-12)
+    ln32 = lambda rows, k: F.layer_norm(rows, (D,), sets[k][0], sets[k][1], eps).to(torch.bfloat16)
+    assert _inside(torch.cat([ln32(x[:M], "self0"), ln32(x[M:], "self1")]), ys, bs)
+    assert _inside(torch.cat([ln32(x[M:], "mem0"), ln32(x[:M], "mem1")]), ym, bm)
+    # norm_y written to its own side's block; side 1 with side 0's affine pair
+    assert not _inside(torch.cat([ln32(x[:M], "mem1"), ln32(x[M:], "mem0")]), ym, bm)
+    assert not _inside(torch.cat([ln32(x[:M], "self0"), ln32(x[M:], "self0")]), ys, bs)
+    y1, b1, none1, none2 = R.layernorm_group_ref(x, sets, M, eps, False)
+    assert torch.equal(y1, ys) and none1 is None and none2 is None
+
+
+@pytest.mark.parametrize("s", [2, 4])
+def test_conv_transpose_ref_matches_torch(s):
+    g = torch.Generator().manual_seed(9 + s)
+    B, H, W, Cin, Cout = 2, 3, 5, 8, 6
+    x, w, bias = R.rand_int(g, (B, Cin, H, W), 4), R.rand_int(g, (Cin, Cout, s, s), 4), R.rand_int(g, (Cout,), 64)
+    got = R.conv_transpose_ref(x, w, bias)
+    want = F.conv_transpose2d(x.double(), w.double(), bias.double(), stride=s).permute(0, 2, 3, 1)
+    assert torch.equal(got, want)
+    # the GEMM form with the kernel's row order co*s*s + i*s + j, scattered by hand
+    Wm = R.conv_transpose_weight(w)
+    assert Wm.shape == (Cout * s * s, Cin)
+    flat = x.permute(0, 2, 3, 1).reshape(-1, Cin).double() @ Wm.double().T       # [B*H*W, Cout*s*s]
+    out = torch.zeros_like(got)
+    for n in range(Cout * s * s):
+        co, i, j = n // (s * s), (n % (s * s)) // s, n % s
+        out[:, i::s, j::s, co] = flat[:, n].reshape(B, H, W) + float(bias[co])
+    assert torch.equal(out, got)
+    # mutation: sub-pixels (i, j) exchanged
+    assert not torch.equal(R.conv_transpose_ref(x, w.transpose(2, 3), bias), got)
+
+
+def test_conv_ref_second_residual():
+    g = torch.Generator().manual_seed(10)
+    x, w, bias = R.rand_int(g, (1, 8, 5, 7), 4), R.rand_int(g, (8, 8, 3, 3), 4), R.rand_int(g, (8,), 64)
+    r1, r2 = R.rand_int(g, (1, 5, 7, 8), 64), R.rand_int(g, (1, 5, 7, 8), 64)
+    for relu_in in (0, 1):
+        base = _conv_direct(x.numpy(), w.numpy(), bias.numpy(), None, 1, relu_in, R.ACT_NONE)
+        for a, b in ((r1, r2), (r1, None), (None, r2)):
+            want = base + (0 if a is None else a.numpy()) + (0 if b is None else b.numpy())
+            assert np.array_equal(R.conv_ref(x, w, bias, a, 1, relu_in, R.ACT_NONE, res2=b).numpy(), want.astype(np.float64))
+
+
+def _upsample_emulate(x):
+    """the kernel's arithmetic in fp32 torch: fp32 scale, coordinate, floor, three lerps"""
+    v = x.float()
+    B, H, W, C = v.shape
+
+    def axis(n):
+        no = 2 * n
+        sc = torch.tensor(float(n - 1)) / torch.tensor(float(no - 1)) if no > 1 else torch.tensor(0.0)
+        f = sc * torch.arange(no, dtype=torch.float32)
+        i0 = f.long().clamp_max(n - 1)
+        return i0, (i0 + 1).clamp_max(n - 1), f - i0
+    y0, y1, wy = axis(H)
+    x0, x1, wx = axis(W)
+    g = lambda yi, xi: v[:, yi][:, :, xi]
+    wx_, wy_ = wx[None, None, :, None], wy[None, :, None, None]
+    top = g(y0, x0) + wx_ * (g(y0, x1) - g(y0, x0))
+    bot = g(y1, x0) + wx_ * (g(y1, x1) - g(y1, x0))
+    return top + wy_ * (bot - top)
+
+
+@pytest.mark.parametrize("B,H,W,C", [(1, 1, 1, 8), (1, 1, 5, 8), (2, 3, 5, 24), (3, 7, 2, 136), (1, 12, 16, 256)])
+def test_upsample2x_ref_matches_interpolate(B, H, W, C):
+    g = torch.Generator().manual_seed(H * 100 + W)
+    x = (torch.randn(B, H, W, C, generator=g) * 2).to(torch.bfloat16)
+    y, f32, bound = R.upsample2x_ref(x)
+    nchw = x.double().permute(0, 3, 1, 2)
+    want = F.interpolate(nchw, scale_factor=2, mode="bilinear", align_corners=True).permute(0, 2, 3, 1)
+    assert float((y - want).abs().max()) <= 1e-12
+    emu = _upsample_emulate(x)
+    assert _ratio(emu, y, f32) <= 0.5, _ratio(emu, y, f32)
+    assert _inside(emu.to(torch.bfloat16), y, bound)
+    if H * W > 1:
+        wrong = F.interpolate(nchw, scale_factor=2, mode="bilinear", align_corners=False).permute(0, 2, 3, 1)
+        assert not _inside(wrong.float().to(torch.bfloat16), y, bound)
+    const = torch.full((B, H, W, C), 1.2345).to(torch.bfloat16)
+    yc, f32c, bc = R.upsample2x_ref(const)
+    assert torch.equal(yc, const.double().expand(B, 1, 1, C).expand(B, 2 * H, 2 * W, C) if H * W == 1 else
+                       const.double()[:, :1, :1].expand(B, 2 * H, 2 * W, C))
+
+
+def _head_emulate(feat, w4, b4, lf, desc, P, swap_ij=False, no_one=False):
+    B, H, W, fc = feat.shape
+    l = feat.float() @ w4.T + b4
+    d = l[..., :3].norm(dim=-1, keepdim=True)
+    X = l[..., :3] * (torch.expm1(d) / d.clamp_min(1e-8))
+    C = torch.exp(l[..., 3]) + (0.0 if no_one else 1.0)
+    lfv = lf[:, :(desc + 1) * P * P]
+    if swap_ij:
+        lfv = lfv.reshape(-1, desc + 1, P, P).transpose(2, 3).reshape(lf.shape[0], -1)
+    sh = R.pixel_shuffle_lf(lfv, B, H, W, P, desc + 1)
+    v = sh[..., :desc]
+    return {"X": X, "C": C, "D": v / v.norm(dim=-1, keepdim=True), "Q": torch.exp(sh[..., desc])}
+
+
+@pytest.mark.parametrize("P,fc,desc,B,H,W,pad", [(16, 128, 24, 1, 16, 16, 0), (8, 64, 16, 1, 16, 24, 5)])
+def test_head_post_ref_matches_pixel_shuffle_and_formulas(P, fc, desc, B, H, W, pad):
+    lf_ld = (desc + 1) * P * P + pad
+    feat, w4, b4, lf = R.head_inputs(B, H, W, P, fc, desc, lf_ld, 11)
+    ref = R.head_post_ref(feat, w4, b4, lf, desc, P)
+    # independent statement: F.pixel_shuffle on the NCHW token map + the post-process formulas of the oracle
+    nh, nw = H // P, W // P
+    tokmap = lf[:, :(desc + 1) * P * P].double().reshape(B, nh, nw, -1).permute(0, 3, 1, 2)
+    sh = F.pixel_shuffle(tokmap, P).permute(0, 2, 3, 1)
+    l = F.conv2d(feat.double().permute(0, 3, 1, 2), w4.double()[:, :, None, None], b4.double()).permute(0, 2, 3, 1)
+    d = l[..., :3].norm(dim=-1, keepdim=True)
+    assert torch.allclose(ref["X"][0], l[..., :3] / d.clip(min=1e-8) * torch.expm1(d), rtol=1e-12, atol=1e-300)
+    assert torch.allclose(ref["C"][0], 1 + l[..., 3].exp(), rtol=1e-12)
+    assert torch.allclose(ref["D"][0], sh[..., :desc] / sh[..., :desc].norm(dim=-1, keepdim=True), rtol=1e-12)
+    assert torch.allclose(ref["Q"][0], sh[..., desc].exp(), rtol=1e-12)
+    assert float(d.max()) > 6.0 and float(l[..., 3].abs().max()) > 12.0
+    zx, zb = ref["X"][0][0, 1 % H, 2 % W], ref["X"][1][0, 1 % H, 2 % W]
+    assert float(zx.abs().max()) == 0.0 and float(zb.max()) == 0.0
+    emu = _head_emulate(feat, w4, b4, lf, desc, P)
+    for k in ("X", "C", "D", "Q"):
+        y, bound = ref[k]
+        assert _inside(emu[k], y, bound), k
+        # where e^l3 < 1 the bound of C is little more than the one rounding of the final sum (half an ulp of C), which
+        # a correct kernel reaches: the half-of-the-bound check is made where the propagated terms lead
+        sel = ref["C"][0] >= 2.0 if k == "C" else torch.ones_like(y, dtype=torch.bool)
+        assert _ratio(emu[k][sel], y[sel], bound[sel]) <= 0.5, (k, _ratio(emu[k][sel], y[sel], bound[sel]))
+    assert bool(torch.isfinite(emu["X"]).all()) and float(emu["X"][0, 1 % H, 2 % W].abs().max()) == 0.0
+    # mutations: sub-pixel (i, j) exchanged; conf without the 1 +
+    sw = _head_emulate(feat, w4, b4, lf, desc, P, swap_ij=True)
+    assert not _inside(sw["D"], *ref["D"]) and not _inside(sw["Q"], *ref["Q"])
+    assert not _inside(_head_emulate(feat, w4, b4, lf, desc, P, no_one=True)["C"], *ref["C"])
+
+
+@pytest.mark.parametrize("P,B,H,W", [(16, 1, 16, 16), (8, 2, 8, 24)])
+def test_patchify_ref_matches_unfold(P, B, H, W):
+    g = torch.Generator().manual_seed(12)
+    img = torch.randn(B, 3, H, W, generator=g)
+    want = F.unfold(img, P, stride=P).transpose(1, 2).reshape(-1, 3 * P * P)     # columns in Conv2d weight order
+    assert torch.equal(R.patchify_ref(img, P), want.to(torch.bfloat16))
+
+
+def test_cast_edge_values_cover_ties_zeros_and_carry():
+    x = R.cast_edge_values(1025, torch.Generator().manual_seed(13))
+    assert bool(torch.isfinite(x).all()) and x.unique().numel() >= 1024
+    want = R.to_bf16_once(x)
+    assert torch.equal(want, x.to(torch.bfloat16))
+    b = want.view(torch.int16).to(torch.int64) & 0xFFFF
+    assert b[:3].tolist() == [0x3F80, 0x3F82, 0x3F80]       # tie down to even, tie up to even, carry into the next binade
+    assert b[6:8].tolist() == [0x0000, 0x8000] and bool(torch.isfinite(want.float()).all())
