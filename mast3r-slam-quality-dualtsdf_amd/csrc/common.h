@@ -49,4 +49,14 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// the same descending tree in f64
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+
+// blocks of `per` threads that cover n elements
+inline unsigned blocks_for(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
+
 }  // namespace mslam

@@ -9,10 +9,9 @@
 // point, moments) followed by ma_solve_kernel (Horn's quaternion solve for the TOTAL transform from the original
 // points: T_{k+1} replaces T_k, nothing is composed).
 //
-// The match is the culled tile scan of md_distance_kernel on q_i = (float)(T_k p_i).  Two differences, neither of which
-// changes an output bit: the boxes are computed once per alignment (mslam_mesh_align_init), and lane i's upper bound
-// starts from md_dist2(q_i, face nearest_prev[i]) when that face exists and is valid.  That is the value of a real face,
-// which is all the invariant in the header comment of mesh_distance.hip asks of `ub`; a block stages its home tile only
+// The match is md_scan of mesh_tri.h, the culled nearest-face scan that md_distance_kernel calls too, on
+// q_i = (float)(T_k p_i).  The boxes are computed once per alignment (mslam_mesh_align_init), and lane i's bound starts
+// from md_dist2(q_i, face nearest_prev[i]) when that face exists and is valid, so a block stages its home tile only
 // when one of its lanes has no such face.
 #include "mesh_tri.h"
 
@@ -63,9 +62,7 @@ __device__ __forceinline__ void ma_block_reduce(double* v, double* s_part, doubl
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
 #pragma unroll
   for (int k = 0; k < kMaSums; k++) {
-    double x = v[k];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, kWave);
+    const double x = wave_sum(v[k]);
     if (lane == 0) s_part[wave * kMaSums + k] = x;
   }
   __syncthreads();
@@ -88,17 +85,17 @@ __global__ __launch_bounds__(kMdBlock) void ma_step_kernel(const float* __restri
   __shared__ double s_part[4 * kMaSums];
   __shared__ int s_home;
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  const size_t i = (size_t)blockIdx.x * kMdBlock + tid;
+  const size_t i0 = (size_t)blockIdx.x * kMdBlock, i = i0 + tid;
   const bool has = i < (size_t)n;
-  const int ntiles = (nf + kMdTile - 1) / kMdTile;
 
-  // 1. the transform, rounded to f32 once
-  double R[9], tt[3], p[3] = {0.0, 0.0, 0.0}, op[3], oc[3], y[3];
+  // 1. the transform, rounded to f32 once; y0: the block's first point
+  double R[9], tt[3], p[3] = {0.0, 0.0, 0.0}, op[3], oc[3], y[3], p0[3], y0[3];
   ma_quat_to_mat(state + 3, R);
   const double s = state[7];
 #pragma unroll
-  for (int d = 0; d < 3; d++) tt[d] = state[d], op[d] = (double)src[d];
+  for (int d = 0; d < 3; d++) tt[d] = state[d], op[d] = (double)src[d], p0[d] = (double)src[3 * i0 + d];
   ma_act(R, tt, s, op, oc);
+  ma_act(R, tt, s, p0, y0);
   if (has) {
 #pragma unroll
     for (int d = 0; d < 3; d++) p[d] = (double)src[3 * i + d];
@@ -107,84 +104,21 @@ __global__ __launch_bounds__(kMdBlock) void ma_step_kernel(const float* __restri
   const float qf[3] = {(float)y[0], (float)y[1], (float)y[2]};
   const double px = (double)qf[0], py = (double)qf[1], pz = (double)qf[2];
 
-  // 2. the culled tile scan of md_distance_kernel; the bound starts from last iteration's face where there is one
-  double best = INFINITY, ub = INFINITY;
-  int best_f = -1, n_skipped = 0;
-  if (cull) {
-    bool warm = false;
-    if (has) {
-      const int wf = nearest[i];
-      double t[kMdTriDoubles];
-      if ((unsigned)wf < (unsigned)nf && md_load_tri(vert, faces, wf, nf, nv, t)) {
-        ub = fmin(ub, md_dist2(px, py, pz, t));                    // fmin: a NaN distance never becomes the bound
-        warm = true;
-      }
-    }
-    if (__syncthreads_or(has && !warm)) {
-      // the tile whose box is nearest to the block's first point gives ub; which tile it is changes no output
-      if (wave == 0) {
-        const size_t i0 = (size_t)blockIdx.x * kMdBlock;
-        double p0[3] = {(double)src[3 * i0], (double)src[3 * i0 + 1], (double)src[3 * i0 + 2]}, y0[3];
-        ma_act(R, tt, s, p0, y0);
-        const double qx = (double)(float)y0[0], qy = (double)(float)y0[1], qz = (double)(float)y0[2];
-        double m = INFINITY, s2;
-        int mt = -1;
-        for (int t = lane; t < ntiles; t += kWave) {
-          const double lb2 = md_box_lb2(qx, qy, qz, box + 6 * (size_t)t, &s2);
-          if (lb2 < m) m = lb2, mt = t;
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-          const double om = __shfl_down(m, off, kWave);
-          const int ot = __shfl_down(mt, off, kWave);
-          if (ot >= 0 && (mt < 0 || om < m || (om == m && ot < mt))) m = om, mt = ot;
-        }
-        if (lane == 0) s_home = mt;
-      }
-      __syncthreads();
-      const int home = s_home;
-      if (home >= 0) {
-        if (tid < kMdTile)
-          md_load_tri(vert, faces, home * kMdTile + tid, nf, nv, s_tri + tid * kMdTriDoubles);
-        __syncthreads();
-        if (!warm) {
-          const int cnt = min(kMdTile, nf - home * kMdTile);
-          for (int k = 0; k < cnt; k++) {
-            const double* t = s_tri + k * kMdTriDoubles;
-            if (t[9] != 0.0) ub = fmin(ub, md_dist2(px, py, pz, t));
-          }
-        }
-      }
+  // 2. the nearest face; the bound starts from last iteration's face where there is one
+  double ub = INFINITY;
+  bool warm = false;
+  if (cull && has) {
+    const int wf = nearest[i];
+    double t[kMdTriDoubles];
+    if ((unsigned)wf < (unsigned)nf && md_load_tri(vert, faces, wf, nf, nv, t)) {
+      ub = fmin(ub, md_dist2(px, py, pz, t));                        // fmin: a NaN distance never becomes the bound
+      warm = true;
     }
   }
-
-  for (int tile = 0; tile < ntiles; tile++) {
-    bool lane_skips = !has;
-    if (cull && has) {
-      double s2;
-      const double lb2 = md_box_lb2(px, py, pz, box + 6 * (size_t)tile, &s2);
-      lane_skips = lb2 > fmin(best, ub) * (1.0 + 0x1p-20) + 0x1p-27 * s2;
-    }
-    const bool wave_skips = cull && __all(lane_skips);
-    // also the barrier between the last tile's reads and this tile's staging
-    if (__syncthreads_and(cull && lane_skips)) {
-      n_skipped++;
-      continue;
-    }
-    if (tid < kMdTile) md_load_tri(vert, faces, tile * kMdTile + tid, nf, nv, s_tri + tid * kMdTriDoubles);
-    __syncthreads();
-    if (wave_skips) {
-      n_skipped++;
-      continue;
-    }
-    const int cnt = min(kMdTile, nf - tile * kMdTile);
-    for (int k = 0; k < cnt; k++) {
-      const double* t = s_tri + k * kMdTriDoubles;       // one address for the whole wave: an LDS broadcast
-      if (t[9] != 0.0) {
-        const double d = md_dist2(px, py, pz, t);
-        if (d < best) best = d, best_f = tile * kMdTile + k;
-      }
-    }
-  }
+  const MdNearest r = md_scan(px, py, pz, has, (double)(float)y0[0], (double)(float)y0[1], (double)(float)y0[2], vert,
+                              faces, nf, nv, cull, box, s_tri, &s_home, ub, !warm);
+  const double best = r.dist2;
+  const int best_f = r.face;
 
   // 3. the closest point on the nearest face, and whether the pair counts
   double c[3] = {NAN, NAN, NAN};
@@ -203,7 +137,7 @@ __global__ __launch_bounds__(kMdBlock) void ma_step_kernel(const float* __restri
     dist2[i] = best;
     nearest[i] = best_f;
   }
-  if (skipped && lane == 0) skipped[4 * (size_t)blockIdx.x + wave] = n_skipped;
+  if (skipped && lane == 0) skipped[4 * (size_t)blockIdx.x + wave] = r.skipped;
 
   // 4., 5. the moments about (p_0, T_k p_0), reduced in a fixed order
   double v[kMaSums];
@@ -333,9 +267,7 @@ __global__ __launch_bounds__(kWave) void ma_solve_kernel(const double* __restric
   for (int k = 0; k < kMaSums; k++) {
     double x = 0.0;
     for (int b = lane; b < nblocks; b += kWave) x += partial[kMaSums * (size_t)b + k];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, kWave);
-    sum[k] = x;
+    sum[k] = wave_sum(x);
   }
   if (lane != 0) return;
   int status = MSLAM_MESH_ALIGN_DEGENERATE;
@@ -390,10 +322,7 @@ __global__ void ma_read_kernel(const double* __restrict__ state, double* __restr
   if (k == 0 && status) *status = *(const int32_t*)(state + 8);
 }
 
-static unsigned ma_blocks(int n, int per) { return (unsigned)(((int64_t)n + per - 1) / per); }
-static size_t ma_box_bytes(int nf) { return (size_t)ma_blocks(nf, kMdTile) * 6 * sizeof(double); }
-static size_t ma_partial_bytes(int n) { return (size_t)ma_blocks(n, kMdBlock) * kMaSums * sizeof(double); }
-static size_t ma_count_bytes(int n) { return (size_t)ma_blocks(n, kMdBlock) * 4 * sizeof(int32_t); }
+static size_t ma_partial_bytes(int n) { return (size_t)blocks_for(n, kMdBlock) * kMaSums * sizeof(double); }
 
 }  // namespace mslam
 
@@ -401,7 +330,7 @@ using namespace mslam;
 
 extern "C" size_t mslam_mesh_align_workspace_bytes(int n, int num_faces, int count_skips) {
   if (n < 0 || num_faces < 0) return 0;
-  return ma_box_bytes(num_faces) + ma_partial_bytes(n) + (count_skips ? ma_count_bytes(n) : 0);
+  return md_box_bytes(num_faces) + ma_partial_bytes(n) + (count_skips ? md_count_bytes(n) : 0);
 }
 
 extern "C" int mslam_mesh_align_init(const float* T0, const float* vertices, const int32_t* faces, int num_faces,
@@ -411,14 +340,14 @@ extern "C" int mslam_mesh_align_init(const float* T0, const float* vertices, con
   MSLAM_REQUIRE(state, "mesh_align_init: null pointer");
   MSLAM_REQUIRE(num_faces == 0 || (faces && workspace && (vertices || num_vertices == 0)),
                 "mesh_align_init: null pointer");
-  if (workspace_bytes < ma_box_bytes(num_faces)) {
-    set_error("mesh_align_init: workspace of %zu bytes, %zu needed", workspace_bytes, ma_box_bytes(num_faces));
+  if (workspace_bytes < md_box_bytes(num_faces)) {
+    set_error("mesh_align_init: workspace of %zu bytes, %zu needed", workspace_bytes, md_box_bytes(num_faces));
     return MSLAM_ENOMEM;
   }
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(ma_init_kernel, dim3(1), dim3(kWave), 0, s, T0, (double*)state);
   if (num_faces > 0)
-    hipLaunchKernelGGL(md_box_kernel, dim3(ma_blocks(num_faces, kMdTile)), dim3(kWave), 0, s, vertices, faces,
+    hipLaunchKernelGGL(md_box_kernel, dim3(blocks_for(num_faces, kMdTile)), dim3(kWave), 0, s, vertices, faces,
                        num_faces, num_vertices, (double*)workspace);
   MSLAM_LAUNCH_CHECK("mesh_align_init");
   return MSLAM_OK;
@@ -434,14 +363,14 @@ extern "C" int mslam_mesh_align_step(const float* src, int n, const float* verti
   MSLAM_REQUIRE(n == 0 || (src && nearest && moved && dist2 && workspace), "mesh_align_step: null pointer");
   MSLAM_REQUIRE(num_faces == 0 || (faces && workspace && (vertices || num_vertices == 0)),
                 "mesh_align_step: null pointer");
-  const size_t box_bytes = ma_box_bytes(num_faces), part_bytes = ma_partial_bytes(n);
-  const size_t need = box_bytes + part_bytes + (count_skips ? ma_count_bytes(n) : 0);
+  const size_t box_bytes = md_box_bytes(num_faces), part_bytes = ma_partial_bytes(n);
+  const size_t need = box_bytes + part_bytes + (count_skips ? md_count_bytes(n) : 0);
   if (workspace_bytes < need) {
     set_error("mesh_align_step: workspace of %zu bytes, %zu needed", workspace_bytes, need);
     return MSLAM_ENOMEM;
   }
   hipStream_t s = (hipStream_t)stream;
-  const unsigned nblocks = ma_blocks(n, kMdBlock);
+  const unsigned nblocks = blocks_for(n, kMdBlock);
   double* partial = (double*)((char*)workspace + box_bytes);
   if (n > 0)
     hipLaunchKernelGGL(ma_step_kernel, dim3(nblocks), dim3(kMdBlock), 0, s, src, n, vertices, faces, num_faces,
@@ -466,7 +395,7 @@ extern "C" int mslam_mesh_align_fit_pairs(const float* src, const float* dst, co
     return MSLAM_ENOMEM;
   }
   hipStream_t s = (hipStream_t)stream;
-  const unsigned nblocks = ma_blocks(n, kMdBlock);
+  const unsigned nblocks = blocks_for(n, kMdBlock);
   hipLaunchKernelGGL(ma_init_kernel, dim3(1), dim3(kWave), 0, s, (const float*)nullptr, (double*)state);
   if (n > 0)
     hipLaunchKernelGGL(ma_pairs_kernel, dim3(nblocks), dim3(kMdBlock), 0, s, src, dst, weights, n,

@@ -178,8 +178,6 @@ __global__ __launch_bounds__(256) void cc_emit_kernel(const float* __restrict__ 
   }
 }
 
-static unsigned cc_blocks(int n) { return (unsigned)(((int64_t)n + 255) / 256); }
-
 }  // namespace mslam
 
 using namespace mslam;
@@ -190,11 +188,11 @@ extern "C" int mslam_mesh_cc_label(const int32_t* faces, int num_faces, int num_
   if (num_vertices == 0) return MSLAM_OK;
   MSLAM_REQUIRE(root && (faces || num_faces == 0), "mesh_cc_label: null pointer");
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(cc_init_kernel, dim3(cc_blocks(num_vertices)), dim3(256), 0, s, num_vertices, root);
+  hipLaunchKernelGGL(cc_init_kernel, dim3(blocks_for(num_vertices, 256)), dim3(256), 0, s, num_vertices, root);
   if (num_faces > 0) {
-    hipLaunchKernelGGL(cc_hook_kernel, dim3(cc_blocks(num_faces)), dim3(256), 0, s, faces, num_faces, num_vertices,
-                       root);
-    hipLaunchKernelGGL(cc_flatten_kernel, dim3(cc_blocks(num_vertices)), dim3(256), 0, s, num_vertices, root);
+    hipLaunchKernelGGL(cc_hook_kernel, dim3(blocks_for(num_faces, 256)), dim3(256), 0, s, faces, num_faces,
+                       num_vertices, root);
+    hipLaunchKernelGGL(cc_flatten_kernel, dim3(blocks_for(num_vertices, 256)), dim3(256), 0, s, num_vertices, root);
   }
   MSLAM_LAUNCH_CHECK("mesh_cc_label");
   return MSLAM_OK;
@@ -206,13 +204,13 @@ extern "C" int mslam_mesh_cc_count(const int32_t* faces, int num_faces, int num_
   if (num_vertices == 0) return MSLAM_OK;
   MSLAM_REQUIRE(root && (faces || num_faces == 0), "mesh_cc_count: null pointer");
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(cc_zero_kernel, dim3(cc_blocks(num_vertices)), dim3(256), 0, s, num_vertices, faces_at_root,
+  hipLaunchKernelGGL(cc_zero_kernel, dim3(blocks_for(num_vertices, 256)), dim3(256), 0, s, num_vertices, faces_at_root,
                      verts_at_root);
   if (faces_at_root && num_faces > 0)
-    hipLaunchKernelGGL(cc_count_faces_kernel, dim3(cc_blocks(num_faces)), dim3(256), 0, s, faces, num_faces,
+    hipLaunchKernelGGL(cc_count_faces_kernel, dim3(blocks_for(num_faces, 256)), dim3(256), 0, s, faces, num_faces,
                        num_vertices, root, faces_at_root, aggregate);
   if (verts_at_root)
-    hipLaunchKernelGGL(cc_count_verts_kernel, dim3(cc_blocks(num_vertices)), dim3(256), 0, s, num_vertices, root,
+    hipLaunchKernelGGL(cc_count_verts_kernel, dim3(blocks_for(num_vertices, 256)), dim3(256), 0, s, num_vertices, root,
                        verts_at_root, aggregate);
   MSLAM_LAUNCH_CHECK("mesh_cc_count");
   return MSLAM_OK;
@@ -225,7 +223,7 @@ extern "C" int mslam_mesh_cc_select(const int32_t* faces, int num_faces, int num
   MSLAM_REQUIRE(root && keep_root && keep_vertex && ((faces && keep_face) || num_faces == 0),
                 "mesh_cc_select: null pointer");
   const int n = num_vertices > num_faces ? num_vertices : num_faces;
-  hipLaunchKernelGGL(cc_select_kernel, dim3(cc_blocks(n)), dim3(256), 0, (hipStream_t)stream, faces, num_faces,
+  hipLaunchKernelGGL(cc_select_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, faces, num_faces,
                      num_vertices, root, keep_root, keep_vertex, keep_face);
   MSLAM_LAUNCH_CHECK("mesh_cc_select");
   return MSLAM_OK;
@@ -246,9 +244,9 @@ extern "C" int mslam_mesh_cc_emit(const float* vertices, const float* normals, c
   MSLAM_REQUIRE(num_faces == 0 || (faces && keep_face && fbase && (out_faces || n_out_faces == 0)),
                 "mesh_cc_emit: null pointer");
   const int n = num_vertices > num_faces ? num_vertices : num_faces;
-  hipLaunchKernelGGL(cc_emit_kernel, dim3(cc_blocks(n)), dim3(256), 0, (hipStream_t)stream, vertices, normals, colors,
-                     faces, num_faces, num_vertices, keep_vertex, keep_face, vbase, fbase, out_vertices, out_normals,
-                     out_colors, out_faces, n_out_vertices, n_out_faces);
+  hipLaunchKernelGGL(cc_emit_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, vertices, normals,
+                     colors, faces, num_faces, num_vertices, keep_vertex, keep_face, vbase, fbase, out_vertices,
+                     out_normals, out_colors, out_faces, n_out_vertices, n_out_faces);
   MSLAM_LAUNCH_CHECK("mesh_cc_emit");
   return MSLAM_OK;
 }

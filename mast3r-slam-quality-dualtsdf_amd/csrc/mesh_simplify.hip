@@ -234,8 +234,6 @@ __global__ __launch_bounds__(256) void ms_mark_kernel(const int32_t* __restrict_
   keep_face[j] = keep ? 1 : 0;
 }
 
-static unsigned ms_blocks(int n, int per) { return (unsigned)(((int64_t)n + per - 1) / per); }
-
 }  // namespace mslam
 
 using namespace mslam;
@@ -246,7 +244,7 @@ extern "C" int mslam_mesh_simplify_keys(const float* vertices, int num_vertices,
   MSLAM_REQUIRE(cell_size > 0.0 && isfinite(cell_size), "mesh_simplify_keys: cell_size must be finite and positive");
   if (num_vertices == 0) return MSLAM_OK;
   MSLAM_REQUIRE(vertices && keys, "mesh_simplify_keys: null pointer");
-  hipLaunchKernelGGL(ms_keys_kernel, dim3(ms_blocks(num_vertices, 256)), dim3(256), 0, (hipStream_t)stream, vertices,
+  hipLaunchKernelGGL(ms_keys_kernel, dim3(blocks_for(num_vertices, 256)), dim3(256), 0, (hipStream_t)stream, vertices,
                      num_vertices, cell_size, keys);
   MSLAM_LAUNCH_CHECK("mesh_simplify_keys");
   return MSLAM_OK;
@@ -263,7 +261,7 @@ extern "C" int mslam_mesh_simplify_faces(const int32_t* faces, int num_faces, in
   if (num_faces == 0) return MSLAM_OK;
   MSLAM_REQUIRE(faces && tri && key_lo && pairs && (cluster || num_vertices == 0) && (key_hi || packed),
                 "mesh_simplify_faces: null pointer");
-  hipLaunchKernelGGL(ms_faces_kernel, dim3(ms_blocks(num_faces, 256)), dim3(256), 0, (hipStream_t)stream, faces,
+  hipLaunchKernelGGL(ms_faces_kernel, dim3(blocks_for(num_faces, 256)), dim3(256), 0, (hipStream_t)stream, faces,
                      num_faces, num_vertices, cluster, num_clusters, packed, tri, key_hi, key_lo, pairs);
   MSLAM_LAUNCH_CHECK("mesh_simplify_faces");
   return MSLAM_OK;
@@ -284,10 +282,10 @@ extern "C" int mslam_mesh_simplify_solve(const float* vertices, const float* nor
                 "mesh_simplify_solve: null pointer");
   MSLAM_REQUIRE((colors == nullptr) == (out_colors == nullptr), "mesh_simplify_solve: colours need an input and an output");
   MSLAM_REQUIRE(!quadric || num_faces == 0 || (faces && sorted_pairs && pair_start), "mesh_simplify_solve: null pointer");
-  hipLaunchKernelGGL(ms_solve_kernel, dim3(ms_blocks(num_clusters, 64)), dim3(64), 0, (hipStream_t)stream, vertices,
-                     normals, colors, faces, num_faces, num_vertices, cell_size, sorted_keys, vertex_order, vertex_start,
-                     sorted_pairs, pair_start, num_clusters, quadric && num_faces > 0 ? 1 : 0, out_vertices, out_normals,
-                     out_colors, out_fallback);
+  hipLaunchKernelGGL(ms_solve_kernel, dim3(blocks_for(num_clusters, 64)), dim3(64), 0, (hipStream_t)stream, vertices,
+                     normals, colors, faces, num_faces, num_vertices, cell_size, sorted_keys, vertex_order,
+                     vertex_start, sorted_pairs, pair_start, num_clusters, quadric && num_faces > 0 ? 1 : 0,
+                     out_vertices, out_normals, out_colors, out_fallback);
   MSLAM_LAUNCH_CHECK("mesh_simplify_solve");
   return MSLAM_OK;
 }
@@ -298,8 +296,8 @@ extern "C" int mslam_mesh_simplify_mark(const int32_t* tri, const int64_t* face_
   if (num_faces == 0) return MSLAM_OK;
   MSLAM_REQUIRE(tri && face_order && sorted_tri && keep_face && (referenced || num_clusters == 0),
                 "mesh_simplify_mark: null pointer");
-  hipLaunchKernelGGL(ms_mark_kernel, dim3(ms_blocks(num_faces, 256)), dim3(256), 0, (hipStream_t)stream, tri, face_order,
-                     num_faces, num_clusters, sorted_tri, keep_face, referenced);
+  hipLaunchKernelGGL(ms_mark_kernel, dim3(blocks_for(num_faces, 256)), dim3(256), 0, (hipStream_t)stream, tri,
+                     face_order, num_faces, num_clusters, sorted_tri, keep_face, referenced);
   MSLAM_LAUNCH_CHECK("mesh_simplify_mark");
   return MSLAM_OK;
 }

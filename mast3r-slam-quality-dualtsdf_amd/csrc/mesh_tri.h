@@ -1,9 +1,25 @@
 // Triangle helpers shared by the mesh-quality kernels (mesh_distance.hip) and the mesh-alignment kernels
-// (mesh_align.hip): the validity rule, the closest point of a triangle by Voronoi regions, the per-tile boxes and the
-// distance from a point to a box.  Semantics in DESIGN.md "Mesh quality"; tests/meshdist_numpy.py states the same
+// (mesh_align.hip): the validity rule, the closest point of a triangle by Voronoi regions, the per-tile boxes, the
+// distance from a point to a box, and md_scan, the one culled nearest-face scan that md_distance_kernel and
+// ma_step_kernel both call.  Semantics in DESIGN.md "Mesh quality"; tests/meshdist_numpy.py states the same
 // definitions, operation by operation, in numpy.  Everything is f64 on the f32 inputs and the build has
-// -ffp-contract=off, so a * b + c below is two roundings, as in numpy.  The invariant that makes culling by these boxes
-// exact is in the header comment of mesh_distance.hip.
+// -ffp-contract=off, so a * b + c below is two roundings, as in numpy.
+//
+// THE INVARIANT that makes culling exact.  md_dist2(p, f) is |p - q|^2 for a computed point q of face f: a vertex
+// itself, a + v (b - a) with a computed 0 <= v <= 1 (both ends of an edge region's division are ordered, and rounding
+// is monotone), or a point of the face's plane.  A tile's box holds every vertex of its valid faces exactly (f32
+// values in f64), so it holds each face, and q lies within eps of the box, eps a small multiple of the rounding unit
+// times the largest coordinate S in play: |p - q| >= lb - eps, where lb is the distance from p to the box.  In the
+// interior region an in-plane error of q adds to the distance from the plane, and a foot point wrongly taken for
+// interior lies outside the face by no more than the same in-plane error.  The scan keeps
+// best = min over scanned faces, and with culling also ub, the value of some real face (so the final minimum is
+// <= ub).  A tile is skipped only when, for every point of the wave (scan) or block (staging),
+//     lb2 > min(best, ub) * (1 + 2^-20) + 2^-27 * S^2 .
+// lb2 itself carries 4 roundings (relative 2^-51, inside the 2^-20), and 2^-27 S^2 >= 2 lb eps for eps = 2^-30 S, a
+// closest-point error four million times the rounding unit: the slack is there for sliver triangles, and it costs
+// nothing, because a tile worth skipping is centimetres away and 2^-27 S^2 is (1e-4 S)^2.  So every face of a skipped
+// tile has md_dist2 > min(best, ub) >= the final minimum: it is neither the minimum nor a tie, and the output is the
+// one of the plain ascending scan with its strict `<`, bit for bit.  tests/test_mesh_metrics_gpu.py is the judge.
 #pragma once
 #include <math.h>
 
@@ -151,5 +167,96 @@ __device__ __forceinline__ double md_box_lb2(double px, double py, double pz, co
   *s2 = s * s;
   return md_dot(dx, dy, dz, dx, dy, dz);
 }
+
+struct MdNearest {
+  double dist2;   // md_dist2 to the nearest valid face, +inf without one
+  int face;       // the lowest index of a face at that distance, -1 without one
+  int skipped;    // the tiles this lane's wave did not scan
+};
+
+// The nearest valid face of the mesh to this lane's point p.  Every thread of the block calls it, also one without a
+// point (`has` false): it reaches the same barriers and never keeps a tile in.
+// `cull` 0 is the plain ascending scan.  With `cull` the two parameters that may differ per lane, neither of which
+// changes an output bit, are
+//   ub         the lane's starting bound: +inf, or md_dist2(p, any valid face), which is the value of a real face
+//              and so all the invariant above asks of it;
+//   need_home  the lane has no such face yet.  When some lane of the block with a point says so, the block stages
+//              its home tile, the one whose box is nearest to the block's first point q0 (which tile it is changes
+//              no output), and those lanes take ub from its faces.
+// s_tri: kMdTile * kMdTriDoubles doubles of LDS; s_home: one LDS word.
+__device__ __forceinline__ MdNearest md_scan(double px, double py, double pz, bool has, double q0x, double q0y,
+                                             double q0z, const float* __restrict__ vert,
+                                             const int32_t* __restrict__ faces, int nf, int nv, int cull,
+                                             const double* __restrict__ box, double* s_tri, int* s_home, double ub,
+                                             bool need_home) {
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  const int ntiles = (nf + kMdTile - 1) / kMdTile;
+  double best = INFINITY;
+  int best_f = -1, n_skipped = 0;
+
+  if (cull && __syncthreads_or(has && need_home)) {
+    if (wave == 0) {
+      double m = INFINITY, s2;
+      int mt = -1;
+      for (int t = lane; t < ntiles; t += kWave) {
+        const double lb2 = md_box_lb2(q0x, q0y, q0z, box + 6 * (size_t)t, &s2);
+        if (lb2 < m) m = lb2, mt = t;
+      }
+      for (int off = 32; off > 0; off >>= 1) {
+        const double om = __shfl_down(m, off, kWave);
+        const int ot = __shfl_down(mt, off, kWave);
+        if (ot >= 0 && (mt < 0 || om < m || (om == m && ot < mt))) m = om, mt = ot;
+      }
+      if (lane == 0) *s_home = mt;
+    }
+    __syncthreads();
+    const int home = *s_home;
+    if (home >= 0) {
+      if (tid < kMdTile) md_load_tri(vert, faces, home * kMdTile + tid, nf, nv, s_tri + tid * kMdTriDoubles);
+      __syncthreads();
+      if (need_home) {
+        const int cnt = min(kMdTile, nf - home * kMdTile);
+        for (int k = 0; k < cnt; k++) {
+          const double* t = s_tri + k * kMdTriDoubles;
+          if (t[9] != 0.0) ub = fmin(ub, md_dist2(px, py, pz, t));     // fmin: a NaN distance never becomes the bound
+        }
+      }
+    }
+  }
+
+  for (int tile = 0; tile < ntiles; tile++) {
+    bool lane_skips = !has;
+    if (cull && has) {
+      double s2;
+      const double lb2 = md_box_lb2(px, py, pz, box + 6 * (size_t)tile, &s2);
+      lane_skips = lb2 > fmin(best, ub) * (1.0 + 0x1p-20) + 0x1p-27 * s2;
+    }
+    const bool wave_skips = cull && __all(lane_skips);
+    // also the barrier between the last tile's reads and this tile's staging
+    if (__syncthreads_and(cull && lane_skips)) {
+      n_skipped++;
+      continue;
+    }
+    if (tid < kMdTile) md_load_tri(vert, faces, tile * kMdTile + tid, nf, nv, s_tri + tid * kMdTriDoubles);
+    __syncthreads();
+    if (wave_skips) {
+      n_skipped++;
+      continue;
+    }
+    const int cnt = min(kMdTile, nf - tile * kMdTile);
+    for (int k = 0; k < cnt; k++) {
+      const double* t = s_tri + k * kMdTriDoubles;       // one address for the whole wave: an LDS broadcast
+      if (t[9] != 0.0) {
+        const double d = md_dist2(px, py, pz, t);
+        if (d < best) best = d, best_f = tile * kMdTile + k;
+      }
+    }
+  }
+  return {best, best_f, n_skipped};
+}
+
+// workspace bytes of the boxes of nf faces, and of the per-wave skip counts of n points (four waves per block)
+inline size_t md_box_bytes(int nf) { return (size_t)blocks_for(nf, kMdTile) * 6 * sizeof(double); }
+inline size_t md_count_bytes(int n) { return (size_t)blocks_for(n, kMdBlock) * 4 * sizeof(int32_t); }
 
 }  // namespace mslam

@@ -12,36 +12,10 @@ import torch
 
 import mslam_hip as _m
 
-from .mesh_metrics import _mesh_arg, _pair, _sample
+from ._mesh_args import _mesh_arg, _pair, _points_arg, _sample, _sim3_arg
 
-STATE_BYTES = 72           # MSLAM_MESH_ALIGN_STATE_BYTES
-LOG_DOUBLES = 24           # MSLAM_MESH_ALIGN_LOG_DOUBLES
-OK, DEGENERATE = 0, 1      # MSLAM_MESH_ALIGN_OK / _DEGENERATE
-
-
-def _points_arg(x, name, what, device=None):
-    """f32[n,3] contiguous device tensor; numpy arrays and lists are moved to `device` (there is no CPU path)."""
-    if not torch.is_tensor(x):
-        if device is None:
-            raise TypeError(f"{what}: {name} must be a device tensor")
-        x = torch.as_tensor(np.asarray(x, np.float32)).to(device)
-    if x.dim() != 2 or x.shape[1] != 3:
-        raise ValueError(f"{what}: {name} must be (n,3), got {tuple(x.shape)}")
-    _m.require_dtype(x, torch.float32, name)
-    _m.ptr(x)
-    if x.shape[0] >= 1 << 31:
-        raise ValueError(f"{what}: too many points for the int32 index range")
-    return x.contiguous()
-
-
-def _sim3_arg(T, what, device, dtype):
-    """A Sim3 given as a tensor, array or sequence of 8 numbers (or a lietorch Sim3) -> tensor[8] on the device."""
-    T = getattr(T, "data", T)
-    T = T.detach().to(device=device, dtype=dtype) if torch.is_tensor(T) else torch.as_tensor(
-        np.asarray(T, np.float64), dtype=dtype, device=device)
-    if T.numel() != 8:
-        raise ValueError(f"{what}: a Sim3 is 8 numbers [t(3), q(xyzw), s], got shape {tuple(T.shape)}")
-    return T.reshape(8).contiguous()
+STATE_BYTES, LOG_DOUBLES, OK, DEGENERATE = (_m.header_constants()["MSLAM_MESH_ALIGN_" + k] for k in (
+    "STATE_BYTES", "LOG_DOUBLES", "OK", "DEGENERATE"))
 
 
 def _read_state(state):

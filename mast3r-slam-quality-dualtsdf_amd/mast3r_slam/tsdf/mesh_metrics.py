@@ -11,56 +11,14 @@ import torch
 
 import mslam_hip as _m
 
-from .mesh_ops import _faces_arg
-
-_MASK64 = (1 << 64) - 1
-
-
-def _mesh_arg(vertices, faces, validate, what):
-    """(vertices f32[V,3], faces i32[F,3], V, F) contiguous device tensors; `validate`: the index range of the faces,
-    one reduction and one host read."""
-    if not torch.is_tensor(vertices):
-        raise TypeError(f"{what}: vertices must be a device tensor")
-    if vertices.dim() != 2 or vertices.shape[1] != 3:
-        raise ValueError(f"{what}: vertices must be (V,3), got {tuple(vertices.shape)}")
-    _m.require_dtype(vertices, torch.float32, "vertices")
-    _m.ptr(vertices)                                        # a host tensor raises here: no CPU path exists
-    faces, V, F = _faces_arg(faces, vertices.shape[0], validate, what)
-    _m.ptr(faces)
-    if faces.device != vertices.device:
-        raise ValueError(f"{what}: vertices and faces are on different devices")
-    return vertices.contiguous(), faces, V, F
-
-
-def _areas(vertices, faces, V, F):
-    area = torch.empty(F, dtype=torch.float64, device=vertices.device)
-    _m.check(_m.lib().mslam_mesh_face_areas(_m.ptr(vertices), _m.ptr(faces), F, V, _m.ptr(area), _m.stream_ptr()),
-             "mesh_face_areas")
-    return area
+from ._mesh_args import _areas, _mesh_arg, _pair, _points_arg, _sample, _sim3_arg
+from .mesh_align import align_meshes, transform_mesh
 
 
 def face_areas(vertices, faces, _validate=True):
     """area f64[F] = 0.5 |(b - a) x (c - a)| of the faces i32[F,3] over vertices f32[V,3] (device tensors), in f64."""
     vertices, faces, V, F = _mesh_arg(vertices, faces, _validate, "face_areas")
     return _areas(vertices, faces, V, F)
-
-
-def _sample(vertices, faces, V, F, n, seed, what):
-    """(points, face, total area as a Python float).  One host read: the total."""
-    n = int(n)
-    if n < 1 or n >= 1 << 31:
-        raise ValueError(f"{what}: n must be in [1, 2^31), got {n}")
-    dev = vertices.device
-    cdf = torch.cumsum(_areas(vertices, faces, V, F), 0) if F else torch.zeros(0, dtype=torch.float64, device=dev)
-    total = float(cdf[-1]) if F else 0.0
-    if not (total > 0.0 and total < float("inf")):
-        raise ValueError(f"{what}: the mesh has no area to sample (total area {total})")
-    points = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    face = torch.empty(n, dtype=torch.int32, device=dev)
-    _m.check(_m.lib().mslam_mesh_sample(_m.ptr(vertices), _m.ptr(faces), F, V, _m.ptr(cdf), total, n,
-                                        int(seed) & _MASK64, _m.ptr(points), _m.ptr(face), _m.stream_ptr()),
-             "mesh_sample")
-    return points, face, total
 
 
 def sample_mesh(vertices, faces, n, seed=0, _validate=True):
@@ -91,28 +49,12 @@ def mesh_distance(points, vertices, faces, skip=True, _validate=True):
     to the closest point of the closest valid face and the lowest index of a face at that distance; +inf and -1 when
     the mesh has no valid face.  `skip`: tiles of faces whose bounding box lies beyond a point block's current best are
     not scanned; the output is the same bit for bit (DESIGN.md "Mesh quality")."""
-    if not torch.is_tensor(points):
-        raise TypeError("mesh_distance: points must be a device tensor")
-    if points.dim() != 2 or points.shape[1] != 3:
-        raise ValueError(f"mesh_distance: points must be (n,3), got {tuple(points.shape)}")
-    _m.require_dtype(points, torch.float32, "points")
-    _m.ptr(points)
-    if points.shape[0] >= 1 << 31:
-        raise ValueError("mesh_distance: too many points for the int32 index range")
+    points = _points_arg(points, "points", "mesh_distance")
     vertices, faces, V, F = _mesh_arg(vertices, faces, _validate, "mesh_distance")
     if points.device != vertices.device:
         raise ValueError("mesh_distance: points and mesh are on different devices")
-    dist2, nearest = _distance2(points.contiguous(), vertices, faces, V, F, bool(skip))
+    dist2, nearest = _distance2(points, vertices, faces, V, F, bool(skip))
     return torch.sqrt(dist2), nearest
-
-
-def _pair(mesh, what):
-    mesh = tuple(mesh)
-    if len(mesh) == 2:
-        return mesh
-    if len(mesh) in (3, 4):                                  # extract_mesh: (vertices, normals, faces[, colors])
-        return mesh[0], mesh[2]
-    raise ValueError(f"compare_meshes: {what} must be (vertices, faces) or an extract_mesh tuple")
 
 
 def compare_meshes(pred, gt, n_samples=200_000, threshold=0.05, seed=0, skip=True, _validate_pred=True, align=None,
@@ -133,8 +75,6 @@ def compare_meshes(pred, gt, n_samples=200_000, threshold=0.05, seed=0, skip=Tru
     threshold = float(threshold)
     alignment = None
     if align is not None:
-        from .mesh_align import _sim3_arg, align_meshes, transform_mesh
-
         pvert, pfaces = _pair(pred, "pred")
         if isinstance(align, str):
             if align != "icp":

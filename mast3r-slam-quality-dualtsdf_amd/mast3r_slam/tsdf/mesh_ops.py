@@ -10,30 +10,12 @@ import torch
 
 import mslam_hip as _m
 
-
-def _faces_arg(faces, num_vertices, validate, what):
-    """faces as a contiguous i32[F,3] device tensor; `validate`: the index range, one reduction and one host read."""
-    if not torch.is_tensor(faces):
-        raise TypeError(f"{what}: faces must be a device tensor")
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f"{what}: faces must be (F,3), got {tuple(faces.shape)}")
-    _m.require_dtype(faces, torch.int32, "faces")
-    faces = faces.contiguous()
-    V, F = int(num_vertices), int(faces.shape[0])
-    if V < 0 or V >= 1 << 31 or 3 * F >= 1 << 31:
-        raise ValueError(f"{what}: {V} vertices / {F} faces are outside the int32 index range")
-    if validate and F > 0:
-        _m.ptr(faces)                                       # a host tensor raises here: no CPU path exists
-        lo, hi = (int(x) for x in torch.stack(torch.aminmax(faces)).cpu())
-        if lo < 0 or hi >= V:
-            raise ValueError(f"{what}: face indices span [{lo}, {hi}], outside [0, {V})")
-    return faces, V, F
+from ._mesh_args import _faces_arg, _mesh_tuple_arg
 
 
 def _label_and_count(faces, V, F, want_vertices=True):
     """(root i32[V], counts i32[2,V]): counts[0] faces / counts[1] vertices of each component at its root's index."""
-    L = _m.lib()
-    stream = _m.stream_ptr()
+    L, stream = _m.lib(), _m.stream_ptr()
     root = torch.empty(V, dtype=torch.int32, device=faces.device)
     counts = torch.empty((2, V), dtype=torch.int32, device=faces.device)
     _m.check(L.mslam_mesh_cc_label(_m.ptr(faces), F, V, _m.ptr(root), stream), "mesh_cc_label")
@@ -62,6 +44,25 @@ def mesh_components(faces, num_vertices):
     return vertex_component, face_component, counts[0][is_root], counts[1][is_root]
 
 
+def _compact(per_vertex, faces, flags, V, F):
+    """The compaction tail of filter_mesh and simplify_mesh: the rows of the contiguous per-vertex tensors f32[V,3] and
+    of `faces` i32[F,3] (re-indexed) whose flag in `flags` i32[V + F] (vertices, then faces) is set -> (out per-vertex
+    tensors, out_faces, base i32[V + F]: the output row of each flagged row, n_v).  One host read: the output sizes."""
+    incl = torch.cumsum(flags, 0)                           # one scan over both flag rows; faces carry n_v in front
+    n_v, n_vf = (int(x) for x in incl[[V - 1, V + F - 1]].cpu())
+    n_f = n_vf - n_v
+    base = incl - flags
+    base[V:] -= n_v
+    out = [torch.empty((n_v, 3), dtype=torch.float32, device=flags.device) for _ in per_vertex]
+    out_faces = torch.empty((n_f, 3), dtype=torch.int32, device=flags.device)
+    src, dst = ([_m.ptr(t) for t in ts] + [0] for ts in (per_vertex, out))     # [0]: no colours
+    _m.check(_m.lib().mslam_mesh_cc_emit(src[0], src[1], src[2], _m.ptr(faces), F, V, _m.ptr(flags),
+                                         _m.ptr(flags[V:]) if F else 0, _m.ptr(base), _m.ptr(base[V:]) if F else 0,
+                                         dst[0], dst[1], dst[2], _m.ptr(out_faces) if n_f else 0, n_v, n_f,
+                                         _m.stream_ptr()), "mesh_cc_emit")
+    return out, out_faces, base, n_v
+
+
 def filter_mesh(mesh, min_faces=0, keep_largest=None, _validate=True):
     """Drops whole components of `mesh` = (vertices f32[V,3], normals f32[V,3], faces i32[F,3][, colors f32[V,3]]), the
     tuple extract_mesh returns; the result has the same arity.  Keeps the components with at least `min_faces` faces;
@@ -71,27 +72,17 @@ def filter_mesh(mesh, min_faces=0, keep_largest=None, _validate=True):
     `keep_largest=None` returns the input tensors unchanged.  Host reads: the index range of the faces, and the output
     sizes."""
     mesh = tuple(mesh)
-    if len(mesh) not in (3, 4):
-        raise ValueError(f"filter_mesh: mesh must hold 3 or 4 tensors, got {len(mesh)}")
+    _mesh_tuple_arg(mesh, "filter_mesh", check=False)
     if keep_largest is not None and int(keep_largest) < 0:
         raise ValueError("filter_mesh: keep_largest must be >= 0")
     if int(min_faces) <= 0 and keep_largest is None:
         return mesh
-    verts, normals, faces = mesh[:3]
-    colors = mesh[3] if len(mesh) == 4 else None
-    per_vertex = [verts, normals] + ([colors] if colors is not None else [])
-    for name, t in zip(("vertices", "normals", "colors"), per_vertex):
-        if not torch.is_tensor(t) or t.dim() != 2 or t.shape[1] != 3 or t.shape[0] != verts.shape[0]:
-            raise ValueError(f"filter_mesh: {name} must be ({int(verts.shape[0])},3)")
-        _m.require_dtype(t, torch.float32, name)
+    verts, _, faces, _, per_vertex = _mesh_tuple_arg(mesh, "filter_mesh")
     faces, V, F = _faces_arg(faces, verts.shape[0], _validate, "filter_mesh")
     if V == 0:
         return mesh
-    verts, normals = verts.contiguous(), normals.contiguous()
-    colors = colors.contiguous() if colors is not None else None
+    per_vertex = [t.contiguous() for t in per_vertex]
     dev = verts.device
-    L = _m.lib()
-    stream = _m.stream_ptr()
     root, counts = _label_and_count(faces, V, F, want_vertices=False)
     nfaces = counts[0]                                      # zero away from the roots
     is_root = root == torch.arange(V, dtype=torch.int32, device=dev)
@@ -104,17 +95,7 @@ def filter_mesh(mesh, min_faces=0, keep_largest=None, _validate=True):
         keep = keep & top
     keep_root = keep.to(torch.uint8)
     flags = torch.empty(V + F, dtype=torch.int32, device=dev)
-    _m.check(L.mslam_mesh_cc_select(_m.ptr(faces), F, V, _m.ptr(root), _m.ptr(keep_root), _m.ptr(flags),
-                                    _m.ptr(flags[V:]) if F else 0, stream), "mesh_cc_select")
-    incl = torch.cumsum(flags, 0)                           # one scan over both flag rows; faces carry V' in front
-    n_v, n_vf = (int(x) for x in incl[[V - 1, V + F - 1]].cpu())
-    n_f = n_vf - n_v
-    base = incl - flags
-    base[V:] -= n_v
-    out = [torch.empty((n_v, 3), dtype=torch.float32, device=dev) for _ in per_vertex]
-    out_faces = torch.empty((n_f, 3), dtype=torch.int32, device=dev)
-    _m.check(L.mslam_mesh_cc_emit(_m.ptr(verts), _m.ptr(normals), _m.ptr(colors), _m.ptr(faces), F, V, _m.ptr(flags),
-                                  _m.ptr(flags[V:]) if F else 0, _m.ptr(base), _m.ptr(base[V:]) if F else 0,
-                                  _m.ptr(out[0]), _m.ptr(out[1]), _m.ptr(out[2]) if colors is not None else 0,
-                                  _m.ptr(out_faces) if n_f else 0, n_v, n_f, stream), "mesh_cc_emit")
-    return (out[0], out[1], out_faces) + ((out[2],) if colors is not None else ())
+    _m.check(_m.lib().mslam_mesh_cc_select(_m.ptr(faces), F, V, _m.ptr(root), _m.ptr(keep_root), _m.ptr(flags),
+                                           _m.ptr(flags[V:]) if F else 0, _m.stream_ptr()), "mesh_cc_select")
+    out, out_faces, _, _ = _compact(per_vertex, faces, flags, V, F)
+    return (out[0], out[1], out_faces, *out[2:])

@@ -11,7 +11,8 @@ import torch
 
 import mslam_hip as _m
 
-from .mesh_ops import _faces_arg
+from ._mesh_args import _faces_arg, _mesh_tuple_arg
+from .mesh_ops import _compact
 
 _KEY_LIMIT = 1 << 20                    # cell keys per axis lie in [-2^20, 2^20): the voxel hash's 21-bit signed range
 
@@ -60,12 +61,9 @@ def simplify_mesh(mesh, cell_size, position="quadric", return_map=False, _valida
     the validation ranges, the number of clusters, the output sizes.  `_two_pass` forces the face sort that meshes of
     1.6 M clusters and more take (two stable passes instead of one packed key); the result is the same."""
     mesh = tuple(mesh)
-    if len(mesh) not in (3, 4):
-        raise ValueError(f"simplify_mesh: mesh must hold 3 or 4 tensors, got {len(mesh)}")
+    verts, normals, faces, colors, per_vertex = _mesh_tuple_arg(mesh, "simplify_mesh", check=False)
     if position not in ("quadric", "mean"):
         raise ValueError(f"simplify_mesh: position must be 'quadric' or 'mean', got {position!r}")
-    verts, normals, faces = mesh[:3]
-    colors = mesh[3] if len(mesh) == 4 else None
     c = None if cell_size is None else float(cell_size)
     if c is not None and not math.isfinite(c):
         raise ValueError(f"simplify_mesh: cell_size must be finite, got {c}")
@@ -73,20 +71,14 @@ def simplify_mesh(mesh, cell_size, position="quadric", return_map=False, _valida
         if not return_map:
             return mesh
         return mesh + (torch.arange(int(verts.shape[0]), dtype=torch.int32, device=verts.device),)
-    per_vertex = [verts, normals] + ([colors] if colors is not None else [])
-    for name, t in zip(("vertices", "normals", "colors"), per_vertex):
-        if not torch.is_tensor(t) or t.dim() != 2 or t.shape[1] != 3 or t.shape[0] != verts.shape[0]:
-            raise ValueError(f"simplify_mesh: {name} must be ({int(verts.shape[0])},3)")
-        _m.require_dtype(t, torch.float32, name)
-        _m.ptr(t)                                           # a host tensor raises here: no CPU path exists
+    _mesh_tuple_arg(mesh, "simplify_mesh", on_device=True)
     faces, V, F = _faces_arg(faces, verts.shape[0], False, "simplify_mesh")
     _m.ptr(faces)
     dev = verts.device
     i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
 
     def result(out, out_faces, vertex_map):
-        res = (out[0], out[1], out_faces) + ((out[2],) if colors is not None else ())
-        return res + ((vertex_map,) if return_map else ())
+        return (out[0], out[1], out_faces, *out[2:]) + ((vertex_map,) if return_map else ())
 
     if V == 0 or F == 0:                                    # no face, so no cluster is used
         return result([torch.empty((0, 3), dtype=torch.float32, device=dev) for _ in per_vertex],
@@ -95,8 +87,7 @@ def simplify_mesh(mesh, cell_size, position="quadric", return_map=False, _valida
     colors = colors.contiguous() if colors is not None else None
     if _validate:
         _validate_ranges(verts, faces, V, c)
-    L = _m.lib()
-    stream = _m.stream_ptr()
+    L, stream = _m.lib(), _m.stream_ptr()
     # clusters: stable sort of the cell keys, heads of the runs, one cumsum
     keys = torch.empty(V, **i64)
     _m.check(L.mslam_mesh_simplify_keys(_m.ptr(verts), V, c, _m.ptr(keys), stream), "mesh_simplify_keys")
@@ -134,23 +125,12 @@ def simplify_mesh(mesh, cell_size, position="quadric", return_map=False, _valida
                                          _m.ptr(sorted_keys), _m.ptr(vorder), _m.ptr(vstart), _m.ptr(sorted_pairs),
                                          _m.ptr(pstart), C, int(quadric), _m.ptr(out[0]), _m.ptr(out[1]),
                                          _m.ptr(out[2]) if colors is not None else 0, 0, stream), "mesh_simplify_solve")
-    # kept faces and the clusters they use; one scan over both flag rows, as in filter_mesh
+    # kept faces and the clusters they use
     flags = torch.zeros(C + F, **i32)
     sorted_tri = torch.empty((F, 3), **i32)
     _m.check(L.mslam_mesh_simplify_mark(_m.ptr(tri), _m.ptr(forder), F, C, _m.ptr(sorted_tri), _m.ptr(flags[C:]),
                                         _m.ptr(flags), stream), "mesh_simplify_mark")
-    incl = torch.cumsum(flags, 0)
-    n_v, n_vf = (int(x) for x in incl[[C - 1, C + F - 1]].cpu())
-    n_f = n_vf - n_v
-    base = incl - flags
-    base[C:] -= n_v
-    res = [torch.empty((n_v, 3), dtype=torch.float32, device=dev) for _ in per_vertex]
-    out_faces = torch.empty((n_f, 3), **i32)
-    _m.check(L.mslam_mesh_cc_emit(_m.ptr(out[0]), _m.ptr(out[1]), _m.ptr(out[2]) if colors is not None else 0,
-                                  _m.ptr(sorted_tri), F, C, _m.ptr(flags), _m.ptr(flags[C:]), _m.ptr(base),
-                                  _m.ptr(base[C:]), _m.ptr(res[0]), _m.ptr(res[1]),
-                                  _m.ptr(res[2]) if colors is not None else 0, _m.ptr(out_faces) if n_f else 0, n_v, n_f,
-                                  stream), "mesh_cc_emit")
+    res, out_faces, base, _ = _compact(out, sorted_tri, flags, C, F)
     vertex_map = None
     if return_map:
         cl = cluster.long()

@@ -4,6 +4,7 @@ This is the only place that touches the shared library.  There is deliberately N
 library is missing, or a tensor is not resident on a HIP device, the call raises.
 """
 import ctypes
+import functools
 import os
 import re
 
@@ -64,26 +65,30 @@ def parse_header(text: str) -> dict:
     return out
 
 
-_signatures = None
+@functools.lru_cache(maxsize=None)
+def _header_text() -> str:
+    """include/mslam_hip.h, read once."""
+    if not os.path.exists(_HEADER_PATH):
+        raise RuntimeError(
+            f"{_HEADER_PATH} not found: the binding reads every signature from the header that "
+            "libmslam_hip.so is built against. There is no hand-written copy to fall back to."
+        )
+    with open(_HEADER_PATH) as f:
+        return f.read()
 
 
-def _header_signatures() -> dict:
-    """parse_header() of include/mslam_hip.h, read once."""
-    global _signatures
-    if _signatures is None:
-        if not os.path.exists(_HEADER_PATH):
-            raise RuntimeError(
-                f"{_HEADER_PATH} not found: the binding reads every signature from the header that "
-                "libmslam_hip.so is built against. There is no hand-written copy to fall back to."
-            )
-        with open(_HEADER_PATH) as f:
-            _signatures = parse_header(f.read())
-    return _signatures
+def header_constants(text: str = None) -> dict:
+    """{name: int} of every `#define MSLAM_<NAME> <integer or (negative integer)>` of include/mslam_hip.h (or `text`),
+    so that no Python module keeps a copy; a define of anything else (a float, an expression, a macro) is left out."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", _header_text() if text is None else text, flags=re.S)
+    value = r"(\d+|\([ \t]*-[ \t]*\d+[ \t]*\))"
+    found = re.findall(r"^[ \t]*#[ \t]*define[ \t]+(MSLAM_\w+)[ \t]+" + value + r"[ \t]*$", text, flags=re.M)
+    return {name: int(re.sub(r"[() \t]", "", v)) for name, v in found}
 
 
 def exported_symbols():
     """Every symbol include/mslam_hip.h declares (used by the CPU-side ABI test)."""
-    return sorted(_header_signatures())
+    return sorted(parse_header(_header_text()))
 
 
 _lib = None
@@ -98,7 +103,7 @@ def lib() -> ctypes.CDLL:
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback for this path."
             )
         handle = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in _header_signatures().items():
+        for name, (restype, argtypes) in parse_header(_header_text()).items():
             fn = getattr(handle, name)
             fn.argtypes = argtypes
             fn.restype = restype

@@ -118,6 +118,38 @@ def test_parse_header_reads_plain_declarations():
     }
 
 
+def test_header_constants():
+    """header_constants() reads the integer #defines of the real header; the literals here are the independent
+    statement."""
+    c = mslam_hip.header_constants()
+    want = {"MSLAM_MESH_ALIGN_STATE_BYTES": 72, "MSLAM_MESH_ALIGN_LOG_DOUBLES": 24, "MSLAM_MESH_ALIGN_OK": 0,
+            "MSLAM_MESH_ALIGN_DEGENERATE": 1, "MSLAM_OK": 0, "MSLAM_EINVAL": -1, "MSLAM_EHIP": -2, "MSLAM_ENOMEM": -3,
+            "MSLAM_ENODEV": -4}
+    assert {k: c.get(k) for k in want} == want
+    with open(os.path.join(ROOT, "include", "mslam_hip.h")) as f:
+        header = f.read()
+    for name, value in want.items():                       # the header's values, read without the parser
+        m = re.search(rf"^#define {name} \(?(-?\d+)\)?", header, flags=re.M)
+        assert m is not None and int(m.group(1)) == value, name
+    assert "MSLAM_HIP_H" not in c                           # the include guard has no value
+    text = """
+#define MSLAM_A 7   /* a comment */
+#define MSLAM_B (-12)  // another
+  #  define MSLAM_C ( - 3 )
+#define MSLAM_RATIO 1.5
+#define MSLAM_HALF 0.5f
+#define MSLAM_SUM (1 + 2)
+#define MSLAM_HEX 0x10
+#define MSLAM_NAME "text"
+#define MSLAM_OTHER MSLAM_A
+#define MSLAM_F(x) 3
+#define MSLAM_EMPTY
+#define OTHER_D 4
+/* #define MSLAM_COMMENTED 9 */
+"""
+    assert mslam_hip.header_constants(text) == {"MSLAM_A": 7, "MSLAM_B": -12, "MSLAM_C": -3}
+
+
 def test_abi_version():
     assert mslam_hip.lib().mslam_abi_version() >= 1
 

@@ -200,6 +200,34 @@ def test_step_matches_mesh_distance_and_numpy(device, nf, n):
     assert cold["status"] == (A.OK if n >= 3 else A.DEGENERATE)
 
 
+@pytest.mark.parametrize("n", [BLOCK - 1, BLOCK + 1])
+@pytest.mark.parametrize("nf", [TILE, TILE + 1, 4 * TILE + 1])
+def test_cold_step_skips_the_tiles_mesh_distance_skips(device, nf, n):
+    """One scan, two callers (md_scan of csrc/mesh_tri.h): a cold step takes its bound from the home tile of the
+    block's first moved point, as mslam_mesh_distance does on the same points, so every wave skips the same number of
+    tiles, the int32 words themselves, and returns the same bytes.  One tile is scanned plainly by both: no tile is
+    skipped."""
+    _m, L, st = _lib()
+    P, V, F = align_case(nf, n)
+    cold = _step(device, P, V, F, count=True)
+    nblk, waves = (n + BLOCK - 1) // BLOCK, (n + 63) // 64
+    step_counts = cold["ws"].view(np.int32)[-4 * nblk:][:waves]
+    box = int(L.mslam_mesh_distance_workspace_bytes(nf))
+    ws = torch.full((box + 16 * nblk,), 0xFF, dtype=torch.uint8, device=device)
+    d2 = torch.empty(n, dtype=torch.float64, device=device)
+    near = torch.empty(n, dtype=torch.int32, device=device)
+    _m.check(L.mslam_mesh_distance(_m.ptr(_dev(device, cold["moved"], np.float32)), n, _m.ptr(cold["v"]),
+                                   _m.ptr(cold["f"]), nf, int(cold["v"].shape[0]), 2, _m.ptr(ws), ws.numel(),
+                                   _m.ptr(d2), _m.ptr(near), st), "mesh_distance")
+    dist_counts = ws[box:].view(torch.int32).cpu().numpy()[:waves]
+    print(f"F={nf} n={n}: skipped per wave, step {step_counts.tolist()}, mesh_distance {dist_counts.tolist()}")
+    assert np.array_equal(step_counts, dist_counts)
+    assert cold["dist2"].tobytes() == d2.cpu().numpy().tobytes()
+    assert cold["nearest"].tobytes() == near.cpu().numpy().tobytes()
+    if nf <= TILE:
+        assert not step_counts.any() and not dist_counts.any()
+
+
 @pytest.mark.parametrize("nf,n", [(4 * TILE + 1, 4 * BLOCK + 1), (TILE + 1, BLOCK - 1), (TILE - 1, 3 * 64 + 7)])
 def test_trimmed_sums_and_solve(device, nf, n):
     """A trim that drops most pairs, a whole block (points 256..511) and whole waves without an inlier, n no multiple

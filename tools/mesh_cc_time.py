@@ -8,18 +8,13 @@ min_component_faces=n).  The mesh is timed at the volume's min_weight and at a h
 many components.  Not part of bench.py.
     python tools/mesh_cc_time.py 60 [--reps 20] [--min-faces 50] [--weights 0 40]"""
 import argparse
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "mast3r-slam-quality-dualtsdf_amd")]
-import numpy as np
 import torch
 
+from _room import build_room, timed   # first: it puts the package on sys.path
 import mslam_hip as _m
-from mast3r_slam import synthetic
 from mast3r_slam.config import config
-from mast3r_slam.tsdf import TSDFVolume, mesh_components
+from mast3r_slam.tsdf import mesh_components
 
 ap = argparse.ArgumentParser()
 ap.add_argument("keyframes", type=int, nargs="+")
@@ -31,35 +26,12 @@ args = ap.parse_args()
 dev = torch.device("cuda:0")
 cfg = config["tsdf_global"]
 vs, trunc = float(cfg["voxel_size"]), float(cfg["trunc_dist"])
-band = int(2.0 * trunc / (0.5 * vs)) + 4
 print(f"voxel_size={vs} trunc={trunc} points/kf={args.points} device={torch.cuda.get_device_name(dev)}", flush=True)
 L = _m.lib()
 
 
-def timed(fn, reps):
-    for _ in range(3):
-        fn()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return f"median={float(np.median(ms)):.3f} min={min(ms):.3f} max={max(ms):.3f}"
-
-
 for n_kf in args.keyframes:
-    vol = TSDFVolume(vs, trunc, cfg["max_weight"], cfg["min_tsdf_weight"], capacity=1 << 22, device=dev)
-    for i in range(n_kf):
-        T = synthetic.camera_pose(i * (1000 // n_kf))
-        X = synthetic.render_pointmap(T, 192, 256).reshape(-1, 3)
-        rng = np.random.default_rng(i)
-        sel = rng.permutation(X.shape[0])[:args.points]
-        vol.maintain(reserve=args.points * band)
-        vol.integrate(synthetic.sim3_act(T, X[sel]).astype(np.float32), rng.uniform(0.5, 2.0, len(sel)),
-                      T[:3].astype(np.float32), return_fused=False)
+    vol = build_room(n_kf, args.points, dev)
     voxels, cap = vol.maintain()
     for mw in args.weights:
         mw = vol.min_weight if mw <= 0 else mw

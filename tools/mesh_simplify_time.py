@@ -10,18 +10,13 @@ emit (mark, scan, gather); (c) simplify_mesh as a whole and extract_mesh(simplif
 result against the unsimplified mesh.  Not part of bench.py.
     python tools/mesh_simplify_time.py 60 [--reps 20] [--cells 2 4]"""
 import argparse
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "mast3r-slam-quality-dualtsdf_amd")]
-import numpy as np
 import torch
 
+from _room import build_room, timed   # first: it puts the package on sys.path
 import mslam_hip as _m
-from mast3r_slam import synthetic
 from mast3r_slam.config import config
-from mast3r_slam.tsdf import TSDFVolume, compare_meshes, simplify_mesh
+from mast3r_slam.tsdf import compare_meshes, simplify_mesh
 
 ap = argparse.ArgumentParser()
 ap.add_argument("keyframes", type=int, nargs="+")
@@ -33,24 +28,9 @@ args = ap.parse_args()
 dev = torch.device("cuda:0")
 cfg = config["tsdf_global"]
 vs, trunc = float(cfg["voxel_size"]), float(cfg["trunc_dist"])
-band = int(2.0 * trunc / (0.5 * vs)) + 4
 print(f"voxel_size={vs} trunc={trunc} points/kf={args.points} device={torch.cuda.get_device_name(dev)}", flush=True)
 L = _m.lib()
 i32, i64, f32 = (dict(dtype=d, device=dev) for d in (torch.int32, torch.int64, torch.float32))
-
-
-def timed(fn, reps):
-    for _ in range(3):
-        fn()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return f"median={float(np.median(ms)):.3f} min={min(ms):.3f} max={max(ms):.3f}"
 
 
 class Stages:
@@ -121,15 +101,7 @@ class Stages:
 
 
 for n_kf in args.keyframes:
-    vol = TSDFVolume(vs, trunc, cfg["max_weight"], cfg["min_tsdf_weight"], capacity=1 << 22, device=dev)
-    for i in range(n_kf):
-        T = synthetic.camera_pose(i * (1000 // n_kf))
-        X = synthetic.render_pointmap(T, 192, 256).reshape(-1, 3)
-        rng = np.random.default_rng(i)
-        sel = rng.permutation(X.shape[0])[:args.points]
-        vol.maintain(reserve=args.points * band)
-        vol.integrate(synthetic.sim3_act(T, X[sel]).astype(np.float32), rng.uniform(0.5, 2.0, len(sel)),
-                      T[:3].astype(np.float32), return_fused=False)
+    vol = build_room(n_kf, args.points, dev)
     voxels, cap = vol.maintain()
     mesh = vol.extract_mesh()
     V, F = int(mesh[0].shape[0]), int(mesh[2].shape[0])

@@ -6,18 +6,14 @@ events after warm-up, medians of repeated calls: the block pre-pass alone, the m
 brute-force march (both without the pre-pass), for 384x512 views from poses of the trajectory.  Not part of bench.py.
     python tools/render_time.py 60 [--reps 20] [--far 10.0]"""
 import argparse
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [ROOT, os.path.join(ROOT, "mast3r-slam-quality-dualtsdf_amd")]
 import numpy as np
 import torch
 
+from _room import build_room, timed   # first: it puts the package on sys.path
 import mslam_hip as _m
 from mast3r_slam import synthetic
 from mast3r_slam.config import config
-from mast3r_slam.tsdf import TSDFVolume
 from mast3r_slam.tsdf.global_volume import pinhole_rays
 
 ap = argparse.ArgumentParser()
@@ -30,37 +26,14 @@ args = ap.parse_args()
 dev = torch.device("cuda:0")
 cfg = config["tsdf_global"]
 vs, trunc = float(cfg["voxel_size"]), float(cfg["trunc_dist"])
-band = int(2.0 * trunc / (0.5 * vs)) + 4
 h, w = args.hw
 print(f"voxel_size={vs} trunc={trunc} points/kf={args.points} view={h}x{w} near=0.05 far={args.far} step={0.5 * vs} "
       f"device={torch.cuda.get_device_name(dev)}", flush=True)
 L = _m.lib()
 
 
-def timed(fn, reps):
-    for _ in range(3):
-        fn()
-    ms = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return float(np.median(ms)), min(ms), max(ms)
-
-
 for n_kf in args.keyframes:
-    vol = TSDFVolume(vs, trunc, cfg["max_weight"], cfg["min_tsdf_weight"], capacity=1 << 22, device=dev)
-    for i in range(n_kf):
-        T = synthetic.camera_pose(i * (1000 // n_kf))
-        X = synthetic.render_pointmap(T, 192, 256).reshape(-1, 3)
-        rng = np.random.default_rng(i)
-        sel = rng.permutation(X.shape[0])[:args.points]
-        vol.maintain(reserve=args.points * band)
-        vol.integrate(synthetic.sim3_act(T, X[sel]).astype(np.float32), rng.uniform(0.5, 2.0, len(sel)),
-                      T[:3].astype(np.float32), return_fused=False)
+    vol = build_room(n_kf, args.points, dev)
     voxels, cap = vol.maintain()
     rays = pinhole_rays(synthetic.intrinsics(h, w), (h, w), dev)
     wsb = L.mslam_tsdf_render_workspace_bytes(cap)
@@ -77,15 +50,13 @@ for n_kf in args.keyframes:
                                      0.05, args.far, 0.5 * vs, skip, _m.ptr(ws), wsb, _m.ptr(out[0]), _m.ptr(out[1]),
                                      _m.ptr(out[2]), _m.stream_ptr()), "tsdf_render")
 
-    b_med, b_min, b_max = timed(blocks, args.reps)
     print(f"keyframes={n_kf} voxels={voxels} capacity={cap} workspace_bytes={wsb} "
-          f"blocks_ms median={b_med:.3f} min={b_min:.3f} max={b_max:.3f}", flush=True)
+          f"blocks_ms {timed(blocks, args.reps)}", flush=True)
     for frame in (5, 505):
         pose = torch.from_numpy(synthetic.camera_pose(frame).astype(np.float32)).to(dev)
-        s_med, s_min, s_max = timed(lambda: march(pose, 1), args.reps)
+        skip_ms = timed(lambda: march(pose, 1), args.reps)
         hits = float(out[2].float().mean())
         keep = [o.clone() for o in out]
-        f_med, f_min, f_max = timed(lambda: march(pose, 0), args.reps)
+        brute_ms = timed(lambda: march(pose, 0), args.reps)
         same = all(torch.equal(x, y) for x, y in zip(keep, out))
-        print(f"  pose={frame} hit_share={hits:.4f} skip_ms median={s_med:.3f} min={s_min:.3f} max={s_max:.3f} "
-              f"brute_ms median={f_med:.3f} min={f_min:.3f} max={f_max:.3f} identical={same}", flush=True)
+        print(f"  pose={frame} hit_share={hits:.4f} skip_ms {skip_ms} brute_ms {brute_ms} identical={same}", flush=True)
