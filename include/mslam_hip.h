@@ -405,6 +405,29 @@ int mslam_tsdf_render(void* table, uint64_t capacity, const float* rays, int h, 
                       const void* workspace, size_t workspace_bytes, float* range, float* normal, uint8_t* hit,
                       void* stream);
 
+/* Ray casting against a triangle mesh (no counterpart in the reference, DESIGN.md "Mesh ray casting").  vertices
+ * f32[V,3], faces i32[F,3], valid faces as for mslam_mesh_distance; nothing but the outputs is written.
+ *   mslam_mesh_raycast_boxes  the boxes of the mesh's 128-face tiles into the workspace, once per mesh (many views
+ *                             reuse them); workspace >= mslam_mesh_raycast_workspace_bytes(F).
+ *   mslam_mesh_raycast        one ray per pixel: rays f32[h*w,3] in the camera frame, moved with pose8 (Sim3 [t,q,s]
+ *                             f32) as mslam_tsdf_render does: origin t, direction d = R rays in f64, not renormalised.
+ *                             The two-sided watertight test of Woop et al. in f64 finds, among the valid faces hit at
+ *                             near <= t <= far (p = o + t d; far may be +inf), the smallest t and the lowest face index
+ *                             at it: range f32[h*w] = t / s (0 on a miss), normal f32[h*w,3] the face's geometric
+ *                             normal, unit, towards the origin (0 on a miss), hit u8[h*w], face i32[h*w] (-1 on a
+ *                             miss; may be NULL), t64 f64[h*w] (+inf on a miss; may be NULL).  A ray with a zero or
+ *                             non-finite direction misses.  h, w only shape the 8x8-pixel wave tiles; h = 1 is a plain
+ *                             list of w rays.  skip = 0: every tile is scanned; != 0: tiles whose box the ray cannot
+ *                             hit before its current best are skipped (the workspace of mslam_mesh_raycast_boxes is
+ *                             read), same output bit for bit.  MSLAM_ENOMEM when the workspace is short. */
+size_t mslam_mesh_raycast_workspace_bytes(int num_faces);
+int mslam_mesh_raycast_boxes(const float* vertices, const int32_t* faces, int num_faces, int num_vertices,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int mslam_mesh_raycast(const float* rays, int h, int w, const float* pose8, const float* vertices,
+                       const int32_t* faces, int num_faces, int num_vertices, double near, double far, int skip,
+                       const void* workspace, size_t workspace_bytes, float* range, float* normal, uint8_t* hit,
+                       int32_t* face, double* t64, void* stream);
+
 /* Colour of the volume (no counterpart in the reference, DESIGN.md "Colour").  `color` is a second caller-owned device
  * buffer of mslam_tsdf_color_bytes(capacity) bytes, addressed by the slot index of `table`: four u64 words per slot,
  * sum_w (units of 2^-20), sum_w * r8, sum_w * g8, sum_w * b8 with 8-bit colours.  The sums are integers: the fused

@@ -1,0 +1,251 @@
+// Ray casting against a triangle mesh: depth / normal views of any mesh and the occlusion test of observed_points.
+// Semantics in DESIGN.md "Mesh ray casting"; tests/raycast_numpy.py states the same definitions, operation by
+// operation, in numpy.  Everything is f64 on the f32 inputs and the build has -ffp-contract=off, so a * b - c below is
+// two roundings, as in numpy.
+//
+// The intersection is the two-sided watertight test of Woop, Benthin and Wald (2013): the ray's largest axis kz becomes
+// the depth axis, the vertices are translated to the ray's origin and sheared so that the ray runs along +z, and the
+// three edge functions U, V, W of the sheared x, y decide.  The sheared coordinates of a vertex depend on the ray and the
+// vertex only, and x y' - y x' is the exact negative of y x' - x y', so two faces that share an edge see opposite signs
+// of its edge function and a ray through a shared edge or vertex hits at least one of them.
+//
+// Structure: md_scan's.  One ray per thread, 8x8 pixels per wave (h = 1: 256 consecutive rays per block), the faces
+// staged through LDS in the 128-face tiles of mesh_tri.h in index order, every lane reading one address (a broadcast).
+// When all rays of a wave share kz and the sign of d[kz] - the rule for a pinhole view - the axis permutation is a
+// compile-time constant of the tile loop; otherwise each lane selects its axes.  Both run the same operations.
+//
+// CULLING (rc_box_skips).  For a vertex v of a tile's valid face, every step of its sheared coordinates is a monotone
+// function of one input: q = v - o, p = S q[kz], x = q[kx] - p, z = Sz q[kz], and rounding keeps order.  The tile's box
+// holds v exactly, so the same operations on the box's ends give intervals [xl, xh], [yl, yh], [zl, zh] that hold the
+// COMPUTED x, y, z of every such vertex, with no margin needed.  Then
+//   depth    a hit has U, V, W of one sign, so t = ((U Az + V Bz) + W Cz) / det is a convex combination of the three z
+//            up to 8 roundings relative to the largest |z| (no cancellation in det): zl - eps <= t <= zh + eps for
+//            eps = 2^-40 max(|zl|, |zh|), 2^10 times the bound.  A tile with zl - eps > min(best, far) or
+//            zh + eps < near holds no face that could replace `best` (strict: a tie is not skipped).
+//   lateral  the sign of a computed edge function is the exact sign of x y' - y x' on the computed coordinates, or zero.
+//            When the rectangle [xl, xh] x [yl, yh] excludes the origin strictly, the exact U, V, W of a face in it have
+//            mixed signs (U Ax + V Bx + W Cx = 0), so the computed ones pass the sign test only if every one of the
+//            minority sign rounds to zero: the three sheared vertices are collinear with the origin to the last bit, a
+//            face seen edge-on whose "hit" is rounding noise.  DESIGN.md states this exception; it is the one case in
+//            which the culled scan could differ from the plain one.
+// Nothing is written except the outputs.
+#include "mesh_tri.h"
+
+namespace mslam {
+
+struct RcRay {
+  double o[3], d[3];
+  double po[3];          // o[kx], o[ky], o[kz]
+  double sx, sy, sz;
+  int kx, ky, kz;
+  int perm;              // 2 kz + (d[kz] < 0), -1 for a lane without a castable ray
+};
+
+template <int K>
+__device__ __forceinline__ double rc_pick(double a0, double a1, double a2, int k) {
+  if (K >= 0) return K == 0 ? a0 : (K == 1 ? a1 : a2);
+  return k == 0 ? a0 : (k == 1 ? a1 : a2);
+}
+
+// The faces of the staged tile against this lane's ray; KX, KY, KZ >= 0: the wave's common permutation, -1: the lane's
+template <int KX, int KY, int KZ>
+__device__ __forceinline__ void rc_scan_tile(const RcRay& r, const double* s_tri, int cnt, int f0, double near,
+                                             double far, double& best, int& best_f) {
+  for (int k = 0; k < cnt; k++) {
+    const double* t = s_tri + k * kMdTriDoubles;         // one address for the whole wave: an LDS broadcast
+    if (t[9] == 0.0) continue;
+    double x[3], y[3], z[3];
+#pragma unroll
+    for (int v = 0; v < 3; v++) {
+      const double q0 = t[3 * v] - r.o[0], q1 = t[3 * v + 1] - r.o[1], q2 = t[3 * v + 2] - r.o[2];
+      const double qx = rc_pick<KX>(q0, q1, q2, r.kx), qy = rc_pick<KY>(q0, q1, q2, r.ky);
+      const double qz = rc_pick<KZ>(q0, q1, q2, r.kz);
+      x[v] = qx - r.sx * qz;
+      y[v] = qy - r.sy * qz;
+      z[v] = r.sz * qz;
+    }
+    const double U = x[2] * y[1] - y[2] * x[1];
+    const double V = x[0] * y[2] - y[0] * x[2];
+    const double W = x[1] * y[0] - y[1] * x[0];
+    if (!((U >= 0.0 && V >= 0.0 && W >= 0.0) || (U <= 0.0 && V <= 0.0 && W <= 0.0))) continue;
+    const double det = (U + V) + W;
+    if (det == 0.0) continue;
+    const double tt = ((U * z[0] + V * z[1]) + W * z[2]) / det;
+    if (tt >= near && tt <= far && tt < best) best = tt, best_f = f0 + k;
+  }
+}
+
+// true when no face of the tile with box b can replace the lane's best (see CULLING above); lim = min(best, far).
+// Every comparison is false on a NaN, so a box that cannot be judged is kept.
+__device__ __forceinline__ bool rc_box_skips(const RcRay& r, const double* __restrict__ b, double near, double lim) {
+  const double qxl = rc_pick<-1>(b[0], b[1], b[2], r.kx) - r.po[0], qxh = rc_pick<-1>(b[3], b[4], b[5], r.kx) - r.po[0];
+  const double qyl = rc_pick<-1>(b[0], b[1], b[2], r.ky) - r.po[1], qyh = rc_pick<-1>(b[3], b[4], b[5], r.ky) - r.po[1];
+  const double qzl = rc_pick<-1>(b[0], b[1], b[2], r.kz) - r.po[2], qzh = rc_pick<-1>(b[3], b[4], b[5], r.kz) - r.po[2];
+  const double pxa = r.sx * qzl, pxb = r.sx * qzh, pya = r.sy * qzl, pyb = r.sy * qzh;
+  const double xl = qxl - fmax(pxa, pxb), xh = qxh - fmin(pxa, pxb);
+  const double yl = qyl - fmax(pya, pyb), yh = qyh - fmin(pya, pyb);
+  const double za = r.sz * qzl, zb = r.sz * qzh;
+  const double zl = fmin(za, zb), zh = fmax(za, zb);
+  const double eps = 0x1p-40 * fmax(fabs(zl), fabs(zh));
+  return xl > 0.0 || xh < 0.0 || yl > 0.0 || yh < 0.0 || zl - eps > lim || zh + eps < near;
+}
+
+__global__ __launch_bounds__(kMdBlock) void rc_kernel(const float* __restrict__ rays, int h, int w,
+                                                      const float* __restrict__ pose8,
+                                                      const float* __restrict__ vert,
+                                                      const int32_t* __restrict__ faces, int nf, int nv, double near,
+                                                      double far, int cull, const double* __restrict__ box,
+                                                      float* __restrict__ range, float* __restrict__ normal,
+                                                      uint8_t* __restrict__ hit, int32_t* __restrict__ face,
+                                                      double* __restrict__ t64) {
+  __shared__ double s_tri[kMdTile * kMdTriDoubles];
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  // h = 1: a list, 256 consecutive rays per block; otherwise 16x16 pixels per block, 8x8 per wave
+  const long long px = h == 1 ? (long long)blockIdx.x * kMdBlock + tid : blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
+  const int py = h == 1 ? 0 : blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+  const bool has = px < w && py < h;
+  const size_t i = (size_t)py * w + (size_t)px;
+
+  RcRay r;
+  r.perm = -1;
+  r.kx = r.ky = r.kz = 0;
+  r.sx = r.sy = r.sz = 0.0;
+#pragma unroll
+  for (int a = 0; a < 3; a++) r.o[a] = r.d[a] = r.po[a] = 0.0;
+  if (has) {
+    const double q[4] = {(double)pose8[3], (double)pose8[4], (double)pose8[5], (double)pose8[6]};
+    const double c[3] = {(double)rays[3 * i], (double)rays[3 * i + 1], (double)rays[3 * i + 2]};
+    const double u0 = 2.0 * (q[1] * c[2] - q[2] * c[1]);
+    const double u1 = 2.0 * (q[2] * c[0] - q[0] * c[2]);
+    const double u2 = 2.0 * (q[0] * c[1] - q[1] * c[0]);
+    r.d[0] = (c[0] + q[3] * u0) + (q[1] * u2 - q[2] * u1);
+    r.d[1] = (c[1] + q[3] * u1) + (q[2] * u0 - q[0] * u2);
+    r.d[2] = (c[2] + q[3] * u2) + (q[0] * u1 - q[1] * u0);
+#pragma unroll
+    for (int a = 0; a < 3; a++) r.o[a] = (double)pose8[a];
+    const double a0 = fabs(r.d[0]), a1 = fabs(r.d[1]), a2 = fabs(r.d[2]);
+    // a zero or non-finite direction misses
+    if (a0 < INFINITY && a1 < INFINITY && a2 < INFINITY && (a0 > 0.0 || a1 > 0.0 || a2 > 0.0)) {
+      int kz = a1 > a0 ? 1 : 0;
+      if (a2 > (kz ? a1 : a0)) kz = 2;
+      int kx = kz == 2 ? 0 : kz + 1, ky = kx == 2 ? 0 : kx + 1;
+      const double dz = rc_pick<-1>(r.d[0], r.d[1], r.d[2], kz);
+      if (dz < 0.0) {
+        const int s = kx;
+        kx = ky, ky = s;
+      }
+      r.kx = kx, r.ky = ky, r.kz = kz;
+      r.sx = rc_pick<-1>(r.d[0], r.d[1], r.d[2], kx) / dz;
+      r.sy = rc_pick<-1>(r.d[0], r.d[1], r.d[2], ky) / dz;
+      r.sz = 1.0 / dz;
+      r.po[0] = rc_pick<-1>(r.o[0], r.o[1], r.o[2], kx);
+      r.po[1] = rc_pick<-1>(r.o[0], r.o[1], r.o[2], ky);
+      r.po[2] = rc_pick<-1>(r.o[0], r.o[1], r.o[2], kz);
+      r.perm = 2 * kz + (dz < 0.0 ? 1 : 0);
+    }
+  }
+  const bool casts = r.perm >= 0;
+  // the wave's common permutation, or -1 when its rays disagree (or none casts)
+  const unsigned long long active = __ballot(casts);
+  int wave_perm = -1;
+  if (active) {
+    wave_perm = __shfl(r.perm, __ffsll((long long)active) - 1, kWave);
+    if (!__all(!casts || r.perm == wave_perm)) wave_perm = -1;
+  }
+
+  const int ntiles = (nf + kMdTile - 1) / kMdTile;
+  double best = INFINITY;
+  int best_f = -1;
+  for (int tile = 0; tile < ntiles; tile++) {
+    bool lane_skips = !casts;
+    if (cull && casts) lane_skips = rc_box_skips(r, box + 6 * (size_t)tile, near, fmin(best, far));
+    const bool wave_skips = __all(lane_skips);
+    // also the barrier between the last tile's reads and this tile's staging
+    if (__syncthreads_and(lane_skips)) continue;
+    if (tid < kMdTile) md_load_tri(vert, faces, tile * kMdTile + tid, nf, nv, s_tri + tid * kMdTriDoubles);
+    __syncthreads();
+    if (wave_skips) continue;
+    const int cnt = min(kMdTile, nf - tile * kMdTile), f0 = tile * kMdTile;
+    switch (wave_perm) {
+      case 0: rc_scan_tile<1, 2, 0>(r, s_tri, cnt, f0, near, far, best, best_f); break;
+      case 1: rc_scan_tile<2, 1, 0>(r, s_tri, cnt, f0, near, far, best, best_f); break;
+      case 2: rc_scan_tile<2, 0, 1>(r, s_tri, cnt, f0, near, far, best, best_f); break;
+      case 3: rc_scan_tile<0, 2, 1>(r, s_tri, cnt, f0, near, far, best, best_f); break;
+      case 4: rc_scan_tile<0, 1, 2>(r, s_tri, cnt, f0, near, far, best, best_f); break;
+      case 5: rc_scan_tile<1, 0, 2>(r, s_tri, cnt, f0, near, far, best, best_f); break;
+      default:
+        if (casts) rc_scan_tile<-1, -1, -1>(r, s_tri, cnt, f0, near, far, best, best_f);
+    }
+  }
+  if (!has) return;
+  if (!casts) best = INFINITY, best_f = -1;      // such a lane ran along in its wave's scan; its ray misses
+
+  float out_range = 0.0f, out_n[3] = {0.0f, 0.0f, 0.0f};
+  if (best_f >= 0) {
+    double t[kMdTriDoubles];
+    md_load_tri(vert, faces, best_f, nf, nv, t);
+    const double abx = t[3] - t[0], aby = t[4] - t[1], abz = t[5] - t[2];
+    const double acx = t[6] - t[0], acy = t[7] - t[1], acz = t[8] - t[2];
+    const double nx = aby * acz - abz * acy, ny = abz * acx - abx * acz, nz = abx * acy - aby * acx;
+    const double len = sqrt(md_dot(nx, ny, nz, nx, ny, nz));
+    const double sign = md_dot(nx, ny, nz, r.d[0], r.d[1], r.d[2]) > 0.0 ? -1.0 : 1.0;    // towards the origin
+    out_n[0] = (float)(sign * (nx / len));
+    out_n[1] = (float)(sign * (ny / len));
+    out_n[2] = (float)(sign * (nz / len));
+    out_range = (float)(best / (double)pose8[7]);
+  }
+  range[i] = out_range;
+  normal[3 * i] = out_n[0], normal[3 * i + 1] = out_n[1], normal[3 * i + 2] = out_n[2];
+  hit[i] = best_f >= 0 ? 1 : 0;
+  if (face) face[i] = best_f;
+  if (t64) t64[i] = best;
+}
+
+}  // namespace mslam
+
+using namespace mslam;
+
+extern "C" size_t mslam_mesh_raycast_workspace_bytes(int num_faces) {
+  return num_faces > 0 ? md_box_bytes(num_faces) : 0;
+}
+
+extern "C" int mslam_mesh_raycast_boxes(const float* vertices, const int32_t* faces, int num_faces, int num_vertices,
+                                        void* workspace, size_t workspace_bytes, void* stream) {
+  MSLAM_REQUIRE(num_faces >= 0 && num_vertices >= 0, "mesh_raycast_boxes: negative size");
+  if (num_faces == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(faces && workspace && (vertices || num_vertices == 0), "mesh_raycast_boxes: null pointer");
+  if (workspace_bytes < md_box_bytes(num_faces)) {
+    set_error("mesh_raycast_boxes: workspace of %zu bytes, %zu needed", workspace_bytes, md_box_bytes(num_faces));
+    return MSLAM_ENOMEM;
+  }
+  hipLaunchKernelGGL(md_box_kernel, dim3(blocks_for(num_faces, kMdTile)), dim3(kWave), 0, (hipStream_t)stream,
+                     vertices, faces, num_faces, num_vertices, (double*)workspace);
+  MSLAM_LAUNCH_CHECK("mesh_raycast_boxes");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_mesh_raycast(const float* rays, int h, int w, const float* pose8, const float* vertices,
+                                  const int32_t* faces, int num_faces, int num_vertices, double near, double far,
+                                  int skip, const void* workspace, size_t workspace_bytes, float* range, float* normal,
+                                  uint8_t* hit, int32_t* face, double* t64, void* stream) {
+  MSLAM_REQUIRE(h >= 0 && w >= 0 && (int64_t)h * w < (1ll << 31), "mesh_raycast: bad image size");
+  MSLAM_REQUIRE(num_faces >= 0 && num_vertices >= 0, "mesh_raycast: negative size");
+  MSLAM_REQUIRE(near <= far, "mesh_raycast: near must not exceed far");
+  if (h == 0 || w == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(rays && pose8 && range && normal && hit, "mesh_raycast: null pointer");
+  MSLAM_REQUIRE(num_faces == 0 || (faces && (vertices || num_vertices == 0)), "mesh_raycast: null pointer");
+  if (num_faces == 0) skip = 0;
+  if (skip) {
+    MSLAM_REQUIRE(workspace, "mesh_raycast: the culled scan needs the workspace of mesh_raycast_boxes");
+    if (workspace_bytes < md_box_bytes(num_faces)) {
+      set_error("mesh_raycast: workspace of %zu bytes, %zu needed", workspace_bytes, md_box_bytes(num_faces));
+      return MSLAM_ENOMEM;
+    }
+  }
+  const dim3 grid = h == 1 ? dim3(blocks_for(w, kMdBlock)) : dim3((unsigned)((w + 15) / 16), (unsigned)((h + 15) / 16));
+  hipLaunchKernelGGL(rc_kernel, grid, dim3(kMdBlock), 0, (hipStream_t)stream, rays, h, w, pose8, vertices, faces,
+                     num_faces, num_vertices, near, far, skip ? 1 : 0, (const double*)workspace, range, normal, hit,
+                     face, t64);
+  MSLAM_LAUNCH_CHECK("mesh_raycast");
+  return MSLAM_OK;
+}

@@ -5,7 +5,8 @@ No counterpart in the reference.  The kernels are csrc/mesh_distance.hip (DESIGN
 statement of the same definitions is tests/meshdist_numpy.py.  A face is valid when its indices lie in [0, V) and its
 cross product is not exactly zero; an invalid face has area 0, is never sampled and is never the nearest face.  The two
 meshes of a comparison must lie in one frame; compare_meshes(align=...) moves the first into the second's frame first
-(mesh_align.py, DESIGN.md "Mesh alignment").
+(mesh_align.py, DESIGN.md "Mesh alignment"), and compare_meshes(observed=...) scores completion and recall over the part
+of the second that given cameras see (mesh_raycast.py, DESIGN.md "Mesh ray casting").
 """
 import torch
 
@@ -58,7 +59,7 @@ def mesh_distance(points, vertices, faces, skip=True, _validate=True):
 
 
 def compare_meshes(pred, gt, n_samples=200_000, threshold=0.05, seed=0, skip=True, _validate_pred=True, align=None,
-                   align_kw=None):
+                   align_kw=None, observed=None):
     """Quality of the mesh `pred` against the ground truth `gt`, both (vertices f32[V,3], faces i32[F,3]) device tensors
     or the tuples extract_mesh returns (normals and colours are ignored), in one frame.  n_samples points are drawn on
     each (sample_mesh with `seed` on pred, `seed + 1` on gt) and measured against the other (mesh_distance).  Returns
@@ -70,7 +71,14 @@ def compare_meshes(pred, gt, n_samples=200_000, threshold=0.05, seed=0, skip=Tru
     `align`: None - the meshes are taken as they are; a Sim3 ([t(3), q(xyzw), s], 8 numbers) - pred is moved by it first
     (transform_mesh); "icp" - pred is moved by align_meshes(pred, gt, **align_kw) first (a local method: pass
     align_kw=dict(init=...) for more than a modest offset).  With alignment the dict gains `alignment`: T (a list of 8
-    floats), rmse and iterations (None for a given Sim3)."""
+    floats), rmse and iterations (None for a given Sim3).
+
+    `observed`: None - every ground-truth sample counts; a dict with `poses` (n Sim3s, world from camera), `K` (3,3),
+    `hw` and optionally `near`, `far`, `tol` (observed_points) and `frame` - only the ground-truth samples that some
+    camera sees, occlusion against the ground-truth mesh included, enter completion, completion_median, recall, fscore
+    and chamfer (DESIGN.md "Mesh ray casting").  `frame`: "gt" (default) - the poses lie in the ground truth's frame;
+    "pred" - in pred's, and the alignment transform moves them first.  The dict gains gt_observed_share and
+    n_gt_observed; ValueError when no sample is observed.  Accuracy and precision do not change."""
     n = int(n_samples)
     threshold = float(threshold)
     alignment = None
@@ -94,15 +102,42 @@ def compare_meshes(pred, gt, n_samples=200_000, threshold=0.05, seed=0, skip=Tru
     gv, gf, gV, gF = _mesh_arg(*_pair(gt, "gt"), True, "compare_meshes")
     p_pts, _, p_area = _sample(pv, pf, pV, pF, n, seed, "compare_meshes (pred)")
     g_pts, _, g_area = _sample(gv, gf, gV, gF, n, int(seed) + 1, "compare_meshes (gt)")
+    n_obs = n
+    if observed is not None:
+        seen = _observed_samples(g_pts, (gv, gf), observed, T if align is not None else None, bool(skip))
+        g_pts = g_pts[seen]
+        n_obs = int(g_pts.shape[0])                                               # a host read
+        if n_obs == 0:
+            raise ValueError("compare_meshes: no ground-truth sample is observed by the given cameras")
     out = []
-    for pts, (v, f, V, F) in ((p_pts, (gv, gf, gV, gF)), (g_pts, (pv, pf, pV, pF))):
+    for pts, m, (v, f, V, F) in ((p_pts, n, (gv, gf, gV, gF)), (g_pts, n_obs, (pv, pf, pV, pF))):
         d = torch.sqrt(_distance2(pts, v, f, V, F, bool(skip))[0])
         s = torch.sort(d)[0]
-        out += [d.sum() / n, 0.5 * (s[(n - 1) // 2] + s[n // 2]), (d <= threshold).sum().to(torch.float64) / n]
+        out += [d.sum() / m, 0.5 * (s[(m - 1) // 2] + s[m // 2]), (d <= threshold).sum().to(torch.float64) / m]
     acc, acc_med, prec, comp, comp_med, rec = torch.stack(out).tolist()          # the one host read of the figures
     out = dict(accuracy=acc, accuracy_median=acc_med, completion=comp, completion_median=comp_med, precision=prec,
                recall=rec, fscore=2.0 * prec * rec / (prec + rec) if prec + rec > 0.0 else 0.0,
                chamfer=0.5 * (acc + comp), n_samples=n, threshold=threshold, pred_area=p_area, gt_area=g_area)
     if alignment is not None:
         out["alignment"] = alignment
+    if observed is not None:
+        out.update(gt_observed_share=n_obs / n, n_gt_observed=n_obs)
     return out
+
+
+def _observed_samples(g_pts, gt, observed, T, skip):
+    """bool[n]: the ground-truth samples the cameras of `observed` see; T: the alignment transform or None."""
+    from .mesh_raycast import _poses_arg, compose_sim3, observed_points
+
+    spec = dict(observed)
+    unknown = set(spec) - {"poses", "K", "hw", "near", "far", "tol", "frame"}
+    if unknown or not {"poses", "K", "hw"} <= set(spec):
+        raise ValueError(f"compare_meshes: observed needs poses, K and hw (and takes near, far, tol, frame); got "
+                         f"{sorted(spec)}")
+    frame = spec.pop("frame", "gt")
+    if frame not in ("gt", "pred"):
+        raise ValueError(f"compare_meshes: observed['frame'] must be 'gt' or 'pred', got {frame!r}")
+    poses = _poses_arg(spec.pop("poses"), "compare_meshes")
+    if frame == "pred" and T is not None:
+        poses = compose_sim3(T, poses)
+    return observed_points(g_pts, gt, poses, spec.pop("K"), spec.pop("hw"), skip=skip, **spec)
