@@ -4,8 +4,11 @@
 // one block sorts one patch in LDS, and one block classifies the whole patch grid.
 //
 // Bit-level conventions followed (torch CPU semantics): median of n values = the (n-1)//2-th smallest
-// (torch.median / nanmedian return the LOWER middle); nanmedian ignores NaN and masked pixels, an empty patch
-// gives NaN -> nan_to_num -> 0; every formula is evaluated in float32 in the reference's operation order.
+// (torch.median / nanmedian return the LOWER middle); nanmedian ignores NaN and masked pixels; an empty patch is NaN,
+// and stays NaN unless a mask is given: only the masked path of the reference ends in nan_to_num (NaN -> 0, +-inf ->
+// +-FLT_MAX).  Every formula is evaluated in float32 in the reference's operation order.
+#include <float.h>
+
 #include "common.h"
 
 namespace mslam {
@@ -13,7 +16,7 @@ namespace mslam {
 constexpr int kQMax = 1024;   // ps * ps <= 1024 and patch-grid size <= 4096 (classify)
 
 // ascending bitonic sort of n (power of two) floats in LDS by all threads of the block; NaN never enters (callers
-// map NaN / masked values to +inf)
+// count NaN / masked values out and store +inf in their place)
 __device__ __forceinline__ void bitonic_sort(float* s, int n) {
   for (int k = 2; k <= n; k <<= 1)
     for (int j = k >> 1; j > 0; j >>= 1) {
@@ -29,9 +32,19 @@ __device__ __forceinline__ void bitonic_sort(float* s, int n) {
     }
 }
 
-// mode 0: nanmedian of x over valid pixels (valid may be null), NaN -> 0 when a mask is given (reduce_grid)
-// mode 1: mean over the patch (valid null) or nanmean over valid pixels, NaN -> 0
-// mode 2: median of U = 1 - sqrt(clamp(clamp(C/(C_thr+1e-8),0,1) * clamp(Q/(Q_thr+1e-8),0,1), 0, 1))  (x = C, y = Q)
+// torch.nan_to_num(v, nan=0.0) of the reference's masked path
+__device__ __forceinline__ float nan_to_num(float v) {
+  if (v != v) return 0.0f;
+  return fminf(fmaxf(v, -FLT_MAX), FLT_MAX);
+}
+
+// torch.clamp(v, 0, 1): NaN stays NaN (fmaxf / fminf would drop it)
+__device__ __forceinline__ float clamp01(float v) { return v != v ? v : fminf(fmaxf(v, 0.0f), 1.0f); }
+
+// mode 0: nanmedian of x over valid pixels (valid may be null); nan_to_num when a mask is given (reduce_grid)
+// mode 1: mean over the patch (valid null: a NaN pixel makes it NaN) or nanmean over valid pixels + nan_to_num
+// mode 2: nanmedian of U = 1 - sqrt(clamp(clamp(C/(C_thr+1e-8),0,1) * clamp(Q/(Q_thr+1e-8),0,1), 0, 1))  (x = C, y = Q);
+//         a NaN in C or Q makes U NaN and the pixel is ignored, a patch of nothing else is NaN
 __global__ __launch_bounds__(kQMax) void quality_reduce_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                                const uint8_t* __restrict__ valid, int h, int w, int ps,
                                                                int mode, float c_div, float q_div, float* __restrict__ out) {
@@ -48,12 +61,12 @@ __global__ __launch_bounds__(kQMax) void quality_reduce_kernel(const float* __re
   if (t < n) {
     const size_t pix = (size_t)(py * ps + t / ps) * w + (size_t)(px * ps + t % ps);
     if (mode == 2) {
-      const float cn = fminf(fmaxf(x[pix] / c_div, 0.0f), 1.0f), qn = fminf(fmaxf(y[pix] / q_div, 0.0f), 1.0f);
-      v = 1.0f - sqrtf(fminf(fmaxf(cn * qn, 0.0f), 1.0f));
-      ok = true;
+      const float cn = clamp01(x[pix] / c_div), qn = clamp01(y[pix] / q_div);
+      v = 1.0f - sqrtf(clamp01(cn * qn));
+      ok = !(v != v);
     } else {
       v = x[pix];
-      ok = (valid == nullptr || valid[pix] != 0) && !(v != v);
+      ok = valid ? (valid[pix] != 0 && !(v != v)) : (mode == 1 || !(v != v));
     }
   }
   if (mode == 1) {   // mean: fixed-order tree sum (the reference's vectorised order is not reproduced; tolerance 1e-6)
@@ -65,8 +78,8 @@ __global__ __launch_bounds__(kQMax) void quality_reduce_kernel(const float* __re
       __syncthreads();
     }
     if (t == 0) {
-      const int denom = valid ? cnt : n;
-      out[blockIdx.x] = denom > 0 ? s[0] / (float)denom : 0.0f;
+      // no mask: X.mean(-1), NaN pixels included; mask: nanmean = sum / count (0 / 0 = NaN), then nan_to_num
+      out[blockIdx.x] = valid ? nan_to_num(s[0] / (float)cnt) : s[0] / (float)n;
     }
     return;
   }
@@ -78,7 +91,10 @@ __global__ __launch_bounds__(kQMax) void quality_reduce_kernel(const float* __re
   for (int i = n + t; i < np2; i += blockDim.x) s[i] = INFINITY;
   __syncthreads();
   bitonic_sort(s, np2);
-  if (t == 0) out[blockIdx.x] = cnt > 0 ? s[(cnt - 1) / 2] : 0.0f;   // empty patch: nanmedian = NaN -> nan_to_num
+  if (t == 0) {
+    const float med = cnt > 0 ? s[(cnt - 1) / 2] : NAN;   // empty patch: nanmedian = NaN
+    out[blockIdx.x] = valid ? nan_to_num(med) : med;
+  }
   (void)fsum;
 }
 
@@ -146,11 +162,12 @@ using namespace mslam;
 
 extern "C" int mslam_quality_reduce_grid(const float* x, const float* y, const uint8_t* valid, int h, int w, int ps,
                                          int mode, double c_thr, double q_thr, float* out, void* stream) {
-  MSLAM_REQUIRE(x && out && h > 0 && w > 0 && ps > 0, "quality_reduce_grid: bad arguments");
+  MSLAM_REQUIRE(x && h > 0 && w > 0 && ps > 0, "quality_reduce_grid: bad arguments");
   MSLAM_REQUIRE(ps * ps <= kQMax, "quality_reduce_grid: patch %d x %d exceeds %d pixels", ps, ps, kQMax);
   MSLAM_REQUIRE(mode >= 0 && mode <= 2 && (mode != 2 || y), "quality_reduce_grid: bad mode %d", mode);
   const int gh = h / ps, gw = w / ps;
-  if (gh * gw == 0) return MSLAM_OK;
+  if (gh * gw == 0) return MSLAM_OK;   // image smaller than a patch: the grid is empty, and so may be `out`
+  MSLAM_REQUIRE(out, "quality_reduce_grid: bad arguments");
   int threads = 64;
   while (threads < ps * ps) threads <<= 1;
   hipLaunchKernelGGL(quality_reduce_kernel, dim3(gh * gw), dim3(threads), 0, (hipStream_t)stream, x, y, valid, h, w, ps, mode,

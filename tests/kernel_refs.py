@@ -11,8 +11,11 @@ import torch.nn.functional as F
 
 # NaN bit patterns the guards and the not-yet-written outputs are filled with (sign 0, exponent all ones, mantissa != 0);
 # neither is the canonical quiet NaN an instruction produces, so "still holds the pattern" means "never stored".
-NAN_BITS = {torch.bfloat16: 0x7FDE, torch.float32: 0x7FD5A5A5}
-_INT_VIEW = {torch.bfloat16: torch.int16, torch.float32: torch.int32}
+NAN_BITS = {torch.bfloat16: 0x7FDE, torch.float32: 0x7FD5A5A5, torch.float64: 0x7FF5A5A5A5A5A5A5}
+_INT_VIEW = {torch.bfloat16: torch.int16, torch.float32: torch.int32, torch.float64: torch.int64}
+# Integer outputs have no NaN: guards and unwritten interior hold a sentinel that no result of the kernels under test
+# takes (class ids are 0..3, hit flags 0 / 1; a 32-bit signature word equals it with probability 2^-32).
+SENTINEL = {torch.int32: 0x5AD5A5A5, torch.int64: 0x5AD5A5A55AD5A5A5, torch.uint8: 0xA5}
 GUARD_BYTES = 4096   # in front and behind; a multiple of 256, so the interior stays 16-byte aligned
 
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
@@ -20,17 +23,18 @@ U23 = 2.0 ** -23
 
 
 class Guarded:
-    """A tensor of `shape` inside a larger allocation: GUARD_BYTES of NaN pattern in front and behind, the interior either
-    a copy of `src` (an input) or the same pattern (an output).  guards_ok(): the guards are bit-identical to what was
-    written; all_written(): no interior element still holds the pattern.  Both return 0-d bool tensors on the device."""
+    """A tensor of `shape` inside a larger allocation: GUARD_BYTES of NaN pattern (integer types: SENTINEL) in front and
+    behind, the interior either a copy of `src` (an input) or the same pattern (an output).  guards_ok(): the guards are
+    bit-identical to what was written; all_written(): no interior element still holds the pattern.  Both return 0-d bool
+    tensors on the device."""
 
     def __init__(self, device, dtype, shape=None, src=None):
         if src is not None:
             shape = tuple(src.shape)
         self.n = int(math.prod(shape))
         self.g = GUARD_BYTES // torch.empty((), dtype=dtype).element_size()
-        self.pat = NAN_BITS[dtype]
-        self.raw = torch.full((self.n + 2 * self.g,), self.pat, dtype=_INT_VIEW[dtype], device=device)
+        self.pat = NAN_BITS[dtype] if dtype in NAN_BITS else SENTINEL[dtype]
+        self.raw = torch.full((self.n + 2 * self.g,), self.pat, dtype=_INT_VIEW.get(dtype, dtype), device=device)
         self.t = self.raw[self.g:self.g + self.n].view(dtype).view(shape)
         assert self.t.data_ptr() % 16 == 0
         if src is not None:
