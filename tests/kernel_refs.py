@@ -11,8 +11,8 @@ import torch.nn.functional as F
 
 # NaN bit patterns the guards and the not-yet-written outputs are filled with (sign 0, exponent all ones, mantissa != 0);
 # neither is the canonical quiet NaN an instruction produces, so "still holds the pattern" means "never stored".
-NAN_BITS = {torch.bfloat16: 0x7FDE, torch.float32: 0x7FD5A5A5, torch.float64: 0x7FF5A5A5A5A5A5A5}
-_INT_VIEW = {torch.bfloat16: torch.int16, torch.float32: torch.int32, torch.float64: torch.int64}
+NAN_BITS = {torch.bfloat16: 0x7FDE, torch.float16: 0x7D5A, torch.float32: 0x7FD5A5A5, torch.float64: 0x7FF5A5A5A5A5A5A5}
+_INT_VIEW = {torch.bfloat16: torch.int16, torch.float16: torch.int16, torch.float32: torch.int32, torch.float64: torch.int64}
 # Integer outputs have no NaN: guards and unwritten interior hold a sentinel that no result of the kernels under test
 # takes (class ids are 0..3, hit flags 0 / 1; a 32-bit signature word equals it with probability 2^-32).
 SENTINEL = {torch.int32: 0x5AD5A5A5, torch.int64: 0x5AD5A5A55AD5A5A5, torch.uint8: 0xA5}
