@@ -428,6 +428,54 @@ int mslam_mesh_raycast(const float* rays, int h, int w, const float* pose8, cons
                        const void* workspace, size_t workspace_bytes, float* range, float* normal, uint8_t* hit,
                        int32_t* face, double* t64, void* stream);
 
+/* Mesh index: Morton-ordered tiles with group boxes above them, so that the culled scans of mslam_mesh_distance,
+ * mslam_mesh_align_step and mslam_mesh_raycast prune whatever order the caller's faces are in (no counterpart in the
+ * reference, DESIGN.md "Mesh index").  The faces are never copied or permuted; all arithmetic is f64 on the f32 inputs in
+ * one fixed order; no atomics.  Sequence, on one stream:
+ *   mslam_mesh_index_keys     keys i64[F]: the 63-bit Morton code (x highest) of each face's centroid ((a + b) + c) / 3,
+ *                             each axis floor((c - lo) / (hi - lo) * 2^21) clamped to [0, 2^21) (a NaN is cell 0) over
+ *                             bounds f32[6] = lo.xyz, hi.xyz, the box of the mesh's vertices formed by the caller;
+ *                             INT64_MAX for an invalid face (mslam_mesh_distance's rule).  The caller sorts the keys
+ *                             (stable) -> order i32[F].
+ *   mslam_mesh_index_point_keys  keys i64[n]: the same code of the points f32[n,3] themselves, the keys that sort
+ *                             queries; a point outside the box lands in the nearest cell.
+ *   mslam_mesh_index_boxes    into the workspace (>= mslam_mesh_index_bytes(F), MSLAM_ENOMEM with the needed size in
+ *                             mslam_last_error when short): f64 boxes lo.xyz, hi.xyz of the tiles of 128 consecutive
+ *                             faces in `order`, then of the groups of 32 tiles; (+inf, -inf) for an empty one.  An
+ *                             entry of `order` outside [0, F) is skipped, not followed.
+ * The _indexed entries below take `order` and that workspace (`index`, only read) and give the outputs of their plain
+ * forms with skip = 0 bit for bit: a tie goes to the lowest ORIGINAL face index, whatever order the tiles are visited
+ * in.  A face that `order` does not name is not seen.  levels: 1 - the tile boxes alone cull; 2 - a group whose box
+ * fails the same test for the whole block is passed over first.  skip_counts (may be NULL): i32[4 * blocks], per wave
+ * the tile scans it skipped, a skipped group counting as all of its tiles (blocks = ceil(n / 256) for points,
+ * mslam_mesh_raycast_blocks(h, w) for rays).
+ *   mslam_mesh_distance_indexed    as mslam_mesh_distance.
+ *   mslam_mesh_raycast_indexed     as mslam_mesh_raycast.
+ *   mslam_mesh_align_init_indexed  state <- T0 as mslam_mesh_align_init; the boxes are the index's.
+ *   mslam_mesh_align_step_indexed  as mslam_mesh_align_step, warm start included; workspace >=
+ *                                  mslam_mesh_align_workspace_bytes(n, 0, count_skips) (no boxes in it). */
+size_t mslam_mesh_index_bytes(int num_faces);
+int mslam_mesh_index_keys(const float* vertices, int num_vertices, const int32_t* faces, int num_faces,
+                          const float* bounds, int64_t* keys, void* stream);
+int mslam_mesh_index_point_keys(const float* points, int n, const float* bounds, int64_t* keys, void* stream);
+int mslam_mesh_index_boxes(const float* vertices, const int32_t* faces, int num_faces, int num_vertices,
+                           const int32_t* order, void* workspace, size_t workspace_bytes, void* stream);
+int mslam_mesh_distance_indexed(const float* points, int n, const float* vertices, const int32_t* faces, int num_faces,
+                                int num_vertices, const int32_t* order, const void* index, size_t index_bytes,
+                                int levels, int32_t* skip_counts, double* dist2, int32_t* nearest, void* stream);
+int mslam_mesh_raycast_blocks(int h, int w);
+int mslam_mesh_raycast_indexed(const float* rays, int h, int w, const float* pose8, const float* vertices,
+                               const int32_t* faces, int num_faces, int num_vertices, double near, double far,
+                               const int32_t* order, const void* index, size_t index_bytes, int levels,
+                               int32_t* skip_counts, float* range, float* normal, uint8_t* hit, int32_t* face,
+                               double* t64, void* stream);
+int mslam_mesh_align_init_indexed(const float* T0, void* state, void* stream);
+int mslam_mesh_align_step_indexed(const float* src, int n, const float* vertices, const int32_t* faces, int num_faces,
+                                  int num_vertices, const int32_t* order, const void* index, size_t index_bytes,
+                                  double trim, int with_scale, int count_skips, void* workspace, size_t workspace_bytes,
+                                  void* state, int32_t* nearest, float* moved, double* dist2, double* closest,
+                                  double* log_row, void* stream);
+
 /* Colour of the volume (no counterpart in the reference, DESIGN.md "Colour").  `color` is a second caller-owned device
  * buffer of mslam_tsdf_color_bytes(capacity) bytes, addressed by the slot index of `table`: four u64 words per slot,
  * sum_w (units of 2^-20), sum_w * r8, sum_w * g8, sum_w * b8 with 8-bit colours.  The sums are integers: the fused

@@ -12,7 +12,8 @@
 // The match is md_scan of mesh_tri.h, the culled nearest-face scan that md_distance_kernel calls too, on
 // q_i = (float)(T_k p_i).  The boxes are computed once per alignment (mslam_mesh_align_init), and lane i's bound starts
 // from md_dist2(q_i, face nearest_prev[i]) when that face exists and is valid, so a block stages its home tile only
-// when one of its lanes has no such face.
+// when one of its lanes has no such face.  The _indexed entries run the same step over the tiles of a mesh index
+// (mesh_index.hip); the warm start is by original face index and does not change.
 #include "mesh_tri.h"
 
 namespace mslam {
@@ -71,12 +72,16 @@ __device__ __forceinline__ void ma_block_reduce(double* v, double* s_part, doubl
         ((s_part[tid] + s_part[kMaSums + tid]) + s_part[2 * kMaSums + tid]) + s_part[3 * kMaSums + tid];
 }
 
-// count: also write, per wave, how many tiles it did not scan to skipped[4 * block + wave] (the timing tool's figure)
+// count: also write, per wave, how many tiles it did not scan to skipped[4 * block + wave] (the timing tool's figure).
+// kIndexed: the tiles follow `order`, `gbox` holds the group boxes (mesh_tri.h); without it neither is read.
+template <bool kIndexed>
 __global__ __launch_bounds__(kMdBlock) void ma_step_kernel(const float* __restrict__ src, int n,
                                                            const float* __restrict__ vert,
                                                            const int32_t* __restrict__ faces, int nf, int nv,
                                                            const double* __restrict__ state, int cull,
-                                                           const double* __restrict__ box, double trim2,
+                                                           const double* __restrict__ box,
+                                                           const int32_t* __restrict__ order,
+                                                           const double* __restrict__ gbox, double trim2,
                                                            int32_t* __restrict__ skipped, int32_t* __restrict__ nearest,
                                                            float* __restrict__ moved, double* __restrict__ dist2,
                                                            double* __restrict__ closest,
@@ -115,8 +120,9 @@ __global__ __launch_bounds__(kMdBlock) void ma_step_kernel(const float* __restri
       warm = true;
     }
   }
-  const MdNearest r = md_scan(px, py, pz, has, (double)(float)y0[0], (double)(float)y0[1], (double)(float)y0[2], vert,
-                              faces, nf, nv, cull, box, s_tri, &s_home, ub, !warm);
+  const MdNearest r = md_scan<kIndexed>(px, py, pz, has, (double)(float)y0[0], (double)(float)y0[1],
+                                        (double)(float)y0[2], vert, faces, nf, nv, cull, box, s_tri, &s_home, ub, !warm,
+                                        order, gbox);
   const double best = r.dist2;
   const int best_f = r.face;
 
@@ -348,8 +354,44 @@ extern "C" int mslam_mesh_align_init(const float* T0, const float* vertices, con
   hipLaunchKernelGGL(ma_init_kernel, dim3(1), dim3(kWave), 0, s, T0, (double*)state);
   if (num_faces > 0)
     hipLaunchKernelGGL(md_box_kernel, dim3(blocks_for(num_faces, kMdTile)), dim3(kWave), 0, s, vertices, faces,
-                       num_faces, num_vertices, (double*)workspace);
+                       num_faces, num_vertices, (const int32_t*)nullptr, (double*)workspace);
   MSLAM_LAUNCH_CHECK("mesh_align_init");
+  return MSLAM_OK;
+}
+
+// One ICP iteration; `order` null: the boxes lie at the head of the workspace (mslam_mesh_align_init), otherwise they
+// are a mesh index's and the workspace starts with the partials.
+static int ma_step(const char* what, const float* src, int n, const float* vertices, const int32_t* faces,
+                   int num_faces, int num_vertices, const int32_t* order, const void* index, size_t index_bytes,
+                   double trim, int with_scale, int count_skips, void* workspace, size_t workspace_bytes, void* state,
+                   int32_t* nearest, float* moved, double* dist2, double* closest, double* log_row, void* stream) {
+  const bool indexed = order != nullptr;
+  const size_t box_bytes = indexed ? 0 : md_box_bytes(num_faces), part_bytes = ma_partial_bytes(n);
+  const size_t need = box_bytes + part_bytes + (count_skips ? md_count_bytes(n) : 0);
+  if (workspace_bytes < need) {
+    set_error("%s: workspace of %zu bytes, %zu needed", what, workspace_bytes, need);
+    return MSLAM_ENOMEM;
+  }
+  if (indexed && index_bytes < md_index_bytes(num_faces)) {
+    set_error("%s: index of %zu bytes, %zu needed", what, index_bytes, md_index_bytes(num_faces));
+    return MSLAM_ENOMEM;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned nblocks = blocks_for(n, kMdBlock);
+  double* partial = (double*)((char*)workspace + box_bytes);
+  int32_t* skipped = count_skips ? (int32_t*)((char*)workspace + box_bytes + part_bytes) : nullptr;
+  if (n > 0 && indexed)
+    hipLaunchKernelGGL(ma_step_kernel<true>, dim3(nblocks), dim3(kMdBlock), 0, s, src, n, vertices, faces, num_faces,
+                       num_vertices, (const double*)state, num_faces > 0 ? 1 : 0, (const double*)index, order,
+                       num_faces > 0 ? md_index_gbox(index, num_faces) : (const double*)nullptr, trim * trim, skipped,
+                       nearest, moved, dist2, closest, partial);
+  else if (n > 0)
+    hipLaunchKernelGGL(ma_step_kernel<false>, dim3(nblocks), dim3(kMdBlock), 0, s, src, n, vertices, faces, num_faces,
+                       num_vertices, (const double*)state, num_faces > kMdTile ? 1 : 0, (const double*)workspace,
+                       (const int32_t*)nullptr, (const double*)nullptr, trim * trim, skipped, nearest, moved, dist2,
+                       closest, partial);
+  hipLaunchKernelGGL(ma_solve_kernel, dim3(1), dim3(kWave), 0, s, (const double*)partial, (int)nblocks, src,
+                     (const float*)nullptr, n, with_scale, (double*)state, log_row);
   return MSLAM_OK;
 }
 
@@ -363,23 +405,38 @@ extern "C" int mslam_mesh_align_step(const float* src, int n, const float* verti
   MSLAM_REQUIRE(n == 0 || (src && nearest && moved && dist2 && workspace), "mesh_align_step: null pointer");
   MSLAM_REQUIRE(num_faces == 0 || (faces && workspace && (vertices || num_vertices == 0)),
                 "mesh_align_step: null pointer");
-  const size_t box_bytes = md_box_bytes(num_faces), part_bytes = ma_partial_bytes(n);
-  const size_t need = box_bytes + part_bytes + (count_skips ? md_count_bytes(n) : 0);
-  if (workspace_bytes < need) {
-    set_error("mesh_align_step: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-    return MSLAM_ENOMEM;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  const unsigned nblocks = blocks_for(n, kMdBlock);
-  double* partial = (double*)((char*)workspace + box_bytes);
-  if (n > 0)
-    hipLaunchKernelGGL(ma_step_kernel, dim3(nblocks), dim3(kMdBlock), 0, s, src, n, vertices, faces, num_faces,
-                       num_vertices, (const double*)state, num_faces > kMdTile ? 1 : 0, (const double*)workspace,
-                       trim * trim, count_skips ? (int32_t*)((char*)workspace + box_bytes + part_bytes) : nullptr,
-                       nearest, moved, dist2, closest, partial);
-  hipLaunchKernelGGL(ma_solve_kernel, dim3(1), dim3(kWave), 0, s, (const double*)partial, (int)nblocks, src,
-                     (const float*)nullptr, n, with_scale, (double*)state, log_row);
+  const int rc = ma_step("mesh_align_step", src, n, vertices, faces, num_faces, num_vertices, nullptr, nullptr, 0, trim,
+                         with_scale, count_skips, workspace, workspace_bytes, state, nearest, moved, dist2, closest,
+                         log_row, stream);
+  if (rc) return rc;
   MSLAM_LAUNCH_CHECK("mesh_align_step");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_mesh_align_init_indexed(const float* T0, void* state, void* stream) {
+  MSLAM_REQUIRE(state, "mesh_align_init_indexed: null pointer");
+  hipLaunchKernelGGL(ma_init_kernel, dim3(1), dim3(kWave), 0, (hipStream_t)stream, T0, (double*)state);
+  MSLAM_LAUNCH_CHECK("mesh_align_init_indexed");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_mesh_align_step_indexed(const float* src, int n, const float* vertices, const int32_t* faces,
+                                             int num_faces, int num_vertices, const int32_t* order, const void* index,
+                                             size_t index_bytes, double trim, int with_scale, int count_skips,
+                                             void* workspace, size_t workspace_bytes, void* state, int32_t* nearest,
+                                             float* moved, double* dist2, double* closest, double* log_row,
+                                             void* stream) {
+  MSLAM_REQUIRE(n >= 0 && num_faces >= 0 && num_vertices >= 0, "mesh_align_step_indexed: negative size");
+  MSLAM_REQUIRE(trim >= 0.0, "mesh_align_step_indexed: trim must be >= 0 (+inf keeps every pair)");
+  MSLAM_REQUIRE(state && log_row && order, "mesh_align_step_indexed: null pointer");
+  MSLAM_REQUIRE(n == 0 || (src && nearest && moved && dist2 && workspace), "mesh_align_step_indexed: null pointer");
+  MSLAM_REQUIRE(num_faces == 0 || (faces && index && (vertices || num_vertices == 0)),
+                "mesh_align_step_indexed: null pointer");
+  const int rc = ma_step("mesh_align_step_indexed", src, n, vertices, faces, num_faces, num_vertices, order, index,
+                         index_bytes, trim, with_scale, count_skips, workspace, workspace_bytes, state, nearest, moved,
+                         dist2, closest, log_row, stream);
+  if (rc) return rc;
+  MSLAM_LAUNCH_CHECK("mesh_align_step_indexed");
   return MSLAM_OK;
 }
 

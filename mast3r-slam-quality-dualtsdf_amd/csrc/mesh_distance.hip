@@ -8,7 +8,7 @@
 //
 // The distance is md_scan of mesh_tri.h, the culled nearest-face scan that mesh_align.hip calls too; the invariant that
 // makes its culling exact is in that header.  Here every lane starts without a bound and takes one from the block's
-// home tile.
+// home tile.  mslam_mesh_distance_indexed is the same scan over the tiles of a mesh index (mesh_index.hip).
 #include "mesh_tri.h"
 
 namespace mslam {
@@ -60,11 +60,15 @@ __global__ __launch_bounds__(256) void md_sample_kernel(const float* __restrict_
 }
 
 // skipped, when given: per wave, how many tiles the culled scan did not scan -> skipped[4 * block + wave] (the timing
-// tool's figure; each wave owns its word).
+// tool's figure; each wave owns its word).  kIndexed: the tiles follow `order`, `gbox` (may be null) holds the group
+// boxes (mesh_tri.h); without it neither is read.
+template <bool kIndexed>
 __global__ __launch_bounds__(kMdBlock) void md_distance_kernel(const float* __restrict__ points, int n,
                                                                const float* __restrict__ vert,
                                                                const int32_t* __restrict__ faces, int nf, int nv,
                                                                int cull, const double* __restrict__ box,
+                                                               const int32_t* __restrict__ order,
+                                                               const double* __restrict__ gbox,
                                                                int32_t* __restrict__ skipped,
                                                                double* __restrict__ dist2,
                                                                int32_t* __restrict__ nearest) {
@@ -76,8 +80,9 @@ __global__ __launch_bounds__(kMdBlock) void md_distance_kernel(const float* __re
   double px = 0.0, py = 0.0, pz = 0.0;
   if (has) px = (double)points[3 * i], py = (double)points[3 * i + 1], pz = (double)points[3 * i + 2];
   const MdNearest r =
-      md_scan(px, py, pz, has, (double)points[3 * i0], (double)points[3 * i0 + 1], (double)points[3 * i0 + 2], vert,
-              faces, nf, nv, cull, box, s_tri, &s_home, INFINITY, true);
+      md_scan<kIndexed>(px, py, pz, has, (double)points[3 * i0], (double)points[3 * i0 + 1],
+                        (double)points[3 * i0 + 2], vert, faces, nf, nv, cull, box, s_tri, &s_home, INFINITY, true, order,
+                        gbox);
   if (has) {
     dist2[i] = r.dist2;
     nearest[i] = r.face;
@@ -138,7 +143,7 @@ extern "C" int mslam_mesh_distance(const float* points, int n, const float* vert
       return MSLAM_ENOMEM;
     }
     hipLaunchKernelGGL(md_box_kernel, dim3(blocks_for(num_faces, kMdTile)), dim3(kWave), 0, s, vertices, faces,
-                       num_faces, num_vertices, (double*)workspace);
+                       num_faces, num_vertices, (const int32_t*)nullptr, (double*)workspace);
     if (num_faces <= kMdTile) {                  // one tile: it is scanned whatever its box says, so scan it once
       if (count_bytes) {
         int rc = check_hip(hipMemsetAsync((char*)workspace + box_bytes, 0, count_bytes, s), "mesh_distance memset");
@@ -148,8 +153,31 @@ extern "C" int mslam_mesh_distance(const float* points, int n, const float* vert
     }
     if (skip == 2) skipped = (int32_t*)((char*)workspace + box_bytes);
   }
-  hipLaunchKernelGGL(md_distance_kernel, dim3(nblocks), dim3(kMdBlock), 0, s, points, n, vertices, faces, num_faces,
-                     num_vertices, skip ? 1 : 0, (const double*)workspace, skipped, dist2, nearest);
+  hipLaunchKernelGGL(md_distance_kernel<false>, dim3(nblocks), dim3(kMdBlock), 0, s, points, n, vertices, faces,
+                     num_faces, num_vertices, skip ? 1 : 0, (const double*)workspace, (const int32_t*)nullptr,
+                     (const double*)nullptr, skipped, dist2, nearest);
   MSLAM_LAUNCH_CHECK("mesh_distance");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_mesh_distance_indexed(const float* points, int n, const float* vertices, const int32_t* faces,
+                                           int num_faces, int num_vertices, const int32_t* order, const void* index,
+                                           size_t index_bytes, int levels, int32_t* skip_counts, double* dist2,
+                                           int32_t* nearest, void* stream) {
+  MSLAM_REQUIRE(n >= 0 && num_faces >= 0 && num_vertices >= 0, "mesh_distance_indexed: negative size");
+  MSLAM_REQUIRE(levels == 1 || levels == 2, "mesh_distance_indexed: levels must be 1 (tiles) or 2 (tiles and groups)");
+  if (n == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(points && dist2 && nearest, "mesh_distance_indexed: null pointer");
+  MSLAM_REQUIRE(num_faces == 0 || (faces && order && index && (vertices || num_vertices == 0)),
+                "mesh_distance_indexed: null pointer");
+  if (index_bytes < md_index_bytes(num_faces)) {
+    set_error("mesh_distance_indexed: index of %zu bytes, %zu needed", index_bytes, md_index_bytes(num_faces));
+    return MSLAM_ENOMEM;
+  }
+  hipLaunchKernelGGL(md_distance_kernel<true>, dim3(blocks_for(n, kMdBlock)), dim3(kMdBlock), 0, (hipStream_t)stream,
+                     points, n, vertices, faces, num_faces, num_vertices, num_faces > 0 ? 1 : 0, (const double*)index,
+                     order, levels == 2 && num_faces > 0 ? md_index_gbox(index, num_faces) : (const double*)nullptr,
+                     skip_counts, dist2, nearest);
+  MSLAM_LAUNCH_CHECK("mesh_distance_indexed");
   return MSLAM_OK;
 }

@@ -28,7 +28,14 @@
 //            minority sign rounds to zero: the three sheared vertices are collinear with the origin to the last bit, a
 //            face seen edge-on whose "hit" is rounding noise.  DESIGN.md states this exception; it is the one case in
 //            which the culled scan could differ from the plain one.
-// Nothing is written except the outputs.
+//
+// WITH AN INDEX (mesh_index.hip; mesh_tri.h's header comment) the tiles follow `order`, a tie on t goes to the lowest
+// ORIGINAL face index, so the output is the plain ascending cast's whatever the order of the visit, and the same
+// rc_box_skips is put to the box of each group of 32 tiles before its tiles are considered.  Both arguments above hold
+// for ANY box that holds the vertices - the shear is monotone per input, and a group's box holds every tile's - so a
+// skipped group holds no face that could replace `best`.  The lateral test's edge-on exception is the same one, for
+// the same faces, no wider: a face whose three sheared vertices are collinear with the origin to the last bit.
+// Nothing is written except the outputs (and, when asked for, the per-wave skip counts).
 #include "mesh_tri.h"
 
 namespace mslam {
@@ -47,8 +54,9 @@ __device__ __forceinline__ double rc_pick(double a0, double a1, double a2, int k
   return k == 0 ? a0 : (k == 1 ? a1 : a2);
 }
 
-// The faces of the staged tile against this lane's ray; KX, KY, KZ >= 0: the wave's common permutation, -1: the lane's
-template <int KX, int KY, int KZ>
+// The faces of the staged tile against this lane's ray; KX, KY, KZ >= 0: the wave's common permutation, -1: the lane's.
+// kIndexed: the face's original index comes from its slot (md_stage) and a tie on t goes to the lowest.
+template <bool kIndexed, int KX, int KY, int KZ>
 __device__ __forceinline__ void rc_scan_tile(const RcRay& r, const double* s_tri, int cnt, int f0, double near,
                                              double far, double& best, int& best_f) {
   for (int k = 0; k < cnt; k++) {
@@ -71,7 +79,13 @@ __device__ __forceinline__ void rc_scan_tile(const RcRay& r, const double* s_tri
     const double det = (U + V) + W;
     if (det == 0.0) continue;
     const double tt = ((U * z[0] + V * z[1]) + W * z[2]) / det;
-    if (tt >= near && tt <= far && tt < best) best = tt, best_f = f0 + k;
+    if (!(tt >= near && tt <= far)) continue;
+    if (kIndexed) {
+      const int f = (int)t[9] - 1;
+      if (tt < best || (tt == best && f < best_f)) best = tt, best_f = f;
+    } else if (tt < best) {
+      best = tt, best_f = f0 + k;
+    }
   }
 }
 
@@ -90,11 +104,16 @@ __device__ __forceinline__ bool rc_box_skips(const RcRay& r, const double* __res
   return xl > 0.0 || xh < 0.0 || yl > 0.0 || yh < 0.0 || zl - eps > lim || zh + eps < near;
 }
 
+// kIndexed: the tiles follow `order`, `gbox` (may be null) holds the group boxes, and `skipped` (may be null) receives,
+// per wave, the tiles it did not scan -> skipped[4 * block + wave]; without it none of the three is read or written.
+template <bool kIndexed>
 __global__ __launch_bounds__(kMdBlock) void rc_kernel(const float* __restrict__ rays, int h, int w,
                                                       const float* __restrict__ pose8,
                                                       const float* __restrict__ vert,
                                                       const int32_t* __restrict__ faces, int nf, int nv, double near,
                                                       double far, int cull, const double* __restrict__ box,
+                                                      const int32_t* __restrict__ order,
+                                                      const double* __restrict__ gbox, int32_t* __restrict__ skipped,
                                                       float* __restrict__ range, float* __restrict__ normal,
                                                       uint8_t* __restrict__ hit, int32_t* __restrict__ face,
                                                       double* __restrict__ t64) {
@@ -155,28 +174,49 @@ __global__ __launch_bounds__(kMdBlock) void rc_kernel(const float* __restrict__ 
 
   const int ntiles = (nf + kMdTile - 1) / kMdTile;
   double best = INFINITY;
-  int best_f = -1;
-  for (int tile = 0; tile < ntiles; tile++) {
-    bool lane_skips = !casts;
-    if (cull && casts) lane_skips = rc_box_skips(r, box + 6 * (size_t)tile, near, fmin(best, far));
-    const bool wave_skips = __all(lane_skips);
-    // also the barrier between the last tile's reads and this tile's staging
-    if (__syncthreads_and(lane_skips)) continue;
-    if (tid < kMdTile) md_load_tri(vert, faces, tile * kMdTile + tid, nf, nv, s_tri + tid * kMdTriDoubles);
-    __syncthreads();
-    if (wave_skips) continue;
-    const int cnt = min(kMdTile, nf - tile * kMdTile), f0 = tile * kMdTile;
-    switch (wave_perm) {
-      case 0: rc_scan_tile<1, 2, 0>(r, s_tri, cnt, f0, near, far, best, best_f); break;
-      case 1: rc_scan_tile<2, 1, 0>(r, s_tri, cnt, f0, near, far, best, best_f); break;
-      case 2: rc_scan_tile<2, 0, 1>(r, s_tri, cnt, f0, near, far, best, best_f); break;
-      case 3: rc_scan_tile<0, 2, 1>(r, s_tri, cnt, f0, near, far, best, best_f); break;
-      case 4: rc_scan_tile<0, 1, 2>(r, s_tri, cnt, f0, near, far, best, best_f); break;
-      case 5: rc_scan_tile<1, 0, 2>(r, s_tri, cnt, f0, near, far, best, best_f); break;
-      default:
-        if (casts) rc_scan_tile<-1, -1, -1>(r, s_tri, cnt, f0, near, far, best, best_f);
+  int best_f = -1, n_skipped = 0;
+  // without an index: one "group" of all tiles, and the loops below are the plain tile loop
+  const int ngroups = kIndexed ? (ntiles + kMdGroup - 1) / kMdGroup : 1;
+  for (int g = 0; g < ngroups; g++) {
+    const int t0 = kIndexed ? g * kMdGroup : 0, t1 = kIndexed ? min(ntiles, t0 + kMdGroup) : ntiles;
+    if (kIndexed && cull && gbox) {
+      // the same test on the group's box; also the barrier between the last tile's reads and the next staging
+      const bool lane_skips = !casts || rc_box_skips(r, gbox + 6 * (size_t)g, near, fmin(best, far));
+      if (__syncthreads_and(lane_skips)) {
+        n_skipped += t1 - t0;
+        continue;
+      }
+    }
+    for (int tile = t0; tile < t1; tile++) {
+      bool lane_skips = !casts;
+      if (cull && casts) lane_skips = rc_box_skips(r, box + 6 * (size_t)tile, near, fmin(best, far));
+      const bool wave_skips = __all(lane_skips);
+      // also the barrier between the last tile's reads and this tile's staging
+      if (__syncthreads_and(lane_skips)) {
+        n_skipped++;
+        continue;
+      }
+      if (tid < kMdTile) md_stage<kIndexed>(vert, faces, nf, nv, order, tile, tid, s_tri);
+      __syncthreads();
+      if (wave_skips) {
+        n_skipped++;
+        continue;
+      }
+      const int cnt = min(kMdTile, nf - tile * kMdTile), f0 = tile * kMdTile;
+      switch (wave_perm) {
+        case 0: rc_scan_tile<kIndexed, 1, 2, 0>(r, s_tri, cnt, f0, near, far, best, best_f); break;
+        case 1: rc_scan_tile<kIndexed, 2, 1, 0>(r, s_tri, cnt, f0, near, far, best, best_f); break;
+        case 2: rc_scan_tile<kIndexed, 2, 0, 1>(r, s_tri, cnt, f0, near, far, best, best_f); break;
+        case 3: rc_scan_tile<kIndexed, 0, 2, 1>(r, s_tri, cnt, f0, near, far, best, best_f); break;
+        case 4: rc_scan_tile<kIndexed, 0, 1, 2>(r, s_tri, cnt, f0, near, far, best, best_f); break;
+        case 5: rc_scan_tile<kIndexed, 1, 0, 2>(r, s_tri, cnt, f0, near, far, best, best_f); break;
+        default:
+          if (casts) rc_scan_tile<kIndexed, -1, -1, -1>(r, s_tri, cnt, f0, near, far, best, best_f);
+      }
     }
   }
+  if (kIndexed && skipped && lane == 0)
+    skipped[4 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x) + wave] = n_skipped;
   if (!has) return;
   if (!casts) best = INFINITY, best_f = -1;      // such a lane ran along in its wave's scan; its ray misses
 
@@ -205,6 +245,11 @@ __global__ __launch_bounds__(kMdBlock) void rc_kernel(const float* __restrict__ 
 
 using namespace mslam;
 
+// h = 1: a list, 256 rays per block; otherwise 16x16 pixels per block
+static dim3 rc_grid(int h, int w) {
+  return h == 1 ? dim3(blocks_for(w, kMdBlock)) : dim3((unsigned)((w + 15) / 16), (unsigned)((h + 15) / 16));
+}
+
 extern "C" size_t mslam_mesh_raycast_workspace_bytes(int num_faces) {
   return num_faces > 0 ? md_box_bytes(num_faces) : 0;
 }
@@ -219,7 +264,7 @@ extern "C" int mslam_mesh_raycast_boxes(const float* vertices, const int32_t* fa
     return MSLAM_ENOMEM;
   }
   hipLaunchKernelGGL(md_box_kernel, dim3(blocks_for(num_faces, kMdTile)), dim3(kWave), 0, (hipStream_t)stream,
-                     vertices, faces, num_faces, num_vertices, (double*)workspace);
+                     vertices, faces, num_faces, num_vertices, (const int32_t*)nullptr, (double*)workspace);
   MSLAM_LAUNCH_CHECK("mesh_raycast_boxes");
   return MSLAM_OK;
 }
@@ -242,10 +287,40 @@ extern "C" int mslam_mesh_raycast(const float* rays, int h, int w, const float* 
       return MSLAM_ENOMEM;
     }
   }
-  const dim3 grid = h == 1 ? dim3(blocks_for(w, kMdBlock)) : dim3((unsigned)((w + 15) / 16), (unsigned)((h + 15) / 16));
-  hipLaunchKernelGGL(rc_kernel, grid, dim3(kMdBlock), 0, (hipStream_t)stream, rays, h, w, pose8, vertices, faces,
-                     num_faces, num_vertices, near, far, skip ? 1 : 0, (const double*)workspace, range, normal, hit,
-                     face, t64);
+  hipLaunchKernelGGL(rc_kernel<false>, rc_grid(h, w), dim3(kMdBlock), 0, (hipStream_t)stream, rays, h, w, pose8,
+                     vertices, faces, num_faces, num_vertices, near, far, skip ? 1 : 0, (const double*)workspace,
+                     (const int32_t*)nullptr, (const double*)nullptr, (int32_t*)nullptr, range, normal, hit, face, t64);
   MSLAM_LAUNCH_CHECK("mesh_raycast");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_mesh_raycast_blocks(int h, int w) {
+  if (h <= 0 || w <= 0) return 0;
+  const dim3 grid = rc_grid(h, w);
+  return (int)(grid.x * grid.y);
+}
+
+extern "C" int mslam_mesh_raycast_indexed(const float* rays, int h, int w, const float* pose8, const float* vertices,
+                                          const int32_t* faces, int num_faces, int num_vertices, double near,
+                                          double far, const int32_t* order, const void* index, size_t index_bytes,
+                                          int levels, int32_t* skip_counts, float* range, float* normal, uint8_t* hit,
+                                          int32_t* face, double* t64, void* stream) {
+  MSLAM_REQUIRE(h >= 0 && w >= 0 && (int64_t)h * w < (1ll << 31), "mesh_raycast_indexed: bad image size");
+  MSLAM_REQUIRE(num_faces >= 0 && num_vertices >= 0, "mesh_raycast_indexed: negative size");
+  MSLAM_REQUIRE(near <= far, "mesh_raycast_indexed: near must not exceed far");
+  MSLAM_REQUIRE(levels == 1 || levels == 2, "mesh_raycast_indexed: levels must be 1 (tiles) or 2 (tiles and groups)");
+  if (h == 0 || w == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(rays && pose8 && range && normal && hit, "mesh_raycast_indexed: null pointer");
+  MSLAM_REQUIRE(num_faces == 0 || (faces && order && index && (vertices || num_vertices == 0)),
+                "mesh_raycast_indexed: null pointer");
+  if (index_bytes < md_index_bytes(num_faces)) {
+    set_error("mesh_raycast_indexed: index of %zu bytes, %zu needed", index_bytes, md_index_bytes(num_faces));
+    return MSLAM_ENOMEM;
+  }
+  hipLaunchKernelGGL(rc_kernel<true>, rc_grid(h, w), dim3(kMdBlock), 0, (hipStream_t)stream, rays, h, w, pose8,
+                     vertices, faces, num_faces, num_vertices, near, far, num_faces > 0 ? 1 : 0, (const double*)index,
+                     order, levels == 2 && num_faces > 0 ? md_index_gbox(index, num_faces) : (const double*)nullptr,
+                     skip_counts, range, normal, hit, face, t64);
+  MSLAM_LAUNCH_CHECK("mesh_raycast_indexed");
   return MSLAM_OK;
 }

@@ -20,6 +20,22 @@
 // nothing, because a tile worth skipping is centimetres away and 2^-27 S^2 is (1e-4 S)^2.  So every face of a skipped
 // tile has md_dist2 > min(best, ub) >= the final minimum: it is neither the minimum nor a tie, and the output is the
 // one of the plain ascending scan with its strict `<`, bit for bit.  tests/test_mesh_metrics_gpu.py is the judge.
+//
+// WITH AN INDEX (mesh_index.hip, DESIGN.md "Mesh index") tile t holds the faces order[128 t + k] instead of the faces
+// 128 t + k, so a tile is a compact patch whatever order the caller's faces are in.  `faces` itself is never permuted:
+// the staging follows `order` (each entry range-checked first) and keeps the face's ORIGINAL index beside its corners,
+// and the scan's rule becomes  d < best || (d == best && f < best_f)  on that original index.  The minimum over a set
+// and the lowest index that attains it do not depend on the order of the visit, so the output is still that of the plain
+// ascending scan of the caller's mesh, bit for bit, and the argument above goes through unchanged: a tile is skipped
+// only when each of its faces is strictly worse than a real face.
+// THE GROUP LEVEL.  Above the tiles lie the boxes of groups of 32 consecutive tiles.  Before a group's tiles are
+// considered, every lane applies the very same test to the group's box, and when the whole block agrees the group is
+// passed over without its 32 barriers.  That is exact by the same proof: the group's box contains each of its tiles'
+// boxes, so its lb is no larger and its S no smaller than any tile's, and
+//     lb2(group) > min(best, ub) (1 + 2^-20) + 2^-27 S(group)^2
+// puts every face of every tile of the group strictly beyond min(best, ub), by the invariant read with the group's box
+// in the place of the tile's (it, too, holds every vertex of its valid faces exactly).  tests/test_mesh_index_gpu.py is
+// the judge.
 #pragma once
 #include <math.h>
 
@@ -30,6 +46,7 @@ namespace mslam {
 constexpr int kMdTile = 128;      // triangles per LDS tile and per box; tests/test_mesh_metrics_gpu.py states it too
 constexpr int kMdBlock = 256;     // one point per thread
 constexpr int kMdTriDoubles = 10; // a, b, c, valid
+constexpr int kMdGroup = 32;      // tiles per group box of a mesh index; tests/test_mesh_index_gpu.py states it too
 
 __device__ __forceinline__ double md_dot(double ax, double ay, double az, double bx, double by, double bz) {
   return ax * bx + ay * by + az * bz;
@@ -125,16 +142,25 @@ __device__ __forceinline__ double md_dist2(double px, double py, double pz, cons
   return md_dot(rx, ry, rz, rx, ry, rz);
 }
 
+// Slot i of the tiles: face i itself, or with an index order[i], range-checked before it is followed (nf: no face).
+__device__ __forceinline__ int md_slot_face(const int32_t* __restrict__ order, int i, int nf) {
+  if (!order || i >= nf) return i;
+  const int f = order[i];
+  return (unsigned)f < (unsigned)nf ? f : nf;
+}
+
 // box[6 * tile + ...] = lo.xyz, hi.xyz over the vertices of the tile's valid faces; (+inf, -inf) for a tile without one.
-// static: one copy per translation unit that includes this header.
+// `order`, when given, names the faces of the tiles (md_slot_face).  static: one copy per translation unit that
+// includes this header.
 static __global__ __launch_bounds__(64) void md_box_kernel(const float* __restrict__ vert,
                                                            const int32_t* __restrict__ faces, int nf, int nv,
+                                                           const int32_t* __restrict__ order,
                                                            double* __restrict__ box) {
   const int tile = blockIdx.x, lane = threadIdx.x;
   double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
   for (int k = lane; k < kMdTile; k += kWave) {
     double t[kMdTriDoubles];
-    if (md_load_tri(vert, faces, tile * kMdTile + k, nf, nv, t)) {
+    if (md_load_tri(vert, faces, md_slot_face(order, tile * kMdTile + k, nf), nf, nv, t)) {
 #pragma unroll
       for (int j = 0; j < 9; j++) {
         lo[j % 3] = fmin(lo[j % 3], t[j]);
@@ -174,6 +200,16 @@ struct MdNearest {
   int skipped;    // the tiles this lane's wave did not scan
 };
 
+// Slot `tid` of `tile` into LDS.  kIndexed: the face is order[128 tile + tid] and t[9] of a valid face is 1 + its
+// original index (exact in a double), which the scans read back for the tie rule.
+template <bool kIndexed>
+__device__ __forceinline__ void md_stage(const float* __restrict__ vert, const int32_t* __restrict__ faces, int nf,
+                                         int nv, const int32_t* __restrict__ order, int tile, int tid, double* s_tri) {
+  const int f = md_slot_face(kIndexed ? order : nullptr, tile * kMdTile + tid, nf);
+  double* t = s_tri + tid * kMdTriDoubles;
+  if (md_load_tri(vert, faces, f, nf, nv, t) && kIndexed) t[9] = (double)f + 1.0;
+}
+
 // The nearest valid face of the mesh to this lane's point p.  Every thread of the block calls it, also one without a
 // point (`has` false): it reaches the same barriers and never keeps a tile in.
 // `cull` 0 is the plain ascending scan.  With `cull` the two parameters that may differ per lane, neither of which
@@ -183,12 +219,16 @@ struct MdNearest {
 //   need_home  the lane has no such face yet.  When some lane of the block with a point says so, the block stages
 //              its home tile, the one whose box is nearest to the block's first point q0 (which tile it is changes
 //              no output), and those lanes take ub from its faces.
+// kIndexed (see the header comment): the tiles follow `order`, ties go to the lowest original index, and `gbox`, when
+// given, holds the boxes of the groups of kMdGroup tiles.  Without it `order` and `gbox` are not read.
 // s_tri: kMdTile * kMdTriDoubles doubles of LDS; s_home: one LDS word.
+template <bool kIndexed>
 __device__ __forceinline__ MdNearest md_scan(double px, double py, double pz, bool has, double q0x, double q0y,
                                              double q0z, const float* __restrict__ vert,
                                              const int32_t* __restrict__ faces, int nf, int nv, int cull,
                                              const double* __restrict__ box, double* s_tri, int* s_home, double ub,
-                                             bool need_home) {
+                                             bool need_home, const int32_t* __restrict__ order = nullptr,
+                                             const double* __restrict__ gbox = nullptr) {
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
   const int ntiles = (nf + kMdTile - 1) / kMdTile;
   double best = INFINITY;
@@ -212,7 +252,7 @@ __device__ __forceinline__ MdNearest md_scan(double px, double py, double pz, bo
     __syncthreads();
     const int home = *s_home;
     if (home >= 0) {
-      if (tid < kMdTile) md_load_tri(vert, faces, home * kMdTile + tid, nf, nv, s_tri + tid * kMdTriDoubles);
+      if (tid < kMdTile) md_stage<kIndexed>(vert, faces, nf, nv, order, home, tid, s_tri);
       __syncthreads();
       if (need_home) {
         const int cnt = min(kMdTile, nf - home * kMdTile);
@@ -224,31 +264,54 @@ __device__ __forceinline__ MdNearest md_scan(double px, double py, double pz, bo
     }
   }
 
-  for (int tile = 0; tile < ntiles; tile++) {
-    bool lane_skips = !has;
-    if (cull && has) {
-      double s2;
-      const double lb2 = md_box_lb2(px, py, pz, box + 6 * (size_t)tile, &s2);
-      lane_skips = lb2 > fmin(best, ub) * (1.0 + 0x1p-20) + 0x1p-27 * s2;
+  // without an index: one "group" of all tiles, and the loops below are the plain tile loop
+  const int ngroups = kIndexed ? (ntiles + kMdGroup - 1) / kMdGroup : 1;
+  for (int g = 0; g < ngroups; g++) {
+    const int t0 = kIndexed ? g * kMdGroup : 0, t1 = kIndexed ? min(ntiles, t0 + kMdGroup) : ntiles;
+    if (kIndexed && cull && gbox) {
+      bool lane_skips = !has;
+      if (has) {
+        double s2;
+        const double lb2 = md_box_lb2(px, py, pz, gbox + 6 * (size_t)g, &s2);
+        lane_skips = lb2 > fmin(best, ub) * (1.0 + 0x1p-20) + 0x1p-27 * s2;
+      }
+      // also the barrier between the last tile's reads and the next staging
+      if (__syncthreads_and(lane_skips)) {
+        n_skipped += t1 - t0;
+        continue;
+      }
     }
-    const bool wave_skips = cull && __all(lane_skips);
-    // also the barrier between the last tile's reads and this tile's staging
-    if (__syncthreads_and(cull && lane_skips)) {
-      n_skipped++;
-      continue;
-    }
-    if (tid < kMdTile) md_load_tri(vert, faces, tile * kMdTile + tid, nf, nv, s_tri + tid * kMdTriDoubles);
-    __syncthreads();
-    if (wave_skips) {
-      n_skipped++;
-      continue;
-    }
-    const int cnt = min(kMdTile, nf - tile * kMdTile);
-    for (int k = 0; k < cnt; k++) {
-      const double* t = s_tri + k * kMdTriDoubles;       // one address for the whole wave: an LDS broadcast
-      if (t[9] != 0.0) {
-        const double d = md_dist2(px, py, pz, t);
-        if (d < best) best = d, best_f = tile * kMdTile + k;
+    for (int tile = t0; tile < t1; tile++) {
+      bool lane_skips = !has;
+      if (cull && has) {
+        double s2;
+        const double lb2 = md_box_lb2(px, py, pz, box + 6 * (size_t)tile, &s2);
+        lane_skips = lb2 > fmin(best, ub) * (1.0 + 0x1p-20) + 0x1p-27 * s2;
+      }
+      const bool wave_skips = cull && __all(lane_skips);
+      // also the barrier between the last tile's reads and this tile's staging
+      if (__syncthreads_and(cull && lane_skips)) {
+        n_skipped++;
+        continue;
+      }
+      if (tid < kMdTile) md_stage<kIndexed>(vert, faces, nf, nv, order, tile, tid, s_tri);
+      __syncthreads();
+      if (wave_skips) {
+        n_skipped++;
+        continue;
+      }
+      const int cnt = min(kMdTile, nf - tile * kMdTile);
+      for (int k = 0; k < cnt; k++) {
+        const double* t = s_tri + k * kMdTriDoubles;       // one address for the whole wave: an LDS broadcast
+        if (t[9] != 0.0) {
+          const double d = md_dist2(px, py, pz, t);
+          if (kIndexed) {
+            const int f = (int)t[9] - 1;
+            if (d < best || (d == best && f < best_f)) best = d, best_f = f;
+          } else if (d < best) {
+            best = d, best_f = tile * kMdTile + k;
+          }
+        }
       }
     }
   }
@@ -258,5 +321,12 @@ __device__ __forceinline__ MdNearest md_scan(double px, double py, double pz, bo
 // workspace bytes of the boxes of nf faces, and of the per-wave skip counts of n points (four waves per block)
 inline size_t md_box_bytes(int nf) { return (size_t)blocks_for(nf, kMdTile) * 6 * sizeof(double); }
 inline size_t md_count_bytes(int n) { return (size_t)blocks_for(n, kMdBlock) * 4 * sizeof(int32_t); }
+
+// A mesh index's workspace: the tile boxes, as above but of the tiles in `order`, then the boxes of the groups
+inline int md_groups(int nf) { return (int)blocks_for(blocks_for(nf, kMdTile), kMdGroup); }
+inline size_t md_index_bytes(int nf) { return md_box_bytes(nf) + (size_t)md_groups(nf) * 6 * sizeof(double); }
+inline const double* md_index_gbox(const void* index, int nf) {
+  return (const double*)((const char*)index + md_box_bytes(nf));
+}
 
 }  // namespace mslam

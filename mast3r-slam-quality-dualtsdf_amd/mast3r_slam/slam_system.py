@@ -393,7 +393,7 @@ class SlamSystem:
         return fit_sim3(est, gt)[0]
 
     def evaluate_mesh(self, gt_vertices, gt_faces, n_samples=200_000, threshold=None, align=None, init=None,
-                      gt_positions=None, align_kw=None, observed=False, gt_K=None, **extract_kw):
+                      gt_positions=None, align_kw=None, observed=False, gt_K=None, index=None, **extract_kw):
         """Quality of the global TSDF's mesh at this point of the run against a ground-truth mesh (gt_vertices f32[V,3],
         gt_faces i32[F,3]; numpy arrays or device tensors): the dict of tsdf.compare_meshes,
         accuracy / completion / precision / recall / fscore / chamfer (DESIGN.md "Mesh quality").  The mesh is
@@ -408,7 +408,11 @@ class SlamSystem:
         `observed=True`: only the part of the ground truth that some keyframe sees enters completion, recall, fscore and
         chamfer (compare_meshes(observed=...), DESIGN.md "Mesh ray casting"): the cameras are the keyframes' T_WC, moved
         by the alignment, with the pinhole `gt_K` (3,3) or else the system's calibration at the keyframes' image size.
-        Without either it raises: the ray-image camera model has no projection."""
+        Without either it raises: the ray-image camera model has no projection.
+
+        `index`: None, True or a tsdf.MeshIndex of the ground-truth tensors (DESIGN.md "Mesh index").  True builds one
+        here, and the alignment, the scoring against the ground truth and the observed-part cull all use it, so that
+        their speed does not depend on the order of the ground truth's faces.  The figures do not change."""
         if self.tsdf_manager is None:
             raise RuntimeError("SlamSystem.evaluate_mesh: the global TSDF is disabled (tsdf_global.enabled = False)")
         from mast3r_slam.tsdf import compare_meshes
@@ -445,10 +449,12 @@ class SlamSystem:
             poses = torch.stack([self.keyframes[i].T_WC.data.reshape(8) for i in range(n_kf)])
             hw = tuple(int(x) for x in self.keyframes[n_kf - 1].img_shape.reshape(-1)[:2].tolist())
             kw["observed"] = dict(poses=poses, K=K, hw=hw, frame="pred")
+        if index is not None and index is not False:
+            kw["index"] = index
         return compare_meshes(mesh, (gt_vertices, gt_faces), n_samples=n_samples, threshold=threshold,
                               _validate_pred=False, **kw)
 
-    def evaluate_depth(self, gt_vertices, gt_faces, align=None, near=0.05, far=10.0):
+    def evaluate_depth(self, gt_vertices, gt_faces, align=None, near=0.05, far=10.0, index=None):
         """The "Depth L1" figure of dense-SLAM evaluations: for every keyframe, the view of the global TSDF
         (TSDFVolume.render) against the view of a ground-truth mesh (tsdf.render_mesh; gt_vertices f32[V,3], gt_faces
         i32[F,3], numpy arrays or device tensors) from the same camera through the same rays - the system's intrinsics
@@ -456,10 +462,13 @@ class SlamSystem:
         `align`: None - the ground truth lies in the map's frame; a Sim3 - it moves the keyframe's pose into the ground
         truth's frame for the mesh view.  `near`, `far`: ground-truth units.  Returns Python numbers: depth_l1 and
         depth_l1_median, mean and median of |range_map - range_gt| times the moved pose's scale (ground-truth units)
-        over the pixels hit in both views (NaN without one), both_hit_share and n_pixels.  Drains the backend first."""
+        over the pixels hit in both views (NaN without one), both_hit_share and n_pixels.  Drains the backend first.
+        `index`: None, True or a tsdf.MeshIndex of the ground-truth tensors: one index serves every keyframe's view of the
+        ground truth (DESIGN.md "Mesh index"); the figures do not change."""
         if self.tsdf_manager is None:
             raise RuntimeError("SlamSystem.evaluate_depth: the global TSDF is disabled (tsdf_global.enabled = False)")
         from mast3r_slam.tsdf import render_mesh
+        from mast3r_slam.tsdf.mesh_index import _index_arg
         from mast3r_slam.tsdf.mesh_raycast import compose_sim3
 
         self.drain()
@@ -468,6 +477,7 @@ class SlamSystem:
             raise RuntimeError("SlamSystem.evaluate_depth: no keyframe yet")
         gt = (torch.as_tensor(gt_vertices, dtype=torch.float32).to(self.device),
               torch.as_tensor(gt_faces, dtype=torch.int32).to(self.device))
+        index = _index_arg(index, *gt, "SlamSystem.evaluate_depth")
         T = None if align is None else torch.as_tensor(getattr(align, "data", align)).detach().double().cpu().reshape(8)
         a_scale = 1.0 if T is None else float(T[7])
         diffs, n_pixels = [], 0
@@ -482,7 +492,7 @@ class SlamSystem:
                 view = dict(rays=X / X.norm(dim=-1, keepdim=True).clamp_min(1.0e-12))
             moved = pose.double().cpu() if T is None else compose_sim3(T, pose.double().cpu().reshape(1, 8))[0]
             r_map, _, hit_map = self.tsdf_manager.render(pose, near=near / a_scale, far=far / a_scale, **view)[:3]
-            r_gt, _, hit_gt = render_mesh(gt, moved, near=near, far=far, validate=i == 0, **view)
+            r_gt, _, hit_gt = render_mesh(gt, moved, near=near, far=far, validate=i == 0, index=index, **view)
             both = hit_map & hit_gt
             diffs.append((r_map.double() - r_gt.double()).abs()[both] * float(moved[7]))
             n_pixels += h * w

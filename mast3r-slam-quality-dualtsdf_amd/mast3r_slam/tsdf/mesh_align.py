@@ -13,6 +13,7 @@ import torch
 import mslam_hip as _m
 
 from ._mesh_args import _mesh_arg, _pair, _points_arg, _sample, _sim3_arg
+from .mesh_index import _index_arg
 
 STATE_BYTES, LOG_DOUBLES, OK, DEGENERATE = (_m.header_constants()["MSLAM_MESH_ALIGN_" + k] for k in (
     "STATE_BYTES", "LOG_DOUBLES", "OK", "DEGENERATE"))
@@ -86,7 +87,7 @@ def transform_mesh(vertices, T, normals=None):
 
 
 def align_meshes(pred, gt, init=None, n_samples=20000, max_iters=50, trim=math.inf, with_scale=True, seed=0, tol=1e-6,
-                 check_every=5):
+                 check_every=5, index=None):
     """Trimmed point-to-mesh ICP of the mesh `pred` onto the mesh `gt` (both (vertices f32[V,3], faces i32[F,3]) device
     tensors or extract_mesh tuples): the Sim3 T with T(pred) ~ gt.
 
@@ -97,6 +98,9 @@ def align_meshes(pred, gt, init=None, n_samples=20000, max_iters=50, trim=math.i
     their closest points (`with_scale=False`: scale 1).  Nothing is read back except the log, once every `check_every`
     iterations; the loop stops when the RMSE of two successive iterations differs by at most `tol` relative, when an
     iteration is degenerate (fewer than 3 pairs within `trim`), or after `max_iters`.
+
+    `index`: None, True or a MeshIndex of `gt`: the scan runs over its Morton-ordered tiles and group boxes instead of
+    the tiles of gt's face order, warm start unchanged; same transform and log, bit for bit (DESIGN.md "Mesh index").
 
     ICP is a LOCAL method: it needs `init` (a Sim3, default the identity) for anything beyond a modest offset.  On a
     partial room, a numpy prototype recovered 8 degrees / 15 cm / scale 0.9 and failed at 15 degrees / 0.3 m / scale
@@ -116,6 +120,7 @@ def align_meshes(pred, gt, init=None, n_samples=20000, max_iters=50, trim=math.i
         raise ValueError(f"{what}: a trim sequence needs one value per iteration ({max_iters}), got {len(trims)}")
     if not all(t >= 0.0 for t in trims):
         raise ValueError(f"{what}: trim must be >= 0 (+inf keeps every pair)")
+    index = _index_arg(index, *_pair(gt, "gt"), what)
     pv, pf, pV, pF = _mesh_arg(*_pair(pred, "pred"), True, what)
     gv, gf, gV, gF = _mesh_arg(*_pair(gt, "gt"), True, what)
     if pv.device != gv.device:
@@ -125,21 +130,31 @@ def align_meshes(pred, gt, init=None, n_samples=20000, max_iters=50, trim=math.i
     n = int(src.shape[0])
     T0 = None if init is None else _sim3_arg(init, what, dev, torch.float32)
     L, st = _m.lib(), _m.stream_ptr()
-    ws_bytes = int(L.mslam_mesh_align_workspace_bytes(n, gF, 0))
+    ws_bytes = int(L.mslam_mesh_align_workspace_bytes(n, gF if index is None else 0, 0))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     state = torch.empty(STATE_BYTES, dtype=torch.uint8, device=dev)
     log = torch.zeros((max_iters, LOG_DOUBLES), dtype=torch.float64, device=dev)
     nearest = torch.full((n,), -1, dtype=torch.int32, device=dev)
     moved = torch.empty((n, 3), dtype=torch.float32, device=dev)
     dist2 = torch.empty(n, dtype=torch.float64, device=dev)
-    _m.check(L.mslam_mesh_align_init(_m.ptr(T0), _m.ptr(gv), _m.ptr(gf), gF, gV, _m.ptr(ws), ws_bytes, _m.ptr(state),
-                                     st), "mesh_align_init")
+    if index is None:
+        _m.check(L.mslam_mesh_align_init(_m.ptr(T0), _m.ptr(gv), _m.ptr(gf), gF, gV, _m.ptr(ws), ws_bytes,
+                                         _m.ptr(state), st), "mesh_align_init")
+    else:
+        _m.check(L.mslam_mesh_align_init_indexed(_m.ptr(T0), _m.ptr(state), st), "mesh_align_init_indexed")
     converged, hist, it = False, None, 0
     for it in range(max_iters):
-        _m.check(L.mslam_mesh_align_step(_m.ptr(src), n, _m.ptr(gv), _m.ptr(gf), gF, gV, trims[it],
-                                         1 if with_scale else 0, 0, _m.ptr(ws), ws_bytes, _m.ptr(state),
-                                         _m.ptr(nearest), _m.ptr(moved), _m.ptr(dist2), 0, _m.ptr(log[it]), st),
-                 "mesh_align_step")
+        if index is None:
+            _m.check(L.mslam_mesh_align_step(_m.ptr(src), n, _m.ptr(gv), _m.ptr(gf), gF, gV, trims[it],
+                                             1 if with_scale else 0, 0, _m.ptr(ws), ws_bytes, _m.ptr(state),
+                                             _m.ptr(nearest), _m.ptr(moved), _m.ptr(dist2), 0, _m.ptr(log[it]), st),
+                     "mesh_align_step")
+        else:
+            _m.check(L.mslam_mesh_align_step_indexed(_m.ptr(src), n, _m.ptr(gv), _m.ptr(gf), gF, gV,
+                                                     _m.ptr(index.order), _m.ptr(index.ws), index.ws_bytes, trims[it],
+                                                     1 if with_scale else 0, 0, _m.ptr(ws), ws_bytes, _m.ptr(state),
+                                                     _m.ptr(nearest), _m.ptr(moved), _m.ptr(dist2), 0,
+                                                     _m.ptr(log[it]), st), "mesh_align_step_indexed")
         if (it + 1) % check_every == 0 or it + 1 == max_iters:
             hist = log[:it + 1, :4].cpu().numpy()                      # the one host read of this stretch
             if hist[it, 3] != OK:

@@ -14,6 +14,7 @@ import mslam_hip as _m
 
 from ._mesh_args import _areas, _mesh_arg, _pair, _points_arg, _sample, _sim3_arg
 from .mesh_align import align_meshes, transform_mesh
+from .mesh_index import _index_arg
 
 
 def face_areas(vertices, faces, _validate=True):
@@ -31,12 +32,25 @@ def sample_mesh(vertices, faces, n, seed=0, _validate=True):
     return _sample(vertices, faces, V, F, n, seed, "sample_mesh")[:2]
 
 
-def _distance2(points, vertices, faces, V, F, skip):
+def _distance2(points, vertices, faces, V, F, skip, index=None, sort_queries=True):
+    """(dist2 f64[n], nearest i32[n]).  `index`: a MeshIndex of this mesh - the scan runs over its tiles, and with
+    `sort_queries` on the points in the order of their Morton keys, the results scattered back."""
     n = int(points.shape[0])
     dev = points.device
     dist2 = torch.empty(n, dtype=torch.float64, device=dev)
     nearest = torch.empty(n, dtype=torch.int32, device=dev)
     L = _m.lib()
+    if index is not None:
+        perm = index.query_order(points) if sort_queries and n > 1 else None
+        pts = points if perm is None else points[perm].contiguous()
+        _m.check(L.mslam_mesh_distance_indexed(_m.ptr(pts), n, _m.ptr(vertices), _m.ptr(faces), F, V,
+                                               _m.ptr(index.order), _m.ptr(index.ws), index.ws_bytes, 2, 0,
+                                               _m.ptr(dist2), _m.ptr(nearest), _m.stream_ptr()),
+                 "mesh_distance_indexed")
+        if perm is None:
+            return dist2, nearest
+        return torch.empty_like(dist2).index_copy_(0, perm, dist2), torch.empty_like(nearest).index_copy_(0, perm,
+                                                                                                       nearest)
     ws_bytes = int(L.mslam_mesh_distance_workspace_bytes(F)) if skip and F else 0
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
     _m.check(L.mslam_mesh_distance(_m.ptr(points), n, _m.ptr(vertices), _m.ptr(faces), F, V, 1 if ws_bytes else 0,
@@ -45,21 +59,25 @@ def _distance2(points, vertices, faces, V, F, skip):
     return dist2, nearest
 
 
-def mesh_distance(points, vertices, faces, skip=True, _validate=True):
+def mesh_distance(points, vertices, faces, skip=True, _validate=True, index=None, sort_queries=True):
     """Exact distance from points f32[n,3] to the mesh -> (distance f64[n], nearest i32[n]) device tensors: the distance
     to the closest point of the closest valid face and the lowest index of a face at that distance; +inf and -1 when
     the mesh has no valid face.  `skip`: tiles of faces whose bounding box lies beyond a point block's current best are
-    not scanned; the output is the same bit for bit (DESIGN.md "Mesh quality")."""
+    not scanned; the output is the same bit for bit (DESIGN.md "Mesh quality").  `index`: None - that path; True - a
+    MeshIndex of the mesh is built first; a MeshIndex built for these tensors - the scan runs over its Morton-ordered
+    tiles and group boxes, and with `sort_queries` the points are scanned in the order of their Morton keys and the
+    results scattered back; the same bits again, for faces in any order (DESIGN.md "Mesh index")."""
     points = _points_arg(points, "points", "mesh_distance")
+    index = _index_arg(index, vertices, faces, "mesh_distance")
     vertices, faces, V, F = _mesh_arg(vertices, faces, _validate, "mesh_distance")
     if points.device != vertices.device:
         raise ValueError("mesh_distance: points and mesh are on different devices")
-    dist2, nearest = _distance2(points, vertices, faces, V, F, bool(skip))
+    dist2, nearest = _distance2(points, vertices, faces, V, F, bool(skip), index, sort_queries)
     return torch.sqrt(dist2), nearest
 
 
 def compare_meshes(pred, gt, n_samples=200_000, threshold=0.05, seed=0, skip=True, _validate_pred=True, align=None,
-                   align_kw=None, observed=None):
+                   align_kw=None, observed=None, index=None):
     """Quality of the mesh `pred` against the ground truth `gt`, both (vertices f32[V,3], faces i32[F,3]) device tensors
     or the tuples extract_mesh returns (normals and colours are ignored), in one frame.  n_samples points are drawn on
     each (sample_mesh with `seed` on pred, `seed + 1` on gt) and measured against the other (mesh_distance).  Returns
@@ -78,8 +96,13 @@ def compare_meshes(pred, gt, n_samples=200_000, threshold=0.05, seed=0, skip=Tru
     camera sees, occlusion against the ground-truth mesh included, enter completion, completion_median, recall, fscore
     and chamfer (DESIGN.md "Mesh ray casting").  `frame`: "gt" (default) - the poses lie in the ground truth's frame;
     "pred" - in pred's, and the alignment transform moves them first.  The dict gains gt_observed_share and
-    n_gt_observed; ValueError when no sample is observed.  Accuracy and precision do not change."""
+    n_gt_observed; ValueError when no sample is observed.  Accuracy and precision do not change.
+
+    `index`: None, True or a MeshIndex of `gt` (DESIGN.md "Mesh index"): the alignment, the distances to gt and the
+    observed-part cull run over it, so their speed does not depend on the order of gt's faces.  The dict is the same,
+    value for value."""
     n = int(n_samples)
+    index = _index_arg(index, *_pair(gt, "gt"), "compare_meshes")
     threshold = float(threshold)
     alignment = None
     if align is not None:
@@ -87,7 +110,7 @@ def compare_meshes(pred, gt, n_samples=200_000, threshold=0.05, seed=0, skip=Tru
         if isinstance(align, str):
             if align != "icp":
                 raise ValueError(f"compare_meshes: align must be None, a Sim3 or 'icp', got {align!r}")
-            res = align_meshes((pvert, pfaces), gt, **(align_kw or {}))
+            res = align_meshes((pvert, pfaces), gt, index=index, **(align_kw or {}))
             T, alignment = res["T"], dict(rmse=res["rmse"], iterations=res["iterations"])
         else:
             if align_kw:
@@ -104,14 +127,15 @@ def compare_meshes(pred, gt, n_samples=200_000, threshold=0.05, seed=0, skip=Tru
     g_pts, _, g_area = _sample(gv, gf, gV, gF, n, int(seed) + 1, "compare_meshes (gt)")
     n_obs = n
     if observed is not None:
-        seen = _observed_samples(g_pts, (gv, gf), observed, T if align is not None else None, bool(skip))
+        seen = _observed_samples(g_pts, _pair(gt, "gt") if index is not None else (gv, gf), observed,
+                                 T if align is not None else None, bool(skip), index)
         g_pts = g_pts[seen]
         n_obs = int(g_pts.shape[0])                                               # a host read
         if n_obs == 0:
             raise ValueError("compare_meshes: no ground-truth sample is observed by the given cameras")
     out = []
-    for pts, m, (v, f, V, F) in ((p_pts, n, (gv, gf, gV, gF)), (g_pts, n_obs, (pv, pf, pV, pF))):
-        d = torch.sqrt(_distance2(pts, v, f, V, F, bool(skip))[0])
+    for pts, m, (v, f, V, F), ix in ((p_pts, n, (gv, gf, gV, gF), index), (g_pts, n_obs, (pv, pf, pV, pF), None)):
+        d = torch.sqrt(_distance2(pts, v, f, V, F, bool(skip), ix)[0])
         s = torch.sort(d)[0]
         out += [d.sum() / m, 0.5 * (s[(m - 1) // 2] + s[m // 2]), (d <= threshold).sum().to(torch.float64) / m]
     acc, acc_med, prec, comp, comp_med, rec = torch.stack(out).tolist()          # the one host read of the figures
@@ -125,7 +149,7 @@ def compare_meshes(pred, gt, n_samples=200_000, threshold=0.05, seed=0, skip=Tru
     return out
 
 
-def _observed_samples(g_pts, gt, observed, T, skip):
+def _observed_samples(g_pts, gt, observed, T, skip, index=None):
     """bool[n]: the ground-truth samples the cameras of `observed` see; T: the alignment transform or None."""
     from .mesh_raycast import _poses_arg, compose_sim3, observed_points
 
@@ -140,4 +164,4 @@ def _observed_samples(g_pts, gt, observed, T, skip):
     poses = _poses_arg(spec.pop("poses"), "compare_meshes")
     if frame == "pred" and T is not None:
         poses = compose_sim3(T, poses)
-    return observed_points(g_pts, gt, poses, spec.pop("K"), spec.pop("hw"), skip=skip, **spec)
+    return observed_points(g_pts, gt, poses, spec.pop("K"), spec.pop("hw"), skip=skip, index=index, **spec)

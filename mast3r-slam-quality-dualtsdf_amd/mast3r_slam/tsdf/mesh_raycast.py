@@ -11,16 +11,20 @@ import mslam_hip as _m
 
 from ._mesh_args import _mesh_arg, _pair, _points_arg
 from .global_volume import _render_args
+from .mesh_index import _index_arg
 
 
 class _Caster:
-    """A mesh with the boxes of its 128-face tiles, computed once and reused by every view."""
+    """A mesh with the boxes of its 128-face tiles, computed once and reused by every view; with `index` (None, True or
+    a MeshIndex of the mesh) the tiles and group boxes are the index's."""
 
-    def __init__(self, vertices, faces, validate, skip, what):
+    def __init__(self, vertices, faces, validate, skip, what, index=None):
+        self.index = _index_arg(index, vertices, faces, what)
         self.v, self.f, self.V, self.F = _mesh_arg(vertices, faces, validate, what)
         self.device = self.v.device
         L = _m.lib()
-        self.ws_bytes = int(L.mslam_mesh_raycast_workspace_bytes(self.F)) if skip and self.F else 0
+        own = skip and self.F and self.index is None
+        self.ws_bytes = int(L.mslam_mesh_raycast_workspace_bytes(self.F)) if own else 0
         self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.device) if self.ws_bytes else None
         if self.ws_bytes:
             _m.check(L.mslam_mesh_raycast_boxes(_m.ptr(self.v), _m.ptr(self.f), self.F, self.V, _m.ptr(self.ws),
@@ -34,6 +38,14 @@ class _Caster:
         hit = torch.empty(n, dtype=torch.uint8, device=dev)
         fc = torch.empty(n, dtype=torch.int32, device=dev) if face else None
         t = torch.empty(n, dtype=torch.float64, device=dev) if t64 else None
+        if self.index is not None:
+            ix = self.index
+            _m.check(_m.lib().mslam_mesh_raycast_indexed(_m.ptr(rays), h, w, _m.ptr(pose), _m.ptr(self.v),
+                                                         _m.ptr(self.f), self.F, self.V, float(near), float(far),
+                                                         _m.ptr(ix.order), _m.ptr(ix.ws), ix.ws_bytes, 2, 0,
+                                                         _m.ptr(rng), _m.ptr(nrm), _m.ptr(hit), _m.ptr(fc), _m.ptr(t),
+                                                         _m.stream_ptr()), "mesh_raycast_indexed")
+            return rng, nrm, hit, fc, t
         _m.check(_m.lib().mslam_mesh_raycast(_m.ptr(rays), h, w, _m.ptr(pose), _m.ptr(self.v), _m.ptr(self.f), self.F,
                                              self.V, float(near), float(far), 1 if self.ws_bytes else 0,
                                              _m.ptr(self.ws), self.ws_bytes, _m.ptr(rng), _m.ptr(nrm), _m.ptr(hit),
@@ -42,7 +54,7 @@ class _Caster:
 
 
 def render_mesh(mesh, pose, rays=None, K=None, hw=None, near=0.05, far=10.0, skip=True, return_face=False,
-                validate=True):
+                validate=True, index=None):
     """Ray cast of a triangle mesh from a camera -> (range f32[h,w], normals f32[h,w,3], hit bool[h,w]) device tensors,
     the arguments and the tuple of TSDFVolume.render (DESIGN.md "Mesh ray casting").  `mesh`: (vertices f32[V,3], faces
     i32[F,3]) device tensors or an extract_mesh tuple.  `pose`: Sim3 (8,) [t, q, s], world from camera.  Either `rays`
@@ -50,9 +62,11 @@ def render_mesh(mesh, pose, rays=None, K=None, hw=None, near=0.05, far=10.0, ski
     [near, far] (world units) divided by the pose's scale, so range * rays is the camera-frame pointmap; 0 on a miss.
     normals: the hit face's geometric normal, unit, world frame, towards the camera.  `skip=False` scans every face
     (same output, for checks and timing).  `return_face`: a fourth tensor i32[h,w], the face hit, -1 on a miss.
-    `validate`: the index range of the faces (one host read; the kernel skips out-of-range faces either way)."""
+    `validate`: the index range of the faces (one host read; the kernel skips out-of-range faces either way).
+    `index`: None, True or a MeshIndex of the mesh - the cast runs over its Morton-ordered tiles and group boxes, same
+    output bit for bit, for faces in any order (DESIGN.md "Mesh index"); image rays are coherent and are not sorted."""
     vertices, faces = _pair(mesh, "mesh")
-    caster = _Caster(vertices, faces, validate, bool(skip), "render_mesh")
+    caster = _Caster(vertices, faces, validate, bool(skip), "render_mesh", index)
     pose, rays, _ = _render_args(pose, rays, K, hw, near, far, 1.0, 1.0, caster.device)
     h, w = int(rays.shape[0]), int(rays.shape[1])
     rng, nrm, hit, fc, _ = caster.cast(rays, h, w, pose, near, far, face=bool(return_face))
@@ -94,20 +108,29 @@ def compose_sim3(T, poses):
     return torch.cat((T[7] * _rotate(a, p[:, :3]) + T[:3], q, (T[7] * p[:, 7]).unsqueeze(-1)), -1)
 
 
-def observed_points(points, mesh, poses, K, hw, near=0.05, far=10.0, tol=0.01, skip=True, compact_every=4):
+def observed_points(points, mesh, poses, K, hw, near=0.05, far=10.0, tol=0.01, skip=True, compact_every=4, index=None,
+                    sort_queries=True):
     """bool[n] device tensor: which of the points f32[n,3] some pinhole camera sees.  A point p is observed when, for
     one of the `poses` (Sim3s [t, q, s], world from camera, rounded to f32) with origin o, all in f64: its camera-frame
     z > 0; its pixel -0.5 <= u < w - 0.5, -0.5 <= v < h - 0.5 (K (3,3), hw = (h, w), pixel centres at integers); its
     distance near <= r = |p - o| <= far; and the ray from o along the f32 unit direction to p misses `mesh` or first
     hits it at t >= r - tol (world units).  The projection and the field-of-view test are torch ops, the occlusion test
     is the ray-cast kernel on the points in view.  Points already observed leave the working set every `compact_every`
-    views (0: never); a point's answer depends on nothing but the point, so the result does not depend on it."""
+    views (0: never); a point's answer depends on nothing but the point, so the result does not depend on it.
+    `index`: None, True or a MeshIndex of the mesh (DESIGN.md "Mesh index"): the casts run over it, and with
+    `sort_queries` the points are worked through in the order of their Morton keys - the rays of a wave then end at
+    neighbouring points - and the answers scattered back; the same answers."""
     points = _points_arg(points, "points", "observed_points")
     vertices, faces = _pair(mesh, "mesh")
-    caster = _Caster(vertices, faces, True, bool(skip), "observed_points")
+    caster = _Caster(vertices, faces, True, bool(skip), "observed_points", index)
     dev = points.device
     if caster.device != dev:
         raise ValueError("observed_points: points and mesh are on different devices")
+    if caster.index is not None and sort_queries and points.shape[0] > 1:
+        perm = caster.index.query_order(points)
+        seen = observed_points(points[perm].contiguous(), mesh, poses, K, hw, near, far, tol, skip, compact_every,
+                               caster.index, False)
+        return torch.empty_like(seen).index_copy_(0, perm, seen)
     poses = _poses_arg(poses, "observed_points").to(torch.float32)
     Kd = torch.as_tensor(np.asarray(torch.as_tensor(K).detach().cpu(), np.float64)).reshape(3, 3).tolist()
     h, w = (int(x) for x in hw)
