@@ -346,15 +346,11 @@ extern "C" int mslam_mesh_align_init(const float* T0, const float* vertices, con
   MSLAM_REQUIRE(state, "mesh_align_init: null pointer");
   MSLAM_REQUIRE(num_faces == 0 || (faces && workspace && (vertices || num_vertices == 0)),
                 "mesh_align_init: null pointer");
-  if (workspace_bytes < md_box_bytes(num_faces)) {
-    set_error("mesh_align_init: workspace of %zu bytes, %zu needed", workspace_bytes, md_box_bytes(num_faces));
-    return MSLAM_ENOMEM;
-  }
+  if (workspace_bytes < md_box_bytes(num_faces))
+    return md_too_small("mesh_align_init", "workspace", workspace_bytes, md_box_bytes(num_faces));
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(ma_init_kernel, dim3(1), dim3(kWave), 0, s, T0, (double*)state);
-  if (num_faces > 0)
-    hipLaunchKernelGGL(md_box_kernel, dim3(blocks_for(num_faces, kMdTile)), dim3(kWave), 0, s, vertices, faces,
-                       num_faces, num_vertices, (const int32_t*)nullptr, (double*)workspace);
+  if (num_faces > 0) md_launch_boxes(vertices, faces, num_faces, num_vertices, nullptr, (double*)workspace, s);
   MSLAM_LAUNCH_CHECK("mesh_align_init");
   return MSLAM_OK;
 }
@@ -368,14 +364,9 @@ static int ma_step(const char* what, const float* src, int n, const float* verti
   const bool indexed = order != nullptr;
   const size_t box_bytes = indexed ? 0 : md_box_bytes(num_faces), part_bytes = ma_partial_bytes(n);
   const size_t need = box_bytes + part_bytes + (count_skips ? md_count_bytes(n) : 0);
-  if (workspace_bytes < need) {
-    set_error("%s: workspace of %zu bytes, %zu needed", what, workspace_bytes, need);
-    return MSLAM_ENOMEM;
-  }
-  if (indexed && index_bytes < md_index_bytes(num_faces)) {
-    set_error("%s: index of %zu bytes, %zu needed", what, index_bytes, md_index_bytes(num_faces));
-    return MSLAM_ENOMEM;
-  }
+  if (workspace_bytes < need) return md_too_small(what, "workspace", workspace_bytes, need);
+  if (indexed && index_bytes < md_index_bytes(num_faces))
+    return md_too_small(what, "index", index_bytes, md_index_bytes(num_faces));
   hipStream_t s = (hipStream_t)stream;
   const unsigned nblocks = blocks_for(n, kMdBlock);
   double* partial = (double*)((char*)workspace + box_bytes);
@@ -392,7 +383,7 @@ static int ma_step(const char* what, const float* src, int n, const float* verti
                        closest, partial);
   hipLaunchKernelGGL(ma_solve_kernel, dim3(1), dim3(kWave), 0, s, (const double*)partial, (int)nblocks, src,
                      (const float*)nullptr, n, with_scale, (double*)state, log_row);
-  return MSLAM_OK;
+  return md_launched(what);
 }
 
 extern "C" int mslam_mesh_align_step(const float* src, int n, const float* vertices, const int32_t* faces,
@@ -405,12 +396,9 @@ extern "C" int mslam_mesh_align_step(const float* src, int n, const float* verti
   MSLAM_REQUIRE(n == 0 || (src && nearest && moved && dist2 && workspace), "mesh_align_step: null pointer");
   MSLAM_REQUIRE(num_faces == 0 || (faces && workspace && (vertices || num_vertices == 0)),
                 "mesh_align_step: null pointer");
-  const int rc = ma_step("mesh_align_step", src, n, vertices, faces, num_faces, num_vertices, nullptr, nullptr, 0, trim,
-                         with_scale, count_skips, workspace, workspace_bytes, state, nearest, moved, dist2, closest,
-                         log_row, stream);
-  if (rc) return rc;
-  MSLAM_LAUNCH_CHECK("mesh_align_step");
-  return MSLAM_OK;
+  return ma_step("mesh_align_step", src, n, vertices, faces, num_faces, num_vertices, nullptr, nullptr, 0, trim,
+                 with_scale, count_skips, workspace, workspace_bytes, state, nearest, moved, dist2, closest, log_row,
+                 stream);
 }
 
 extern "C" int mslam_mesh_align_init_indexed(const float* T0, void* state, void* stream) {
@@ -432,12 +420,9 @@ extern "C" int mslam_mesh_align_step_indexed(const float* src, int n, const floa
   MSLAM_REQUIRE(n == 0 || (src && nearest && moved && dist2 && workspace), "mesh_align_step_indexed: null pointer");
   MSLAM_REQUIRE(num_faces == 0 || (faces && index && (vertices || num_vertices == 0)),
                 "mesh_align_step_indexed: null pointer");
-  const int rc = ma_step("mesh_align_step_indexed", src, n, vertices, faces, num_faces, num_vertices, order, index,
-                         index_bytes, trim, with_scale, count_skips, workspace, workspace_bytes, state, nearest, moved,
-                         dist2, closest, log_row, stream);
-  if (rc) return rc;
-  MSLAM_LAUNCH_CHECK("mesh_align_step_indexed");
-  return MSLAM_OK;
+  return ma_step("mesh_align_step_indexed", src, n, vertices, faces, num_faces, num_vertices, order, index,
+                 index_bytes, trim, with_scale, count_skips, workspace, workspace_bytes, state, nearest, moved, dist2,
+                 closest, log_row, stream);
 }
 
 extern "C" int mslam_mesh_align_fit_pairs(const float* src, const float* dst, const float* weights, int n,
@@ -447,10 +432,7 @@ extern "C" int mslam_mesh_align_fit_pairs(const float* src, const float* dst, co
   MSLAM_REQUIRE(state && log_row, "mesh_align_fit_pairs: null pointer");
   MSLAM_REQUIRE(n == 0 || (src && dst && workspace), "mesh_align_fit_pairs: null pointer");
   const size_t need = ma_partial_bytes(n);
-  if (workspace_bytes < need) {
-    set_error("mesh_align_fit_pairs: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-    return MSLAM_ENOMEM;
-  }
+  if (workspace_bytes < need) return md_too_small("mesh_align_fit_pairs", "workspace", workspace_bytes, need);
   hipStream_t s = (hipStream_t)stream;
   const unsigned nblocks = blocks_for(n, kMdBlock);
   hipLaunchKernelGGL(ma_init_kernel, dim3(1), dim3(kWave), 0, s, (const float*)nullptr, (double*)state);

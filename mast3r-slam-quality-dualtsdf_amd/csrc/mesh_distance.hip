@@ -122,6 +122,40 @@ extern "C" size_t mslam_mesh_distance_workspace_bytes(int num_faces) {
   return num_faces > 0 ? md_box_bytes(num_faces) : 0;
 }
 
+// Both distance queries after their argument checks.  Plain: `skip` 1 or 2 builds the boxes at the head of the
+// workspace and culls by them, 2 also counts behind them.  `indexed`: the tiles follow `order`, the boxes are the
+// index's, its groups are used at `levels` 2, and `skip_counts` (may be null) receives the per-wave counts.
+static int md_distance_impl(const char* what, bool indexed, const float* points, int n, const float* vertices,
+                            const int32_t* faces, int num_faces, int num_vertices, int skip, void* workspace,
+                            size_t workspace_bytes, const int32_t* order, const void* index, size_t index_bytes,
+                            int levels, int32_t* skip_counts, double* dist2, int32_t* nearest, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  int cull = num_faces > 0 && (indexed || skip);
+  const double* box = (const double*)(indexed ? index : workspace);
+  if (indexed) {
+    if (index_bytes < md_index_bytes(num_faces))
+      return md_too_small(what, "index", index_bytes, md_index_bytes(num_faces));
+  } else if (cull) {
+    const size_t box_bytes = md_box_bytes(num_faces), count_bytes = skip == 2 ? md_count_bytes(n) : 0;
+    if (workspace_bytes < box_bytes + count_bytes)
+      return md_too_small(what, "workspace", workspace_bytes, box_bytes + count_bytes);
+    md_launch_boxes(vertices, faces, num_faces, num_vertices, nullptr, (double*)workspace, s);
+    if (count_bytes) skip_counts = (int32_t*)((char*)workspace + box_bytes);
+    if (num_faces <= kMdTile) {                  // one tile: it is scanned whatever its box says, so scan it once
+      if (count_bytes) {
+        int rc = check_hip(hipMemsetAsync(skip_counts, 0, count_bytes, s), "mesh_distance memset");
+        if (rc) return rc;
+      }
+      cull = 0, skip_counts = nullptr;
+    }
+  }
+  const double* gbox = indexed && levels == 2 && num_faces > 0 ? md_index_gbox(index, num_faces) : nullptr;
+  hipLaunchKernelGGL(indexed ? md_distance_kernel<true> : md_distance_kernel<false>, dim3(blocks_for(n, kMdBlock)),
+                     dim3(kMdBlock), 0, s, points, n, vertices, faces, num_faces, num_vertices, cull, box, order, gbox,
+                     skip_counts, dist2, nearest);
+  return md_launched(what);
+}
+
 extern "C" int mslam_mesh_distance(const float* points, int n, const float* vertices, const int32_t* faces,
                                    int num_faces, int num_vertices, int skip, void* workspace, size_t workspace_bytes,
                                    double* dist2, int32_t* nearest, void* stream) {
@@ -130,34 +164,9 @@ extern "C" int mslam_mesh_distance(const float* points, int n, const float* vert
   if (n == 0) return MSLAM_OK;
   MSLAM_REQUIRE(points && dist2 && nearest, "mesh_distance: null pointer");
   MSLAM_REQUIRE(num_faces == 0 || (faces && (vertices || num_vertices == 0)), "mesh_distance: null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  const unsigned nblocks = blocks_for(n, kMdBlock);
-  if (num_faces == 0) skip = 0;
-  const size_t box_bytes = md_box_bytes(num_faces);
-  int32_t* skipped = nullptr;
-  if (skip) {
-    const size_t count_bytes = skip == 2 ? md_count_bytes(n) : 0;
-    MSLAM_REQUIRE(workspace, "mesh_distance: the culled scan needs a workspace");
-    if (workspace_bytes < box_bytes + count_bytes) {
-      set_error("mesh_distance: workspace of %zu bytes, %zu needed", workspace_bytes, box_bytes + count_bytes);
-      return MSLAM_ENOMEM;
-    }
-    hipLaunchKernelGGL(md_box_kernel, dim3(blocks_for(num_faces, kMdTile)), dim3(kWave), 0, s, vertices, faces,
-                       num_faces, num_vertices, (const int32_t*)nullptr, (double*)workspace);
-    if (num_faces <= kMdTile) {                  // one tile: it is scanned whatever its box says, so scan it once
-      if (count_bytes) {
-        int rc = check_hip(hipMemsetAsync((char*)workspace + box_bytes, 0, count_bytes, s), "mesh_distance memset");
-        if (rc) return rc;
-      }
-      skip = 0;
-    }
-    if (skip == 2) skipped = (int32_t*)((char*)workspace + box_bytes);
-  }
-  hipLaunchKernelGGL(md_distance_kernel<false>, dim3(nblocks), dim3(kMdBlock), 0, s, points, n, vertices, faces,
-                     num_faces, num_vertices, skip ? 1 : 0, (const double*)workspace, (const int32_t*)nullptr,
-                     (const double*)nullptr, skipped, dist2, nearest);
-  MSLAM_LAUNCH_CHECK("mesh_distance");
-  return MSLAM_OK;
+  MSLAM_REQUIRE(!skip || num_faces == 0 || workspace, "mesh_distance: the culled scan needs a workspace");
+  return md_distance_impl("mesh_distance", false, points, n, vertices, faces, num_faces, num_vertices, skip,
+                          workspace, workspace_bytes, nullptr, nullptr, 0, 0, nullptr, dist2, nearest, stream);
 }
 
 extern "C" int mslam_mesh_distance_indexed(const float* points, int n, const float* vertices, const int32_t* faces,
@@ -170,14 +179,6 @@ extern "C" int mslam_mesh_distance_indexed(const float* points, int n, const flo
   MSLAM_REQUIRE(points && dist2 && nearest, "mesh_distance_indexed: null pointer");
   MSLAM_REQUIRE(num_faces == 0 || (faces && order && index && (vertices || num_vertices == 0)),
                 "mesh_distance_indexed: null pointer");
-  if (index_bytes < md_index_bytes(num_faces)) {
-    set_error("mesh_distance_indexed: index of %zu bytes, %zu needed", index_bytes, md_index_bytes(num_faces));
-    return MSLAM_ENOMEM;
-  }
-  hipLaunchKernelGGL(md_distance_kernel<true>, dim3(blocks_for(n, kMdBlock)), dim3(kMdBlock), 0, (hipStream_t)stream,
-                     points, n, vertices, faces, num_faces, num_vertices, num_faces > 0 ? 1 : 0, (const double*)index,
-                     order, levels == 2 && num_faces > 0 ? md_index_gbox(index, num_faces) : (const double*)nullptr,
-                     skip_counts, dist2, nearest);
-  MSLAM_LAUNCH_CHECK("mesh_distance_indexed");
-  return MSLAM_OK;
+  return md_distance_impl("mesh_distance_indexed", true, points, n, vertices, faces, num_faces, num_vertices, 0,
+                          nullptr, 0, order, index, index_bytes, levels, skip_counts, dist2, nearest, stream);
 }

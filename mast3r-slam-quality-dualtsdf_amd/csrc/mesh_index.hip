@@ -112,15 +112,12 @@ extern "C" int mslam_mesh_index_boxes(const float* vertices, const int32_t* face
   MSLAM_REQUIRE(num_faces >= 0 && num_vertices >= 0, "mesh_index_boxes: negative size");
   if (num_faces == 0) return MSLAM_OK;
   MSLAM_REQUIRE(faces && order && workspace && (vertices || num_vertices == 0), "mesh_index_boxes: null pointer");
-  if (workspace_bytes < md_index_bytes(num_faces)) {
-    set_error("mesh_index_boxes: workspace of %zu bytes, %zu needed", workspace_bytes, md_index_bytes(num_faces));
-    return MSLAM_ENOMEM;
-  }
+  if (workspace_bytes < md_index_bytes(num_faces))
+    return md_too_small("mesh_index_boxes", "workspace", workspace_bytes, md_index_bytes(num_faces));
   hipStream_t s = (hipStream_t)stream;
   const int ntiles = (int)blocks_for(num_faces, kMdTile), ngroups = md_groups(num_faces);
   double* box = (double*)workspace;
-  hipLaunchKernelGGL(md_box_kernel, dim3(ntiles), dim3(kWave), 0, s, vertices, faces, num_faces, num_vertices, order,
-                     box);
+  md_launch_boxes(vertices, faces, num_faces, num_vertices, order, box, s);
   hipLaunchKernelGGL(mi_group_kernel, dim3(blocks_for(6 * ngroups, 256)), dim3(256), 0, s, (const double*)box, ntiles,
                      ngroups, box + 6 * (size_t)ntiles);
   MSLAM_LAUNCH_CHECK("mesh_index_boxes");

@@ -259,14 +259,29 @@ extern "C" int mslam_mesh_raycast_boxes(const float* vertices, const int32_t* fa
   MSLAM_REQUIRE(num_faces >= 0 && num_vertices >= 0, "mesh_raycast_boxes: negative size");
   if (num_faces == 0) return MSLAM_OK;
   MSLAM_REQUIRE(faces && workspace && (vertices || num_vertices == 0), "mesh_raycast_boxes: null pointer");
-  if (workspace_bytes < md_box_bytes(num_faces)) {
-    set_error("mesh_raycast_boxes: workspace of %zu bytes, %zu needed", workspace_bytes, md_box_bytes(num_faces));
-    return MSLAM_ENOMEM;
-  }
-  hipLaunchKernelGGL(md_box_kernel, dim3(blocks_for(num_faces, kMdTile)), dim3(kWave), 0, (hipStream_t)stream,
-                     vertices, faces, num_faces, num_vertices, (const int32_t*)nullptr, (double*)workspace);
+  if (workspace_bytes < md_box_bytes(num_faces))
+    return md_too_small("mesh_raycast_boxes", "workspace", workspace_bytes, md_box_bytes(num_faces));
+  md_launch_boxes(vertices, faces, num_faces, num_vertices, nullptr, (double*)workspace, (hipStream_t)stream);
   MSLAM_LAUNCH_CHECK("mesh_raycast_boxes");
   return MSLAM_OK;
+}
+
+// Both casts after their argument checks.  Plain: culled (`cull`) by the boxes `box` of mslam_mesh_raycast_boxes.
+// `indexed`: the tiles follow `order`, `box` is a mesh index, its groups are used at `levels` 2, and `skip_counts` (may
+// be null) receives the per-wave counts.
+static int rc_cast_impl(const char* what, bool indexed, const float* rays, int h, int w, const float* pose8,
+                        const float* vertices, const int32_t* faces, int num_faces, int num_vertices, double near,
+                        double far, int cull, const void* box, size_t box_bytes, const int32_t* order, int levels,
+                        int32_t* skip_counts, float* range, float* normal, uint8_t* hit, int32_t* face, double* t64,
+                        void* stream) {
+  const size_t need = indexed ? md_index_bytes(num_faces) : md_box_bytes(num_faces);
+  if ((indexed || cull) && box_bytes < need)
+    return md_too_small(what, indexed ? "index" : "workspace", box_bytes, need);
+  const double* gbox = indexed && levels == 2 && num_faces > 0 ? md_index_gbox(box, num_faces) : nullptr;
+  hipLaunchKernelGGL(indexed ? rc_kernel<true> : rc_kernel<false>, rc_grid(h, w), dim3(kMdBlock), 0,
+                     (hipStream_t)stream, rays, h, w, pose8, vertices, faces, num_faces, num_vertices, near, far, cull,
+                     (const double*)box, order, gbox, skip_counts, range, normal, hit, face, t64);
+  return md_launched(what);
 }
 
 extern "C" int mslam_mesh_raycast(const float* rays, int h, int w, const float* pose8, const float* vertices,
@@ -279,19 +294,10 @@ extern "C" int mslam_mesh_raycast(const float* rays, int h, int w, const float* 
   if (h == 0 || w == 0) return MSLAM_OK;
   MSLAM_REQUIRE(rays && pose8 && range && normal && hit, "mesh_raycast: null pointer");
   MSLAM_REQUIRE(num_faces == 0 || (faces && (vertices || num_vertices == 0)), "mesh_raycast: null pointer");
-  if (num_faces == 0) skip = 0;
-  if (skip) {
-    MSLAM_REQUIRE(workspace, "mesh_raycast: the culled scan needs the workspace of mesh_raycast_boxes");
-    if (workspace_bytes < md_box_bytes(num_faces)) {
-      set_error("mesh_raycast: workspace of %zu bytes, %zu needed", workspace_bytes, md_box_bytes(num_faces));
-      return MSLAM_ENOMEM;
-    }
-  }
-  hipLaunchKernelGGL(rc_kernel<false>, rc_grid(h, w), dim3(kMdBlock), 0, (hipStream_t)stream, rays, h, w, pose8,
-                     vertices, faces, num_faces, num_vertices, near, far, skip ? 1 : 0, (const double*)workspace,
-                     (const int32_t*)nullptr, (const double*)nullptr, (int32_t*)nullptr, range, normal, hit, face, t64);
-  MSLAM_LAUNCH_CHECK("mesh_raycast");
-  return MSLAM_OK;
+  const int cull = skip && num_faces > 0;
+  MSLAM_REQUIRE(!cull || workspace, "mesh_raycast: the culled scan needs the workspace of mesh_raycast_boxes");
+  return rc_cast_impl("mesh_raycast", false, rays, h, w, pose8, vertices, faces, num_faces, num_vertices, near, far,
+                      cull, workspace, workspace_bytes, nullptr, 0, nullptr, range, normal, hit, face, t64, stream);
 }
 
 extern "C" int mslam_mesh_raycast_blocks(int h, int w) {
@@ -313,14 +319,7 @@ extern "C" int mslam_mesh_raycast_indexed(const float* rays, int h, int w, const
   MSLAM_REQUIRE(rays && pose8 && range && normal && hit, "mesh_raycast_indexed: null pointer");
   MSLAM_REQUIRE(num_faces == 0 || (faces && order && index && (vertices || num_vertices == 0)),
                 "mesh_raycast_indexed: null pointer");
-  if (index_bytes < md_index_bytes(num_faces)) {
-    set_error("mesh_raycast_indexed: index of %zu bytes, %zu needed", index_bytes, md_index_bytes(num_faces));
-    return MSLAM_ENOMEM;
-  }
-  hipLaunchKernelGGL(rc_kernel<true>, rc_grid(h, w), dim3(kMdBlock), 0, (hipStream_t)stream, rays, h, w, pose8,
-                     vertices, faces, num_faces, num_vertices, near, far, num_faces > 0 ? 1 : 0, (const double*)index,
-                     order, levels == 2 && num_faces > 0 ? md_index_gbox(index, num_faces) : (const double*)nullptr,
-                     skip_counts, range, normal, hit, face, t64);
-  MSLAM_LAUNCH_CHECK("mesh_raycast_indexed");
-  return MSLAM_OK;
+  return rc_cast_impl("mesh_raycast_indexed", true, rays, h, w, pose8, vertices, faces, num_faces, num_vertices, near,
+                      far, num_faces > 0, index, index_bytes, order, levels, skip_counts, range, normal, hit, face,
+                      t64, stream);
 }

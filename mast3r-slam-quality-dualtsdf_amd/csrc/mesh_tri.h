@@ -329,4 +329,24 @@ inline const double* md_index_gbox(const void* index, int nf) {
   return (const double*)((const char*)index + md_box_bytes(nf));
 }
 
+// The boxes of the tiles of nf > 0 faces -> box; `order` null: the tiles of the caller's face order
+inline void md_launch_boxes(const float* vert, const int32_t* faces, int nf, int nv, const int32_t* order, double* box,
+                            hipStream_t stream) {
+  hipLaunchKernelGGL(md_box_kernel, dim3(blocks_for(nf, kMdTile)), dim3(kWave), 0, stream, vert, faces, nf, nv, order,
+                     box);
+}
+
+// The error of entry point `what` whose `thing` ("workspace", "index") is too small
+inline int md_too_small(const char* what, const char* thing, size_t have, size_t need) {
+  set_error("%s: %s of %zu bytes, %zu needed", what, thing, have, need);
+  return MSLAM_ENOMEM;
+}
+
+// MSLAM_LAUNCH_CHECK for an entry point whose name is known at run time: the status to return after the launches
+inline int md_launched(const char* what) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) set_error("%s launch: %s", what, hipGetErrorString(e));
+  return e == hipSuccess ? MSLAM_OK : MSLAM_EHIP;
+}
+
 }  // namespace mslam

@@ -16,7 +16,7 @@ import color_numpy as C  # noqa: E402
 import render_numpy as R  # noqa: E402
 from test_color_writers_cpu import read_ply  # noqa: E402
 from test_slam_system_gpu import H, W, RoomModel  # noqa: E402
-from test_tsdf_color_gpu import color_checks  # noqa: E402
+from mesh_support import color_checks  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 

@@ -17,7 +17,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import cc_numpy as C  # noqa: E402
 import mc_numpy as M  # noqa: E402
-from test_tsdf_mesh_gpu import VS, _host, _room, _same, _vol  # noqa: E402
+from mesh_support import VS, _host, _room, _same, _vol  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 

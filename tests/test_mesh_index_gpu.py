@@ -19,15 +19,11 @@ import mc_numpy as M  # noqa: E402
 import meshdist_numpy as D  # noqa: E402
 import meshindex_numpy as X  # noqa: E402
 from test_mesh_index_cpu import fan_trap, random_mesh, ray_trap, shuffled, subdivide  # noqa: E402
-from test_mesh_metrics_gpu import _raw_distance  # noqa: E402
-from test_mesh_raycast_gpu import Guarded, _raw_cast, _same_bytes  # noqa: E402
-from test_tsdf_mesh_gpu import VS, _host  # noqa: E402
+from mesh_support import (BLOCK, G, T, VS, Operands, _build, _host, _indexed_cast, _raw_cast,  # noqa: E402
+                          _raw_distance, _same_bytes)
 
 pytestmark = pytest.mark.gpu
 
-T = 128            # kMdTile of csrc/mesh_tri.h: faces per tile and per box
-G = 32             # kMdGroup: tiles per group box
-BLOCK = 256        # points or rays per block
 # one face; one short of a tile, a tile, one more; one short of a group of 32 tiles, a group, one face more; a group and
 # a tile and a face
 SIZES_F = (1, T - 1, T, T + 1, T * G - 1, T * G, T * G + 1, T * G + T + 1)
@@ -35,62 +31,6 @@ SIZES_N = (1, 63, 64, 65, 257)
 NEAR, FAR = 0.0, 10.0
 POSE = np.concatenate([[0.45, 0.55, 0.5], synthetic.quat_from_rotvec(np.array([0.3, 0.5, -0.2])),
                        [1.3]]).astype(np.float32)
-CAST_KEYS = ("range", "normal", "hit", "face", "t64")
-
-
-class Operands:
-    """Device copies of the inputs and the outputs of one call, each inside a guarded allocation."""
-
-    def __init__(self, device):
-        self.device, self.all, self.outputs = device, [], []
-
-    def put(self, a, dtype):
-        a = np.ascontiguousarray(a, dtype)
-        g = Guarded(self.device, torch.from_numpy(a).dtype, a.shape)
-        g.t.copy_(torch.from_numpy(a))
-        self.all.append(g)
-        return g.t
-
-    def out(self, dtype, shape):
-        g = Guarded(self.device, dtype, shape)
-        self.all.append(g)
-        self.outputs.append(g)
-        return g.t
-
-    def check(self):
-        assert all(g.guards_ok() for g in self.all)
-        assert all(g.written() for g in self.outputs if g.size)
-
-
-def _build(device, V, F, order=None):
-    """mslam_mesh_index_keys, a stable torch.sort and mslam_mesh_index_boxes through the C entry points -> dict with
-    the device operands (v, f, order, ws) and numpy copies of keys, order, tile and group boxes.  `order`: put this one
-    in the place of the sorted one."""
-    import mslam_hip as _m
-
-    L, st = _m.lib(), _m.stream_ptr()
-    ops = Operands(device)
-    V, F = np.reshape(V, (-1, 3)), np.reshape(F, (-1, 3))
-    nv, nf = len(V), len(F)
-    v, f = ops.put(V, np.float32), ops.put(F, np.int32)
-    bnd = ops.put(X.bounds(V), np.float32)
-    if nv:
-        assert torch.equal(bnd, torch.cat((v.amin(0), v.amax(0))))
-    keys = ops.out(torch.int64, (nf,))
-    _m.check(L.mslam_mesh_index_keys(_m.ptr(v), nv, _m.ptr(f), nf, _m.ptr(bnd), _m.ptr(keys), st), "mesh_index_keys")
-    srt = torch.sort(keys, stable=True)[1].to(torch.int32).cpu().numpy() if order is None else order
-    o = ops.put(srt, np.int32)
-    ntiles = (nf + T - 1) // T
-    ngroups = (ntiles + G - 1) // G
-    need = int(L.mslam_mesh_index_bytes(nf))
-    assert need == 48 * (ntiles + ngroups)
-    ws = ops.out(torch.float64, (need // 8,)).view(torch.uint8)
-    _m.check(L.mslam_mesh_index_boxes(_m.ptr(v), _m.ptr(f), nf, nv, _m.ptr(o), _m.ptr(ws), ws.numel(), st),
-             "mesh_index_boxes")
-    ops.check()
-    box = ws[:need].cpu().numpy().view(np.float64).reshape(-1, 6)
-    return dict(ops=ops, V=V, F=F, v=v, f=f, nv=nv, nf=nf, o=o, ws=ws, bnd=bnd, keys=keys.cpu().numpy(), order=srt,
-                tile=box[:ntiles], group=box[ntiles:])
 
 
 def _share(counts, waves, nf):
@@ -121,26 +61,8 @@ def _distance(device, ix, P, levels=2):
 
 def _cast(device, ix, rays, h, w, pose, levels=2, near=NEAR, far=FAR):
     """mslam_mesh_raycast_indexed -> (dict of numpy arrays as _raw_cast, share skipped); guards checked."""
-    import mslam_hip as _m
-
-    L = _m.lib()
-    ops = Operands(device)
-    n = h * w
-    r, p = ops.put(np.reshape(rays, (-1, 3)), np.float32), ops.put(pose, np.float32)
-    shapes = dict(range=(torch.float32, (n,)), normal=(torch.float32, (n, 3)), hit=(torch.uint8, (n,)),
-                  face=(torch.int32, (n,)), t64=(torch.float64, (n,)))
-    out = {k: ops.out(*shapes[k]) for k in CAST_KEYS}
-    blocks = int(L.mslam_mesh_raycast_blocks(h, w))
-    assert blocks == ((n + BLOCK - 1) // BLOCK if h == 1 else ((w + 15) // 16) * ((h + 15) // 16))
-    counts = ops.out(torch.int32, (4 * blocks,))
-    _m.check(L.mslam_mesh_raycast_indexed(_m.ptr(r), h, w, _m.ptr(p), _m.ptr(ix["v"]), _m.ptr(ix["f"]), ix["nf"],
-                                          ix["nv"], near, far, _m.ptr(ix["o"]), _m.ptr(ix["ws"]), ix["ws"].numel(),
-                                          levels, _m.ptr(counts), *(_m.ptr(out[k]) for k in CAST_KEYS),
-                                          _m.stream_ptr()), "mesh_raycast_indexed")
-    ops.check()
-    ix["ops"].check()
-    share = _share(counts, 4 * blocks if h > 1 else (n + 63) // 64, ix["nf"])
-    return {k: t.cpu().numpy() for k, t in out.items()}, share
+    out, counts = _indexed_cast(device, ix, rays, h, w, pose, levels, near, far)
+    return out, _share(counts, len(counts) if h > 1 else (h * w + 63) // 64, ix["nf"])
 
 
 def _same_distance(a, b):

@@ -19,43 +19,14 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import mc_numpy as M  # noqa: E402
 import meshdist_numpy as D  # noqa: E402
 from test_mesh_metrics_cpu import tie_share  # noqa: E402
-from test_tsdf_mesh_gpu import VS, _host, _room, _vol  # noqa: E402
+from kernel_refs import Guarded, check_guards  # noqa: E402
+from mesh_support import BLOCK, T, VS, _dev, _host, _raw_distance, _room, _vol  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-T = 128            # kMdTile of csrc/mesh_distance.hip: triangles per LDS tile and per box
-BLOCK = 256        # kMdBlock: points per block
 REL = 1e-12
 TILE_F = (1, T - 1, T, T + 1, 4 * T + 1)
 TILE_N = (1, BLOCK - 1, BLOCK, BLOCK + 1)
-
-
-def _dev(device, a, dtype):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype)).to(device)
-
-
-def _raw_distance(device, P, V, F, skip):
-    """mslam_mesh_distance through the C entry point -> (dist2, nearest, share of (wave, tile) scans skipped)."""
-    import mslam_hip as _m
-
-    L = _m.lib()
-    p, v, f = _dev(device, P, np.float32), _dev(device, V, np.float32), _dev(device, F, np.int32)
-    n, nf = len(P), len(F)
-    d2 = torch.empty(n, dtype=torch.float64, device=device)
-    nearest = torch.empty(n, dtype=torch.int32, device=device)
-    nblk = (n + BLOCK - 1) // BLOCK
-    box = int(L.mslam_mesh_distance_workspace_bytes(nf))
-    assert box == 48 * ((nf + T - 1) // T)
-    ws = torch.zeros(box + 16 * nblk, dtype=torch.uint8, device=device) if skip else None
-    _m.check(L.mslam_mesh_distance(_m.ptr(p), n, _m.ptr(v), _m.ptr(f), nf, len(V), 2 if skip else 0, _m.ptr(ws),
-                                   ws.numel() if skip else 0, _m.ptr(d2), _m.ptr(nearest), _m.stream_ptr()),
-             "mesh_distance")
-    share = 0.0
-    if skip and nf:
-        waves = (n + 63) // 64                    # the waves that hold a point
-        counts = ws[box:].view(torch.int32).cpu().numpy().reshape(nblk, 4).reshape(-1)[:waves]
-        share = float(counts.sum()) / (waves * ((nf + T - 1) // T))
-    return d2.cpu().numpy(), nearest.cpu().numpy(), share
 
 
 @functools.lru_cache(maxsize=None)
@@ -169,28 +140,6 @@ def test_sphere_culled_equals_plain(device):
 # ----------------------------------------------------------------------------------------------------------------------
 # guarded buffers: nothing is written in front of or behind dist2, nearest, points and face
 # ----------------------------------------------------------------------------------------------------------------------
-_PAT = {torch.float64: (torch.int64, 0x7FF8A5A55A5A1234), torch.int32: (torch.int32, 0x7FD5A5A5),
-        torch.float32: (torch.int32, 0x7FD5A5A5)}
-GUARD_BYTES = 4096
-
-
-class Guarded:
-    """The pattern of tests/kernel_refs.py Guarded for the dtypes of these kernels: an output tensor inside a larger
-    allocation filled with a NaN bit pattern (for i32: a value no kernel here writes)."""
-
-    def __init__(self, device, dtype, shape):
-        view, self.pat = _PAT[dtype]
-        self.n = int(np.prod(shape))
-        self.g = GUARD_BYTES // torch.empty((), dtype=dtype).element_size()
-        self.raw = torch.full((self.n + 2 * self.g,), self.pat, dtype=view, device=device)
-        self.t = self.raw[self.g:self.g + self.n].view(dtype).view(shape)
-
-    def ok(self):
-        front, back = self.raw[:self.g], self.raw[self.g + self.n:]
-        return bool(((front == self.pat).all() & (back == self.pat).all() &
-                     (self.raw[self.g:self.g + self.n] != self.pat).all()).item())
-
-
 @pytest.mark.parametrize("n", [1, BLOCK + 1])
 def test_guarded_buffers(device, n):
     import mslam_hip as _m
@@ -204,17 +153,16 @@ def test_guarded_buffers(device, n):
     pts, face = Guarded(device, torch.float32, (n, 3)), Guarded(device, torch.int32, (n,))
     _m.check(L.mslam_mesh_sample(_m.ptr(v), _m.ptr(f), len(F), len(V), _m.ptr(cdf), float(cdf[-1]), n, 7,
                                  _m.ptr(pts.t), _m.ptr(face.t), st), "mesh_sample")
-    assert area.ok() and pts.ok() and face.ok()
+    inputs = dict(area=area, pts=pts, face=face)
+    check_guards(inputs, list(inputs), "mesh_face_areas, mesh_sample")
     wb = int(L.mslam_mesh_distance_workspace_bytes(len(F)))
     for skip in (0, 1):
         d2, near = Guarded(device, torch.float64, (n,)), Guarded(device, torch.int32, (n,))
         ws = Guarded(device, torch.float64, (wb // 8,))
         _m.check(L.mslam_mesh_distance(_m.ptr(pts.t), n, _m.ptr(v), _m.ptr(f), len(F), len(V), skip, _m.ptr(ws.t), wb,
                                        _m.ptr(d2.t), _m.ptr(near.t), st), "mesh_distance")
-        assert d2.ok() and near.ok() and pts.ok() and face.ok(), skip
-        front, back = ws.raw[:ws.g], ws.raw[ws.g + ws.n:]
-        assert bool((front == ws.pat).all()) and bool((back == ws.pat).all())
-        assert bool((ws.raw[ws.g:ws.g + ws.n] != ws.pat).all()) == bool(skip)        # skip = 0 leaves the workspace alone
+        check_guards(dict(d2=d2, near=near, pts=pts, face=face, ws=ws), ("d2", "near", "pts", "face"), f"skip={skip}")
+        assert bool(ws.all_written()) == bool(skip)                      # skip = 0 leaves the workspace alone
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -2,7 +2,8 @@
 mast3r_slam.tsdf.render_mesh / observed_points / compare_meshes(observed=...) and SlamSystem.evaluate_mesh(observed=True)
 / evaluate_depth: parity with the numpy statement (tests/raycast_numpy.py) at the kernel's tile edges - face, hit and t64
 exactly, range and normal as its f32 roundings - culled against plain scan byte for byte, the room against
-synthetic.ray_box_depth, guarded buffers, invalid faces, refused arguments, the observed mask, and the product path."""
+synthetic.ray_box_depth, guarded buffers, waves without a casting ray, invalid faces, refused arguments, the observed
+mask, and the product path."""
 import functools
 import os
 import sys
@@ -18,80 +19,19 @@ import mc_numpy as M  # noqa: E402
 import meshdist_numpy as D  # noqa: E402
 import raycast_numpy as R  # noqa: E402
 from test_mesh_raycast_cpu import occluder_scene, t_bound  # noqa: E402
-from test_tsdf_mesh_gpu import VS, _host  # noqa: E402
+from mesh_support import (CAST_KEYS, FAR, NEAR, G, T, VS, _build, _dev, _host, _indexed_cast,  # noqa: E402
+                          _raw_cast, _same_bytes)
 
 pytestmark = pytest.mark.gpu
 
-T = 128            # kMdTile of csrc/mesh_tri.h: triangles per LDS tile and per box
-BLOCK = 256        # rays per block
-NEAR, FAR = 0.05, 10.0
 POSE = np.concatenate([[0.1, -0.2, 0.05], synthetic.quat_from_rotvec(np.array([0.3, 0.5, -0.2])),
                        [1.7]]).astype(np.float32)
 BACK = np.array([0.2, 0.1, -0.1, 0, 1, 0, 0, 1], np.float32)       # a half turn about y: the camera looks along -z
-KEYS = ("range", "normal", "hit", "face", "t64")
-
-
-def _dev(device, a, dtype):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype)).to(device)
-
-
-class Guarded:
-    """An output tensor inside a larger allocation whose every byte is 0xA5, a pattern no output of the kernel holds
-    (as f32 -2.9e-16, as f64 -1.2e-128, as i32 a large negative number, as u8 165)."""
-    GUARD = 4096
-
-    def __init__(self, device, dtype, shape):
-        self.size = int(np.prod(shape)) * torch.empty((), dtype=dtype).element_size()
-        self.raw = torch.full((self.size + 2 * self.GUARD,), 0xA5, dtype=torch.uint8, device=device)
-        self.t = self.raw[self.GUARD:self.GUARD + self.size].view(dtype).view(shape)
-
-    def guards_ok(self):
-        return bool(((self.raw[:self.GUARD] == 0xA5).all() & (self.raw[self.GUARD + self.size:] == 0xA5).all()).item())
-
-    def written(self):
-        flat = self.raw[self.GUARD:self.GUARD + self.size].view(-1, self.t.element_size())
-        return bool((flat != 0xA5).any(1).all().item())
-
-
-def _raw_cast(device, rays, h, w, pose, V, F, skip, near=NEAR, far=FAR, face=True, t64=True, guarded=False):
-    """mslam_mesh_raycast_boxes + mslam_mesh_raycast through the C entry points -> dict of numpy arrays."""
-    import mslam_hip as _m
-
-    L, st = _m.lib(), _m.stream_ptr()
-    r, p = _dev(device, np.reshape(rays, (-1, 3)), np.float32), _dev(device, pose, np.float32)
-    v, f = _dev(device, np.reshape(V, (-1, 3)), np.float32), _dev(device, np.reshape(F, (-1, 3)), np.int32)
-    n, nf = h * w, len(f)
-    assert len(r) == n
-    wb = int(L.mslam_mesh_raycast_workspace_bytes(nf))
-    assert wb == 48 * ((nf + T - 1) // T)
-    ws = None
-    if skip and nf:
-        ws = torch.empty(wb, dtype=torch.uint8, device=device)
-        _m.check(L.mslam_mesh_raycast_boxes(_m.ptr(v), _m.ptr(f), nf, len(v), _m.ptr(ws), wb, st), "mesh_raycast_boxes")
-    shapes = dict(range=(torch.float32, (n,)), normal=(torch.float32, (n, 3)), hit=(torch.uint8, (n,)),
-                  face=(torch.int32, (n,)), t64=(torch.float64, (n,)))
-    out = {k: Guarded(device, *shapes[k]) for k in KEYS if (k != "face" or face) and (k != "t64" or t64)}
-    arg = lambda k: _m.ptr(out[k].t) if k in out else 0
-    ws_before = ws.clone() if ws is not None else None
-    _m.check(L.mslam_mesh_raycast(_m.ptr(r), h, w, _m.ptr(p), _m.ptr(v), _m.ptr(f), nf, len(v), near, far,
-                                  1 if skip else 0, _m.ptr(ws), wb if ws is not None else 0, arg("range"),
-                                  arg("normal"), arg("hit"), arg("face"), arg("t64"), st), "mesh_raycast")
-    if guarded:
-        for k, g in out.items():
-            assert g.guards_ok() and g.written(), k
-        assert ws is None or torch.equal(ws, ws_before)                  # the cast only reads the boxes
-    return {k: g.t.cpu().numpy() for k, g in out.items()}
-
-
-def _same_bytes(a, b):
-    assert sorted(a) == sorted(b)
-    for k in a:
-        assert a[k].dtype == b[k].dtype and a[k].tobytes() == b[k].tobytes(), k
 
 
 def _parity(got, want):
     """face, hit and t64 exactly; range and normal equal the statement's f32 roundings."""
-    for k, w in zip(KEYS, want):
+    for k, w in zip(CAST_KEYS, want):
         if k in got:
             assert got[k].dtype == w.dtype and got[k].shape == w.shape, k
             assert got[k].tobytes() == w.tobytes(), (k, int((got[k] != w).sum()))
@@ -321,6 +261,54 @@ def test_guards_null_outputs_invalid_faces_and_arguments(device):
     assert call(1, _m.ptr(ws), wb, h=-1) != 0
     assert call(1, _m.ptr(ws), wb) == 0 and call(0, 0, 0) == 0
     torch.cuda.synchronize()
+
+
+@functools.lru_cache(maxsize=None)
+def dead_wave_case(nf, dead):
+    """257 rays in every direction whose first `dead` (a wave, or the whole first block) have a zero or a non-finite
+    direction, the same list with copies of its casting rays in their place, and the numpy answer for the first."""
+    V, F = tile_mesh(nf)
+    rng = np.random.default_rng(300 * nf + dead)
+    filled = rng.normal(size=(257, 3))
+    filled = (filled / np.linalg.norm(filled, axis=1, keepdims=True)).astype(np.float32)
+    filled[:dead] = filled[dead + np.arange(dead) % (257 - dead)]
+    rays = filled.copy()
+    rays[:dead] = np.array([[0, 0, 0], [np.inf, 0, 0], [np.nan, 1, 0], [0, -np.inf, 0]], np.float32)[np.arange(dead) % 4]
+    with np.errstate(invalid="ignore"):
+        want = R.render(POSE, rays, V, F, NEAR, FAR)
+    return rays, filled, V, F, want
+
+
+_INDEXES = {}
+
+
+@pytest.mark.parametrize("dead", [64, 256])
+@pytest.mark.parametrize("nf", [T + 1, T * G + T + 1])
+def test_waves_without_a_casting_ray(device, nf, dead):
+    """The one place where the tile loops of rc_kernel and md_scan (csrc/mesh_tri.h) vote differently: rc_kernel lets a
+    wave none of whose rays casts skip every tile, culled or not.  Whatever the vote, its rays miss, the others'
+    answers are the statement's, a wholly dead wave counts every tile, and - a wave's count depends on its own rays
+    alone - the waves behind count what they count when casting rays stand in front of them."""
+    rays, filled, V, F, want = dead_wave_case(nf, dead)
+    n, first, waves, ntiles = len(rays), dead // 64, (len(rays) + 63) // 64, (nf + T - 1) // T
+
+    def check(got):
+        _parity(got, want)
+        assert not got["hit"][:dead].any() and (got["face"][:dead] == -1).all() and np.isposinf(got["t64"][:dead]).all()
+        assert not got["range"][:dead].any() and not got["normal"][:dead].any()
+
+    for skip in (0, 1):
+        check(_raw_cast(device, rays, 1, n, POSE, V, F, skip, guarded=True))
+    if nf not in _INDEXES:
+        _INDEXES[nf] = _build(device, V, F)
+    for levels in (1, 2):
+        got, counts = _indexed_cast(device, _INDEXES[nf], rays, 1, n, POSE, levels, NEAR, FAR)       # guards checked
+        check(got)
+        other, behind = _indexed_cast(device, _INDEXES[nf], filled, 1, n, POSE, levels, NEAR, FAR)
+        assert counts.dtype == torch.int32 and torch.equal(counts[first:waves], behind[first:waves])
+        assert (counts[:first] == ntiles).all()
+        _same_bytes({k: x[dead:] for k, x in got.items()}, {k: x[dead:] for k, x in other.items()})
+        print(f"F={nf} dead={dead} levels={levels}: tiles skipped per wave {counts[:waves].tolist()} of {ntiles}")
 
 
 # ----------------------------------------------------------------------------------------------------------------------

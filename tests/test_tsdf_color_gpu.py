@@ -3,7 +3,6 @@ room of tests/test_tsdf_render_gpu.py, coloured with the room texture (synthetic
 fused world points: fusion against the numpy statement (tests/color_numpy.py), order independence bit for bit, the TSDF
 left untouched, sample_color / coloured mesh / coloured view against numpy, and the colours themselves against the
 analytic texture."""
-import itertools
 import os
 import sys
 
@@ -16,7 +15,7 @@ from mast3r_slam import synthetic
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import color_numpy as C  # noqa: E402
 import render_numpy as R  # noqa: E402
-from test_tsdf_render_gpu import POSES, VS, _rays, _room, _vol  # noqa: E402
+from mesh_support import POSES, VS, _rays, _room, _vol, color_checks  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -213,26 +212,6 @@ def test_mesh_and_view_colors(device):
     ghit = _host(gv[2])
     assert ghit.any() and np.array_equal(_host(gv[3])[ghit], np.full((int(ghit.sum()), 3), 0.5, np.float32))
     assert not _host(gv[3])[~ghit].any()
-
-
-def color_checks(rgb, hit, truth, full_image, label):
-    """Checks (a) and (b) of the colour view: `rgb` f[h,w,3] the rendered colours, `truth` f[h,w,3] the texture at the hit
-    points, `full_image` f[h,w,3] the texture image of the whole frame (for the mirror images).  Returns (max, mean)
-    absolute error over the hit pixels."""
-    err = np.abs(rgb - truth)[hit]
-    mean = float(err.mean())
-    const = float(np.abs(truth[hit] - truth[hit].mean(0, keepdims=True)).mean())   # the best constant image
-    print(f"{label}: {int(hit.sum())} hit pixels, max error {err.max():.4f}, mean error {mean:.5f}, best constant image "
-          f"{const:.4f} (per channel {np.abs(truth[hit] - truth[hit].mean(0)).mean(0).round(3).tolist()})")
-    assert mean < const, (mean, const)
-    for p in itertools.permutations(range(3)):
-        if p != (0, 1, 2):
-            other = float(np.abs(rgb - truth[..., list(p)])[hit].mean())
-            assert mean < other, ("channel permutation", p, mean, other)
-    for name, img in (("left-right", full_image[:, ::-1]), ("up-down", full_image[::-1])):
-        other = float(np.abs(rgb - img)[hit].mean())
-        assert mean < other, (name, mean, other)
-    return float(err.max()), mean
 
 
 def test_colors_are_the_right_ones(device):

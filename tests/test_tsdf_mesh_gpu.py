@@ -13,37 +13,9 @@ from mast3r_slam import synthetic
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import mc_numpy as M  # noqa: E402
+from mesh_support import VS, _host, _room, _same, _vol  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-VS = 0.03
-
-
-def _vol(device, capacity=1 << 20, **kw):
-    from mast3r_slam.tsdf import TSDFVolume
-
-    return TSDFVolume(VS, 0.12, 100.0, 1.0e-3, capacity=capacity, device=device, **kw)
-
-
-def _room(n_kf=3, n_pts=20000, h=192, w=256):
-    out = []
-    for kf in range(n_kf):
-        T = synthetic.camera_pose(kf * 10)
-        X = synthetic.render_pointmap(T, h, w).reshape(-1, 3)
-        rng = np.random.default_rng(kf)
-        sel = rng.permutation(X.shape[0])[:n_pts]
-        out.append((synthetic.sim3_act(T, X[sel]).astype(np.float32), rng.uniform(0.1, 8.0, len(sel)),
-                    T[:3].astype(np.float32)))
-    return out
-
-
-def _host(mesh):
-    return tuple(a.cpu().numpy() for a in mesh)
-
-
-def _same(a, b):
-    for x, y in zip(_host(a), _host(b)):
-        assert x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x, y)
 
 
 def _match_numpy(mesh, keys, t, w, min_weight, level=0.0):

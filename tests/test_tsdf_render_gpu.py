@@ -14,28 +14,9 @@ from mast3r_slam import synthetic
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import render_numpy as R  # noqa: E402
+from mesh_support import POSES, VS, _host, _pose, _rays, _room, _same, _vol  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-
-VS = 0.03
-
-
-def _vol(device, capacity=1 << 20, **kw):
-    from mast3r_slam.tsdf import TSDFVolume
-
-    return TSDFVolume(VS, 0.12, 100.0, 1.0e-3, capacity=capacity, device=device, **kw)
-
-
-def _room(n_kf=3, n_pts=20000, h=192, w=256):
-    out = []
-    for kf in range(n_kf):
-        T = synthetic.camera_pose(kf * 10)
-        X = synthetic.render_pointmap(T, h, w).reshape(-1, 3)
-        rng = np.random.default_rng(kf)
-        sel = rng.permutation(X.shape[0])[:n_pts]
-        out.append((synthetic.sim3_act(T, X[sel]).astype(np.float32), rng.uniform(0.1, 8.0, len(sel)),
-                    T[:3].astype(np.float32)))
-    return out
 
 
 def _fused(device, capacity=1 << 20):
@@ -43,32 +24,6 @@ def _fused(device, capacity=1 << 20):
     for pw, conf, org in _room():
         vol.integrate(pw, conf, org)
     return vol
-
-
-def _rays(h, w):
-    return R.unit_rays(h, w, synthetic.intrinsics(h, w))
-
-
-def _pose(t, rotvec, s=1.0):
-    return np.concatenate((t, synthetic.quat_from_rotvec(np.asarray(rotvec, np.float64)), [s])).astype(np.float32)
-
-
-# a pose off the trajectory with a generic rotation and a scale, one of the trajectory that was not fused, one outside
-# the room looking away
-POSES = {
-    "generic": _pose(synthetic.camera_pose(12)[:3] + [0.1, -0.05, 0.08], [0.2, 0.3, 0.25], 1.25),
-    "unfused": synthetic.camera_pose(15).astype(np.float32),
-    "outside": _pose([0.0, 0.0, 5.0], [0.0, 0.0, 0.0]),
-}
-
-
-def _host(view):
-    return tuple(a.cpu().numpy() for a in view)
-
-
-def _same(a, b):
-    for x, y in zip(_host(a), _host(b)):
-        assert x.dtype == y.dtype and x.shape == y.shape and np.array_equal(x, y)
 
 
 def _match_numpy(view, voxels, min_weight, pose, rays, **kw):
