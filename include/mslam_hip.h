@@ -507,6 +507,24 @@ int mslam_tsdf_color_sample(void* table, uint64_t capacity, const void* color, c
                             uint8_t* out_count, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Render quality (NOT a reference interface): PSNR and SSIM of image pairs in one pass (csrc/image_metrics.hip,
+ * DESIGN.md "Render quality"; the definition is tests/imgmetrics_numpy.py).
+ *   a, b f32[n,h,w,c] (c in 1..4, data range 1), mask u8[n,h,w] (torch.bool storage) or NULL = all pixels.
+ *   window  f64[11]: the normalised Gaussian taps (sigma 1.5), computed once by the caller.
+ *   sums    f64[n,2]: the squared error over masked-in pixels and channels; S over valid window centres and channels.
+ *   counts  i64[n,2]: n_pixels (masked-in); n_windows (centres whose 11x11 window lies in the image and is masked-in).
+ *   ssim_map f32[n,h,w] or NULL: the channel mean of S at valid centres, NaN elsewhere.
+ * A MSLAM_IMAGE_METRICS_TILE_H x _TILE_W tile of centres per 256-thread workgroup; the workspace holds one partial per
+ * workgroup and quantity, which a second launch adds in block order: no atomics, bit-identical results from call to
+ * call and for any position of an image in the batch.  h or w below 11 is legal (n_windows = 0). */
+#define MSLAM_IMAGE_METRICS_TILE_H 16
+#define MSLAM_IMAGE_METRICS_TILE_W 32
+size_t mslam_image_metrics_workspace_bytes(int n, int h, int w, int c);
+int mslam_image_metrics(const float* a, const float* b, const uint8_t* mask, int n, int h, int w, int c,
+                        const double* window, double* sums, int64_t* counts, float* ssim_map, void* workspace,
+                        void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * MASt3R two-view forward. Replaces the three model methods the SLAM front/back-end call
  * (mast3r_slam/mast3r_utils.py:34-40,57-64,74): model._encode_image, model._decoder,
  * model._downstream_head (thirdparty/mast3r/dust3r/dust3r/model.py:127-139,171-196;

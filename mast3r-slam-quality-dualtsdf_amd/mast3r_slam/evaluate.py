@@ -223,6 +223,13 @@ def save_mesh_metrics(savedir, filename, metrics):
     return path
 
 
+def save_render_metrics(savedir, filename, metrics):
+    """The dict of SlamSystem.evaluate_render (psnr, ssim, shares, per_view lists) as JSON with sorted keys, in the form
+    of save_mesh_metrics; a NaN or an infinity is written as Python's json writes it (NaN, Infinity).  Returns the
+    path."""
+    return save_mesh_metrics(savedir, filename, metrics)
+
+
 def save_tsdf_mesh(savedir, filename, source, min_weight=None, level=0.0, colors=False, min_component_faces=0,
                    keep_largest=None, simplify_cell=0.0, simplify_position="quadric"):
     """The global TSDF's triangle mesh (marching cubes) as PLY with normals, beside save_reconstruction's point cloud.

@@ -501,6 +501,97 @@ class SlamSystem:
         l1, med = (float("nan"),) * 2 if m == 0 else torch.stack((d.sum() / m, 0.5 * (d[(m - 1) // 2] + d[m // 2]))).tolist()
         return dict(depth_l1=l1, depth_l1_median=med, both_hit_share=m / n_pixels, n_pixels=n_pixels)
 
+    def evaluate_render(self, images=None, poses=None, rays=None, K=None, near=0.05, far=10.0, chunk=8):
+        """The photometric figures of dense-SLAM evaluations: PSNR and SSIM of the colour views of the global TSDF
+        against camera images (tsdf.image_metrics, DESIGN.md "Render quality").  Needs tsdf_global.color.
+
+        Without `images`, the training views: every keyframe's pose, through the rays evaluate_depth uses (the
+        system's intrinsics when it is calibrated, otherwise the keyframe's canonical pointmap normalised to unit
+        length), against the keyframe's `uimg`; where uimg is smaller than the pointmap (dataset.img_downsample > 1) it is
+        read by the colour fusion's rule, uimg[r h // H, c w // W] (tsdf.global_manager.gather_uimg), so a training view
+        is compared with exactly what was fused.  With `images` f32[M,h,w,3] in [0,1], held-out views: `poses` Sim3
+        [M,8] in the map's frame and a pinhole `K` (3,3; the images' shape) or `rays` f32[h,w,3] / [M,h,w,3].
+
+        The mask of a view is its hit image: a pixel enters the squared error when its ray hit the surface, a window
+        enters SSIM when all its 121 pixels did.  Views are rendered `chunk` at a time and scored by one launch per
+        chunk.  Returns Python numbers: psnr / ssim, the means over the views that have a pixel / a window (NaN without
+        one), psnr_min / ssim_min, hit_share and window_share (of all pixels of all views), n_views, and per_view: lists
+        of psnr, ssim, n_pixels, n_windows.  Drains the backend first."""
+        what = "SlamSystem.evaluate_render"
+        if self.tsdf_manager is None:
+            raise RuntimeError(f"{what}: the global TSDF is disabled (tsdf_global.enabled = False)")
+        if not self.tsdf_manager.volume.color:
+            raise RuntimeError(f"{what}: the global TSDF carries no colour (tsdf_global.color = False)")
+        from mast3r_slam.tsdf import image_metrics
+        from mast3r_slam.tsdf.global_manager import gather_uimg
+
+        self.drain()
+        if images is None:
+            if poses is not None or rays is not None or K is not None:
+                raise ValueError(f"{what}: poses, rays and K go with images")
+            n_views = len(self.keyframes)
+            if n_views == 0:
+                raise RuntimeError(f"{what}: no keyframe yet")
+        else:
+            images = torch.as_tensor(images)
+            if images.dim() != 4 or images.shape[3] != 3 or not images.is_floating_point():
+                raise ValueError(f"{what}: images must be float (M,h,w,3), got {tuple(images.shape)} {images.dtype}")
+            n_views, h, w = (int(x) for x in images.shape[:3])
+            if len(self.keyframes) == 0:
+                raise RuntimeError(f"{what}: no keyframe yet")
+            if poses is None or (rays is None) == (K is None):
+                raise ValueError(f"{what}: images need poses and either K or rays")
+            poses = torch.as_tensor(getattr(poses, "data", poses)).detach().reshape(-1, 8)
+            if poses.shape[0] != n_views:
+                raise ValueError(f"{what}: {n_views} images but {poses.shape[0]} poses")
+            if rays is not None:
+                rays = torch.as_tensor(rays).to(self.device)
+                if tuple(rays.shape) not in ((h, w, 3), (n_views, h, w, 3)):
+                    raise ValueError(f"{what}: rays must be {(h, w, 3)} or {(n_views, h, w, 3)}, got {tuple(rays.shape)}")
+
+        def view(i):
+            """(pose, render arguments, target f32[h,w,3] on the device) of view i."""
+            if images is not None:
+                r = dict(K=K, hw=(h, w)) if rays is None else dict(rays=rays if rays.dim() == 3 else rays[i])
+                return poses[i], r, images[i].to(device=self.device, dtype=torch.float32)
+            kf = self.keyframes[i]
+            H, W = (int(x) for x in kf.img_shape.reshape(-1)[:2].tolist())
+            if config["use_calib"] and self.K is not None:
+                r = dict(K=self.K, hw=(H, W))
+            else:
+                X = kf.X_canon.detach().reshape(H, W, 3).float()
+                r = dict(rays=X / X.norm(dim=-1, keepdim=True).clamp_min(1.0e-12))
+            if kf.uimg is None:
+                raise ValueError(f"{what}: keyframe {i} has no uimg to compare with")
+            pixels = torch.arange(H * W, device=self.device)
+            return kf.T_WC.data.detach().reshape(8), r, gather_uimg(kf.uimg.detach(), pixels, (H, W)).reshape(H, W, 3)
+
+        per = dict(psnr=[], ssim=[], n_pixels=[], n_windows=[])
+        total = 0
+        for start in range(0, n_views, max(int(chunk), 1)):
+            rgb, hit, tgt = [], [], []
+            for i in range(start, min(start + max(int(chunk), 1), n_views)):
+                pose, r, target = view(i)
+                out = self.tsdf_manager.render(pose, near=near, far=far, colors=True, **r)
+                if out[3].shape != target.shape:
+                    raise ValueError(f"{what}: view {i} renders {tuple(out[3].shape)} against an image of "
+                                     f"{tuple(target.shape)}")
+                rgb.append(out[3]), hit.append(out[2]), tgt.append(target)
+            if any(x.shape != rgb[0].shape for x in rgb):
+                raise ValueError(f"{what}: the views {start}.. differ in shape; score them with chunk=1")
+            m = image_metrics(torch.stack(rgb), torch.stack(tgt), mask=torch.stack(hit))     # one launch, one host read
+            for v in torch.stack((m["psnr"], m["ssim"], m["n_pixels"].double(), m["n_windows"].double()), 1).tolist():
+                per["psnr"].append(v[0]), per["ssim"].append(v[1])
+                per["n_pixels"].append(int(v[2])), per["n_windows"].append(int(v[3]))
+            total += len(rgb) * int(rgb[0].shape[0]) * int(rgb[0].shape[1])
+        ps = [p for p, k in zip(per["psnr"], per["n_pixels"]) if k > 0]
+        ss = [s for s, k in zip(per["ssim"], per["n_windows"]) if k > 0]
+        nan = float("nan")
+        return dict(psnr=sum(ps) / len(ps) if ps else nan, ssim=sum(ss) / len(ss) if ss else nan,
+                    psnr_min=min(ps) if ps else nan, ssim_min=min(ss) if ss else nan,
+                    hit_share=sum(per["n_pixels"]) / total, window_share=sum(per["n_windows"]) / total,
+                    n_views=n_views, per_view=per)
+
     def render_view(self, pose=None, rays=None, K=None, hw=None, **kw):
         """Depth / normal view of the global TSDF at this point of the run: (range f32[h,w], normals f32[h,w,3],
         hit bool[h,w]) device tensors (TSDFVolume.render; `kw`: near, far, min_weight, level, step, skip, and - with
