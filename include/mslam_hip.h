@@ -320,6 +320,46 @@ int mslam_mesh_simplify_solve(const float* vertices, const float* normals, const
 int mslam_mesh_simplify_mark(const int32_t* tri, const int64_t* face_order, int num_faces, int num_clusters,
                              int32_t* sorted_tri, int32_t* keep_face, int32_t* referenced, void* stream);
 
+/* Mesh smoothing: Taubin lambda|mu steps over the vertex neighbour table, and vertex normals from the winding over the
+ * vertex face table (no counterpart in the reference, DESIGN.md "Mesh smoothing").  faces i32[F,3]; a face COUNTS when
+ * its three indices lie in [0, V) and are pairwise different (area plays no part).  Every index read from memory is
+ * checked before it is followed and an element that fails is skipped.  The state is f64, every sum runs in one fixed
+ * order, nothing is atomic: the same input gives the same bits.  Sequence, on one stream (3 F < 2^31, V F < 2^62):
+ *   mslam_mesh_smooth_edges    keys i64[6 F]: per counting face the directed edge keys a V + b of its three edges in
+ *                              both directions, INT64_MAX in all six slots of any other face.  The caller sorts them;
+ *                              the E distinct keys below V V give nbr i32[E] = key mod V, mult i32[E] = how often the key
+ *                              occurs (the counting faces on that edge) and row_start i64[V+1], the first key >= v V:
+ *                              row v holds the neighbours of v, each once, in ascending index.
+ *   mslam_mesh_smooth_step     one Jacobi step x_out = x_in + factor (S / n - x_in), each operation rounded on its own.
+ *                              x_in, x_out f64[V,stride], stride 3, or 4 with both 32-byte aligned (x y z 0), never the
+ *                              same buffer.  S = 0.0 + the positions of the row's neighbours in ascending index, n their
+ *                              number.  A vertex with an edge of mult 1 is a boundary vertex: MSLAM_MESH_SMOOTH_FIXED
+ *                              copies it, _CURVE sums only over its neighbours behind edges of mult 1, _FREE treats it
+ *                              as any other.  A vertex with an empty row is copied.  vclass u8[V] (may be NULL) receives
+ *                              MSLAM_MESH_SMOOTH_INTERIOR, _BOUNDARY or _ISOLATED.  num_edges: the length of nbr and
+ *                              mult; rows are clipped to it.
+ *   mslam_mesh_vertex_faces    pairs i64[3 F]: vertex F + face for the three vertices of a counting face, INT64_MAX in
+ *                              the three slots of any other.  The caller sorts them -> sorted_pairs, and pair_start
+ *                              i64[V+1], the first pair >= v F.
+ *   mslam_mesh_vertex_normals  normals f32[V,3]: the sum over the vertex's counting faces, in ascending face index, of
+ *                              (b - a) x (c - a) in f64 on the f32 vertices, divided by its length; zero when the sum is
+ *                              zero or not finite; normals_in f32[V,3] (NULL: zero) for a vertex without a counting
+ *                              face.  normals_in is only read and must not be `normals`. */
+#define MSLAM_MESH_SMOOTH_FIXED 0
+#define MSLAM_MESH_SMOOTH_CURVE 1
+#define MSLAM_MESH_SMOOTH_FREE 2
+#define MSLAM_MESH_SMOOTH_INTERIOR 0
+#define MSLAM_MESH_SMOOTH_BOUNDARY 1
+#define MSLAM_MESH_SMOOTH_ISOLATED 2
+int mslam_mesh_smooth_edges(const int32_t* faces, int num_faces, int num_vertices, int64_t* keys, void* stream);
+int mslam_mesh_smooth_step(const double* x_in, double* x_out, int stride, const int64_t* row_start, const int32_t* nbr,
+                           const int32_t* mult, int num_vertices, int64_t num_edges, double factor, int boundary_mode,
+                           uint8_t* vclass, void* stream);
+int mslam_mesh_vertex_faces(const int32_t* faces, int num_faces, int num_vertices, int64_t* pairs, void* stream);
+int mslam_mesh_vertex_normals(const float* vertices, const int32_t* faces, int num_faces, int num_vertices,
+                              const int64_t* sorted_pairs, const int64_t* pair_start, const float* normals_in,
+                              float* normals, void* stream);
+
 /* Mesh quality: face areas, a surface sampler and the exact point-to-mesh distance (no counterpart in the reference,
  * DESIGN.md "Mesh quality").  vertices f32[V,3], faces i32[F,3]; every index is checked against [0, V) before use.  A
  * face is valid when its indices are in range and (b - a) x (c - a), in f64, is not exactly zero; an invalid face has

@@ -40,6 +40,7 @@ _BASE = {
         "color": False,     # fuse the keyframes' uimg into the volume: coloured meshes and views (DESIGN.md "Colour")
         "mesh_min_component_faces": 0,   # SlamSystem.extract_mesh drops smaller components (DESIGN.md "Mesh components")
         "mesh_simplify_voxels": 0.0,     # ... and simplifies on cells of this many voxels, 0 = off ("Mesh simplification")
+        "mesh_smooth_iterations": 0,     # ... after this many Taubin iterations, 0 = off ("Mesh smoothing")
         "mesh_eval_threshold": 0.05,     # SlamSystem.evaluate_mesh: precision / recall distance (DESIGN.md "Mesh quality")
     },
 }

@@ -231,13 +231,15 @@ def save_render_metrics(savedir, filename, metrics):
 
 
 def save_tsdf_mesh(savedir, filename, source, min_weight=None, level=0.0, colors=False, min_component_faces=0,
-                   keep_largest=None, simplify_cell=0.0, simplify_position="quadric"):
+                   keep_largest=None, simplify_cell=0.0, simplify_position="quadric", smooth_iterations=0,
+                   smooth_lambda=0.5, smooth_mu=-0.53, smooth_boundary="fixed"):
     """The global TSDF's triangle mesh (marching cubes) as PLY with normals, beside save_reconstruction's point cloud.
     `source`: a SlamSystem, a TSDFGlobalManager or a TSDFVolume.  `colors=True` (a volume with tsdf_global.color): the
     vertices carry the fused colour as red / green / blue.  `min_component_faces` > 0 / `keep_largest`: small connected
     components are dropped first (DESIGN.md "Mesh components").  `simplify_cell` > 0 (world units) /
-    `simplify_position`: the mesh is then simplified by vertex clustering (DESIGN.md "Mesh simplification").  Returns
-    (V, F)."""
+    `simplify_position`: the mesh is then simplified by vertex clustering (DESIGN.md "Mesh simplification").
+    `smooth_iterations` > 0 / `smooth_lambda`, `smooth_mu`, `smooth_boundary`: Taubin smoothing between the two (DESIGN.md
+    "Mesh smoothing").  Returns (V, F)."""
     savedir = pathlib.Path(savedir)
     savedir.mkdir(exist_ok=True, parents=True)
     kw = {}
@@ -245,6 +247,9 @@ def save_tsdf_mesh(savedir, filename, source, min_weight=None, level=0.0, colors
         kw = dict(min_component_faces=min_component_faces, keep_largest=keep_largest)
     if simplify_cell is not None and simplify_cell > 0:
         kw = dict(kw, simplify_cell=simplify_cell, simplify_position=simplify_position)
+    if smooth_iterations is not None and smooth_iterations > 0:
+        kw = dict(kw, smooth_iterations=smooth_iterations, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu,
+                  smooth_boundary=smooth_boundary)
     if colors:
         v, n, f, c = source.extract_mesh(min_weight=min_weight, level=level, colors=True, **kw)
         save_mesh(savedir / filename, v, f, normals=n, colors=c)

@@ -1,6 +1,8 @@
-"""Argument checks shared by mesh_ops, mesh_simplify, mesh_metrics and mesh_align; `what`, the caller's name, is the
-prefix of every message.  There is no CPU path: a host tensor raises in mslam_hip.ptr.  Below them the sampler's core:
-mesh_metrics and mesh_align both draw from it, and mesh_metrics imports mesh_align."""
+"""Argument checks shared by mesh_ops, mesh_simplify, mesh_smooth, mesh_metrics and mesh_align; `what`, the caller's
+name, is the prefix of every message.  There is no CPU path: a host tensor raises in mslam_hip.ptr.  Below them the
+sampler's core: mesh_metrics and mesh_align both draw from it, and mesh_metrics imports mesh_align."""
+import math
+
 import numpy as np
 import torch
 
@@ -56,6 +58,25 @@ def _mesh_tuple_arg(mesh, what, check=True, on_device=False):
         if on_device:
             _m.ptr(t)
     return verts, normals, faces, colors, per_vertex
+
+
+def _ranges(verts, faces):
+    """(lowest and highest coordinate, lowest and highest face index, all coordinates finite) of a non-empty mesh as
+    Python floats: one stacked reduction, one host read."""
+    vlo, vhi = torch.aminmax(verts)
+    flo, fhi = torch.aminmax(faces)
+    finite = torch.isfinite(verts).all()
+    return torch.stack([x.double() for x in (vlo, vhi, flo, fhi, finite)]).cpu().tolist()
+
+
+def _check_finite(what, vlo, vhi, finite):
+    if not finite or not (math.isfinite(vlo) and math.isfinite(vhi)):
+        raise ValueError(f"{what}: vertex coordinates span [{vlo}, {vhi}] and are not all finite")
+
+
+def _check_face_range(what, flo, fhi, V):
+    if flo < 0 or fhi >= V:
+        raise ValueError(f"{what}: face indices span [{int(flo)}, {int(fhi)}], outside [0, {V})")
 
 
 def _points_arg(x, name, what, device=None):

@@ -15,6 +15,7 @@ import mslam_hip as _m
 
 from .mesh_ops import filter_mesh
 from .mesh_simplify import simplify_mesh
+from .mesh_smooth import smooth_mesh
 
 
 _KEY_BIAS = 1 << 20
@@ -349,7 +350,8 @@ class TSDFVolume:
                                                     _m.ptr(c), n, _m.stream_ptr()), "tsdf_color_load")
 
     def extract_mesh(self, min_weight=None, level=0.0, colors=False, default_color=(0.5, 0.5, 0.5),
-                     min_component_faces=0, keep_largest=None, simplify_cell=0.0, simplify_position="quadric"):
+                     min_component_faces=0, keep_largest=None, simplify_cell=0.0, simplify_position="quadric",
+                     smooth_iterations=0, smooth_lambda=0.5, smooth_mu=-0.53, smooth_boundary="fixed"):
         """Marching cubes over the fused volume -> (vertices f32[V,3], normals f32[V,3], faces i32[F,3]) device tensors in
         canonical order (DESIGN.md "Mesh extraction").  Corners are voxel centres with weight >= min_weight (default
         self.min_weight), inside = tsdf < level, normals point to free space, faces are counter-clockwise seen from
@@ -361,7 +363,12 @@ class TSDFVolume:
         read); the defaults leave the mesh as extracted.  `simplify_cell` > 0 (world units; a whole number of voxels keeps
         the cells aligned with them): the mesh is then simplified by clustering its vertices on that grid, placed by
         `simplify_position` = "quadric" | "mean" (mesh_simplify.simplify_mesh, DESIGN.md "Mesh simplification"; three more
-        host reads).  It runs last, so floaters are dropped before anything could merge them into the surface."""
+        host reads).  It runs last, so floaters are dropped before anything could merge them into the surface.
+        `smooth_iterations` > 0: that many Taubin iterations with `smooth_lambda`, `smooth_mu`, `smooth_boundary`
+        (mesh_smooth.smooth_mesh, DESIGN.md "Mesh smoothing"; two more host reads) after the component filter and before
+        the simplification, whose plane quadrics then see the smoothed surface; normals are recomputed."""
+        smooth = dict(smooth_iterations=smooth_iterations, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu,
+                      smooth_boundary=smooth_boundary)
         mw = self.min_weight if min_weight is None else float(min_weight)
         if colors and not self.color:
             raise ValueError("TSDFVolume.extract_mesh: colors=True needs a volume built with color=True")
@@ -369,16 +376,18 @@ class TSDFVolume:
             if colors:
                 return self._union().extract_mesh(min_weight=mw, level=level, colors=True, default_color=default_color,
                                                   min_component_faces=min_component_faces, keep_largest=keep_largest,
-                                                  simplify_cell=simplify_cell, simplify_position=simplify_position)
+                                                  simplify_cell=simplify_cell, simplify_position=simplify_position,
+                                                  **smooth)
             keys, t, w = self.voxels()
             return mesh_from_voxels(keys, t, w, self.voxel_size, mw, level, device=self.device,
                                     min_component_faces=min_component_faces, keep_largest=keep_largest,
-                                    simplify_cell=simplify_cell, simplify_position=simplify_position)
+                                    simplify_cell=simplify_cell, simplify_position=simplify_position, **smooth)
         mesh = _extract(self._table, self.capacity, self.voxel_size, mw, float(level), self.device)
         if colors:
             mesh = mesh + (_sample_color(self._table, self.capacity, self._color, mesh[0], 0, self.voxel_size,
                                          default_color)[0],)
         mesh = filter_mesh(mesh, min_component_faces, keep_largest, _validate=False)
+        mesh = smooth_mesh(mesh, smooth_iterations, smooth_lambda, smooth_mu, smooth_boundary)       # off: `mesh` itself
         return simplify_mesh(mesh, simplify_cell, simplify_position)        # off (None or <= 0): `mesh` itself
 
     def render(self, pose, rays=None, K=None, hw=None, near=0.05, far=10.0, min_weight=None, level=0.0, step=None,
@@ -568,12 +577,15 @@ def render_from_voxels(keys, tsdf, weight, voxel_size, min_weight, pose, rays, n
 
 def mesh_from_voxels(keys, tsdf, weight, voxel_size, min_weight, level=0.0, device="cuda", colors=None,
                      default_color=(0.5, 0.5, 0.5), min_component_faces=0, keep_largest=None, simplify_cell=0.0,
-                     simplify_position="quadric"):
+                     simplify_position="quadric", smooth_iterations=0, smooth_lambda=0.5, smooth_mu=-0.53,
+                     smooth_boundary="fixed"):
     """Mesh of a voxel set given as arrays (keys i64[n,3] distinct, tsdf f64[n], weight f64[n]; numpy or device): loads
-    a temporary table of at least 2n slots and extracts from it (TSDFVolume.extract_mesh semantics, its component filter
-    and its simplification included).  `colors` u64[n,4]: the voxels' colour sums (voxel_color_sums()); the mesh then
-    carries vertex colours as a fourth tensor."""
+    a temporary table of at least 2n slots and extracts from it (TSDFVolume.extract_mesh semantics, its component filter,
+    its smoothing and its simplification included).  `colors` u64[n,4]: the voxels' colour sums (voxel_color_sums()); the
+    mesh then carries vertex colours as a fourth tensor."""
     vol = _loaded(keys, tsdf, weight, voxel_size, min_weight, device, colors)
     return vol.extract_mesh(min_weight=min_weight, level=level, colors=colors is not None, default_color=default_color,
                             min_component_faces=min_component_faces, keep_largest=keep_largest,
-                            simplify_cell=simplify_cell, simplify_position=simplify_position)
+                            simplify_cell=simplify_cell, simplify_position=simplify_position,
+                            smooth_iterations=smooth_iterations, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu,
+                            smooth_boundary=smooth_boundary)

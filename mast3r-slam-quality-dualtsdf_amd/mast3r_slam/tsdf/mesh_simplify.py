@@ -11,7 +11,7 @@ import torch
 
 import mslam_hip as _m
 
-from ._mesh_args import _faces_arg, _mesh_tuple_arg
+from ._mesh_args import _check_face_range, _check_finite, _faces_arg, _mesh_tuple_arg, _ranges
 from .mesh_ops import _compact
 
 _KEY_LIMIT = 1 << 20                    # cell keys per axis lie in [-2^20, 2^20): the voxel hash's 21-bit signed range
@@ -19,19 +19,14 @@ _KEY_LIMIT = 1 << 20                    # cell keys per axis lie in [-2^20, 2^20
 
 def _validate_ranges(verts, faces, V, c):
     """One host read: the coordinate range (finite, cells within the key range) and the face index range."""
-    vlo, vhi = torch.aminmax(verts)
-    flo, fhi = torch.aminmax(faces)
-    finite = torch.isfinite(verts).all()
-    vlo, vhi, flo, fhi, finite = torch.stack([x.double() for x in (vlo, vhi, flo, fhi, finite)]).cpu().tolist()
-    if not finite or not (math.isfinite(vlo) and math.isfinite(vhi)):
-        raise ValueError(f"simplify_mesh: vertex coordinates span [{vlo}, {vhi}] and are not all finite")
+    vlo, vhi, flo, fhi, finite = _ranges(verts, faces)
+    _check_finite("simplify_mesh", vlo, vhi, finite)
     klo, khi = vlo / c, vhi / c
     if not (klo >= -_KEY_LIMIT and math.floor(khi) < _KEY_LIMIT):
         raise ValueError(f"simplify_mesh: cells span [{math.floor(klo) if math.isfinite(klo) else klo}, "
                          f"{math.floor(khi) if math.isfinite(khi) else khi}] at cell_size {c}, outside "
                          f"[{-_KEY_LIMIT}, {_KEY_LIMIT})")
-    if flo < 0 or fhi >= V:
-        raise ValueError(f"simplify_mesh: face indices span [{int(flo)}, {int(fhi)}], outside [0, {V})")
+    _check_face_range("simplify_mesh", flo, fhi, V)
 
 
 def simplify_mesh(mesh, cell_size, position="quadric", return_map=False, _validate=True, _two_pass=False):
