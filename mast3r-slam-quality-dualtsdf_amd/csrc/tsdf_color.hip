@@ -26,11 +26,6 @@ namespace mslam {
 constexpr double kColorWeightScale = 1048576.0;   // 2^20 units per unit of weight
 constexpr int kColorWords = 4;
 
-// floor(float32 / float32(voxel_size)) per axis: tsdf_global.hip world_to_key
-__device__ __forceinline__ bool color_world_to_key(float px, float py, float pz, float vs, uint64_t& key) {
-  return pack_key((long long)floorf(px / vs), (long long)floorf(py / vs), (long long)floorf(pz / vs), key);
-}
-
 // One sample of one point, exactly as tsdf_emit_kernel sees it: returns the weight in fixed point (0: nothing to add)
 // and the slot of its voxel.
 __device__ __forceinline__ unsigned long long color_sample(const TsdfTable& t, float o0, float o1, float o2, float d0,
@@ -47,7 +42,7 @@ __device__ __forceinline__ unsigned long long color_sample(const TsdfTable& t, f
   const double w = cf * exp((double)e);
   if (!(w > 0.0)) return 0ull;
   uint64_t key;
-  if (!color_world_to_key(s0, s1, s2, vs, key)) return 0ull;
+  if (!world_to_key(s0, s1, s2, vs, key)) return 0ull;   // tsdf_table.h: the key function of the emit pass
   const int64_t s = table_find(t, key);     // not in this table (another shard owns it, or the insert overflowed)
   if (s < 0) return 0ull;
   slot = (uint64_t)s;

@@ -26,11 +26,6 @@
 
 namespace mslam {
 
-// floor(float32 / float32(voxel_size)) per axis  (global_volume.py:133-134 under NumPy-2 promotion)
-__device__ __forceinline__ bool world_to_key(float px, float py, float pz, float vs, uint64_t& key) {
-  return pack_key((long long)floorf(px / vs), (long long)floorf(py / vs), (long long)floorf(pz / vs), key);
-}
-
 __global__ void tsdf_init_kernel(void* base, uint64_t cap) {
   TsdfTable t = table_carve(base, cap);
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -294,7 +289,12 @@ __global__ __launch_bounds__(64) void tsdf_replay_big_kernel(void* base, uint64_
 struct VoxelVal { int state; double w, v; };
 
 __device__ __forceinline__ void voxel_keys7(float px, float py, float pz, float vs, uint64_t (&keys)[7], bool (&ok)[7]) {
-  const long long k[3] = {(long long)floorf(px / vs), (long long)floorf(py / vs), (long long)floorf(pz / vs)};
+  long long k[3];
+  if (!world_to_index(px, py, pz, vs, k)) {   // NaN / inf / far out of range: the point has no voxel and no neighbours
+#pragma unroll
+    for (int j = 0; j < 7; j++) { ok[j] = false; keys[j] = kEmptyKey; }
+    return;
+  }
   ok[0] = pack_key(k[0], k[1], k[2], keys[0]);
 #pragma unroll
   for (int a = 0; a < 3; a++) {
@@ -451,7 +451,9 @@ __global__ __launch_bounds__(256) void tsdf_pose_accum_kernel(void* base, uint64
     J[5] = -(P[0] * g[1] - P[1] * g[0]);
     J[6] = P[0] * g[0] + P[1] * g[1] + P[2] * g[2];
     const float wf = lambda * conf[i];
-    const double sw = sqrt(wf > 1.0e-6f ? (double)wf : 1.0e-6);
+    // python's max(w, 1.0e-6) keeps the float32 product unless the constant is GREATER: at wf == 1.0e-6f the root is
+    // that of the float32 value (9.99999997e-7), below it that of the double constant
+    const double sw = sqrt(wf >= 1.0e-6f ? (double)wf : 1.0e-6);
     double Jw[7];
 #pragma unroll
     for (int k = 0; k < 7; k++) Jw[k] = sw * J[k];

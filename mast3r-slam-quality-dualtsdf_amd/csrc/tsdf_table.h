@@ -74,6 +74,25 @@ __device__ __forceinline__ void unpack_key(uint64_t key, long long& x, long long
   z = (long long)(key & 0x1FFFFF) - kKeyBias;
 }
 
+// Integer voxel index of a world point, floor(float32 / float32(voxel_size)) per axis (global_volume.py:133-134 under
+// NumPy-2 promotion), for every kernel that turns a position into a key.  A quotient that is NaN, +-inf or beyond
+// +-2^21 has no voxel: the reference's np.floor(..).astype(int) gives INT64_MIN there, which no dict entry has, while
+// the C++ cast of such a float is undefined (gfx950 turns NaN into 0, a voxel that exists).  It is decided on the
+// float, before any cast; every other value casts exactly (|q| < 2^21 is an integer in float32) and its neighbours
+// k +- 1 are out of the key range whenever q itself was refused.
+__device__ __forceinline__ bool world_to_index(float px, float py, float pz, float vs, long long (&k)[3]) {
+  const float q[3] = {floorf(px / vs), floorf(py / vs), floorf(pz / vs)};
+  const float lim = 2.0f * (float)kKeyBias;
+  if (!(fabsf(q[0]) < lim) || !(fabsf(q[1]) < lim) || !(fabsf(q[2]) < lim)) return false;
+  k[0] = (long long)q[0]; k[1] = (long long)q[1]; k[2] = (long long)q[2];
+  return true;
+}
+
+__device__ __forceinline__ bool world_to_key(float px, float py, float pz, float vs, uint64_t& key) {
+  long long k[3];
+  return world_to_index(px, py, pz, vs, k) && pack_key(k[0], k[1], k[2], key);
+}
+
 // Probe sequences are bounded: the host keeps the load factor <= 1/2 (TSDFVolume.maintain grows and rehashes), where a
 // linear-probe cluster of kMaxProbe slots does not occur; an insert that would need more reports overflow instead of
 // scanning a multi-million-slot table.

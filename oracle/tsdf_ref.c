@@ -221,7 +221,8 @@ int oracle_tsdf_pose_system(void* pv, const float* points, const float* conf, in
     J[5] = -(p[0] * g[1] - p[1] * g[0]);
     J[6] = p[0] * g[0] + p[1] * g[1] + p[2] * g[2];
     const float wf = (float)lambda * conf[i]; /* python float * np.float32 -> np.float32 */
-    const double sw = sqrt(wf > 1.0e-6f ? (double)wf : 1.0e-6);
+    /* max(w, 1.0e-6) returns w unless 1.0e-6 > w (compared in float32): at equality the float32 product stays */
+    const double sw = sqrt(wf >= 1.0e-6f ? (double)wf : 1.0e-6);
     const double r = value[i];
     if (!isfinite(r)) continue;
     double Jw[7];
