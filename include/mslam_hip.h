@@ -360,6 +360,57 @@ int mslam_mesh_vertex_normals(const float* vertices, const int32_t* faces, int n
                               const int64_t* sorted_pairs, const int64_t* pair_start, const float* normals_in,
                               float* normals, void* stream);
 
+/* Mesh holes: the boundary loops of a welded mesh, and a centroid fan over the small, well-behaved ones (no counterpart
+ * in the reference, DESIGN.md "Mesh holes").  faces i32[F,3]; a face COUNTS as in the smoothing.  A boundary dart is a
+ * directed edge of a counting face, in its winding, whose undirected edge lies on exactly one counting face; its id is
+ * 3 face + corner, the edge from corner c to corner c + 1.  Every index read from memory is checked before it is
+ * followed; all arithmetic is f64 on the f32 inputs, every sum runs in walk order, nothing is atomic: the same input gives
+ * the same bits.  `state` is i32[B,2], 8-byte aligned: per boundary dart (successor or -1, smallest tail so far).
+ * Sequence, on one stream (3 F < 2^31):
+ *   mslam_mesh_holes_keys     keys i64[3 F]: slot 3 f + c holds min V + max of that edge of a counting face, INT64_MAX
+ *                             in the three slots of any other face.  The caller sorts them, stable, with the permutation.
+ *   mslam_mesh_holes_mark     flag u8[3 F]: flag[order[i]] = 1 when sorted slot i is a run of length 1 below INT64_MAX,
+ *                             else 0.  The caller compacts the flagged slots, ascending: dart i32[B].
+ *   mslam_mesh_holes_darts    tail, head i32[B] of every boundary dart; -1 for a dart or a vertex out of range.  The
+ *                             caller sorts the tails (sorted_tail, tail_order i64[B]) and the heads (sorted_head).
+ *   mslam_mesh_holes_link     state[d] = (next(d), tail[d]): next(d) is the dart whose tail is head(d) when head(d)
+ *                             occurs exactly once in sorted_tail and once in sorted_head (a simple vertex), else -1.
+ *   mslam_mesh_holes_double   one round of pointer doubling from state_in to state_out (never the same buffer):
+ *                             (p, m) -> (p of p, min(m, m of p)); a dart whose p is -1 keeps its m.  After r rounds with
+ *                             2^r >= B, p >= 0 exactly on the cycles of next, and m is the cycle's smallest vertex.
+ *   mslam_mesh_holes_labels   keys i32[B+1]: m for a dart on a cycle, INT32_MAX for any other, INT32_MAX in slot B.  The
+ *                             caller sorts them; the runs below the last give loop_id i32[L], ascending, and length.
+ *   mslam_mesh_holes_assign   dart_loop i32[B]: the position of the dart's m in loop_id, -1 off the cycles; start i32[L]:
+ *                             the dart of each loop whose tail is the loop id (the caller presets -1).
+ *   mslam_mesh_holes_measure  one lane per loop, walking from start along next: perimeter f64[L] (NaN when not walked),
+ *                             centre f64[L,3] (the f64 mean of the tails) and fillable u8[L]: 3 <= n <= max_edges and
+ *                             every dart's fan face (head, tail, centre) turns the way of the dart's own face.  A loop
+ *                             longer than max_edges is walked only when all_perimeters is set.
+ *   mslam_mesh_holes_emit     one lane per fillable loop: row V + vertex_base[l] of out_vertices, out_normals and
+ *                             out_colors (NULL with colors NULL), rows F + face_base[l] ... + n of out_faces.  Rows
+ *                             below V and F are not touched: the caller copies the input there. */
+int mslam_mesh_holes_keys(const int32_t* faces, int num_faces, int num_vertices, int64_t* keys, void* stream);
+int mslam_mesh_holes_mark(const int64_t* sorted_keys, const int64_t* order, int64_t num_keys, uint8_t* flag,
+                          void* stream);
+int mslam_mesh_holes_darts(const int32_t* faces, int num_faces, int num_vertices, const int32_t* dart, int num_darts,
+                           int32_t* tail, int32_t* head, void* stream);
+int mslam_mesh_holes_link(const int32_t* tail, const int32_t* head, const int32_t* sorted_tail,
+                          const int64_t* tail_order, const int32_t* sorted_head, int num_darts, int num_vertices,
+                          int32_t* state, void* stream);
+int mslam_mesh_holes_double(const int32_t* state_in, int32_t* state_out, int num_darts, void* stream);
+int mslam_mesh_holes_labels(const int32_t* state, int num_darts, int32_t* keys, void* stream);
+int mslam_mesh_holes_assign(const int32_t* state, const int32_t* tail, int num_darts, const int32_t* loop_id,
+                            int num_loops, int32_t* dart_loop, int32_t* start, void* stream);
+int mslam_mesh_holes_measure(const float* vertices, const int32_t* faces, int num_faces, int num_vertices,
+                             const int32_t* dart, const int32_t* tail, const int32_t* head, const int32_t* state,
+                             int num_darts, const int32_t* start, const int32_t* length, int num_loops, int max_edges,
+                             int all_perimeters, double* perimeter, double* centre, uint8_t* fillable, void* stream);
+int mslam_mesh_holes_emit(const float* vertices, const float* colors, const int32_t* tail, const int32_t* head,
+                          const int32_t* state, int num_darts, const int32_t* start, const int32_t* length,
+                          const uint8_t* fillable, const int64_t* vertex_base, const int64_t* face_base, int num_loops,
+                          int num_vertices, int num_faces, int new_vertices, int new_faces, const double* centre,
+                          float* out_vertices, float* out_normals, float* out_colors, int32_t* out_faces, void* stream);
+
 /* Mesh quality: face areas, a surface sampler and the exact point-to-mesh distance (no counterpart in the reference,
  * DESIGN.md "Mesh quality").  vertices f32[V,3], faces i32[F,3]; every index is checked against [0, V) before use.  A
  * face is valid when its indices are in range and (b - a) x (c - a), in f64, is not exactly zero; an invalid face has

@@ -1,0 +1,427 @@
+// Boundary loops of a welded triangle mesh, and the closing of the small, well-behaved ones with a centroid fan.
+// Semantics in DESIGN.md "Mesh holes"; tests/holes_numpy.py states the same definitions, operation by operation, in
+// numpy.  All arithmetic is f64 on the f32 inputs, the build has -ffp-contract=off, every sum runs in walk order.
+//
+//   keys     one thread per face: the three undirected edge keys min V + max of a counting face (indices in [0, V),
+//            pairwise different) in dart order (slot 3 f + c: the edge from corner c to corner c + 1), INT64_MAX in all
+//            three slots of any other face.
+//   (caller)   sorts the keys, stable, with the permutation: sorted slot i came from dart order[i].
+//   mark     one thread per sorted slot: a run of length 1 below INT64_MAX is a boundary dart; flag[order[i]] says so.
+//   (caller)   compacts the flagged darts in ascending dart id (B of them, one host read).
+//   darts    one thread per boundary dart: its tail and head from the face.
+//   (caller)   sorts the tails (with the permutation) and the heads.
+//   link     one thread per boundary dart: its head is simple when it occurs exactly once among the tails and once among
+//            the heads (two binary searches); then next = the dart with that tail, else none.  state = (next, tail).
+//   double   one round of pointer doubling, Jacobi style from state_in to state_out: (ptr, lab)[d] becomes
+//            (ptr[ptr[d]], min(lab[d], lab[ptr[d]])), and stays when ptr[d] is none.  After r rounds ptr is the 2^r-th
+//            successor, or none if the chain ends before it, and lab the smallest tail on the way: with 2^r >= B a dart
+//            whose ptr is not none lies on a cycle and lab is the loop id.
+//   labels   one thread per boundary dart: the sort key lab, or INT32_MAX for an open dart, and one more INT32_MAX.
+//   (caller)   sorts them; unique_consecutive with counts gives the loop ids, ascending, and their lengths (one host read);
+//            the last run, less one, counts the open darts.
+//   assign   one thread per boundary dart: the number of its loop (binary search of lab in the loop ids) or -1, and the
+//            loop's first dart: the one whose tail is the loop id.
+//   measure  one thread per loop: walks it from its first dart and writes the perimeter, the centre and whether the loop
+//            is fillable.  Loops longer than max_edges are walked only when all perimeters are asked for.
+//   (caller)   exclusive scans of the fillable flags and lengths give the bases (one host read: the new sizes).
+//   emit     one thread per fillable loop: the new vertex, its normal and colour, and the n fan faces.
+// No atomics, and no thread reads what another writes within a launch.  Every index read from memory is checked against
+// its array before it is followed; a walk that meets a bad one stops and its loop is not fillable.
+#include <math.h>
+
+#include "common.h"
+
+namespace mslam {
+
+constexpr int64_t kMhNoKey = INT64_MAX;
+constexpr int32_t kMhNoLabel = INT32_MAX;
+
+__device__ __forceinline__ bool mh_counts(int a, int b, int c, int nv) {
+  return (unsigned)a < (unsigned)nv && (unsigned)b < (unsigned)nv && (unsigned)c < (unsigned)nv && a != b && b != c &&
+         a != c;
+}
+
+__global__ __launch_bounds__(256) void mh_keys_kernel(const int32_t* __restrict__ faces, int nf, int nv,
+                                                      int64_t* __restrict__ keys) {
+  const int f = blockIdx.x * 256 + threadIdx.x;
+  if (f >= nf) return;
+  const int a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
+  const bool ok = mh_counts(a, b, c, nv);
+  int64_t* k = keys + 3 * (size_t)f;
+  k[0] = ok ? (int64_t)min(a, b) * nv + max(a, b) : kMhNoKey;
+  k[1] = ok ? (int64_t)min(b, c) * nv + max(b, c) : kMhNoKey;
+  k[2] = ok ? (int64_t)min(c, a) * nv + max(c, a) : kMhNoKey;
+}
+
+__global__ __launch_bounds__(256) void mh_mark_kernel(const int64_t* __restrict__ sorted_keys,
+                                                      const int64_t* __restrict__ order, int64_t n,
+                                                      uint8_t* __restrict__ flag) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int64_t k = sorted_keys[i];
+  const bool single = k != kMhNoKey && (i == 0 || sorted_keys[i - 1] != k) && (i + 1 == n || sorted_keys[i + 1] != k);
+  const int64_t d = order[i];
+  if ((uint64_t)d < (uint64_t)n) flag[d] = single ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void mh_darts_kernel(const int32_t* __restrict__ faces, int nf, int nv,
+                                                       const int32_t* __restrict__ dart, int nb,
+                                                       int32_t* __restrict__ tail, int32_t* __restrict__ head) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nb) return;
+  const int d = dart[i];
+  int t = -1, h = -1;
+  if ((unsigned)d < 3u * (unsigned)nf) {
+    const int f = d / 3, c = d - 3 * f;
+    const int a = faces[3 * (size_t)f + c], b = faces[3 * (size_t)f + (c == 2 ? 0 : c + 1)];
+    if ((unsigned)a < (unsigned)nv && (unsigned)b < (unsigned)nv) t = a, h = b;
+  }
+  tail[i] = t;
+  head[i] = h;
+}
+
+// the first position of `sorted` (ascending, n entries) that is >= v
+__device__ __forceinline__ int mh_lower(const int32_t* __restrict__ sorted, int n, int v) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (sorted[mid] < v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// the position of v in `sorted` when it occurs exactly once, else -1
+__device__ __forceinline__ int mh_once(const int32_t* __restrict__ sorted, int n, int v) {
+  const int p = mh_lower(sorted, n, v);
+  if (p >= n || sorted[p] != v) return -1;
+  return (p + 1 < n && sorted[p + 1] == v) ? -1 : p;
+}
+
+__global__ __launch_bounds__(256) void mh_link_kernel(const int32_t* __restrict__ tail,
+                                                      const int32_t* __restrict__ head,
+                                                      const int32_t* __restrict__ sorted_tail,
+                                                      const int64_t* __restrict__ tail_order,
+                                                      const int32_t* __restrict__ sorted_head, int nb, int nv,
+                                                      int2* __restrict__ state) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nb) return;
+  const int h = head[i];
+  int nxt = -1;
+  if ((unsigned)h < (unsigned)nv) {
+    const int p = mh_once(sorted_tail, nb, h);
+    if (p >= 0 && mh_once(sorted_head, nb, h) >= 0) {
+      const int64_t j = tail_order[p];
+      if ((uint64_t)j < (uint64_t)nb) nxt = (int)j;
+    }
+  }
+  state[i] = make_int2(nxt, tail[i]);
+}
+
+__global__ __launch_bounds__(256) void mh_double_kernel(const int2* __restrict__ state_in, int2* __restrict__ state_out,
+                                                        int nb) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nb) return;
+  int2 s = state_in[i];
+  if ((unsigned)s.x < (unsigned)nb) {
+    const int2 t = state_in[s.x];
+    s.x = (unsigned)t.x < (unsigned)nb ? t.x : -1;
+    s.y = min(s.y, t.y);
+  } else {
+    s.x = -1;
+  }
+  state_out[i] = s;
+}
+
+__global__ __launch_bounds__(256) void mh_labels_kernel(const int2* __restrict__ state, int nb,
+                                                        int32_t* __restrict__ keys) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i > nb) return;
+  int32_t k = kMhNoLabel;
+  if (i < nb) {
+    const int2 s = state[i];
+    if (s.x >= 0) k = s.y;
+  }
+  keys[i] = k;
+}
+
+__global__ __launch_bounds__(256) void mh_assign_kernel(const int2* __restrict__ state, const int32_t* __restrict__ tail,
+                                                        int nb, const int32_t* __restrict__ loop_id, int nl,
+                                                        int32_t* __restrict__ dart_loop, int32_t* __restrict__ start) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nb) return;
+  const int2 s = state[i];
+  int l = -1;
+  if (s.x >= 0) {
+    const int p = mh_lower(loop_id, nl, s.y);
+    if (p < nl && loop_id[p] == s.y) l = p;
+  }
+  dart_loop[i] = l;
+  if (l >= 0 && tail[i] == s.y) start[l] = i;          // one dart leaves the loop id: it is a simple vertex
+}
+
+__device__ __forceinline__ void mh_point(const float* __restrict__ v, int i, double (&p)[3]) {
+  p[0] = (double)v[3 * (size_t)i], p[1] = (double)v[3 * (size_t)i + 1], p[2] = (double)v[3 * (size_t)i + 2];
+}
+
+__device__ __forceinline__ void mh_sub(const double (&a)[3], const double (&b)[3], double (&r)[3]) {
+  r[0] = a[0] - b[0], r[1] = a[1] - b[1], r[2] = a[2] - b[2];
+}
+
+__device__ __forceinline__ void mh_cross(const double (&u)[3], const double (&v)[3], double (&r)[3]) {
+  r[0] = u[1] * v[2] - u[2] * v[1];
+  r[1] = u[2] * v[0] - u[0] * v[2];
+  r[2] = u[0] * v[1] - u[1] * v[0];
+}
+
+__device__ __forceinline__ double mh_dot(const double (&u)[3], const double (&v)[3]) {
+  return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2];
+}
+
+// tail and head of boundary dart d, both in [0, V); false for a dart outside [0, B) or a vertex outside [0, V)
+__device__ __forceinline__ bool mh_ends(const int32_t* __restrict__ tail, const int32_t* __restrict__ head, int d, int nb,
+                                        int nv, int& a, int& b) {
+  if ((unsigned)d >= (unsigned)nb) return false;
+  a = tail[d], b = head[d];
+  return (unsigned)a < (unsigned)nv && (unsigned)b < (unsigned)nv;
+}
+
+__global__ __launch_bounds__(256) void mh_measure_kernel(
+    const float* __restrict__ vert, const int32_t* __restrict__ faces, int nf, int nv, const int32_t* __restrict__ dart,
+    const int32_t* __restrict__ tail, const int32_t* __restrict__ head, const int2* __restrict__ state, int nb,
+    const int32_t* __restrict__ start, const int32_t* __restrict__ length, int nl, int max_edges, int all_perimeters,
+    double* __restrict__ perimeter, double* __restrict__ centre, uint8_t* __restrict__ fillable) {
+  const int l = blockIdx.x * 256 + threadIdx.x;
+  if (l >= nl) return;
+  const int n = length[l], d0 = start[l];
+  const bool small = n >= 3 && n <= max_edges;
+  const bool walk = n >= 1 && n <= nb && (small || all_perimeters);
+  double per = 0.0, s[3] = {0.0, 0.0, 0.0};
+  bool ok = walk;
+  int d = d0;
+  for (int i = 0; ok && i < n; i++) {
+    int a, b;
+    ok = mh_ends(tail, head, d, nb, nv, a, b);
+    if (!ok) break;
+    double pa[3], pb[3], e[3];
+    mh_point(vert, a, pa);
+    mh_point(vert, b, pb);
+    mh_sub(pb, pa, e);
+    per = per + sqrt(mh_dot(e, e));
+#pragma unroll
+    for (int k = 0; k < 3; k++) s[k] = s[k] + pa[k];
+    d = state[d].x;
+  }
+  ok = ok && d == d0;                                    // n steps close the loop
+  double c[3];
+#pragma unroll
+  for (int k = 0; k < 3; k++) c[k] = s[k] / (double)n;
+  bool fill = ok && small;
+  d = d0;
+  for (int i = 0; fill && i < n; i++) {
+    int a, b;
+    if (!mh_ends(tail, head, d, nb, nv, a, b)) { fill = false; break; }
+    const int f = dart[d] / 3;
+    if ((unsigned)f >= (unsigned)nf) { fill = false; break; }
+    const int i0 = faces[3 * (size_t)f], i1 = faces[3 * (size_t)f + 1], i2 = faces[3 * (size_t)f + 2];
+    if (!mh_counts(i0, i1, i2, nv)) { fill = false; break; }
+    double pa[3], pb[3], q0[3], q1[3], q2[3], u[3], w[3], e1[3], e2[3], fan[3], own[3];
+    mh_point(vert, a, pa);
+    mh_point(vert, b, pb);
+    mh_point(vert, i0, q0);
+    mh_point(vert, i1, q1);
+    mh_point(vert, i2, q2);
+    mh_sub(pa, pb, u);
+    mh_sub(c, pb, w);
+    mh_cross(u, w, fan);
+    mh_sub(q1, q0, e1);
+    mh_sub(q2, q0, e2);
+    mh_cross(e1, e2, own);
+    fill = mh_dot(fan, own) > 0.0;                       // false for zero and for NaN
+    d = state[d].x;
+  }
+  perimeter[l] = ok ? per : (double)NAN;
+#pragma unroll
+  for (int k = 0; k < 3; k++) centre[3 * (size_t)l + k] = ok ? c[k] : 0.0;
+  fillable[l] = fill ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void mh_emit_kernel(
+    const float* __restrict__ vert, const float* __restrict__ colors, const int32_t* __restrict__ tail,
+    const int32_t* __restrict__ head, const int2* __restrict__ state, int nb, const int32_t* __restrict__ start,
+    const int32_t* __restrict__ length, const uint8_t* __restrict__ fillable, const int64_t* __restrict__ vbase,
+    const int64_t* __restrict__ fbase, int nl, int nv, int nf, int new_v, int new_f, const double* __restrict__ centre,
+    float* __restrict__ out_vert, float* __restrict__ out_nrm, float* __restrict__ out_col,
+    int32_t* __restrict__ out_faces) {
+  const int l = blockIdx.x * 256 + threadIdx.x;
+  if (l >= nl || !fillable[l]) return;
+  const int n = length[l];
+  const int64_t kv = vbase[l], kf = fbase[l];
+  if (n < 3 || (uint64_t)kv >= (uint64_t)new_v || kf < 0 || kf + n > new_f) return;
+  float c32[3];
+  double c[3], s[3] = {0.0, 0.0, 0.0}, col[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    c32[k] = (float)centre[3 * (size_t)l + k];
+    c[k] = (double)c32[k];
+  }
+  const int vnew = nv + (int)kv;
+  int d = start[l];
+  for (int i = 0; i < n; i++) {
+    int a = -1, b = -1;
+    const bool ok = mh_ends(tail, head, d, nb, nv, a, b);
+    int32_t* face = out_faces + 3 * ((size_t)nf + kf + i);
+    face[0] = ok ? b : 0, face[1] = ok ? a : 0, face[2] = ok ? vnew : 0;      // measure has walked this loop: ok
+    if (!ok) continue;
+    double x[3], y[3], e1[3], e2[3], nrm[3];
+    mh_point(vert, b, x);
+    mh_point(vert, a, y);
+    mh_sub(y, x, e1);
+    mh_sub(c, x, e2);
+    mh_cross(e1, e2, nrm);
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      s[k] = s[k] + nrm[k];
+      if (colors) col[k] = col[k] + (double)colors[3 * (size_t)a + k];
+    }
+    d = state[d].x;
+  }
+  const double ln = sqrt(mh_dot(s, s));
+  const bool unit = ln > 0.0 && ln < (double)INFINITY;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const size_t o = 3 * (size_t)vnew + k;
+    out_vert[o] = c32[k];
+    out_nrm[o] = unit ? (float)(s[k] / ln) : 0.0f;
+    if (out_col) out_col[o] = (float)(col[k] / (double)n);
+  }
+}
+
+}  // namespace mslam
+
+using namespace mslam;
+
+#define MH_LAUNCH(kernel, count, ...) \
+  hipLaunchKernelGGL(kernel, dim3(blocks_for(count, 256)), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__)
+
+extern "C" int mslam_mesh_holes_keys(const int32_t* faces, int num_faces, int num_vertices, int64_t* keys,
+                                     void* stream) {
+  MSLAM_REQUIRE(num_faces >= 0 && num_vertices >= 0, "mesh_holes_keys: negative size");
+  MSLAM_REQUIRE((int64_t)num_faces * 3 < ((int64_t)1 << 31), "mesh_holes_keys: too many faces");
+  if (num_faces == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(faces && keys, "mesh_holes_keys: null pointer");
+  MH_LAUNCH(mh_keys_kernel, num_faces, faces, num_faces, num_vertices, keys);
+  MSLAM_LAUNCH_CHECK("mesh_holes_keys");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_mesh_holes_mark(const int64_t* sorted_keys, const int64_t* order, int64_t num_keys, uint8_t* flag,
+                                     void* stream) {
+  MSLAM_REQUIRE(num_keys >= 0 && num_keys < ((int64_t)1 << 31), "mesh_holes_mark: size outside [0, 2^31)");
+  if (num_keys == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(sorted_keys && order && flag, "mesh_holes_mark: null pointer");
+  MH_LAUNCH(mh_mark_kernel, num_keys, sorted_keys, order, num_keys, flag);
+  MSLAM_LAUNCH_CHECK("mesh_holes_mark");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_mesh_holes_darts(const int32_t* faces, int num_faces, int num_vertices, const int32_t* dart,
+                                      int num_darts, int32_t* tail, int32_t* head, void* stream) {
+  MSLAM_REQUIRE(num_faces >= 0 && num_vertices >= 0 && num_darts >= 0, "mesh_holes_darts: negative size");
+  MSLAM_REQUIRE((int64_t)num_faces * 3 < ((int64_t)1 << 31), "mesh_holes_darts: too many faces");
+  if (num_darts == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(dart && tail && head && (faces || num_faces == 0), "mesh_holes_darts: null pointer");
+  MH_LAUNCH(mh_darts_kernel, num_darts, faces, num_faces, num_vertices, dart, num_darts, tail, head);
+  MSLAM_LAUNCH_CHECK("mesh_holes_darts");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_mesh_holes_link(const int32_t* tail, const int32_t* head, const int32_t* sorted_tail,
+                                     const int64_t* tail_order, const int32_t* sorted_head, int num_darts,
+                                     int num_vertices, int32_t* state, void* stream) {
+  MSLAM_REQUIRE(num_darts >= 0 && num_vertices >= 0, "mesh_holes_link: negative size");
+  if (num_darts == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(tail && head && sorted_tail && tail_order && sorted_head && state, "mesh_holes_link: null pointer");
+  MSLAM_REQUIRE((uintptr_t)state % 8 == 0, "mesh_holes_link: state must be 8-byte aligned");
+  MH_LAUNCH(mh_link_kernel, num_darts, tail, head, sorted_tail, tail_order, sorted_head, num_darts, num_vertices,
+            reinterpret_cast<int2*>(state));
+  MSLAM_LAUNCH_CHECK("mesh_holes_link");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_mesh_holes_double(const int32_t* state_in, int32_t* state_out, int num_darts, void* stream) {
+  MSLAM_REQUIRE(num_darts >= 0, "mesh_holes_double: negative size");
+  if (num_darts == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(state_in && state_out && state_in != state_out, "mesh_holes_double: null pointer or out == in");
+  MSLAM_REQUIRE((uintptr_t)state_in % 8 == 0 && (uintptr_t)state_out % 8 == 0,
+                "mesh_holes_double: states must be 8-byte aligned");
+  MH_LAUNCH(mh_double_kernel, num_darts, reinterpret_cast<const int2*>(state_in), reinterpret_cast<int2*>(state_out),
+            num_darts);
+  MSLAM_LAUNCH_CHECK("mesh_holes_double");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_mesh_holes_labels(const int32_t* state, int num_darts, int32_t* keys, void* stream) {
+  MSLAM_REQUIRE(num_darts >= 0 && num_darts < INT32_MAX, "mesh_holes_labels: size outside [0, 2^31 - 1)");
+  MSLAM_REQUIRE(keys && (state || num_darts == 0), "mesh_holes_labels: null pointer");
+  MSLAM_REQUIRE((uintptr_t)state % 8 == 0, "mesh_holes_labels: state must be 8-byte aligned");
+  MH_LAUNCH(mh_labels_kernel, (int64_t)num_darts + 1, reinterpret_cast<const int2*>(state), num_darts, keys);
+  MSLAM_LAUNCH_CHECK("mesh_holes_labels");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_mesh_holes_assign(const int32_t* state, const int32_t* tail, int num_darts, const int32_t* loop_id,
+                                       int num_loops, int32_t* dart_loop, int32_t* start, void* stream) {
+  MSLAM_REQUIRE(num_darts >= 0 && num_loops >= 0, "mesh_holes_assign: negative size");
+  if (num_darts == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(state && tail && dart_loop && (num_loops == 0 || (loop_id && start)), "mesh_holes_assign: null pointer");
+  MSLAM_REQUIRE((uintptr_t)state % 8 == 0, "mesh_holes_assign: state must be 8-byte aligned");
+  MH_LAUNCH(mh_assign_kernel, num_darts, reinterpret_cast<const int2*>(state), tail, num_darts, loop_id, num_loops,
+            dart_loop, start);
+  MSLAM_LAUNCH_CHECK("mesh_holes_assign");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_mesh_holes_measure(const float* vertices, const int32_t* faces, int num_faces, int num_vertices,
+                                        const int32_t* dart, const int32_t* tail, const int32_t* head,
+                                        const int32_t* state, int num_darts, const int32_t* start,
+                                        const int32_t* length, int num_loops, int max_edges, int all_perimeters,
+                                        double* perimeter, double* centre, uint8_t* fillable, void* stream) {
+  MSLAM_REQUIRE(num_faces >= 0 && num_vertices >= 0 && num_darts >= 0 && num_loops >= 0,
+                "mesh_holes_measure: negative size");
+  MSLAM_REQUIRE((int64_t)num_faces * 3 < ((int64_t)1 << 31), "mesh_holes_measure: too many faces");
+  if (num_loops == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(start && length && perimeter && centre && fillable, "mesh_holes_measure: null pointer");
+  MSLAM_REQUIRE(num_darts == 0 || (vertices && faces && dart && tail && head && state),
+                "mesh_holes_measure: null pointer");
+  MSLAM_REQUIRE((uintptr_t)state % 8 == 0, "mesh_holes_measure: state must be 8-byte aligned");
+  MH_LAUNCH(mh_measure_kernel, num_loops, vertices, faces, num_faces, num_vertices, dart, tail, head,
+            reinterpret_cast<const int2*>(state), num_darts, start, length, num_loops, max_edges, all_perimeters,
+            perimeter, centre, fillable);
+  MSLAM_LAUNCH_CHECK("mesh_holes_measure");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_mesh_holes_emit(const float* vertices, const float* colors, const int32_t* tail,
+                                     const int32_t* head, const int32_t* state, int num_darts, const int32_t* start,
+                                     const int32_t* length, const uint8_t* fillable, const int64_t* vertex_base,
+                                     const int64_t* face_base, int num_loops, int num_vertices, int num_faces,
+                                     int new_vertices, int new_faces, const double* centre, float* out_vertices,
+                                     float* out_normals, float* out_colors, int32_t* out_faces, void* stream) {
+  MSLAM_REQUIRE(num_darts >= 0 && num_loops >= 0 && num_vertices >= 0 && num_faces >= 0 && new_vertices >= 0 &&
+                    new_faces >= 0,
+                "mesh_holes_emit: negative size");
+  MSLAM_REQUIRE((int64_t)num_vertices + new_vertices < ((int64_t)1 << 31) &&
+                    ((int64_t)num_faces + new_faces) * 3 < ((int64_t)1 << 31),
+                "mesh_holes_emit: the output leaves the int32 index range");
+  if (num_loops == 0 || new_vertices == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(vertices && tail && head && state && start && length && fillable && vertex_base && face_base &&
+                    centre && out_vertices && out_normals && out_faces,
+                "mesh_holes_emit: null pointer");
+  MSLAM_REQUIRE((colors == nullptr) == (out_colors == nullptr), "mesh_holes_emit: colors and out_colors go together");
+  MSLAM_REQUIRE((uintptr_t)state % 8 == 0, "mesh_holes_emit: state must be 8-byte aligned");
+  MH_LAUNCH(mh_emit_kernel, num_loops, vertices, colors, tail, head, reinterpret_cast<const int2*>(state), num_darts,
+            start, length, fillable, vertex_base, face_base, num_loops, num_vertices, num_faces, new_vertices,
+            new_faces, centre, out_vertices, out_normals, out_colors, out_faces);
+  MSLAM_LAUNCH_CHECK("mesh_holes_emit");
+  return MSLAM_OK;
+}

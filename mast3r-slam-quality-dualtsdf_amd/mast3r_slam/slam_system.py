@@ -357,7 +357,7 @@ class SlamSystem:
 
     def extract_mesh(self, min_weight=None, level=0.0, colors=False, min_component_faces=None, keep_largest=None,
                      simplify_cell=None, simplify_position="quadric", smooth_iterations=None, smooth_lambda=0.5,
-                     smooth_mu=-0.53, smooth_boundary="fixed", **kw):
+                     smooth_mu=-0.53, smooth_boundary="fixed", fill_holes=None, **kw):
         """Triangle mesh of the global TSDF at this point of the run: (vertices f32[V,3], normals f32[V,3], faces i32[F,3])
         device tensors (TSDFVolume.extract_mesh).  Drains the backend first, so every fusion it has issued is ordered
         before the read.  `colors=True` (tsdf_global.color on): vertex colours f32[V,3] as a fourth tensor.
@@ -366,7 +366,9 @@ class SlamSystem:
         tsdf_global.mesh_simplify_voxels voxel sizes, 0 = off) / `simplify_position`: simplify the result by vertex
         clustering (DESIGN.md "Mesh simplification").  `smooth_iterations` (default
         tsdf_global.mesh_smooth_iterations, 0 = off) / `smooth_lambda`, `smooth_mu`, `smooth_boundary`: Taubin smoothing
-        after the component filter and before the simplification (DESIGN.md "Mesh smoothing")."""
+        after the component filter and before the simplification (DESIGN.md "Mesh smoothing").  `fill_holes` (default
+        tsdf_global.mesh_fill_holes, 0 = off): holes of at most that many edges are closed before the smoothing (DESIGN.md
+        "Mesh holes")."""
         if self.tsdf_manager is None:
             raise RuntimeError("SlamSystem.extract_mesh: the global TSDF is disabled (tsdf_global.enabled = False)")
         if min_component_faces is None:
@@ -376,12 +378,15 @@ class SlamSystem:
                              * float(self.tsdf_manager.volume.voxel_size))
         if smooth_iterations is None:
             smooth_iterations = int(self.tsdf_manager.cfg.get("mesh_smooth_iterations", 0))
+        if fill_holes is None:
+            fill_holes = int(self.tsdf_manager.cfg.get("mesh_fill_holes", 0))
         self.drain()
         return self.tsdf_manager.extract_mesh(min_weight=min_weight, level=level, colors=colors,
                                               min_component_faces=min_component_faces, keep_largest=keep_largest,
                                               simplify_cell=simplify_cell, simplify_position=simplify_position,
                                               smooth_iterations=smooth_iterations, smooth_lambda=smooth_lambda,
-                                              smooth_mu=smooth_mu, smooth_boundary=smooth_boundary, **kw)
+                                              smooth_mu=smooth_mu, smooth_boundary=smooth_boundary, fill_holes=fill_holes,
+                                              **kw)
 
     def align_trajectory(self, gt_positions):
         """The Sim3 that moves the map's frame onto a ground truth's, from camera centres: tsdf.fit_sim3 of the keyframes'

@@ -1,6 +1,6 @@
-"""Argument checks shared by mesh_ops, mesh_simplify, mesh_smooth, mesh_metrics and mesh_align; `what`, the caller's
-name, is the prefix of every message.  There is no CPU path: a host tensor raises in mslam_hip.ptr.  Below them the
-sampler's core: mesh_metrics and mesh_align both draw from it, and mesh_metrics imports mesh_align."""
+"""Argument checks shared by mesh_ops, mesh_simplify, mesh_smooth, mesh_holes, mesh_metrics and mesh_align; `what`, the
+caller's name, is the prefix of every message.  There is no CPU path: a host tensor raises in mslam_hip.ptr.  Below them
+the sampler's core: mesh_metrics and mesh_align both draw from it, and mesh_metrics imports mesh_align."""
 import math
 
 import numpy as np

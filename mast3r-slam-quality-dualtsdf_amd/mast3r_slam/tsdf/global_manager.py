@@ -170,13 +170,14 @@ class TSDFGlobalManager:
 
     def extract_mesh(self, min_weight=None, level=0.0, colors=False, min_component_faces=0, keep_largest=None,
                      simplify_cell=0.0, simplify_position="quadric", smooth_iterations=0, smooth_lambda=0.5,
-                     smooth_mu=-0.53, smooth_boundary="fixed", **kw):
+                     smooth_mu=-0.53, smooth_boundary="fixed", fill_holes=0, **kw):
         """Triangle mesh of the global volume: (vertices f32[V,3], normals f32[V,3], faces i32[F,3]) device tensors
         (TSDFVolume.extract_mesh); `colors=True`: vertex colours f32[V,3] as a fourth tensor.  `min_component_faces` /
         `keep_largest`: drop small connected components (DESIGN.md "Mesh components"); off by default.  `simplify_cell`
         > 0 (world units) / `simplify_position`: simplify the result by vertex clustering (DESIGN.md "Mesh
         simplification"); off by default.  `smooth_iterations` > 0 / `smooth_lambda`, `smooth_mu`, `smooth_boundary`:
-        Taubin smoothing between the two (DESIGN.md "Mesh smoothing"); off by default."""
+        Taubin smoothing between the two (DESIGN.md "Mesh smoothing"); off by default.  `fill_holes` = n > 0: holes of at
+        most n edges are closed before the smoothing (DESIGN.md "Mesh holes"); off by default."""
         if min_component_faces > 0 or keep_largest is not None:
             kw = dict(kw, min_component_faces=min_component_faces, keep_largest=keep_largest)
         if simplify_cell is not None and simplify_cell > 0:
@@ -184,6 +185,8 @@ class TSDFGlobalManager:
         if smooth_iterations is not None and smooth_iterations > 0:
             kw = dict(kw, smooth_iterations=smooth_iterations, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu,
                       smooth_boundary=smooth_boundary)
+        if fill_holes is not None and fill_holes > 0:
+            kw = dict(kw, fill_holes=fill_holes)
         if not colors and not kw:
             return self.volume.extract_mesh(min_weight=min_weight, level=level)
         return self.volume.extract_mesh(min_weight=min_weight, level=level, colors=colors, **kw)
