@@ -411,6 +411,66 @@ int mslam_mesh_holes_emit(const float* vertices, const float* colors, const int3
                           int num_vertices, int num_faces, int new_vertices, int new_faces, const double* centre,
                           float* out_vertices, float* out_normals, float* out_colors, int32_t* out_faces, void* stream);
 
+/* Mesh holes, bow-tie mode (DESIGN.md "Mesh holes", tests/bowtie_numpy.py): boundary darts are paired across the hole
+ * they bound, so that the rims of holes that meet in a vertex close.  Runs between mslam_mesh_holes_darts and
+ * mslam_mesh_holes_measure in place of link .. assign; measure and emit read the paired state.  state, labelled, rank and
+ * paired are i32[B,2], 8-byte aligned.  One lane per element, no atomics, every index read from memory is checked.
+ *   mslam_mesh_holes_dkeys        keys i64[3 F]: slot 3 f + c holds tail V + head of that directed edge of a counting
+ *                                 face, INT64_MAX in the three slots of any other face.  The caller sorts them, stable,
+ *                                 with the permutation (sorted_keys, key_order), gathers dart_key i64[B] = keys[dart] and
+ *                                 sorts that too: a dart's name is the position of its key there.
+ *   mslam_mesh_holes_fan          fan i32[B]: for the dart u -> v on face f, the rotation about v from f across interior
+ *                                 edges to the boundary dart that leaves v across the same hole, or -1.  An edge v -> w
+ *                                 is crossed only when it and w -> v occur exactly once among the keys; at most as many
+ *                                 steps as keys have the tail v.  The caller sorts fan (sorted_fan).
+ *   mslam_mesh_holes_claim        state[d] = (fan[d] when it occurs exactly once in sorted_fan, else -1; name of d).
+ *                                 mslam_mesh_holes_double on it gives labelled: p >= 0 exactly on the closed walks of
+ *                                 fan, m the walk's smallest name.
+ *   mslam_mesh_holes_rank_init    rank[d] = (fan[d], 1) on a closed walk, (-1, 1) when fan[d] is the walk's first dart
+ *                                 (the one whose name is the label), (-1, 0) off the walks.
+ *   mslam_mesh_holes_rank_double  one round of (p, c) -> (p of p, c + c of p), never in place: after r rounds with
+ *                                 2^r >= B, c is the number of steps to the walk's first dart, n for that dart itself.
+ *   mslam_mesh_holes_walk_keys    keys i64[B]: label B + (B - c), INT64_MAX off the walks.  Sorted by the caller with
+ *                                 the permutation (walk_order): by walk, then by rank.
+ *   mslam_mesh_holes_pair_keys    keys i64[B], slot j for the dart walk_order[j]: head B + label, INT64_MAX off the
+ *                                 walks.  Sorted by the caller, stable, with the permutation (pair_order): a run is the
+ *                                 darts of one walk into one vertex, by ascending rank.
+ *   mslam_mesh_holes_repair       paired[d_m] = (fan of d_(m-1 mod k), name of d_m) for the run d_0 .. d_(k-1) of the
+ *                                 slot, its ends found by binary search; (-1, name) off the walks.  Every row is
+ *                                 written.  mslam_mesh_holes_double on it gives the cycles of next and their labels.
+ *   mslam_mesh_holes_tail_keys    keys i64[B]: label V + tail on a cycle of next, INT64_MAX elsewhere.  The caller sorts.
+ *   mslam_mesh_holes_tail_flag    flag u8[B], zeroed by the caller: flag[label] = 1 when a sorted key equals the one
+ *                                 before it: that cycle has a vertex as a tail twice and stays open.
+ *   mslam_mesh_holes_loop_labels  mslam_mesh_holes_labels without the flagged cycles: the runs give loop_name i32[L],
+ *                                 the smallest dart name of every loop, ascending, and the lengths.
+ *   mslam_mesh_holes_loop_assign  dart_loop i32[B] as mslam_mesh_holes_assign; start, loop_id, loop_head i32[L]: the
+ *                                 dart whose name is the loop's, its tail and its head. */
+int mslam_mesh_holes_dkeys(const int32_t* faces, int num_faces, int num_vertices, int64_t* keys, void* stream);
+int mslam_mesh_holes_fan(const int32_t* faces, int num_faces, int num_vertices, const int32_t* dart,
+                         const int32_t* head, int num_darts, const int64_t* sorted_keys, const int64_t* key_order,
+                         int32_t* fan, void* stream);
+int mslam_mesh_holes_claim(const int32_t* fan, const int32_t* sorted_fan, const int64_t* dart_key,
+                           const int64_t* sorted_dart_key, int num_darts, int32_t* state, void* stream);
+int mslam_mesh_holes_rank_init(const int32_t* state, const int32_t* labelled, int num_darts, int32_t* rank,
+                               void* stream);
+int mslam_mesh_holes_rank_double(const int32_t* rank_in, int32_t* rank_out, int num_darts, void* stream);
+int mslam_mesh_holes_walk_keys(const int32_t* labelled, const int32_t* rank, int num_darts, int64_t* keys,
+                               void* stream);
+int mslam_mesh_holes_pair_keys(const int32_t* labelled, const int32_t* head, const int64_t* sorted_walk_keys,
+                               const int64_t* walk_order, int num_darts, int num_vertices, int64_t* keys, void* stream);
+int mslam_mesh_holes_repair(const int64_t* sorted_pair_keys, const int64_t* pair_order, const int64_t* walk_order,
+                            const int32_t* state, int num_darts, int32_t* paired, void* stream);
+int mslam_mesh_holes_tail_keys(const int32_t* labelled, const int32_t* tail, int num_darts, int num_vertices,
+                               int64_t* keys, void* stream);
+int mslam_mesh_holes_tail_flag(const int64_t* sorted_keys, int num_darts, int num_vertices, uint8_t* flag,
+                               void* stream);
+int mslam_mesh_holes_loop_labels(const int32_t* labelled, const uint8_t* flag, int num_darts, int32_t* keys,
+                                 void* stream);
+int mslam_mesh_holes_loop_assign(const int32_t* labelled, const int32_t* paired, const uint8_t* flag,
+                                 const int32_t* tail, const int32_t* head, int num_darts, const int32_t* loop_name,
+                                 int num_loops, int32_t* dart_loop, int32_t* start, int32_t* loop_id,
+                                 int32_t* loop_head, void* stream);
+
 /* Mesh quality: face areas, a surface sampler and the exact point-to-mesh distance (no counterpart in the reference,
  * DESIGN.md "Mesh quality").  vertices f32[V,3], faces i32[F,3]; every index is checked against [0, V) before use.  A
  * face is valid when its indices are in range and (b - a) x (c - a), in f64, is not exactly zero; an invalid face has

@@ -296,6 +296,242 @@ __global__ __launch_bounds__(256) void mh_emit_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Bow-tie mode (DESIGN.md "Mesh holes", tests/bowtie_numpy.py): boundary darts are paired across the hole they bound, so
+// the rims of holes that meet in a vertex close.  Between keys .. darts above and measure, emit above:
+//   dkeys    one thread per face: the directed edge keys tail V + head of a counting face in dart order, INT64_MAX else.
+//   (caller)   sorts them, stable, with the permutation; gathers the keys of the boundary darts and sorts those too.
+//   fan      one thread per boundary dart u -> v: rotates about v, from the dart's face across interior edges, until the
+//            edge after the one it came in by is a boundary dart: fan(d).  An edge is crossed only when it and its reverse
+//            occur exactly once among the sorted keys; at most as many steps as keys have the tail v.
+//   (caller)   sorts the successors.
+//   claim    one thread per boundary dart: state = (fan(d) when nobody else claims it, else none; name), name = the
+//            position of the dart's key among the sorted keys of the boundary darts.
+//   double   as above: ptr >= 0 exactly on the closed walks of fan, lab = the walk's smallest name.
+//   rank_init, rank_double   a second pointer doubling over (successor, steps), cut in front of the walk's first dart:
+//            steps becomes the distance to that dart along fan, n for the first dart itself, so n - steps is the rank.
+//   walk_keys  label B + (B - steps): the order by (walk, rank).  (caller) sorts with the permutation.
+//   pair_keys  in that order, head B + label.  (caller) sorts, stable: runs of one (head, walk) by ascending rank.
+//   repair   one thread per sorted slot: the ends of its run by binary search, next(d_m) = fan(d_(m-1 mod k)).
+//   double   on (next, name): the cycles of next and their smallest names.
+//   tail_keys, tail_flag   label V + tail, sorted by the caller; a repeated key stores 1 to the flag of that label (many
+//            lanes may store the same byte; nobody reads it in that launch).
+//   loop_labels, loop_assign   as labels and assign, without the flagged cycles, the first dart found by its name.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void mh_dkeys_kernel(const int32_t* __restrict__ faces, int nf, int nv,
+                                                       int64_t* __restrict__ keys) {
+  const int f = blockIdx.x * 256 + threadIdx.x;
+  if (f >= nf) return;
+  const int a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
+  const bool ok = mh_counts(a, b, c, nv);
+  int64_t* k = keys + 3 * (size_t)f;
+  k[0] = ok ? (int64_t)a * nv + b : kMhNoKey;
+  k[1] = ok ? (int64_t)b * nv + c : kMhNoKey;
+  k[2] = ok ? (int64_t)c * nv + a : kMhNoKey;
+}
+
+// the first position of `sorted` (ascending, n entries) that is >= v
+__device__ __forceinline__ int64_t mh_lower64(const int64_t* __restrict__ sorted, int64_t n, int64_t v) {
+  int64_t lo = 0, hi = n;
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (sorted[mid] < v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// the position of v in `sorted` when it occurs exactly once, else -1
+__device__ __forceinline__ int64_t mh_once64(const int64_t* __restrict__ sorted, int64_t n, int64_t v) {
+  const int64_t p = mh_lower64(sorted, n, v);
+  if (p >= n || sorted[p] != v) return -1;
+  return (p + 1 < n && sorted[p + 1] == v) ? -1 : p;
+}
+
+__global__ __launch_bounds__(256) void mh_fan_kernel(const int32_t* __restrict__ faces, int nf, int nv,
+                                                     const int32_t* __restrict__ dart,
+                                                     const int32_t* __restrict__ head, int nb,
+                                                     const int64_t* __restrict__ sorted_keys,
+                                                     const int64_t* __restrict__ key_order, int32_t* __restrict__ fan) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nb) return;
+  const int64_t n = 3 * (int64_t)nf;
+  const int v = head[i];
+  int64_t s = dart[i];
+  int out = -1;
+  if ((uint64_t)s < (uint64_t)n && (unsigned)v < (unsigned)nv) {
+    const int64_t row = (int64_t)v * nv;
+    const int64_t bound = mh_lower64(sorted_keys, n, row + nv) - mh_lower64(sorted_keys, n, row);
+    for (int64_t step = 0; step < bound; step++) {
+      const int64_t f = s / 3;
+      const int c = (int)(s - 3 * f), c1 = c == 2 ? 0 : c + 1, c2 = c1 == 2 ? 0 : c1 + 1;
+      const int w = faces[3 * f + c2];
+      if (faces[3 * f + c1] != v || (unsigned)w >= (unsigned)nv) break;    // the edge after s in its face is v -> w
+      const int p = mh_once(dart, nb, (int)(3 * f + c1));
+      if (p >= 0) { out = p; break; }
+      const int64_t q = mh_once64(sorted_keys, n, (int64_t)w * nv + v);
+      if (q < 0 || mh_once64(sorted_keys, n, row + w) < 0) break;
+      s = key_order[q];
+      if ((uint64_t)s >= (uint64_t)n) break;
+    }
+  }
+  fan[i] = out;
+}
+
+__global__ __launch_bounds__(256) void mh_claim_kernel(const int32_t* __restrict__ fan,
+                                                       const int32_t* __restrict__ sorted_fan,
+                                                       const int64_t* __restrict__ dart_key,
+                                                       const int64_t* __restrict__ sorted_dart_key, int nb,
+                                                       int2* __restrict__ state) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nb) return;
+  const int s = fan[i];
+  const bool mine = (unsigned)s < (unsigned)nb && mh_once(sorted_fan, nb, s) >= 0;
+  state[i] = make_int2(mine ? s : -1, (int)mh_lower64(sorted_dart_key, nb, dart_key[i]));
+}
+
+__global__ __launch_bounds__(256) void mh_rank_init_kernel(const int2* __restrict__ state,
+                                                           const int2* __restrict__ labelled, int nb,
+                                                           int2* __restrict__ rank) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nb) return;
+  int2 r = make_int2(-1, 0);
+  const int s = state[i].x;
+  if (labelled[i].x >= 0 && (unsigned)s < (unsigned)nb) {
+    r.y = 1;
+    if (state[s].y != labelled[i].y) r.x = s;             // the walk's first dart carries the label as its name
+  }
+  rank[i] = r;
+}
+
+__global__ __launch_bounds__(256) void mh_rank_double_kernel(const int2* __restrict__ rank_in,
+                                                             int2* __restrict__ rank_out, int nb) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nb) return;
+  int2 r = rank_in[i];
+  if ((unsigned)r.x < (unsigned)nb) {
+    const int2 t = rank_in[r.x];
+    r.x = (unsigned)t.x < (unsigned)nb ? t.x : -1;
+    r.y = (int)min((int64_t)r.y + (int64_t)t.y, (int64_t)nb + 1);
+  } else {
+    r.x = -1;
+  }
+  rank_out[i] = r;
+}
+
+__global__ __launch_bounds__(256) void mh_walk_keys_kernel(const int2* __restrict__ labelled,
+                                                           const int2* __restrict__ rank, int nb,
+                                                           int64_t* __restrict__ keys) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nb) return;
+  const int2 l = labelled[i];
+  const int steps = rank[i].y;
+  const bool ok = l.x >= 0 && (unsigned)l.y < (unsigned)nb && steps >= 1 && steps <= nb;
+  keys[i] = ok ? (int64_t)l.y * nb + (nb - steps) : kMhNoKey;
+}
+
+__global__ __launch_bounds__(256) void mh_pair_keys_kernel(const int2* __restrict__ labelled,
+                                                           const int32_t* __restrict__ head,
+                                                           const int64_t* __restrict__ sorted_walk_keys,
+                                                           const int64_t* __restrict__ walk_order, int nb, int nv,
+                                                           int64_t* __restrict__ keys) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= nb) return;
+  const int64_t d = walk_order[j];
+  int64_t k = kMhNoKey;
+  if (sorted_walk_keys[j] != kMhNoKey && (uint64_t)d < (uint64_t)nb) {
+    const int h = head[d], l = labelled[d].y;
+    if ((unsigned)h < (unsigned)nv && (unsigned)l < (unsigned)nb) k = (int64_t)h * nb + l;
+  }
+  keys[j] = k;
+}
+
+// the dart in slot j of the order by (head, walk, rank), or -1
+__device__ __forceinline__ int mh_slot_dart(const int64_t* __restrict__ pair_order,
+                                            const int64_t* __restrict__ walk_order, int64_t j, int nb) {
+  const int64_t a = pair_order[j];
+  if ((uint64_t)a >= (uint64_t)nb) return -1;
+  const int64_t d = walk_order[a];
+  return (uint64_t)d < (uint64_t)nb ? (int)d : -1;
+}
+
+__global__ __launch_bounds__(256) void mh_repair_kernel(const int64_t* __restrict__ sorted_pair_keys,
+                                                        const int64_t* __restrict__ pair_order,
+                                                        const int64_t* __restrict__ walk_order,
+                                                        const int2* __restrict__ state, int nb,
+                                                        int2* __restrict__ paired) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= nb) return;
+  const int d = mh_slot_dart(pair_order, walk_order, j, nb);
+  if (d < 0) return;
+  const int64_t k = sorted_pair_keys[j];
+  int nxt = -1;
+  if (k != kMhNoKey) {
+    const int64_t lo = mh_lower64(sorted_pair_keys, nb, k), hi = mh_lower64(sorted_pair_keys, nb, k + 1);
+    const int64_t prev = j == lo ? hi - 1 : (int64_t)j - 1;
+    const int dp = prev >= 0 && prev < nb ? mh_slot_dart(pair_order, walk_order, prev, nb) : -1;
+    if (dp >= 0) {
+      const int s = state[dp].x;
+      if ((unsigned)s < (unsigned)nb) nxt = s;
+    }
+  }
+  paired[d] = make_int2(nxt, state[d].y);
+}
+
+__global__ __launch_bounds__(256) void mh_tail_keys_kernel(const int2* __restrict__ labelled,
+                                                           const int32_t* __restrict__ tail, int nb, int nv,
+                                                           int64_t* __restrict__ keys) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nb) return;
+  const int2 l = labelled[i];
+  const int t = tail[i];
+  const bool ok = l.x >= 0 && (unsigned)l.y < (unsigned)nb && (unsigned)t < (unsigned)nv;
+  keys[i] = ok ? (int64_t)l.y * nv + t : kMhNoKey;
+}
+
+__global__ __launch_bounds__(256) void mh_tail_flag_kernel(const int64_t* __restrict__ sorted_keys, int nb, int nv,
+                                                           uint8_t* __restrict__ flag) {
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= nb || j == 0) return;
+  const int64_t k = sorted_keys[j];
+  if (k == kMhNoKey || sorted_keys[j - 1] != k) return;
+  const int64_t l = k / nv;
+  if ((uint64_t)l < (uint64_t)nb) flag[l] = 1;
+}
+
+__global__ __launch_bounds__(256) void mh_loop_labels_kernel(const int2* __restrict__ labelled,
+                                                             const uint8_t* __restrict__ flag, int nb,
+                                                             int32_t* __restrict__ keys) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i > nb) return;
+  int32_t k = kMhNoLabel;
+  if (i < nb) {
+    const int2 s = labelled[i];
+    if (s.x >= 0 && (unsigned)s.y < (unsigned)nb && !flag[s.y]) k = s.y;
+  }
+  keys[i] = k;
+}
+
+__global__ __launch_bounds__(256) void mh_loop_assign_kernel(
+    const int2* __restrict__ labelled, const int2* __restrict__ paired, const uint8_t* __restrict__ flag,
+    const int32_t* __restrict__ tail, const int32_t* __restrict__ head, int nb, const int32_t* __restrict__ loop_name,
+    int nl, int32_t* __restrict__ dart_loop, int32_t* __restrict__ start, int32_t* __restrict__ loop_id,
+    int32_t* __restrict__ loop_head) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= nb) return;
+  const int2 s = labelled[i];
+  int l = -1;
+  if (s.x >= 0 && (unsigned)s.y < (unsigned)nb && !flag[s.y]) {
+    const int p = mh_lower(loop_name, nl, s.y);
+    if (p < nl && loop_name[p] == s.y) l = p;
+  }
+  dart_loop[i] = l;
+  if (l >= 0 && paired[i].y == s.y) {                     // names are distinct: one dart of the loop has this one
+    start[l] = i;
+    loop_id[l] = tail[i];
+    loop_head[l] = head[i];
+  }
+}
+
 }  // namespace mslam
 
 using namespace mslam;
@@ -423,5 +659,155 @@ extern "C" int mslam_mesh_holes_emit(const float* vertices, const float* colors,
             start, length, fillable, vertex_base, face_base, num_loops, num_vertices, num_faces, new_vertices,
             new_faces, centre, out_vertices, out_normals, out_colors, out_faces);
   MSLAM_LAUNCH_CHECK("mesh_holes_emit");
+  return MSLAM_OK;
+}
+
+// ---- bow-tie mode ----------------------------------------------------------------------------------------------------
+#define MH_STATE(p) reinterpret_cast<const int2*>(p)
+#define MH_ALIGNED(p) ((uintptr_t)(p) % 8 == 0)
+
+extern "C" int mslam_mesh_holes_dkeys(const int32_t* faces, int num_faces, int num_vertices, int64_t* keys,
+                                      void* stream) {
+  MSLAM_REQUIRE(num_faces >= 0 && num_vertices >= 0, "mesh_holes_dkeys: negative size");
+  MSLAM_REQUIRE((int64_t)num_faces * 3 < ((int64_t)1 << 31), "mesh_holes_dkeys: too many faces");
+  if (num_faces == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(faces && keys, "mesh_holes_dkeys: null pointer");
+  MH_LAUNCH(mh_dkeys_kernel, num_faces, faces, num_faces, num_vertices, keys);
+  MSLAM_LAUNCH_CHECK("mesh_holes_dkeys");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_mesh_holes_fan(const int32_t* faces, int num_faces, int num_vertices, const int32_t* dart,
+                                    const int32_t* head, int num_darts, const int64_t* sorted_keys,
+                                    const int64_t* key_order, int32_t* fan, void* stream) {
+  MSLAM_REQUIRE(num_faces >= 0 && num_vertices >= 0 && num_darts >= 0, "mesh_holes_fan: negative size");
+  MSLAM_REQUIRE((int64_t)num_faces * 3 < ((int64_t)1 << 31), "mesh_holes_fan: too many faces");
+  if (num_darts == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(dart && head && fan && (num_faces == 0 || (faces && sorted_keys && key_order)),
+                "mesh_holes_fan: null pointer");
+  MH_LAUNCH(mh_fan_kernel, num_darts, faces, num_faces, num_vertices, dart, head, num_darts, sorted_keys, key_order,
+            fan);
+  MSLAM_LAUNCH_CHECK("mesh_holes_fan");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_mesh_holes_claim(const int32_t* fan, const int32_t* sorted_fan, const int64_t* dart_key,
+                                      const int64_t* sorted_dart_key, int num_darts, int32_t* state, void* stream) {
+  MSLAM_REQUIRE(num_darts >= 0, "mesh_holes_claim: negative size");
+  if (num_darts == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(fan && sorted_fan && dart_key && sorted_dart_key && state, "mesh_holes_claim: null pointer");
+  MSLAM_REQUIRE(MH_ALIGNED(state), "mesh_holes_claim: state must be 8-byte aligned");
+  MH_LAUNCH(mh_claim_kernel, num_darts, fan, sorted_fan, dart_key, sorted_dart_key, num_darts,
+            reinterpret_cast<int2*>(state));
+  MSLAM_LAUNCH_CHECK("mesh_holes_claim");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_mesh_holes_rank_init(const int32_t* state, const int32_t* labelled, int num_darts, int32_t* rank,
+                                          void* stream) {
+  MSLAM_REQUIRE(num_darts >= 0, "mesh_holes_rank_init: negative size");
+  if (num_darts == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(state && labelled && rank, "mesh_holes_rank_init: null pointer");
+  MSLAM_REQUIRE(MH_ALIGNED(state) && MH_ALIGNED(labelled) && MH_ALIGNED(rank),
+                "mesh_holes_rank_init: states must be 8-byte aligned");
+  MH_LAUNCH(mh_rank_init_kernel, num_darts, MH_STATE(state), MH_STATE(labelled), num_darts,
+            reinterpret_cast<int2*>(rank));
+  MSLAM_LAUNCH_CHECK("mesh_holes_rank_init");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_mesh_holes_rank_double(const int32_t* rank_in, int32_t* rank_out, int num_darts, void* stream) {
+  MSLAM_REQUIRE(num_darts >= 0, "mesh_holes_rank_double: negative size");
+  if (num_darts == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(rank_in && rank_out && rank_in != rank_out, "mesh_holes_rank_double: null pointer or out == in");
+  MSLAM_REQUIRE(MH_ALIGNED(rank_in) && MH_ALIGNED(rank_out), "mesh_holes_rank_double: states must be 8-byte aligned");
+  MH_LAUNCH(mh_rank_double_kernel, num_darts, MH_STATE(rank_in), reinterpret_cast<int2*>(rank_out), num_darts);
+  MSLAM_LAUNCH_CHECK("mesh_holes_rank_double");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_mesh_holes_walk_keys(const int32_t* labelled, const int32_t* rank, int num_darts, int64_t* keys,
+                                          void* stream) {
+  MSLAM_REQUIRE(num_darts >= 0, "mesh_holes_walk_keys: negative size");
+  if (num_darts == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(labelled && rank && keys, "mesh_holes_walk_keys: null pointer");
+  MSLAM_REQUIRE(MH_ALIGNED(labelled) && MH_ALIGNED(rank), "mesh_holes_walk_keys: states must be 8-byte aligned");
+  MH_LAUNCH(mh_walk_keys_kernel, num_darts, MH_STATE(labelled), MH_STATE(rank), num_darts, keys);
+  MSLAM_LAUNCH_CHECK("mesh_holes_walk_keys");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_mesh_holes_pair_keys(const int32_t* labelled, const int32_t* head,
+                                          const int64_t* sorted_walk_keys, const int64_t* walk_order, int num_darts,
+                                          int num_vertices, int64_t* keys, void* stream) {
+  MSLAM_REQUIRE(num_darts >= 0 && num_vertices >= 0, "mesh_holes_pair_keys: negative size");
+  if (num_darts == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(labelled && head && sorted_walk_keys && walk_order && keys, "mesh_holes_pair_keys: null pointer");
+  MSLAM_REQUIRE(MH_ALIGNED(labelled), "mesh_holes_pair_keys: state must be 8-byte aligned");
+  MH_LAUNCH(mh_pair_keys_kernel, num_darts, MH_STATE(labelled), head, sorted_walk_keys, walk_order, num_darts,
+            num_vertices, keys);
+  MSLAM_LAUNCH_CHECK("mesh_holes_pair_keys");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_mesh_holes_repair(const int64_t* sorted_pair_keys, const int64_t* pair_order,
+                                       const int64_t* walk_order, const int32_t* state, int num_darts, int32_t* paired,
+                                       void* stream) {
+  MSLAM_REQUIRE(num_darts >= 0, "mesh_holes_repair: negative size");
+  if (num_darts == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(sorted_pair_keys && pair_order && walk_order && state && paired && state != paired,
+                "mesh_holes_repair: null pointer or out == in");
+  MSLAM_REQUIRE(MH_ALIGNED(state) && MH_ALIGNED(paired), "mesh_holes_repair: states must be 8-byte aligned");
+  MH_LAUNCH(mh_repair_kernel, num_darts, sorted_pair_keys, pair_order, walk_order, MH_STATE(state), num_darts,
+            reinterpret_cast<int2*>(paired));
+  MSLAM_LAUNCH_CHECK("mesh_holes_repair");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_mesh_holes_tail_keys(const int32_t* labelled, const int32_t* tail, int num_darts, int num_vertices,
+                                          int64_t* keys, void* stream) {
+  MSLAM_REQUIRE(num_darts >= 0 && num_vertices >= 0, "mesh_holes_tail_keys: negative size");
+  if (num_darts == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(labelled && tail && keys, "mesh_holes_tail_keys: null pointer");
+  MSLAM_REQUIRE(MH_ALIGNED(labelled), "mesh_holes_tail_keys: state must be 8-byte aligned");
+  MH_LAUNCH(mh_tail_keys_kernel, num_darts, MH_STATE(labelled), tail, num_darts, num_vertices, keys);
+  MSLAM_LAUNCH_CHECK("mesh_holes_tail_keys");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_mesh_holes_tail_flag(const int64_t* sorted_keys, int num_darts, int num_vertices, uint8_t* flag,
+                                          void* stream) {
+  MSLAM_REQUIRE(num_darts >= 0 && num_vertices >= 0, "mesh_holes_tail_flag: negative size");
+  if (num_darts == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(num_vertices > 0, "mesh_holes_tail_flag: darts without vertices");
+  MSLAM_REQUIRE(sorted_keys && flag, "mesh_holes_tail_flag: null pointer");
+  MH_LAUNCH(mh_tail_flag_kernel, num_darts, sorted_keys, num_darts, num_vertices, flag);
+  MSLAM_LAUNCH_CHECK("mesh_holes_tail_flag");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_mesh_holes_loop_labels(const int32_t* labelled, const uint8_t* flag, int num_darts, int32_t* keys,
+                                            void* stream) {
+  MSLAM_REQUIRE(num_darts >= 0 && num_darts < INT32_MAX, "mesh_holes_loop_labels: size outside [0, 2^31 - 1)");
+  MSLAM_REQUIRE(keys && ((labelled && flag) || num_darts == 0), "mesh_holes_loop_labels: null pointer");
+  MSLAM_REQUIRE(MH_ALIGNED(labelled), "mesh_holes_loop_labels: state must be 8-byte aligned");
+  MH_LAUNCH(mh_loop_labels_kernel, (int64_t)num_darts + 1, MH_STATE(labelled), flag, num_darts, keys);
+  MSLAM_LAUNCH_CHECK("mesh_holes_loop_labels");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_mesh_holes_loop_assign(const int32_t* labelled, const int32_t* paired, const uint8_t* flag,
+                                            const int32_t* tail, const int32_t* head, int num_darts,
+                                            const int32_t* loop_name, int num_loops, int32_t* dart_loop, int32_t* start,
+                                            int32_t* loop_id, int32_t* loop_head, void* stream) {
+  MSLAM_REQUIRE(num_darts >= 0 && num_loops >= 0, "mesh_holes_loop_assign: negative size");
+  if (num_darts == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(labelled && paired && flag && tail && head && dart_loop &&
+                    (num_loops == 0 || (loop_name && start && loop_id && loop_head)),
+                "mesh_holes_loop_assign: null pointer");
+  MSLAM_REQUIRE(MH_ALIGNED(labelled) && MH_ALIGNED(paired), "mesh_holes_loop_assign: states must be 8-byte aligned");
+  MH_LAUNCH(mh_loop_assign_kernel, num_darts, MH_STATE(labelled), MH_STATE(paired), flag, tail, head, num_darts,
+            loop_name, num_loops, dart_loop, start, loop_id, loop_head);
+  MSLAM_LAUNCH_CHECK("mesh_holes_loop_assign");
   return MSLAM_OK;
 }

@@ -42,6 +42,7 @@ _BASE = {
         "mesh_simplify_voxels": 0.0,     # ... and simplifies on cells of this many voxels, 0 = off ("Mesh simplification")
         "mesh_smooth_iterations": 0,     # ... after this many Taubin iterations, 0 = off ("Mesh smoothing")
         "mesh_fill_holes": 0,            # ... after closing holes of at most this many edges, 0 = off ("Mesh holes")
+        "mesh_fill_bowties": False,      # ... those that meet in a vertex included (bow-tie mode of "Mesh holes")
         "mesh_eval_threshold": 0.05,     # SlamSystem.evaluate_mesh: precision / recall distance (DESIGN.md "Mesh quality")
     },
 }

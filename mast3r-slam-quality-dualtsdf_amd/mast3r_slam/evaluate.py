@@ -232,7 +232,7 @@ def save_render_metrics(savedir, filename, metrics):
 
 def save_tsdf_mesh(savedir, filename, source, min_weight=None, level=0.0, colors=False, min_component_faces=0,
                    keep_largest=None, simplify_cell=0.0, simplify_position="quadric", smooth_iterations=0,
-                   smooth_lambda=0.5, smooth_mu=-0.53, smooth_boundary="fixed", fill_holes=0):
+                   smooth_lambda=0.5, smooth_mu=-0.53, smooth_boundary="fixed", fill_holes=0, **fill_options):
     """The global TSDF's triangle mesh (marching cubes) as PLY with normals, beside save_reconstruction's point cloud.
     `source`: a SlamSystem, a TSDFGlobalManager or a TSDFVolume.  `colors=True` (a volume with tsdf_global.color): the
     vertices carry the fused colour as red / green / blue.  `min_component_faces` > 0 / `keep_largest`: small connected
@@ -240,7 +240,11 @@ def save_tsdf_mesh(savedir, filename, source, min_weight=None, level=0.0, colors
     `simplify_position`: the mesh is then simplified by vertex clustering (DESIGN.md "Mesh simplification").
     `smooth_iterations` > 0 / `smooth_lambda`, `smooth_mu`, `smooth_boundary`: Taubin smoothing between the two (DESIGN.md
     "Mesh smoothing").  `fill_holes` = n > 0: holes of at most n edges are closed before the smoothing (DESIGN.md "Mesh
-    holes").  Returns (V, F)."""
+    holes"); `fill_bowties=True` (the one keyword `fill_options` takes): holes that meet in a vertex too.  Returns
+    (V, F)."""
+    from mast3r_slam.tsdf._mesh_args import _fill_options
+
+    fill_bowties = _fill_options(fill_options, "save_tsdf_mesh")
     savedir = pathlib.Path(savedir)
     savedir.mkdir(exist_ok=True, parents=True)
     kw = {}
@@ -252,7 +256,7 @@ def save_tsdf_mesh(savedir, filename, source, min_weight=None, level=0.0, colors
         kw = dict(kw, smooth_iterations=smooth_iterations, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu,
                   smooth_boundary=smooth_boundary)
     if fill_holes is not None and fill_holes > 0:
-        kw = dict(kw, fill_holes=fill_holes)
+        kw = dict(kw, fill_holes=fill_holes, **(dict(fill_bowties=True) if fill_bowties else {}))
     if colors:
         v, n, f, c = source.extract_mesh(min_weight=min_weight, level=level, colors=True, **kw)
         save_mesh(savedir / filename, v, f, normals=n, colors=c)

@@ -368,7 +368,7 @@ class SlamSystem:
         tsdf_global.mesh_smooth_iterations, 0 = off) / `smooth_lambda`, `smooth_mu`, `smooth_boundary`: Taubin smoothing
         after the component filter and before the simplification (DESIGN.md "Mesh smoothing").  `fill_holes` (default
         tsdf_global.mesh_fill_holes, 0 = off): holes of at most that many edges are closed before the smoothing (DESIGN.md
-        "Mesh holes")."""
+        "Mesh holes"); `fill_bowties` (in `kw`; default tsdf_global.mesh_fill_bowties, off): holes that meet in a vertex too."""
         if self.tsdf_manager is None:
             raise RuntimeError("SlamSystem.extract_mesh: the global TSDF is disabled (tsdf_global.enabled = False)")
         if min_component_faces is None:
@@ -380,6 +380,10 @@ class SlamSystem:
             smooth_iterations = int(self.tsdf_manager.cfg.get("mesh_smooth_iterations", 0))
         if fill_holes is None:
             fill_holes = int(self.tsdf_manager.cfg.get("mesh_fill_holes", 0))
+        if kw.get("fill_bowties") is None:                     # the config's switch; off adds nothing to the call
+            kw = {k: v for k, v in kw.items() if k != "fill_bowties"}
+            if self.tsdf_manager.cfg.get("mesh_fill_bowties", False):
+                kw["fill_bowties"] = True
         self.drain()
         return self.tsdf_manager.extract_mesh(min_weight=min_weight, level=level, colors=colors,
                                               min_component_faces=min_component_faces, keep_largest=keep_largest,

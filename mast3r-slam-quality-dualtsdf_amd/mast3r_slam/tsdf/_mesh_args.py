@@ -60,6 +60,22 @@ def _mesh_tuple_arg(mesh, what, check=True, on_device=False):
     return verts, normals, faces, colors, per_vertex
 
 
+def _bool_arg(value, name, what):
+    """A switch such as fill_holes' `bowties` / extract_mesh's `fill_bowties`: a bool (numpy's too), nothing else."""
+    if not isinstance(value, (bool, np.bool_)):
+        raise ValueError(f"{what}: {name} must be a bool, got {value!r}")
+    return bool(value)
+
+
+def _fill_options(options, what):
+    """The keywords that may follow `fill_holes` in extract_mesh, mesh_from_voxels and save_tsdf_mesh, as the dict their
+    `**fill_options` caught -> fill_bowties.  Any other name raises the TypeError a def would."""
+    for name in options:
+        if name != "fill_bowties":
+            raise TypeError(f"{what}() got an unexpected keyword argument {name!r}")
+    return _bool_arg(options.get("fill_bowties", False), "fill_bowties", what)
+
+
 def _ranges(verts, faces):
     """(lowest and highest coordinate, lowest and highest face index, all coordinates finite) of a non-empty mesh as
     Python floats: one stacked reduction, one host read."""

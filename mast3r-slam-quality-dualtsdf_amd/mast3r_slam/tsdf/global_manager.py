@@ -17,6 +17,8 @@ import torch
 from lietorch_hip import Sim3
 from mast3r_slam.config import config
 
+from ._mesh_args import _bool_arg
+
 
 def gather_uimg(uimg, choice, map_hw):
     """Colours f32[n,3] of the pointmap pixels `choice` (linear indices, device) from the keyframe image `uimg`
@@ -177,7 +179,10 @@ class TSDFGlobalManager:
         > 0 (world units) / `simplify_position`: simplify the result by vertex clustering (DESIGN.md "Mesh
         simplification"); off by default.  `smooth_iterations` > 0 / `smooth_lambda`, `smooth_mu`, `smooth_boundary`:
         Taubin smoothing between the two (DESIGN.md "Mesh smoothing"); off by default.  `fill_holes` = n > 0: holes of at
-        most n edges are closed before the smoothing (DESIGN.md "Mesh holes"); off by default."""
+        most n edges are closed before the smoothing (DESIGN.md "Mesh holes"); off by default.  `fill_bowties=True`
+        (in `kw`): holes that meet in a vertex are closed too; it does nothing without `fill_holes`."""
+        kw = dict(kw)
+        fill_bowties = _bool_arg(kw.pop("fill_bowties", False), "fill_bowties", "TSDFGlobalManager.extract_mesh")
         if min_component_faces > 0 or keep_largest is not None:
             kw = dict(kw, min_component_faces=min_component_faces, keep_largest=keep_largest)
         if simplify_cell is not None and simplify_cell > 0:
@@ -186,7 +191,7 @@ class TSDFGlobalManager:
             kw = dict(kw, smooth_iterations=smooth_iterations, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu,
                       smooth_boundary=smooth_boundary)
         if fill_holes is not None and fill_holes > 0:
-            kw = dict(kw, fill_holes=fill_holes)
+            kw = dict(kw, fill_holes=fill_holes, **(dict(fill_bowties=True) if fill_bowties else {}))
         if not colors and not kw:
             return self.volume.extract_mesh(min_weight=min_weight, level=level)
         return self.volume.extract_mesh(min_weight=min_weight, level=level, colors=colors, **kw)

@@ -13,6 +13,7 @@ import torch
 
 import mslam_hip as _m
 
+from ._mesh_args import _fill_options
 from .mesh_ops import filter_mesh
 from .mesh_simplify import simplify_mesh
 from .mesh_holes import fill_holes as _fill_holes
@@ -352,7 +353,8 @@ class TSDFVolume:
 
     def extract_mesh(self, min_weight=None, level=0.0, colors=False, default_color=(0.5, 0.5, 0.5),
                      min_component_faces=0, keep_largest=None, simplify_cell=0.0, simplify_position="quadric",
-                     smooth_iterations=0, smooth_lambda=0.5, smooth_mu=-0.53, smooth_boundary="fixed", fill_holes=0):
+                     smooth_iterations=0, smooth_lambda=0.5, smooth_mu=-0.53, smooth_boundary="fixed", fill_holes=0,
+                     **fill_options):
         """Marching cubes over the fused volume -> (vertices f32[V,3], normals f32[V,3], faces i32[F,3]) device tensors in
         canonical order (DESIGN.md "Mesh extraction").  Corners are voxel centres with weight >= min_weight (default
         self.min_weight), inside = tsdf < level, normals point to free space, faces are counter-clockwise seen from
@@ -370,9 +372,12 @@ class TSDFVolume:
         the simplification, whose plane quadrics then see the smoothed surface; normals are recomputed.
         `fill_holes` = n > 0: boundary loops of at most n edges that are holes are closed with a centroid fan
         (mesh_holes.fill_holes, DESIGN.md "Mesh holes"; four more host reads) after the component filter and before the
-        smoothing, which then fairs the patches."""
+        smoothing, which then fairs the patches.  `fill_bowties=True` (the one keyword `fill_options` takes): holes that
+        meet in a vertex, as two diagonal missing voxels leave them, are told apart and closed too (fill_holes' bow-tie
+        mode; no further host read); without `fill_holes` it does nothing."""
+        fill_bowties = _fill_options(fill_options, "TSDFVolume.extract_mesh")
         smooth = dict(smooth_iterations=smooth_iterations, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu,
-                      smooth_boundary=smooth_boundary, fill_holes=fill_holes)
+                      smooth_boundary=smooth_boundary, fill_holes=fill_holes, fill_bowties=fill_bowties)
         mw = self.min_weight if min_weight is None else float(min_weight)
         if colors and not self.color:
             raise ValueError("TSDFVolume.extract_mesh: colors=True needs a volume built with color=True")
@@ -391,7 +396,7 @@ class TSDFVolume:
             mesh = mesh + (_sample_color(self._table, self.capacity, self._color, mesh[0], 0, self.voxel_size,
                                          default_color)[0],)
         mesh = filter_mesh(mesh, min_component_faces, keep_largest, _validate=False)
-        mesh = _fill_holes(mesh, fill_holes)                                # off (None or <= 0): `mesh` itself
+        mesh = _fill_holes(mesh, fill_holes, bowties=fill_bowties)          # off (None or <= 0): `mesh` itself
         mesh = smooth_mesh(mesh, smooth_iterations, smooth_lambda, smooth_mu, smooth_boundary)       # off: `mesh` itself
         return simplify_mesh(mesh, simplify_cell, simplify_position)        # off (None or <= 0): `mesh` itself
 
@@ -583,7 +588,7 @@ def render_from_voxels(keys, tsdf, weight, voxel_size, min_weight, pose, rays, n
 def mesh_from_voxels(keys, tsdf, weight, voxel_size, min_weight, level=0.0, device="cuda", colors=None,
                      default_color=(0.5, 0.5, 0.5), min_component_faces=0, keep_largest=None, simplify_cell=0.0,
                      simplify_position="quadric", smooth_iterations=0, smooth_lambda=0.5, smooth_mu=-0.53,
-                     smooth_boundary="fixed", fill_holes=0):
+                     smooth_boundary="fixed", fill_holes=0, **fill_options):
     """Mesh of a voxel set given as arrays (keys i64[n,3] distinct, tsdf f64[n], weight f64[n]; numpy or device): loads
     a temporary table of at least 2n slots and extracts from it (TSDFVolume.extract_mesh semantics, its component filter,
     its hole filling, its smoothing and its simplification included).  `colors` u64[n,4]: the voxels' colour sums
@@ -593,4 +598,4 @@ def mesh_from_voxels(keys, tsdf, weight, voxel_size, min_weight, level=0.0, devi
                             min_component_faces=min_component_faces, keep_largest=keep_largest,
                             simplify_cell=simplify_cell, simplify_position=simplify_position,
                             smooth_iterations=smooth_iterations, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu,
-                            smooth_boundary=smooth_boundary, fill_holes=fill_holes)
+                            smooth_boundary=smooth_boundary, fill_holes=fill_holes, **fill_options)

@@ -2,7 +2,8 @@
 
 No counterpart in the reference.  The kernels are csrc/mesh_holes.hip (DESIGN.md "Mesh holes"); the numpy statement of
 the same definitions is tests/holes_numpy.py.  torch sorts and scans, the kernels do the rest.  Works on any welded mesh,
-not only on what extract_mesh returns.
+not only on what extract_mesh returns.  `bowties=True` pairs the boundary darts across the hole they bound, so that holes
+which meet in a vertex are loops of their own (_pair, _named_loops; tests/bowtie_numpy.py); it adds no host read.
 """
 import operator
 
@@ -10,7 +11,8 @@ import torch
 
 import mslam_hip as _m
 
-from ._mesh_args import _check_face_range, _check_finite, _faces_arg, _mesh_arg, _mesh_tuple_arg, _ranges
+from ._mesh_args import (_bool_arg, _check_face_range, _check_finite, _faces_arg, _mesh_arg, _mesh_tuple_arg,
+                         _ranges)
 
 _I32_MAX = (1 << 31) - 1
 
@@ -93,6 +95,95 @@ def _trace(faces, V, F):
                 start=start, n_open=n_open)
 
 
+def _double_ranks(rank, rounds):
+    """`rounds` rounds of the (successor, steps) doubling."""
+    B = int(rank.shape[0])
+    buf = [rank, torch.empty_like(rank)]
+    for r in range(rounds):
+        _m.check(_m.lib().mslam_mesh_holes_rank_double(_m.ptr(buf[r & 1]), _m.ptr(buf[~r & 1]), B, _m.stream_ptr()),
+                 "mesh_holes_rank_double")
+    return buf[rounds & 1]
+
+
+def _pair(faces, V, F, dart, tail, head):
+    """Bow-tie mode's state i32[B,2]: per dart (next or -1, its name).  No host read."""
+    dev, B = faces.device, int(dart.shape[0])
+    L, stream = _m.lib(), _m.stream_ptr()
+    i64 = lambda n: torch.empty(n, dtype=torch.int64, device=dev)
+    pairs = lambda: torch.empty((B, 2), dtype=torch.int32, device=dev)
+    keys = i64(3 * F)
+    _m.check(L.mslam_mesh_holes_dkeys(_m.ptr(faces), F, V, _m.ptr(keys), stream), "mesh_holes_dkeys")
+    skeys, order = torch.sort(keys, stable=True)
+    fan = torch.empty(B, dtype=torch.int32, device=dev)
+    _m.check(L.mslam_mesh_holes_fan(_m.ptr(faces), F, V, _m.ptr(dart), _m.ptr(head), B, _m.ptr(skeys), _m.ptr(order),
+                                    _m.ptr(fan), stream), "mesh_holes_fan")
+    dart_key = keys[dart.long()]
+    sorted_fan, sorted_dart_key = torch.sort(fan)[0], torch.sort(dart_key)[0]
+    state = pairs()
+    _m.check(L.mslam_mesh_holes_claim(_m.ptr(fan), _m.ptr(sorted_fan), _m.ptr(dart_key), _m.ptr(sorted_dart_key), B,
+                                      _m.ptr(state), stream), "mesh_holes_claim")
+    rounds = _rounds(B)
+    labelled = _double(state, rounds)                       # the closed walks of fan, labelled by their smallest name
+    rank = pairs()
+    _m.check(L.mslam_mesh_holes_rank_init(_m.ptr(state), _m.ptr(labelled), B, _m.ptr(rank), stream),
+             "mesh_holes_rank_init")
+    rank = _double_ranks(rank, rounds)
+    walk_keys = i64(B)
+    _m.check(L.mslam_mesh_holes_walk_keys(_m.ptr(labelled), _m.ptr(rank), B, _m.ptr(walk_keys), stream),
+             "mesh_holes_walk_keys")
+    walk_keys, walk_order = torch.sort(walk_keys)           # distinct below INT64_MAX
+    pair_keys = i64(B)
+    _m.check(L.mslam_mesh_holes_pair_keys(_m.ptr(labelled), _m.ptr(head), _m.ptr(walk_keys), _m.ptr(walk_order), B, V,
+                                          _m.ptr(pair_keys), stream), "mesh_holes_pair_keys")
+    pair_keys, pair_order = torch.sort(pair_keys, stable=True)
+    paired = pairs()
+    _m.check(L.mslam_mesh_holes_repair(_m.ptr(pair_keys), _m.ptr(pair_order), _m.ptr(walk_order), _m.ptr(state), B,
+                                       _m.ptr(paired), stream), "mesh_holes_repair")
+    return paired
+
+
+def _named_loops(paired, tail, head, V):
+    """(loop_id, loop_head, length i32[L], dart_loop i32[B], start i32[L], n_open i64[]) of the cycles of bow-tie mode's
+    next on which no vertex is a tail twice.  One host read: L."""
+    B, dev = int(tail.shape[0]), tail.device
+    L, stream = _m.lib(), _m.stream_ptr()
+    labelled = _double(paired, _rounds(B))
+    tail_keys = torch.empty(B, dtype=torch.int64, device=dev)
+    _m.check(L.mslam_mesh_holes_tail_keys(_m.ptr(labelled), _m.ptr(tail), B, V, _m.ptr(tail_keys), stream),
+             "mesh_holes_tail_keys")
+    tail_keys = torch.sort(tail_keys)[0]
+    flag = torch.zeros(B, dtype=torch.uint8, device=dev)
+    _m.check(L.mslam_mesh_holes_tail_flag(_m.ptr(tail_keys), B, V, _m.ptr(flag), stream), "mesh_holes_tail_flag")
+    keys = torch.empty(B + 1, dtype=torch.int32, device=dev)
+    _m.check(L.mslam_mesh_holes_loop_labels(_m.ptr(labelled), _m.ptr(flag), B, _m.ptr(keys), stream),
+             "mesh_holes_loop_labels")
+    runs, counts = torch.unique_consecutive(torch.sort(keys)[0], return_counts=True)
+    loop_name, length = runs[:-1].contiguous(), counts[:-1].to(torch.int32)
+    nl = int(loop_name.shape[0])
+    dart_loop = torch.empty(B, dtype=torch.int32, device=dev)
+    start, loop_id, loop_head = (torch.full((nl,), -1, dtype=torch.int32, device=dev) for _ in range(3))
+    _m.check(L.mslam_mesh_holes_loop_assign(_m.ptr(labelled), _m.ptr(paired), _m.ptr(flag), _m.ptr(tail), _m.ptr(head),
+                                            B, _m.ptr(loop_name), nl, _m.ptr(dart_loop), _m.ptr(start), _m.ptr(loop_id),
+                                            _m.ptr(loop_head), stream), "mesh_holes_loop_assign")
+    return loop_id, loop_head, length, dart_loop, start, counts[-1] - 1
+
+
+def _trace_bowties(faces, V, F):
+    """_trace in bow-tie mode: the same dict plus loop_head; `state` holds bow-tie mode's next.  Two host reads."""
+    dev = faces.device
+    i32 = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
+    dart, tail, head = _darts(faces, V, F) if F and V else (i32(0), i32(0), i32(0))
+    B = int(dart.shape[0])
+    if B == 0:
+        return dict(dart=dart, tail=tail, head=head, state=torch.zeros((0, 2), dtype=torch.int32, device=dev),
+                    loop_id=i32(0), loop_head=i32(0), length=i32(0), dart_loop=i32(0), start=i32(0),
+                    n_open=torch.zeros((), dtype=torch.int64, device=dev))
+    state = _pair(faces, V, F, dart, tail, head)
+    loop_id, loop_head, length, dart_loop, start, n_open = _named_loops(state, tail, head, V)
+    return dict(dart=dart, tail=tail, head=head, state=state, loop_id=loop_id, loop_head=loop_head, length=length,
+                dart_loop=dart_loop, start=start, n_open=n_open)
+
+
 def _measure(verts, faces, V, F, tr, max_edges, all_perimeters):
     """(perimeter f64[L], centre f64[L,3], fillable u8[L])."""
     nl, dev = int(tr["loop_id"].shape[0]), faces.device
@@ -113,6 +204,8 @@ def _info(tr, perimeter=None, filled=None):
                dart_head=tr["head"], dart_loop=tr["dart_loop"],
                n_boundary_edges=torch.tensor(int(tr["dart"].shape[0]), dtype=torch.int64, device=tr["dart"].device),
                n_open=tr["n_open"])
+    if "loop_head" in tr:
+        out["loop_head"] = tr["loop_head"]
     if perimeter is not None:
         out["loop_perimeter"] = perimeter
     if filled is not None:
@@ -120,7 +213,7 @@ def _info(tr, perimeter=None, filled=None):
     return out
 
 
-def mesh_boundaries(faces, num_vertices, vertices=None, _validate=True):
+def mesh_boundaries(faces, num_vertices, vertices=None, bowties=False, _validate=True):
     """The boundary of any welded mesh (faces i32[F,3] device tensor over `num_vertices` vertices) as a dict of device
     tensors.  DESIGN.md "Mesh holes" has the definitions; in short: a boundary dart is a directed edge of a counting face
     (indices pairwise different), in the face's winding, whose undirected edge lies on exactly one counting face; its id
@@ -132,9 +225,18 @@ def mesh_boundaries(faces, num_vertices, vertices=None, _validate=True):
       not simple); n_boundary_edges (B) and n_open, 0-d i64; with `vertices` f32[V,3] also loop_perimeter f64[L], the sum of
       the edge lengths in walk order (from the loop id along the winding) in f64.
 
+    `bowties=True`: darts are paired across the hole they bound instead (DESIGN.md "Mesh holes", bow-tie mode): the
+    successor of u -> v is found by rotating about v from the dart's face across interior edges, and a closed walk that
+    visits a vertex several times is cut there, so the rims of holes that meet in a vertex are loops of their own.  OPEN
+    are then only darts at non-manifold or inconsistently wound edges and cycles whose visits of two vertices
+    interleave.  A loop is named by (its smallest vertex, the head of the dart leaving it); loops are numbered by
+    ascending name, loop_id can repeat, and the dict also has loop_head i32[L].  No further host reads.
+
     L == 0 and n_open == 0: the mesh is watertight.  The result does not depend on the order of the faces.  Raises
-    ValueError for a face index outside [0, V).  Host reads: the index range, B and L."""
+    ValueError for a face index outside [0, V) or a `bowties` that is not a bool.  Host reads: the index range, B and
+    L."""
     what = "mesh_boundaries"
+    bowties = _bool_arg(bowties, "bowties", what)
     if vertices is not None:
         verts, faces, V, F = _mesh_arg(vertices, faces, _validate, what)
         if V != int(num_vertices):
@@ -142,14 +244,14 @@ def mesh_boundaries(faces, num_vertices, vertices=None, _validate=True):
     else:
         faces, V, F = _faces_arg(faces, num_vertices, _validate, what)
         _m.ptr(faces)
-    tr = _trace(faces, V, F)
+    tr = _trace_bowties(faces, V, F) if bowties else _trace(faces, V, F)
     perimeter = None
     if vertices is not None:
         perimeter = _measure(verts, faces, V, F, tr, 0, True)[0]
     return _info(tr, perimeter)
 
 
-def fill_holes(mesh, max_edges, return_info=False, _validate=True):
+def fill_holes(mesh, max_edges, return_info=False, bowties=False, _validate=True):
     """Closes the small holes of `mesh` = (vertices f32[V,3], normals f32[V,3], faces i32[F,3][, colors f32[V,3]]), the
     tuple extract_mesh / filter_mesh / smooth_mesh / simplify_mesh use; the result has the same arity.  DESIGN.md "Mesh
     holes" has the definitions; in short:
@@ -166,11 +268,15 @@ def fill_holes(mesh, max_edges, return_info=False, _validate=True):
     the vertex numbering only through the order of the sums.  Open darts are never filled.  When no loop is filled the
     input tuple itself is returned.
 
+    `bowties=True`: the loops are those of mesh_boundaries(bowties=True), so holes that meet in a vertex are closed too;
+    new vertices and faces then follow in the order of the loops' names.  No further host reads.
+
     `max_edges` None or <= 0: off, the input tuple itself.  `return_info`: also the dict of mesh_boundaries (with
-    loop_perimeter) plus loop_filled bool[L].  Raises ValueError for a `max_edges` that is not an integer, a non-finite
-    coordinate or a face index outside [0, V), before any kernel follows an index.  Host reads: the validation ranges,
-    B, L and the new sizes."""
+    loop_perimeter) plus loop_filled bool[L].  Raises ValueError for a `max_edges` that is not an integer, a `bowties`
+    that is not a bool, a non-finite coordinate or a face index outside [0, V), before any kernel follows an index.
+    Host reads: the validation ranges, B, L and the new sizes."""
     what = "fill_holes"
+    bowties = _bool_arg(bowties, "bowties", what)
     mesh = tuple(mesh)
     verts_in, nrm_in, faces_in, colors, _ = _mesh_tuple_arg(mesh, what, check=False)
     if max_edges is not None:
@@ -190,7 +296,7 @@ def fill_holes(mesh, max_edges, return_info=False, _validate=True):
         _check_finite(what, vlo, vhi, finite)
         _check_face_range(what, flo, fhi, V)
     dev = verts.device
-    tr = _trace(faces, V, F)
+    tr = _trace_bowties(faces, V, F) if bowties else _trace(faces, V, F)
     nl = int(tr["loop_id"].shape[0])
     perimeter, centre, fillable = _measure(verts, faces, V, F, tr, 0 if off else max_edges, return_info)
     out, filled = mesh, fillable.bool()

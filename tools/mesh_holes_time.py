@@ -7,13 +7,17 @@ keys, stable sort, mark, compaction with its host read, tails and heads); (b) th
 doubling rounds alone; (c) the loops (label keys, sort, unique_consecutive with its host read, assign); (d) measure, with
 the cap and with every perimeter; (e) fill_holes(16) and mesh_boundaries as a whole, host reads included.  Then the room
 figures: the loops found and compare_meshes of the mesh against synthetic.room_mesh() before and after fill_holes, at the
-volume's min_weight and at `--min-weight`, where the surface is thinner and has more holes.  Not part of bench.py.
+volume's min_weight and at `--min-weight`, where the surface is thinner and has more holes.  (f) the bow-tie mode in
+the same run, on the room and on the `--min-weight` mesh: fill_holes(16) against fill_holes(16, bowties=True), the pairing
+(directed keys and their sort alone, then the whole of it) and the named loops; the room figures carry a bow-tie row.
+Not part of bench.py.
     python tools/mesh_holes_time.py 60 [--reps 20] [--splits 2]"""
 import argparse
 
 import torch
 
 from _room import build_room, timed   # first: it puts the package on sys.path
+import mslam_hip as _m
 from mast3r_slam import synthetic
 from mast3r_slam.config import config
 from mast3r_slam.tsdf import compare_meshes, fill_holes, mesh_boundaries, smooth_mesh
@@ -81,6 +85,37 @@ def measure(verts, faces, label):
     print(f"  (e) mesh_boundaries_ms {timed(lambda: mesh_boundaries(faces, V, _validate=False), args.reps)}", flush=True)
 
 
+def bowties(verts, faces, label):
+    """(f): the plain call against the bow-tie mode on one mesh, and where the bow-tie mode's time goes."""
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    mesh = (verts, torch.zeros_like(verts), faces)
+    dart, tail, head = MH._darts(faces, V, F)
+    B = int(dart.shape[0])
+    if B == 0:
+        return
+    out = fill_holes(mesh, args.max_edges, return_info=True, bowties=True)
+    info = out[-1]
+    print(f"  (f) {label} bowties: loops={int(info['loop_id'].shape[0])} longest={int(info['loop_length'].max())} "
+          f"filled={int(info['loop_filled'].sum())} new_faces={int(out[2].shape[0]) - F} "
+          f"open_darts={int(info['n_open'])} of {B}", flush=True)
+    print(f"  (f) {label} fill_holes_{args.max_edges}_ms {timed(lambda: fill_holes(mesh, args.max_edges), args.reps)}",
+          flush=True)
+    print(f"  (f) {label} fill_holes_{args.max_edges}_bowties_ms "
+          f"{timed(lambda: fill_holes(mesh, args.max_edges, bowties=True), args.reps)}", flush=True)
+    print(f"  (f) {label} mesh_boundaries_bowties_ms "
+          f"{timed(lambda: mesh_boundaries(faces, V, bowties=True, _validate=False), args.reps)}", flush=True)
+
+    def directed():
+        keys = torch.empty(3 * F, dtype=torch.int64, device=dev)
+        _m.check(_m.lib().mslam_mesh_holes_dkeys(_m.ptr(faces), F, V, _m.ptr(keys), _m.stream_ptr()), "dkeys")
+        return torch.sort(keys, stable=True)
+
+    paired = MH._pair(faces, V, F, dart, tail, head)
+    print(f"  (f) {label} directed_keys_sort_ms {timed(directed, args.reps)}", flush=True)
+    print(f"  (f) {label} pair_ms {timed(lambda: MH._pair(faces, V, F, dart, tail, head), args.reps)}", flush=True)
+    print(f"  (f) {label} named_loops_ms {timed(lambda: MH._named_loops(paired, tail, head, V), args.reps)}", flush=True)
+
+
 def quality(mesh, gt, label):
     m = compare_meshes(mesh, gt, n_samples=args.samples, threshold=float(cfg["mesh_eval_threshold"]))
     print(f"  {label}: V={int(mesh[0].shape[0])} F={int(mesh[2].shape[0])} accuracy={m['accuracy']:.5f} "
@@ -95,6 +130,7 @@ for n_kf in args.keyframes:
     print(f"keyframes={n_kf} voxels={voxels} capacity={cap}", flush=True)
     v, f = mesh[0], mesh[2]
     measure(v, f, "room")
+    bowties(v, f, "room")
     for k in range(args.splits):
         v, f = split(v, f)
         measure(v, f, f"room split {k + 1}x")
@@ -112,3 +148,11 @@ for n_kf in args.keyframes:
         quality(mesh, gt, "as extracted")
         quality(out[:3], gt, f"fill_holes={args.max_edges}")
         quality(smooth_mesh(out[:3], 5), gt, f"fill_holes={args.max_edges} + 5 iterations")
+        both = fill_holes(mesh, args.max_edges, return_info=True, bowties=True)
+        info = both[-1]
+        print(f"  bowties: loops={int(info['loop_id'].shape[0])} filled={int(info['loop_filled'].sum())} "
+              f"open_darts={int(info['n_open'])} of {int(info['n_boundary_edges'])}", flush=True)
+        quality(both[:3], gt, f"fill_holes={args.max_edges}, bowties")
+        quality(smooth_mesh(both[:3], 5), gt, f"fill_holes={args.max_edges}, bowties + 5 iterations")
+        if mw is not None:
+            bowties(mesh[0], mesh[2], f"min_weight={mw}")
