@@ -360,6 +360,54 @@ int mslam_mesh_vertex_normals(const float* vertices, const int32_t* faces, int n
                               const int64_t* sorted_pairs, const int64_t* pair_start, const float* normals_in,
                               float* normals, void* stream);
 
+/* Mesh decimation: round-based half-edge collapse with plane quadrics to a target face count or error (no counterpart
+ * in the reference, DESIGN.md "Mesh decimation", tests/decimate_numpy.py).  vertices f32[V,3] are only read: a removed
+ * vertex is merged into a neighbour.  faces i32[F,3] is the caller's working copy; a face COUNTS as in the smoothing, and
+ * the tables of a round are mslam_mesh_smooth_edges / mslam_mesh_vertex_faces on it.  state f64[V,MSLAM_MESH_DECIMATE_STATE]:
+ * the quadric xx xy xz xd yy yz yd zz zd dd, then the area.  Every index read from memory is checked before it is
+ * followed; all arithmetic is f64 on the f32 inputs, each operation rounded on its own, every sum in one fixed order,
+ * nothing is atomic: the same input gives the same bits.  Sequence, on one stream (3 F < 2^31, V F < 2^62):
+ *   mslam_mesh_decimate_state       once: state[v] = 0.0 + (A g_i) g_j and A over the counting faces of v in ascending
+ *                                   face index, g = (k, -k . a), k the unit normal, A the area; a face whose cross
+ *                                   product has no finite positive length adds nothing.
+ *   mslam_mesh_decimate_candidates  per vertex u: vclass u8[V] (may be NULL) = _ISOLATED (no neighbour), _BOUNDARY (an
+ *                                   edge of mult 1), _REMOVABLE (every edge of mult 2 and as many faces as neighbours)
+ *                                   or _OTHER.  For a removable u, best i32[V] = the neighbour v of lowest (cost, v)
+ *                                   among those that pass the link condition (exactly two common neighbours, neither a
+ *                                   closed fan of three faces or fewer), the flip
+ *                                   test (every face of u without v keeps a positive dot of its cross product with the
+ *                                   one before) and, with gate >= 0, cost <= gate (area u + area v); cost f64[V] =
+ *                                   max(0, h^T (Q_u + Q_v) h) at h = (x_v, 1).  -1 and +inf without one.  key i64[V] =
+ *                                   hash32(u, round) 2^31 + u, INT64_MAX without one.  The caller ranks the candidates
+ *                                   by (cost, key): rank i32[V], INT32_MAX for the others.
+ *   mslam_mesh_decimate_spread      rank_out[v] = the minimum of rank_in over v and its neighbours; never in place.
+ *                                   Twice: a candidate whose own rank comes back is selected.
+ *   mslam_mesh_decimate_apply       per selected u (selected u8[V]), v = best[u]: every face corner u becomes v (in
+ *                                   place), state[v] += state[u], parent[u] = v.  Selected vertices must be three hops
+ *                                   apart, which the two spreads give.
+ *   mslam_mesh_decimate_finish      keep_face i32[F] = the face counts; referenced i32[V] (zeroed by the caller) = 1 at
+ *                                   the corners of a counting face; end i32[V] = the end of the parent chain, followed
+ *                                   for at most max_steps links.
+ * The caller then scans the flags and calls mslam_mesh_cc_emit on the input rows and the working faces. */
+#define MSLAM_MESH_DECIMATE_STATE 11
+#define MSLAM_MESH_DECIMATE_OTHER 0
+#define MSLAM_MESH_DECIMATE_BOUNDARY 1
+#define MSLAM_MESH_DECIMATE_ISOLATED 2
+#define MSLAM_MESH_DECIMATE_REMOVABLE 3
+int mslam_mesh_decimate_state(const float* vertices, const int32_t* faces, int num_faces, int num_vertices,
+                              const int64_t* sorted_pairs, const int64_t* pair_start, double* state, void* stream);
+int mslam_mesh_decimate_candidates(const float* vertices, const int32_t* faces, int num_faces, int num_vertices,
+                                   const int64_t* row_start, const int32_t* nbr, const int32_t* mult, int64_t num_edges,
+                                   const int64_t* sorted_pairs, const int64_t* pair_start, const double* state,
+                                   double gate, int round, int32_t* best, double* cost, int64_t* key, uint8_t* vclass,
+                                   void* stream);
+int mslam_mesh_decimate_spread(const int32_t* rank_in, const int64_t* row_start, const int32_t* nbr, int num_vertices,
+                               int64_t num_edges, int32_t* rank_out, void* stream);
+int mslam_mesh_decimate_apply(int32_t* faces, int num_faces, int num_vertices, const uint8_t* selected,
+                              const int32_t* best, double* state, int32_t* parent, void* stream);
+int mslam_mesh_decimate_finish(const int32_t* faces, int num_faces, int num_vertices, const int32_t* parent,
+                               int max_steps, int32_t* keep_face, int32_t* referenced, int32_t* end, void* stream);
+
 /* Mesh holes: the boundary loops of a welded mesh, and a centroid fan over the small, well-behaved ones (no counterpart
  * in the reference, DESIGN.md "Mesh holes").  faces i32[F,3]; a face COUNTS as in the smoothing.  A boundary dart is a
  * directed edge of a counting face, in its winding, whose undirected edge lies on exactly one counting face; its id is

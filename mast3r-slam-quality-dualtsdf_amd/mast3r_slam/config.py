@@ -43,6 +43,8 @@ _BASE = {
         "mesh_smooth_iterations": 0,     # ... after this many Taubin iterations, 0 = off ("Mesh smoothing")
         "mesh_fill_holes": 0,            # ... after closing holes of at most this many edges, 0 = off ("Mesh holes")
         "mesh_fill_bowties": False,      # ... those that meet in a vertex included (bow-tie mode of "Mesh holes")
+        "mesh_decimate_faces": 0,        # ... and last decimates to this many faces, 0 = off ("Mesh decimation")
+        "mesh_decimate_error": 0.0,      # ... within this quadric error, in voxel sizes, 0 = off ("Mesh decimation")
         "mesh_eval_threshold": 0.05,     # SlamSystem.evaluate_mesh: precision / recall distance (DESIGN.md "Mesh quality")
     },
 }

@@ -240,11 +240,13 @@ def save_tsdf_mesh(savedir, filename, source, min_weight=None, level=0.0, colors
     `simplify_position`: the mesh is then simplified by vertex clustering (DESIGN.md "Mesh simplification").
     `smooth_iterations` > 0 / `smooth_lambda`, `smooth_mu`, `smooth_boundary`: Taubin smoothing between the two (DESIGN.md
     "Mesh smoothing").  `fill_holes` = n > 0: holes of at most n edges are closed before the smoothing (DESIGN.md "Mesh
-    holes"); `fill_bowties=True` (the one keyword `fill_options` takes): holes that meet in a vertex too.  Returns
-    (V, F)."""
+    holes").  `fill_options` takes four more keywords.  `fill_bowties=True`: holes that meet in a vertex too.
+    `decimate_faces` = n > 0 / `decimate_ratio` in (0, 1] / `decimate_error` > 0 (world units): edge-collapse decimation
+    to n faces / that share of the faces / while the quadric error allows, last of all (DESIGN.md "Mesh decimation").
+    Returns (V, F)."""
     from mast3r_slam.tsdf._mesh_args import _fill_options
 
-    fill_bowties = _fill_options(fill_options, "save_tsdf_mesh")
+    fill_bowties, decimate = _fill_options(fill_options, "save_tsdf_mesh")
     savedir = pathlib.Path(savedir)
     savedir.mkdir(exist_ok=True, parents=True)
     kw = {}
@@ -257,6 +259,7 @@ def save_tsdf_mesh(savedir, filename, source, min_weight=None, level=0.0, colors
                   smooth_boundary=smooth_boundary)
     if fill_holes is not None and fill_holes > 0:
         kw = dict(kw, fill_holes=fill_holes, **(dict(fill_bowties=True) if fill_bowties else {}))
+    kw = dict(kw, **decimate)                                # those of the three that are on
     if colors:
         v, n, f, c = source.extract_mesh(min_weight=min_weight, level=level, colors=True, **kw)
         save_mesh(savedir / filename, v, f, normals=n, colors=c)

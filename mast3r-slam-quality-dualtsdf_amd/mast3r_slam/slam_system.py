@@ -368,7 +368,11 @@ class SlamSystem:
         tsdf_global.mesh_smooth_iterations, 0 = off) / `smooth_lambda`, `smooth_mu`, `smooth_boundary`: Taubin smoothing
         after the component filter and before the simplification (DESIGN.md "Mesh smoothing").  `fill_holes` (default
         tsdf_global.mesh_fill_holes, 0 = off): holes of at most that many edges are closed before the smoothing (DESIGN.md
-        "Mesh holes"); `fill_bowties` (in `kw`; default tsdf_global.mesh_fill_bowties, off): holes that meet in a vertex too."""
+        "Mesh holes"); `fill_bowties` (in `kw`; default tsdf_global.mesh_fill_bowties, off): holes that meet in a vertex too.
+        `decimate_faces` (default tsdf_global.mesh_decimate_faces, 0 = off) / `decimate_ratio` / `decimate_error` (world
+        units; default tsdf_global.mesh_decimate_error voxel sizes, 0 = off), all three in `kw`: edge-collapse decimation
+        to that many faces / that share of the faces / while the quadric error allows, last of all (DESIGN.md "Mesh
+        decimation")."""
         if self.tsdf_manager is None:
             raise RuntimeError("SlamSystem.extract_mesh: the global TSDF is disabled (tsdf_global.enabled = False)")
         if min_component_faces is None:
@@ -380,6 +384,12 @@ class SlamSystem:
             smooth_iterations = int(self.tsdf_manager.cfg.get("mesh_smooth_iterations", 0))
         if fill_holes is None:
             fill_holes = int(self.tsdf_manager.cfg.get("mesh_fill_holes", 0))
+        kw = dict(kw)
+        if kw.get("decimate_faces") is None:
+            kw["decimate_faces"] = int(self.tsdf_manager.cfg.get("mesh_decimate_faces", 0))
+        if kw.get("decimate_error") is None:
+            kw["decimate_error"] = (float(self.tsdf_manager.cfg.get("mesh_decimate_error", 0.0))
+                                    * float(self.tsdf_manager.volume.voxel_size))
         if kw.get("fill_bowties") is None:                     # the config's switch; off adds nothing to the call
             kw = {k: v for k, v in kw.items() if k != "fill_bowties"}
             if self.tsdf_manager.cfg.get("mesh_fill_bowties", False):

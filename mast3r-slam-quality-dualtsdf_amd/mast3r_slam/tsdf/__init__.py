@@ -1,6 +1,7 @@
 from .global_volume import TSDFVolume, mesh_from_voxels, render_from_voxels  # noqa: F401
 from .mesh_ops import filter_mesh, mesh_components  # noqa: F401
 from .mesh_simplify import simplify_mesh  # noqa: F401
+from .mesh_decimate import decimate_mesh  # noqa: F401
 from .mesh_holes import fill_holes, mesh_boundaries  # noqa: F401
 from .mesh_smooth import smooth_mesh, vertex_normals  # noqa: F401
 from .mesh_metrics import compare_meshes, face_areas, mesh_distance, sample_mesh  # noqa: F401

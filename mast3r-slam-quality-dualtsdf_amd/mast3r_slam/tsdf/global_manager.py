@@ -17,7 +17,7 @@ import torch
 from lietorch_hip import Sim3
 from mast3r_slam.config import config
 
-from ._mesh_args import _bool_arg
+from ._mesh_args import _DECIMATE_OPTIONS, _bool_arg
 
 
 def gather_uimg(uimg, choice, map_hw):
@@ -180,7 +180,10 @@ class TSDFGlobalManager:
         simplification"); off by default.  `smooth_iterations` > 0 / `smooth_lambda`, `smooth_mu`, `smooth_boundary`:
         Taubin smoothing between the two (DESIGN.md "Mesh smoothing"); off by default.  `fill_holes` = n > 0: holes of at
         most n edges are closed before the smoothing (DESIGN.md "Mesh holes"); off by default.  `fill_bowties=True`
-        (in `kw`): holes that meet in a vertex are closed too; it does nothing without `fill_holes`."""
+        (in `kw`): holes that meet in a vertex are closed too; it does nothing without `fill_holes`.  `decimate_faces` =
+        n > 0 / `decimate_ratio` in (0, 1] / `decimate_error` > 0 (world units; all three in `kw`): edge-collapse
+        decimation to n faces / that share of the faces / while the quadric error allows, last of all (DESIGN.md "Mesh
+        decimation"); off by default, and an argument that is off is not handed on."""
         kw = dict(kw)
         fill_bowties = _bool_arg(kw.pop("fill_bowties", False), "fill_bowties", "TSDFGlobalManager.extract_mesh")
         if min_component_faces > 0 or keep_largest is not None:
@@ -192,6 +195,9 @@ class TSDFGlobalManager:
                       smooth_boundary=smooth_boundary)
         if fill_holes is not None and fill_holes > 0:
             kw = dict(kw, fill_holes=fill_holes, **(dict(fill_bowties=True) if fill_bowties else {}))
+        for name in _DECIMATE_OPTIONS:
+            if name in kw and (kw[name] is None or kw[name] <= 0):
+                del kw[name]
         if not colors and not kw:
             return self.volume.extract_mesh(min_weight=min_weight, level=level)
         return self.volume.extract_mesh(min_weight=min_weight, level=level, colors=colors, **kw)

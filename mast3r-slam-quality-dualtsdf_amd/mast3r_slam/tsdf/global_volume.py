@@ -15,6 +15,7 @@ import mslam_hip as _m
 
 from ._mesh_args import _fill_options
 from .mesh_ops import filter_mesh
+from .mesh_decimate import _decimate
 from .mesh_simplify import simplify_mesh
 from .mesh_holes import fill_holes as _fill_holes
 from .mesh_smooth import smooth_mesh
@@ -372,12 +373,16 @@ class TSDFVolume:
         the simplification, whose plane quadrics then see the smoothed surface; normals are recomputed.
         `fill_holes` = n > 0: boundary loops of at most n edges that are holes are closed with a centroid fan
         (mesh_holes.fill_holes, DESIGN.md "Mesh holes"; four more host reads) after the component filter and before the
-        smoothing, which then fairs the patches.  `fill_bowties=True` (the one keyword `fill_options` takes): holes that
+        smoothing, which then fairs the patches.  `fill_options` takes four more keywords.  `fill_bowties=True`: holes that
         meet in a vertex, as two diagonal missing voxels leave them, are told apart and closed too (fill_holes' bow-tie
-        mode; no further host read); without `fill_holes` it does nothing."""
-        fill_bowties = _fill_options(fill_options, "TSDFVolume.extract_mesh")
+        mode; no further host read); without `fill_holes` it does nothing.
+        `decimate_faces` = n > 0 / `decimate_ratio` in (0, 1] / `decimate_error` > 0 (world units): the mesh is decimated
+        by edge collapses to n faces / that share of its faces / while the quadric error allows
+        (mesh_decimate.decimate_mesh, DESIGN.md "Mesh decimation"; two host reads and one more per round).  It runs last,
+        after the cluster simplification, so both can be combined; each is off when None or <= 0 (the default)."""
+        fill_bowties, decimate = _fill_options(fill_options, "TSDFVolume.extract_mesh")
         smooth = dict(smooth_iterations=smooth_iterations, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu,
-                      smooth_boundary=smooth_boundary, fill_holes=fill_holes, fill_bowties=fill_bowties)
+                      smooth_boundary=smooth_boundary, fill_holes=fill_holes, fill_bowties=fill_bowties, **decimate)
         mw = self.min_weight if min_weight is None else float(min_weight)
         if colors and not self.color:
             raise ValueError("TSDFVolume.extract_mesh: colors=True needs a volume built with color=True")
@@ -398,7 +403,8 @@ class TSDFVolume:
         mesh = filter_mesh(mesh, min_component_faces, keep_largest, _validate=False)
         mesh = _fill_holes(mesh, fill_holes, bowties=fill_bowties)          # off (None or <= 0): `mesh` itself
         mesh = smooth_mesh(mesh, smooth_iterations, smooth_lambda, smooth_mu, smooth_boundary)       # off: `mesh` itself
-        return simplify_mesh(mesh, simplify_cell, simplify_position)        # off (None or <= 0): `mesh` itself
+        mesh = simplify_mesh(mesh, simplify_cell, simplify_position)        # off (None or <= 0): `mesh` itself
+        return _decimate(mesh, **decimate)                                  # off (none of the three): `mesh` itself
 
     def render(self, pose, rays=None, K=None, hw=None, near=0.05, far=10.0, min_weight=None, level=0.0, step=None,
                skip=True, colors=False, default_color=(0.5, 0.5, 0.5)):
@@ -591,8 +597,8 @@ def mesh_from_voxels(keys, tsdf, weight, voxel_size, min_weight, level=0.0, devi
                      smooth_boundary="fixed", fill_holes=0, **fill_options):
     """Mesh of a voxel set given as arrays (keys i64[n,3] distinct, tsdf f64[n], weight f64[n]; numpy or device): loads
     a temporary table of at least 2n slots and extracts from it (TSDFVolume.extract_mesh semantics, its component filter,
-    its hole filling, its smoothing and its simplification included).  `colors` u64[n,4]: the voxels' colour sums
-    (voxel_color_sums()); the mesh then carries vertex colours as a fourth tensor."""
+    its hole filling, its smoothing, its simplification and, through `fill_options`, its decimation included).  `colors`
+    u64[n,4]: the voxels' colour sums (voxel_color_sums()); the mesh then carries vertex colours as a fourth tensor."""
     vol = _loaded(keys, tsdf, weight, voxel_size, min_weight, device, colors)
     return vol.extract_mesh(min_weight=min_weight, level=level, colors=colors is not None, default_color=default_color,
                             min_component_faces=min_component_faces, keep_largest=keep_largest,
