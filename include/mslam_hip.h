@@ -675,6 +675,46 @@ int mslam_mesh_align_step_indexed(const float* src, int n, const float* vertices
                                   void* state, int32_t* nearest, float* moved, double* dist2, double* closest,
                                   double* log_row, void* stream);
 
+/* Mesh textures: keyframe images baked into a per-face atlas, and the shading of a ray cast (no counterpart in the
+ * reference, DESIGN.md "Mesh textures"; the definition is tests/texture_numpy.py).  The atlas is a pure function of
+ * (F, texels = R >= 4): face f is half f & 1 of cell f >> 1, a cell is R + 1 texels wide and R high, the cells lie
+ * row-major in `cols` columns and `rows` rows (cols * rows >= (F + 1) / 2), H = rows R, W = cols (R + 1), n = H W < 2^31.
+ * All arithmetic is f64 on the f32 inputs in one fixed order; one thread per texel, no atomics; nothing but the outputs
+ * is written.  A face with an index outside [0, V) is seen by no view and takes the default colour.
+ *   mslam_mesh_texture_layout      owner i32[n]: the face that owns each texel, -1 for none.
+ *   mslam_mesh_texture_rays        one view: pose8 f32[8] (Sim3 [t,q,s], world from camera), pinhole fx, fy, cx, cy, an
+ *                                  image of h x w >= 2x2.  Per texel the point p of its face at the texel's clamped
+ *                                  barycentrics, v = p - t, r = |v|, cos = -(n . v) / r for the face's unit normal n.
+ *                                  Where z > 0, -0.5 <= u < w - 0.5, -0.5 <= v < h - 0.5, near <= r <= far and
+ *                                  cos >= cos_min and > 0: dir f32[n,3] = v / r (the occlusion ray from t), r f64[n],
+ *                                  cos f64[n], uv f64[n,2]; zeros everywhere else.
+ *   mslam_mesh_texture_accumulate  one view, after mslam_mesh_raycast of `dir` from t (h = 1, identity rotation, near 0,
+ *                                  far inf) gave t64: a texel with cos > 0 and t64 >= r - tol adds wgt = (cos (s / r))
+ *                                  (s / r) and wgt times the bilinear sample of image f32[h,w,3] at uv into sums
+ *                                  f64[n,4], and 1 into views i32[n].  The caller zeroes both before the first view.
+ *   mslam_mesh_texture_resolve     atlas f32[n,3]: sums[1..3] / sums[0] where sums[0] > 0; otherwise the vertex colours
+ *                                  colors f32[V,3] (may be NULL) at the texel's barycentrics, or default_color; 0
+ *                                  without an owner.
+ *   mslam_mesh_shade               rgb f32[h*w,3] of a ray cast: for every pixel with face[i] >= 0 the edge functions
+ *                                  U, V, W of that face as mslam_mesh_raycast computes them (same rays, h, w, pose8) and
+ *                                  det = (U + V) + W; with colors f32[V,3]: ((U ca + V cb) + W cc) / det; with an atlas
+ *                                  f32[H,W,3] (and texels, cols, rows): its bilinear sample at the atlas coordinates of
+ *                                  beta = V / det, gamma = W / det.  Exactly one of the two is given.  0 on a miss. */
+int mslam_mesh_texture_layout(int num_faces, int texels, int cols, int rows, int32_t* owner, void* stream);
+int mslam_mesh_texture_rays(const float* vertices, const int32_t* faces, int num_faces, int num_vertices, int texels,
+                            int cols, int rows, const float* pose8, double fx, double fy, double cx, double cy, int h,
+                            int w, double near, double far, double cos_min, float* dir, double* r, double* cos,
+                            double* uv, void* stream);
+int mslam_mesh_texture_accumulate(const double* t64, const double* r, const double* cos, const double* uv,
+                                  const float* image, int h, int w, const float* pose8, double tol, int n, double* sums,
+                                  int32_t* views, void* stream);
+int mslam_mesh_texture_resolve(const int32_t* faces, int num_faces, int num_vertices, int texels, int cols, int rows,
+                               const double* sums, const float* colors, double default_color, float* atlas,
+                               void* stream);
+int mslam_mesh_shade(const int32_t* face, const float* rays, int h, int w, const float* pose8, const float* vertices,
+                     const int32_t* faces, int num_faces, int num_vertices, const float* colors, const float* atlas,
+                     int texels, int cols, int rows, float* rgb, void* stream);
+
 /* Colour of the volume (no counterpart in the reference, DESIGN.md "Colour").  `color` is a second caller-owned device
  * buffer of mslam_tsdf_color_bytes(capacity) bytes, addressed by the slot index of `table`: four u64 words per slot,
  * sum_w (units of 2^-20), sum_w * r8, sum_w * g8, sum_w * b8 with 8-bit colours.  The sums are integers: the fused

@@ -289,6 +289,49 @@ def save_color_view(savedir, filename, rgb, hit):
     return path
 
 
+def save_textured_mesh(savedir, stem, vertices, faces, texture, normals=None):
+    """A textured mesh (tsdf.bake_texture's MeshTexture) as three files: `<stem>.obj` - `v` with %.9g, `vn` with
+    `normals`, three `vt` per face (corner k of face f is entry 3 f + k + 1) and `f a/ta[/na]`; `<stem>.mtl` - one
+    material whose map_Kd is `<stem>.png`; `<stem>.png` - the atlas as 8-bit RGB, rint(255 c), written as save_color_view
+    writes.  The atlas coordinates (x, y) of texture.uv(), texel centres at integers, become
+    vt = ((x + 0.5) / W, 1 - (y + 0.5) / H).  Arrays may be numpy or device tensors.  Returns the three paths."""
+    from PIL import Image
+
+    def host(a, dtype):
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        return a.astype(dtype)
+
+    savedir = pathlib.Path(savedir)
+    savedir.mkdir(exist_ok=True, parents=True)
+    v, f = host(vertices, np.float32).reshape(-1, 3), host(faces, np.int64).reshape(-1, 3)
+    atlas = host(texture.atlas, np.float64)
+    H, W = atlas.shape[:2]
+    if H * W == 0:
+        raise ValueError("save_textured_mesh: the texture's atlas is empty (a mesh without faces)")
+    uv = host(texture.uv(), np.float64).reshape(-1, 2)
+    if len(uv) != 3 * len(f):
+        raise ValueError(f"save_textured_mesh: the texture holds {len(uv) // 3} faces, the mesh {len(f)}")
+    n = None if normals is None else host(normals, np.float32).reshape(-1, 3)
+    if n is not None and len(n) != len(v):
+        raise ValueError(f"save_textured_mesh: {len(n)} normals for {len(v)} vertices")
+    obj, mtl, png = (savedir / f"{stem}.{ext}" for ext in ("obj", "mtl", "png"))
+    lines = [f"mtllib {stem}.mtl", "usemtl atlas"]
+    lines += ["v %.9g %.9g %.9g" % tuple(float(c) for c in p) for p in v]
+    if n is not None:
+        lines += ["vn %.9g %.9g %.9g" % tuple(float(c) for c in p) for p in n]
+    lines += ["vt %.9g %.9g" % ((x + 0.5) / W, 1.0 - (y + 0.5) / H) for x, y in uv]
+    for k, (a, b, c) in enumerate(f + 1):
+        t = 3 * k + 1
+        lines.append(f"f {a}/{t}/{a} {b}/{t + 1}/{b} {c}/{t + 2}/{c}" if n is not None else
+                     f"f {a}/{t} {b}/{t + 1} {c}/{t + 2}")
+    with open(obj, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    with open(mtl, "w") as fh:
+        fh.write(f"newmtl atlas\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {stem}.png\n")
+    Image.fromarray(np.clip(np.rint(255.0 * atlas), 0, 255).astype(np.uint8).reshape(H, W, 3)).save(png)
+    return obj, mtl, png
+
+
 def save_depth_view(savedir, filename, range_or_depth, normals, hit, pose=None):
     """A rendered view (TSDFVolume.render) as two images beside `filename`'s stem: `<stem>_depth.png`, 16-bit grey,
     the given range or depth in millimetres (rounded, clipped to 65535; 0 = miss), and `<stem>_normal.png`, 8-bit RGB of

@@ -548,6 +548,17 @@ class SlamSystem:
             raise RuntimeError(f"{what}: the global TSDF is disabled (tsdf_global.enabled = False)")
         if not self.tsdf_manager.volume.color:
             raise RuntimeError(f"{what}: the global TSDF carries no colour (tsdf_global.color = False)")
+
+        def render(pose, r):
+            out = self.tsdf_manager.render(pose, near=near, far=far, colors=True, **r)
+            return out[3], out[2]
+
+        return self._score_views(what, render, images, poses, rays, K, chunk, True)
+
+    def _score_views(self, what, render, images, poses, rays, K, chunk, need_keyframe):
+        """The view loop of evaluate_render and evaluate_mesh_render: the training views (images None) or the held-out
+        views, `render(pose, rays-or-K arguments)` -> (rgb f32[h,w,3], hit bool[h,w]) for each, `chunk` views scored by
+        one image_metrics launch -> the dict evaluate_render documents.  Drains the backend first."""
         from mast3r_slam.tsdf import image_metrics
         from mast3r_slam.tsdf.global_manager import gather_uimg
 
@@ -563,7 +574,7 @@ class SlamSystem:
             if images.dim() != 4 or images.shape[3] != 3 or not images.is_floating_point():
                 raise ValueError(f"{what}: images must be float (M,h,w,3), got {tuple(images.shape)} {images.dtype}")
             n_views, h, w = (int(x) for x in images.shape[:3])
-            if len(self.keyframes) == 0:
+            if need_keyframe and len(self.keyframes) == 0:
                 raise RuntimeError(f"{what}: no keyframe yet")
             if poses is None or (rays is None) == (K is None):
                 raise ValueError(f"{what}: images need poses and either K or rays")
@@ -598,11 +609,11 @@ class SlamSystem:
             rgb, hit, tgt = [], [], []
             for i in range(start, min(start + max(int(chunk), 1), n_views)):
                 pose, r, target = view(i)
-                out = self.tsdf_manager.render(pose, near=near, far=far, colors=True, **r)
-                if out[3].shape != target.shape:
-                    raise ValueError(f"{what}: view {i} renders {tuple(out[3].shape)} against an image of "
+                view_rgb, view_hit = render(pose, r)
+                if view_rgb.shape != target.shape:
+                    raise ValueError(f"{what}: view {i} renders {tuple(view_rgb.shape)} against an image of "
                                      f"{tuple(target.shape)}")
-                rgb.append(out[3]), hit.append(out[2]), tgt.append(target)
+                rgb.append(view_rgb), hit.append(view_hit), tgt.append(target)
             if any(x.shape != rgb[0].shape for x in rgb):
                 raise ValueError(f"{what}: the views {start}.. differ in shape; score them with chunk=1")
             m = image_metrics(torch.stack(rgb), torch.stack(tgt), mask=torch.stack(hit))     # one launch, one host read
@@ -617,6 +628,67 @@ class SlamSystem:
                     psnr_min=min(ps) if ps else nan, ssim_min=min(ss) if ss else nan,
                     hit_share=sum(per["n_pixels"]) / total, window_share=sum(per["n_windows"]) / total,
                     n_views=n_views, per_view=per)
+
+    def bake_texture(self, mesh=None, K=None, **kw):
+        """A texture atlas for a mesh of the map from the keyframes' images: tsdf.bake_texture (DESIGN.md "Mesh
+        textures"; `kw`: its further arguments) with the keyframes' T_WC as poses and their `uimg`, read at the
+        pointmap's size by the colour fusion's rule (tsdf.global_manager.gather_uimg), as images -> MeshTexture.
+        `mesh=None`: self.extract_mesh(colors=...) with the configured chain, with colours where the volume carries them.
+        `K` (3,3) or else the system's calibration; with neither it raises, as evaluate_mesh(observed=True) does: a
+        texel is projected, and the ray-image camera model has no projection.  The occlusion casts run over a mesh
+        index built here unless `index=` says otherwise (the same atlas bit for bit).  Drains the backend first."""
+        what = "SlamSystem.bake_texture"
+        from mast3r_slam.tsdf import bake_texture
+        from mast3r_slam.tsdf.global_manager import gather_uimg
+
+        self.drain()
+        K = K if K is not None else self.K
+        if K is None:
+            raise ValueError(f"{what}: needs a pinhole camera, K or the system's calibration: the ray-image camera "
+                             "model has no projection")
+        if mesh is None:
+            if self.tsdf_manager is None:
+                raise RuntimeError(f"{what}: the global TSDF is disabled (tsdf_global.enabled = False); give a mesh")
+            mesh = self.extract_mesh(colors=bool(self.tsdf_manager.volume.color))
+        n_kf = len(self.keyframes)
+        if n_kf == 0:
+            raise RuntimeError(f"{what}: no keyframe yet")
+        images = []
+        for i in range(n_kf):
+            kf = self.keyframes[i]
+            if kf.uimg is None:
+                raise ValueError(f"{what}: keyframe {i} has no uimg to bake")
+            H, W = (int(x) for x in kf.img_shape.reshape(-1)[:2].tolist())
+            pixels = torch.arange(H * W, device=self.device)
+            images.append(gather_uimg(kf.uimg.detach(), pixels, (H, W)).reshape(H, W, 3).float())
+        if any(x.shape != images[0].shape for x in images):
+            raise ValueError(f"{what}: the keyframes differ in image size")
+        poses = torch.stack([self.keyframes[i].T_WC.data.detach().reshape(8) for i in range(n_kf)])
+        kw.setdefault("index", True)          # the same bytes; a decimated mesh's casts are 3x faster over an index
+        return bake_texture(mesh, torch.stack(images), poses, K, **kw)
+
+    def evaluate_mesh_render(self, mesh, colors=None, texture=None, images=None, poses=None, rays=None, K=None,
+                             near=0.05, far=10.0, chunk=8):
+        """evaluate_render for a triangle mesh of the map: PSNR and SSIM of its colour views (tsdf.render_mesh_color,
+        from vertex `colors` f32[V,3] - True: those of a 4-tensor extract_mesh tuple - or from a `texture` of
+        bake_texture; exactly one of the two) against camera images, so that an exported mesh is scored by the figures
+        that score the TSDF.  `mesh`: (vertices, faces) device tensors or an extract_mesh tuple.  The training views,
+        the held-out views (`images`, `poses`, `rays` / `K`), the mask - the hit image - and the returned dict are
+        evaluate_render's.  Drains the backend first."""
+        what = "SlamSystem.evaluate_mesh_render"
+        from mast3r_slam.tsdf import build_mesh_index, render_mesh_color
+
+        if (colors is None) == (texture is None):
+            raise ValueError(f"{what}: give exactly one of colors and texture")
+        mesh = tuple(mesh)
+        index = build_mesh_index(mesh)                           # validated here; one index serves every view
+
+        def render(pose, r):
+            out = render_mesh_color(mesh, pose, colors=colors, texture=texture, near=near, far=far, index=index,
+                                    validate=False, **r)
+            return out[3], out[2]
+
+        return self._score_views(what, render, images, poses, rays, K, chunk, False)
 
     def render_view(self, pose=None, rays=None, K=None, hw=None, **kw):
         """Depth / normal view of the global TSDF at this point of the run: (range f32[h,w], normals f32[h,w,3],
