@@ -865,6 +865,12 @@ int mslam_conv2d_nhwc_bf16(const void* in, const void* W, const float* bias, con
 /* O[B,Nq,H*64] = softmax(Q K^T) V ; Q,K bf16 [B,H,N,64] (Q pre-scaled by 1/8), VT bf16 [B,H,64,Nk]. */
 int mslam_attention_bf16(const void* Q, const void* K, const void* VT, void* O, int batch, int heads,
                          int nq, int nk, void* stream);
+/* The same product (Attention.forward / CrossAttention.forward, dust3r/croco/models/blocks.py:95-112,149-169) under a
+ * forced work decomposition: `split` key splits x `qg` query groups of 32 rows per block, where mslam_attention_bf16
+ * picks both from the shape.  For kernel tests and tools/attn_tune.py: the result depends on `split` only, every qg
+ * gives the same bits.  A (split, qg) pair that the library does not hold returns MSLAM_EINVAL. */
+int mslam_attention_bf16_cfg(const void* Q, const void* K, const void* VT, void* O, int batch, int heads,
+                             int nq, int nk, int split, int qg, void* stream);
 /* torch.nn.LayerNorm over the last dim (D <= 2048): x f32[rows,D] -> bf16 and/or f32 outputs. */
 int mslam_layernorm_f32(const float* x, const float* w, const float* b, void* out_bf16, float* out_f32,
                         int rows, int D, float eps, void* stream);

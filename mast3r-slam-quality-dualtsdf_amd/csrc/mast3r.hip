@@ -20,6 +20,8 @@ namespace mslam {
 
 int launch_attention(const bf16* Q, const bf16* K, const bf16* VT, bf16* O, int batch, int heads, int nq, int nk,
                      hipStream_t stream);
+int launch_attention_cfg(const bf16* Q, const bf16* K, const bf16* VT, bf16* O, int batch, int heads, int nq, int nk,
+                         int split, int qg, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------
 // small kernels
@@ -1068,6 +1070,14 @@ extern "C" int mslam_attention_bf16(const void* Q, const void* K, const void* VT
   MSLAM_REQUIRE(Q && K && VT && O, "attention: null pointer");
   return launch_attention((const bf16*)Q, (const bf16*)K, (const bf16*)VT, (bf16*)O, batch, heads, nq, nk,
                           (hipStream_t)stream);
+}
+
+// the same under a forced (key split, query groups per block); MSLAM_EINVAL for a pair that is not instantiated
+extern "C" int mslam_attention_bf16_cfg(const void* Q, const void* K, const void* VT, void* O, int batch, int heads,
+                                        int nq, int nk, int split, int qg, void* stream) {
+  MSLAM_REQUIRE(Q && K && VT && O, "attention: null pointer");
+  return launch_attention_cfg((const bf16*)Q, (const bf16*)K, (const bf16*)VT, (bf16*)O, batch, heads, nq, nk, split, qg,
+                              (hipStream_t)stream);
 }
 
 extern "C" int mslam_layernorm_f32(const float* x, const float* w, const float* b, void* out_bf16, float* out_f32,

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the hand-written network kernels (not part of the test suite):
-python tools/bench_kernels.py [shipped]  -> one line per shape with us/launch and TFLOP/s (shipped: the shapes of the
-round-3 loop: encoder batches of 12, decode groups of 6)."""
+python tools/bench_kernels.py [shipped | attention] [attn=SPLIT,QG]  -> one line per shape with us/launch and TFLOP/s
+(shipped: the shapes of the round-3 loop: encoder batches of 12, decode groups of 6; attention: its two attention launches
+alone; attn=SPLIT,QG: the attention lines run that key split and that many query groups per block, not the library's
+choice)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "mast3r-slam-quality-dualtsdf_amd")]
@@ -52,13 +54,25 @@ def conv(B, H, W, Cin, Cout, ks=3, stride=1):
     print(f"conv B={B} {H}x{W} {Cin}->{Cout} k{ks}s{stride}: {us:8.1f} us  {fl / us * 1e-6:7.1f} TFLOP/s")
 
 
-def attn(B, Hh, N):
+ATTN_CFG = None   # (split, qg) from the command line (attn=SPLIT,QG): the attention lines run that decomposition
+
+
+def attn(B, Hh, N, cfg=None):
+    """cfg = (key split, query groups per block) through mslam_attention_bf16_cfg; None: the library's own choice."""
+    cfg = cfg or ATTN_CFG
     q = torch.randn(B, Hh, N, 64, device=dev).to(torch.bfloat16) * 0.125
     k = torch.randn(B, Hh, N, 64, device=dev).to(torch.bfloat16)
     vt = torch.randn(B, Hh, 64, N, device=dev).to(torch.bfloat16)
     o = torch.empty(B, N, Hh * 64, device=dev, dtype=torch.bfloat16)
-    us = timeit(lambda: L.mslam_attention_bf16(m.ptr(q), m.ptr(k), m.ptr(vt), m.ptr(o), B, Hh, N, N, m.stream_ptr()))
-    print(f"attn B={B} H={Hh} N={N}: {us:8.1f} us  {4 * B * Hh * N * N * 64 / us * 1e-6:7.1f} TFLOP/s")
+    p = (m.ptr(q), m.ptr(k), m.ptr(vt), m.ptr(o), B, Hh, N, N)
+    if cfg is None:
+        us = timeit(lambda: L.mslam_attention_bf16(*p, m.stream_ptr()))
+    else:
+        m.check(L.mslam_attention_bf16_cfg(*p, cfg[0], cfg[1], m.stream_ptr()), f"attention split {cfg[0]} qg {cfg[1]}")
+        us = timeit(lambda: L.mslam_attention_bf16_cfg(*p, cfg[0], cfg[1], m.stream_ptr()))
+    tag = "" if cfg is None else f" split={cfg[0]} qg={cfg[1]}"
+    print(f"attn B={B} H={Hh} N={N}{tag}: {us:8.1f} us  {4 * B * Hh * N * N * 64 / us * 1e-6:7.1f} TFLOP/s")
+    return us
 
 
 def ln(rows, D):
@@ -68,6 +82,18 @@ def ln(rows, D):
     us = timeit(lambda: L.mslam_layernorm_f32(m.ptr(x), m.ptr(w), m.ptr(b), m.ptr(ob), 0, rows, D, 1e-6, m.stream_ptr()))
     print(f"layernorm {rows}x{D}: {us:8.1f} us  {rows * D * 6 / us * 1e-3:7.1f} GB/s")
 
+
+if __name__ == "__main__" and os.path.basename(sys.argv[0]) == "bench_kernels.py":
+    for a in sys.argv[1:]:
+        if a.startswith("attn="):
+            ATTN_CFG = tuple(int(x) for x in a[5:].split(","))
+            assert len(ATTN_CFG) == 2, "attn=SPLIT,QG"
+
+if __name__ == "__main__" and os.path.basename(sys.argv[0]) == "bench_kernels.py" and "attention" in sys.argv[1:]:
+    # the two attention launches of the shipped loop alone: encoder on 12 frames, decoder on 6 pairs (both sides)
+    attn(12, 16, 768)
+    attn(12, 12, 768)
+    sys.exit(0)
 
 if __name__ == "__main__" and os.path.basename(sys.argv[0]) == "bench_kernels.py" and "shipped" in sys.argv[1:]:
     # the shapes of the shipped loop (round 3): encoder on 12 frames (9 216 rows), decoder + heads on 6 pairs (4 608 rows per
