@@ -230,36 +230,16 @@ def save_render_metrics(savedir, filename, metrics):
     return save_mesh_metrics(savedir, filename, metrics)
 
 
-def save_tsdf_mesh(savedir, filename, source, min_weight=None, level=0.0, colors=False, min_component_faces=0,
-                   keep_largest=None, simplify_cell=0.0, simplify_position="quadric", smooth_iterations=0,
-                   smooth_lambda=0.5, smooth_mu=-0.53, smooth_boundary="fixed", fill_holes=0, **fill_options):
+def save_tsdf_mesh(savedir, filename, source, min_weight=None, level=0.0, colors=False, **chain):
     """The global TSDF's triangle mesh (marching cubes) as PLY with normals, beside save_reconstruction's point cloud.
     `source`: a SlamSystem, a TSDFGlobalManager or a TSDFVolume.  `colors=True` (a volume with tsdf_global.color): the
-    vertices carry the fused colour as red / green / blue.  `min_component_faces` > 0 / `keep_largest`: small connected
-    components are dropped first (DESIGN.md "Mesh components").  `simplify_cell` > 0 (world units) /
-    `simplify_position`: the mesh is then simplified by vertex clustering (DESIGN.md "Mesh simplification").
-    `smooth_iterations` > 0 / `smooth_lambda`, `smooth_mu`, `smooth_boundary`: Taubin smoothing between the two (DESIGN.md
-    "Mesh smoothing").  `fill_holes` = n > 0: holes of at most n edges are closed before the smoothing (DESIGN.md "Mesh
-    holes").  `fill_options` takes four more keywords.  `fill_bowties=True`: holes that meet in a vertex too.
-    `decimate_faces` = n > 0 / `decimate_ratio` in (0, 1] / `decimate_error` > 0 (world units): edge-collapse decimation
-    to n faces / that share of the faces / while the quadric error allows, last of all (DESIGN.md "Mesh decimation").
-    Returns (V, F)."""
-    from mast3r_slam.tsdf._mesh_args import _fill_options
+    vertices carry the fused colour as red / green / blue.  `chain`: the options of the export chain
+    (tsdf/mesh_chain.py); an option that is off is not handed on.  Returns (V, F)."""
+    from mast3r_slam.tsdf.mesh_chain import chain_options
 
-    fill_bowties, decimate = _fill_options(fill_options, "save_tsdf_mesh")
+    kw = chain_options(chain, "save_tsdf_mesh")
     savedir = pathlib.Path(savedir)
     savedir.mkdir(exist_ok=True, parents=True)
-    kw = {}
-    if min_component_faces > 0 or keep_largest is not None:
-        kw = dict(min_component_faces=min_component_faces, keep_largest=keep_largest)
-    if simplify_cell is not None and simplify_cell > 0:
-        kw = dict(kw, simplify_cell=simplify_cell, simplify_position=simplify_position)
-    if smooth_iterations is not None and smooth_iterations > 0:
-        kw = dict(kw, smooth_iterations=smooth_iterations, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu,
-                  smooth_boundary=smooth_boundary)
-    if fill_holes is not None and fill_holes > 0:
-        kw = dict(kw, fill_holes=fill_holes, **(dict(fill_bowties=True) if fill_bowties else {}))
-    kw = dict(kw, **decimate)                                # those of the three that are on
     if colors:
         v, n, f, c = source.extract_mesh(min_weight=min_weight, level=level, colors=True, **kw)
         save_mesh(savedir / filename, v, f, normals=n, colors=c)

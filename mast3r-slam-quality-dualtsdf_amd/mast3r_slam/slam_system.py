@@ -355,52 +355,19 @@ class SlamSystem:
             with self._critical("main"):
                 self._apply_commits(wait=True)
 
-    def extract_mesh(self, min_weight=None, level=0.0, colors=False, min_component_faces=None, keep_largest=None,
-                     simplify_cell=None, simplify_position="quadric", smooth_iterations=None, smooth_lambda=0.5,
-                     smooth_mu=-0.53, smooth_boundary="fixed", fill_holes=None, **kw):
+    def extract_mesh(self, min_weight=None, level=0.0, colors=False, **chain):
         """Triangle mesh of the global TSDF at this point of the run: (vertices f32[V,3], normals f32[V,3], faces i32[F,3])
         device tensors (TSDFVolume.extract_mesh).  Drains the backend first, so every fusion it has issued is ordered
-        before the read.  `colors=True` (tsdf_global.color on): vertex colours f32[V,3] as a fourth tensor.
-        `min_component_faces` (default tsdf_global.mesh_min_component_faces, 0 = off) / `keep_largest`: drop small
-        connected components (DESIGN.md "Mesh components").  `simplify_cell` (world units; default
-        tsdf_global.mesh_simplify_voxels voxel sizes, 0 = off) / `simplify_position`: simplify the result by vertex
-        clustering (DESIGN.md "Mesh simplification").  `smooth_iterations` (default
-        tsdf_global.mesh_smooth_iterations, 0 = off) / `smooth_lambda`, `smooth_mu`, `smooth_boundary`: Taubin smoothing
-        after the component filter and before the simplification (DESIGN.md "Mesh smoothing").  `fill_holes` (default
-        tsdf_global.mesh_fill_holes, 0 = off): holes of at most that many edges are closed before the smoothing (DESIGN.md
-        "Mesh holes"); `fill_bowties` (in `kw`; default tsdf_global.mesh_fill_bowties, off): holes that meet in a vertex too.
-        `decimate_faces` (default tsdf_global.mesh_decimate_faces, 0 = off) / `decimate_ratio` / `decimate_error` (world
-        units; default tsdf_global.mesh_decimate_error voxel sizes, 0 = off), all three in `kw`: edge-collapse decimation
-        to that many faces / that share of the faces / while the quadric error allows, last of all (DESIGN.md "Mesh
-        decimation")."""
+        before the read.  `colors=True` (tsdf_global.color on): vertex colours f32[V,3] as a fourth tensor.  `chain`: the
+        options of the export chain (tsdf/mesh_chain.py); one that is absent or None takes tsdf_global's value
+        (mesh_chain.CONFIG), anything else, an explicit 0 included, stays as given."""
         if self.tsdf_manager is None:
             raise RuntimeError("SlamSystem.extract_mesh: the global TSDF is disabled (tsdf_global.enabled = False)")
-        if min_component_faces is None:
-            min_component_faces = int(self.tsdf_manager.cfg.get("mesh_min_component_faces", 0))
-        if simplify_cell is None:
-            simplify_cell = (float(self.tsdf_manager.cfg.get("mesh_simplify_voxels", 0.0))
-                             * float(self.tsdf_manager.volume.voxel_size))
-        if smooth_iterations is None:
-            smooth_iterations = int(self.tsdf_manager.cfg.get("mesh_smooth_iterations", 0))
-        if fill_holes is None:
-            fill_holes = int(self.tsdf_manager.cfg.get("mesh_fill_holes", 0))
-        kw = dict(kw)
-        if kw.get("decimate_faces") is None:
-            kw["decimate_faces"] = int(self.tsdf_manager.cfg.get("mesh_decimate_faces", 0))
-        if kw.get("decimate_error") is None:
-            kw["decimate_error"] = (float(self.tsdf_manager.cfg.get("mesh_decimate_error", 0.0))
-                                    * float(self.tsdf_manager.volume.voxel_size))
-        if kw.get("fill_bowties") is None:                     # the config's switch; off adds nothing to the call
-            kw = {k: v for k, v in kw.items() if k != "fill_bowties"}
-            if self.tsdf_manager.cfg.get("mesh_fill_bowties", False):
-                kw["fill_bowties"] = True
+        from mast3r_slam.tsdf.mesh_chain import config_defaults
+
+        chain = config_defaults(chain, self.tsdf_manager.cfg, self.tsdf_manager.volume.voxel_size)
         self.drain()
-        return self.tsdf_manager.extract_mesh(min_weight=min_weight, level=level, colors=colors,
-                                              min_component_faces=min_component_faces, keep_largest=keep_largest,
-                                              simplify_cell=simplify_cell, simplify_position=simplify_position,
-                                              smooth_iterations=smooth_iterations, smooth_lambda=smooth_lambda,
-                                              smooth_mu=smooth_mu, smooth_boundary=smooth_boundary, fill_holes=fill_holes,
-                                              **kw)
+        return self.tsdf_manager.extract_mesh(min_weight=min_weight, level=level, colors=colors, **chain)
 
     def align_trajectory(self, gt_positions):
         """The Sim3 that moves the map's frame onto a ground truth's, from camera centres: tsdf.fit_sim3 of the keyframes'

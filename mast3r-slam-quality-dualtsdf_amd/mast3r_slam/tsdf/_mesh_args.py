@@ -67,20 +67,6 @@ def _bool_arg(value, name, what):
     return bool(value)
 
 
-_DECIMATE_OPTIONS = ("decimate_faces", "decimate_ratio", "decimate_error")
-
-
-def _fill_options(options, what):
-    """The keywords that may follow `fill_holes` in extract_mesh, mesh_from_voxels and save_tsdf_mesh, as the dict their
-    `**fill_options` caught -> (fill_bowties, the decimate_* among them that are on: not None and not <= 0).  Any other
-    name raises the TypeError a def would."""
-    for name in options:
-        if name != "fill_bowties" and name not in _DECIMATE_OPTIONS:
-            raise TypeError(f"{what}() got an unexpected keyword argument {name!r}")
-    decimate = {k: options[k] for k in _DECIMATE_OPTIONS if options.get(k) is not None and not options[k] <= 0}
-    return _bool_arg(options.get("fill_bowties", False), "fill_bowties", what), decimate
-
-
 def _ranges(verts, faces, *more):
     """(lowest and highest coordinate, lowest and highest face index, all coordinates finite) of a non-empty mesh as
     Python floats: one stacked reduction, one host read.  `more`: further 0-d tensors that ride along in that read."""

@@ -17,7 +17,7 @@ import torch
 from lietorch_hip import Sim3
 from mast3r_slam.config import config
 
-from ._mesh_args import _DECIMATE_OPTIONS, _bool_arg
+from .mesh_chain import chain_options
 
 
 def gather_uimg(uimg, choice, map_hw):
@@ -170,37 +170,14 @@ class TSDFGlobalManager:
         if self.enabled:
             self.volume.maintain()   # samples dropped by the last solve are reported here
 
-    def extract_mesh(self, min_weight=None, level=0.0, colors=False, min_component_faces=0, keep_largest=None,
-                     simplify_cell=0.0, simplify_position="quadric", smooth_iterations=0, smooth_lambda=0.5,
-                     smooth_mu=-0.53, smooth_boundary="fixed", fill_holes=0, **kw):
+    def extract_mesh(self, min_weight=None, level=0.0, colors=False, **chain):
         """Triangle mesh of the global volume: (vertices f32[V,3], normals f32[V,3], faces i32[F,3]) device tensors
-        (TSDFVolume.extract_mesh); `colors=True`: vertex colours f32[V,3] as a fourth tensor.  `min_component_faces` /
-        `keep_largest`: drop small connected components (DESIGN.md "Mesh components"); off by default.  `simplify_cell`
-        > 0 (world units) / `simplify_position`: simplify the result by vertex clustering (DESIGN.md "Mesh
-        simplification"); off by default.  `smooth_iterations` > 0 / `smooth_lambda`, `smooth_mu`, `smooth_boundary`:
-        Taubin smoothing between the two (DESIGN.md "Mesh smoothing"); off by default.  `fill_holes` = n > 0: holes of at
-        most n edges are closed before the smoothing (DESIGN.md "Mesh holes"); off by default.  `fill_bowties=True`
-        (in `kw`): holes that meet in a vertex are closed too; it does nothing without `fill_holes`.  `decimate_faces` =
-        n > 0 / `decimate_ratio` in (0, 1] / `decimate_error` > 0 (world units; all three in `kw`): edge-collapse
-        decimation to n faces / that share of the faces / while the quadric error allows, last of all (DESIGN.md "Mesh
-        decimation"); off by default, and an argument that is off is not handed on."""
-        kw = dict(kw)
-        fill_bowties = _bool_arg(kw.pop("fill_bowties", False), "fill_bowties", "TSDFGlobalManager.extract_mesh")
-        if min_component_faces > 0 or keep_largest is not None:
-            kw = dict(kw, min_component_faces=min_component_faces, keep_largest=keep_largest)
-        if simplify_cell is not None and simplify_cell > 0:
-            kw = dict(kw, simplify_cell=simplify_cell, simplify_position=simplify_position)
-        if smooth_iterations is not None and smooth_iterations > 0:
-            kw = dict(kw, smooth_iterations=smooth_iterations, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu,
-                      smooth_boundary=smooth_boundary)
-        if fill_holes is not None and fill_holes > 0:
-            kw = dict(kw, fill_holes=fill_holes, **(dict(fill_bowties=True) if fill_bowties else {}))
-        for name in _DECIMATE_OPTIONS:
-            if name in kw and (kw[name] is None or kw[name] <= 0):
-                del kw[name]
-        if not colors and not kw:
+        (TSDFVolume.extract_mesh); `colors=True`: vertex colours f32[V,3] as a fourth tensor.  `chain`: the options of
+        the export chain (mesh_chain); an option that is off is not handed on."""
+        chain = chain_options(chain, "TSDFGlobalManager.extract_mesh")
+        if not colors and not chain:
             return self.volume.extract_mesh(min_weight=min_weight, level=level)
-        return self.volume.extract_mesh(min_weight=min_weight, level=level, colors=colors, **kw)
+        return self.volume.extract_mesh(min_weight=min_weight, level=level, colors=colors, **chain)
 
     def render(self, pose, rays=None, K=None, hw=None, **kw):
         """Depth / normal view of the global volume from `pose`: (range f32[h,w], normals f32[h,w,3], hit bool[h,w])

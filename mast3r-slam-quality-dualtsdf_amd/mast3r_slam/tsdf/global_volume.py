@@ -13,12 +13,7 @@ import torch
 
 import mslam_hip as _m
 
-from ._mesh_args import _fill_options
-from .mesh_ops import filter_mesh
-from .mesh_decimate import _decimate
-from .mesh_simplify import simplify_mesh
-from .mesh_holes import fill_holes as _fill_holes
-from .mesh_smooth import smooth_mesh
+from .mesh_chain import chain_options, run_chain
 
 
 _KEY_BIAS = 1 << 20
@@ -352,59 +347,29 @@ class TSDFVolume:
             _m.check(_m.lib().mslam_tsdf_color_load(_m.ptr(self._table), self.capacity, _m.ptr(self._color), _m.ptr(k),
                                                     _m.ptr(c), n, _m.stream_ptr()), "tsdf_color_load")
 
-    def extract_mesh(self, min_weight=None, level=0.0, colors=False, default_color=(0.5, 0.5, 0.5),
-                     min_component_faces=0, keep_largest=None, simplify_cell=0.0, simplify_position="quadric",
-                     smooth_iterations=0, smooth_lambda=0.5, smooth_mu=-0.53, smooth_boundary="fixed", fill_holes=0,
-                     **fill_options):
+    def extract_mesh(self, min_weight=None, level=0.0, colors=False, default_color=(0.5, 0.5, 0.5), **chain):
         """Marching cubes over the fused volume -> (vertices f32[V,3], normals f32[V,3], faces i32[F,3]) device tensors in
         canonical order (DESIGN.md "Mesh extraction").  Corners are voxel centres with weight >= min_weight (default
         self.min_weight), inside = tsdf < level, normals point to free space, faces are counter-clockwise seen from
         there.  The table is only read.  One host read (the output sizes).  Sharded volumes: cubes span owners, so the
         union of the shards (voxels(), collective) is meshed on every rank.  `colors=True` (needs color=True): a fourth
-        tensor f32[V,3] in [0, 1], the colour sampled at each f32 vertex position (sample_color).
-        `min_component_faces` > 0 / `keep_largest`=k: connected components with fewer faces / all but the k largest are
-        dropped after extraction and colour sampling (mesh_ops.filter_mesh, DESIGN.md "Mesh components"; one more host
-        read); the defaults leave the mesh as extracted.  `simplify_cell` > 0 (world units; a whole number of voxels keeps
-        the cells aligned with them): the mesh is then simplified by clustering its vertices on that grid, placed by
-        `simplify_position` = "quadric" | "mean" (mesh_simplify.simplify_mesh, DESIGN.md "Mesh simplification"; three more
-        host reads).  It runs last, so floaters are dropped before anything could merge them into the surface.
-        `smooth_iterations` > 0: that many Taubin iterations with `smooth_lambda`, `smooth_mu`, `smooth_boundary`
-        (mesh_smooth.smooth_mesh, DESIGN.md "Mesh smoothing"; two more host reads) after the component filter and before
-        the simplification, whose plane quadrics then see the smoothed surface; normals are recomputed.
-        `fill_holes` = n > 0: boundary loops of at most n edges that are holes are closed with a centroid fan
-        (mesh_holes.fill_holes, DESIGN.md "Mesh holes"; four more host reads) after the component filter and before the
-        smoothing, which then fairs the patches.  `fill_options` takes four more keywords.  `fill_bowties=True`: holes that
-        meet in a vertex, as two diagonal missing voxels leave them, are told apart and closed too (fill_holes' bow-tie
-        mode; no further host read); without `fill_holes` it does nothing.
-        `decimate_faces` = n > 0 / `decimate_ratio` in (0, 1] / `decimate_error` > 0 (world units): the mesh is decimated
-        by edge collapses to n faces / that share of its faces / while the quadric error allows
-        (mesh_decimate.decimate_mesh, DESIGN.md "Mesh decimation"; two host reads and one more per round).  It runs last,
-        after the cluster simplification, so both can be combined; each is off when None or <= 0 (the default)."""
-        fill_bowties, decimate = _fill_options(fill_options, "TSDFVolume.extract_mesh")
-        smooth = dict(smooth_iterations=smooth_iterations, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu,
-                      smooth_boundary=smooth_boundary, fill_holes=fill_holes, fill_bowties=fill_bowties, **decimate)
+        tensor f32[V,3] in [0, 1], the colour sampled at each f32 vertex position (sample_color).  `chain`: the options
+        of the export chain, which then runs on the result (mesh_chain); the defaults leave the mesh as extracted."""
+        chain = chain_options(chain, "TSDFVolume.extract_mesh")
         mw = self.min_weight if min_weight is None else float(min_weight)
         if colors and not self.color:
             raise ValueError("TSDFVolume.extract_mesh: colors=True needs a volume built with color=True")
         if self.num_shards > 1:
             if colors:
                 return self._union().extract_mesh(min_weight=mw, level=level, colors=True, default_color=default_color,
-                                                  min_component_faces=min_component_faces, keep_largest=keep_largest,
-                                                  simplify_cell=simplify_cell, simplify_position=simplify_position,
-                                                  **smooth)
+                                                  **chain)
             keys, t, w = self.voxels()
-            return mesh_from_voxels(keys, t, w, self.voxel_size, mw, level, device=self.device,
-                                    min_component_faces=min_component_faces, keep_largest=keep_largest,
-                                    simplify_cell=simplify_cell, simplify_position=simplify_position, **smooth)
+            return mesh_from_voxels(keys, t, w, self.voxel_size, mw, level, device=self.device, **chain)
         mesh = _extract(self._table, self.capacity, self.voxel_size, mw, float(level), self.device)
         if colors:
             mesh = mesh + (_sample_color(self._table, self.capacity, self._color, mesh[0], 0, self.voxel_size,
                                          default_color)[0],)
-        mesh = filter_mesh(mesh, min_component_faces, keep_largest, _validate=False)
-        mesh = _fill_holes(mesh, fill_holes, bowties=fill_bowties)          # off (None or <= 0): `mesh` itself
-        mesh = smooth_mesh(mesh, smooth_iterations, smooth_lambda, smooth_mu, smooth_boundary)       # off: `mesh` itself
-        mesh = simplify_mesh(mesh, simplify_cell, simplify_position)        # off (None or <= 0): `mesh` itself
-        return _decimate(mesh, **decimate)                                  # off (none of the three): `mesh` itself
+        return run_chain(mesh, chain)
 
     def render(self, pose, rays=None, K=None, hw=None, near=0.05, far=10.0, min_weight=None, level=0.0, step=None,
                skip=True, colors=False, default_color=(0.5, 0.5, 0.5)):
@@ -592,16 +557,11 @@ def render_from_voxels(keys, tsdf, weight, voxel_size, min_weight, pose, rays, n
 
 
 def mesh_from_voxels(keys, tsdf, weight, voxel_size, min_weight, level=0.0, device="cuda", colors=None,
-                     default_color=(0.5, 0.5, 0.5), min_component_faces=0, keep_largest=None, simplify_cell=0.0,
-                     simplify_position="quadric", smooth_iterations=0, smooth_lambda=0.5, smooth_mu=-0.53,
-                     smooth_boundary="fixed", fill_holes=0, **fill_options):
+                     default_color=(0.5, 0.5, 0.5), **chain):
     """Mesh of a voxel set given as arrays (keys i64[n,3] distinct, tsdf f64[n], weight f64[n]; numpy or device): loads
-    a temporary table of at least 2n slots and extracts from it (TSDFVolume.extract_mesh semantics, its component filter,
-    its hole filling, its smoothing, its simplification and, through `fill_options`, its decimation included).  `colors`
-    u64[n,4]: the voxels' colour sums (voxel_color_sums()); the mesh then carries vertex colours as a fourth tensor."""
+    a temporary table of at least 2n slots and extracts from it (TSDFVolume.extract_mesh semantics, the export chain of
+    mesh_chain included).  `colors` u64[n,4]: the voxels' colour sums (voxel_color_sums()); the mesh then carries vertex
+    colours as a fourth tensor."""
     vol = _loaded(keys, tsdf, weight, voxel_size, min_weight, device, colors)
     return vol.extract_mesh(min_weight=min_weight, level=level, colors=colors is not None, default_color=default_color,
-                            min_component_faces=min_component_faces, keep_largest=keep_largest,
-                            simplify_cell=simplify_cell, simplify_position=simplify_position,
-                            smooth_iterations=smooth_iterations, smooth_lambda=smooth_lambda, smooth_mu=smooth_mu,
-                            smooth_boundary=smooth_boundary, fill_holes=fill_holes, **fill_options)
+                            **chain)

@@ -45,15 +45,6 @@ def _decimate_args(target_faces, ratio, max_error, what="decimate_mesh"):
     return target_faces, ratio, max_error
 
 
-def _decimate(mesh, decimate_faces=None, decimate_ratio=None, decimate_error=None):
-    """The last stage of every extract_mesh: decimate_mesh(mesh, target_faces=decimate_faces, ratio=decimate_ratio,
-    max_error=decimate_error), each of the three off when None or <= 0; all off: `mesh` itself."""
-    given = [None if x is None or x <= 0 else x for x in (decimate_faces, decimate_ratio, decimate_error)]
-    if given == [None, None, None]:
-        return mesh
-    return decimate_mesh(mesh, *given, _validate=False)
-
-
 class _Round:
     """The tables of one round on the working faces, and its candidates."""
 

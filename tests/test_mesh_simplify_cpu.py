@@ -109,22 +109,14 @@ def test_sphere_at_three_voxels():
 
 
 def test_simplify_entry_points_exist_without_a_device():
-    import inspect
-
     import torch
 
     import mslam_hip
-    from mast3r_slam import evaluate, tsdf
+    from mast3r_slam import tsdf
     from mast3r_slam.config import config
-    from mast3r_slam.slam_system import SlamSystem
 
     assert callable(tsdf.simplify_mesh)
-    for fn in (tsdf.TSDFVolume.extract_mesh, tsdf.mesh_from_voxels, tsdf.TSDFGlobalManager.extract_mesh,
-               evaluate.save_tsdf_mesh):
-        p = inspect.signature(fn).parameters
-        assert p["simplify_cell"].default == 0.0 and p["simplify_position"].default == "quadric", fn
-    p = inspect.signature(SlamSystem.extract_mesh).parameters
-    assert p["simplify_cell"].default is None and p["simplify_position"].default == "quadric"
+    # simplify_cell / simplify_position of the five export functions: test_mesh_chain_cpu.py
     assert config["tsdf_global"]["mesh_simplify_voxels"] == 0.0
     declared = mslam_hip.exported_symbols()
     for s in ("mslam_mesh_simplify_keys", "mslam_mesh_simplify_faces", "mslam_mesh_simplify_solve",

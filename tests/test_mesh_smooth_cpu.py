@@ -246,21 +246,14 @@ def test_normals_edge_cases():
 
 
 def test_entry_points_exist_without_a_device():
-    import inspect
-
     import torch
 
     import mslam_hip
-    from mast3r_slam import evaluate, tsdf
+    from mast3r_slam import tsdf
     from mast3r_slam.config import config
-    from mast3r_slam.slam_system import SlamSystem
 
     assert callable(tsdf.smooth_mesh) and callable(tsdf.vertex_normals)
-    for fn in (tsdf.TSDFVolume.extract_mesh, tsdf.mesh_from_voxels, tsdf.TSDFGlobalManager.extract_mesh,
-               evaluate.save_tsdf_mesh, SlamSystem.extract_mesh):
-        p = inspect.signature(fn).parameters
-        assert p["smooth_iterations"].default == (None if fn is SlamSystem.extract_mesh else 0), fn
-        assert (p["smooth_lambda"].default, p["smooth_mu"].default, p["smooth_boundary"].default) == (0.5, -0.53, "fixed")
+    # smooth_iterations / smooth_lambda / smooth_mu / smooth_boundary of the five export functions: test_mesh_chain_cpu.py
     assert config["tsdf_global"]["mesh_smooth_iterations"] == 0
     declared = mslam_hip.exported_symbols()
     for s in ("mslam_mesh_smooth_edges", "mslam_mesh_smooth_step", "mslam_mesh_vertex_faces",
