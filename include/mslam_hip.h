@@ -715,6 +715,55 @@ int mslam_mesh_shade(const int32_t* face, const float* rays, int h, int w, const
                      const int32_t* faces, int num_faces, int num_vertices, const float* colors, const float* atlas,
                      int texels, int cols, int rows, float* rgb, void* stream);
 
+/* Mesh textures, the sized atlas (DESIGN.md "Mesh textures: sized atlas"; the definition is
+ * tests/texture_sized_numpy.py).  Every face has its own R_f, one of the 13 classes 4, 6, 8, 12, 16, 24, ..., 192, 256
+ * (class c has R = (c odd ? 6 : 4) << (c / 2)); the cells of a class lie in one band of the atlas.  Inside a cell
+ * everything is the uniform atlas's with R_f for R.  256-thread blocks, integers and f64 in one fixed order, no atomics,
+ * nothing but the outputs written, bit-identical from call to call.
+ *   mslam_mesh_texture_classes        per face cls i32[F], the class index of R_f, and clamped i32[F] (0 / 1):
+ *                                     L = max(max(e_ab, e_bc), e_ca), e = sqrt((dx dx + dy dy) + dz dz) in f64,
+ *                                     need = ceil(density L + 3.5); the smallest class >= need, at least floor_class, at
+ *                                     most cap_class; clamped where need exceeds the cap's R.  A face with an index
+ *                                     outside [0, V) or an edge that is not finite: floor_class, not clamped.
+ *   mslam_mesh_texture_rank_table_ints  the ints of `table` below: 14 (ceil(F / 256) + 1).
+ *   mslam_mesh_texture_rank           the stable counting sort by class in three launches: rank i32[F] = the faces of a
+ *                                     smaller index in the same class; order i32[F] = the faces class by class, largest
+ *                                     R first, each by rising index; counts i32[14] = the 13 class counts and the
+ *                                     number of clamped faces (also written for F = 0).  `table` is device scratch of
+ *                                     the caller's.
+ *   mslam_mesh_texture_layout_sized   bands: 13 rows (R, cols, rows, y0, base, count) of int32 in HOST memory, read
+ *                                     before the call returns and checked against (F, H, W): bands from the largest
+ *                                     class down, y0 and base the running sums of rows R and count.  owner i32[H W] and
+ *                                     face_cell i32[F,4] = (x0, y0, R_f, half): face f is half k & 1 of cell k >> 1 of
+ *                                     its band, k its rank; texels right of a band's last column, in unused cells and
+ *                                     in the absent half of an odd class's last cell have owner -1.
+ *   mslam_mesh_texture_rays_sized,
+ *   mslam_mesh_texture_resolve_sized  mslam_mesh_texture_rays / _resolve on the texels of the sized atlas: the texel's
+ *                                     face from owner, its local (i, j) = (x - x0, y - y0), mirrored (R - i, R - 1 - j)
+ *                                     for half 1, from face_cell; an owner outside [0, F) counts as none.
+ *                                     mslam_mesh_texture_accumulate serves both atlases.
+ *   mslam_mesh_shade_sized            mslam_mesh_shade from a sized atlas f32[H,W,3]: the cell of the face hit from
+ *                                     face_cell; a cell that does not lie inside the atlas shades as a miss. */
+int mslam_mesh_texture_classes(const float* vertices, const int32_t* faces, int num_faces, int num_vertices,
+                               double density, int floor_class, int cap_class, int32_t* cls, int32_t* clamped,
+                               void* stream);
+size_t mslam_mesh_texture_rank_table_ints(int num_faces);
+int mslam_mesh_texture_rank(const int32_t* cls, const int32_t* clamped, int num_faces, int32_t* table,
+                            size_t table_ints, int32_t* rank, int32_t* order, int32_t* counts, void* stream);
+int mslam_mesh_texture_layout_sized(const int32_t* bands, int num_faces, int H, int W, const int32_t* cls,
+                                    const int32_t* rank, const int32_t* order, int32_t* owner, int32_t* face_cell,
+                                    void* stream);
+int mslam_mesh_texture_rays_sized(const float* vertices, const int32_t* faces, int num_faces, int num_vertices,
+                                  const int32_t* owner, const int32_t* face_cell, int H, int W, const float* pose8,
+                                  double fx, double fy, double cx, double cy, int h, int w, double near, double far,
+                                  double cos_min, float* dir, double* r, double* cos, double* uv, void* stream);
+int mslam_mesh_texture_resolve_sized(const int32_t* faces, int num_faces, int num_vertices, const int32_t* owner,
+                                     const int32_t* face_cell, int H, int W, const double* sums, const float* colors,
+                                     double default_color, float* atlas, void* stream);
+int mslam_mesh_shade_sized(const int32_t* face, const float* rays, int h, int w, const float* pose8,
+                           const float* vertices, const int32_t* faces, int num_faces, int num_vertices,
+                           const float* atlas, const int32_t* face_cell, int H, int W, float* rgb, void* stream);
+
 /* Colour of the volume (no counterpart in the reference, DESIGN.md "Colour").  `color` is a second caller-owned device
  * buffer of mslam_tsdf_color_bytes(capacity) bytes, addressed by the slot index of `table`: four u64 words per slot,
  * sum_w (units of 2^-20), sum_w * r8, sum_w * g8, sum_w * b8 with 8-bit colours.  The sums are integers: the fused

@@ -45,6 +45,7 @@ _BASE = {
         "mesh_fill_bowties": False,      # ... those that meet in a vertex included (bow-tie mode of "Mesh holes")
         "mesh_decimate_faces": 0,        # ... and last decimates to this many faces, 0 = off ("Mesh decimation")
         "mesh_decimate_error": 0.0,      # ... within this quadric error, in voxel sizes, 0 = off ("Mesh decimation")
+        "mesh_texture_density": 0.0,     # SlamSystem.bake_texture: texels per voxel size of the sized atlas, 0 = off
         "mesh_eval_threshold": 0.05,     # SlamSystem.evaluate_mesh: precision / recall distance (DESIGN.md "Mesh quality")
     },
 }

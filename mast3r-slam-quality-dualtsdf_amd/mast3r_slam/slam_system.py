@@ -632,6 +632,12 @@ class SlamSystem:
             raise ValueError(f"{what}: the keyframes differ in image size")
         poses = torch.stack([self.keyframes[i].T_WC.data.detach().reshape(8) for i in range(n_kf)])
         kw.setdefault("index", True)          # the same bytes; a decimated mesh's casts are 3x faster over an index
+        if kw.get("density") is None:         # absent or None: the configured one, as mesh_chain.config_defaults does
+            mgr = self.tsdf_manager
+            cfg = mgr.cfg if mgr is not None else config["tsdf_global"]
+            voxel = mgr.volume.voxel_size if mgr is not None else cfg["voxel_size"]
+            per_voxel = float(cfg.get("mesh_texture_density", 0.0))
+            kw["density"] = per_voxel / float(voxel) if per_voxel > 0.0 else None
         return bake_texture(mesh, torch.stack(images), poses, K, **kw)
 
     def evaluate_mesh_render(self, mesh, colors=None, texture=None, images=None, poses=None, rays=None, K=None,

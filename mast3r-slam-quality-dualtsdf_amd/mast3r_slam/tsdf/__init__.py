@@ -8,7 +8,8 @@ from .mesh_metrics import compare_meshes, face_areas, mesh_distance, sample_mesh
 from .mesh_align import align_meshes, fit_sim3, transform_mesh  # noqa: F401
 from .mesh_raycast import observed_points, render_mesh  # noqa: F401
 from .mesh_index import MeshIndex, build_mesh_index  # noqa: F401
-from .mesh_texture import MeshTexture, bake_texture, render_mesh_color  # noqa: F401
+from .mesh_texture import (MeshTexture, atlas_classes, atlas_layout, bake_texture, render_mesh_color,  # noqa: F401
+                           sized_layout)
 from .image_metrics import image_metrics  # noqa: F401
 from .tsdf_optimizer import TSDFPoseOptimizer  # noqa: F401
 from .global_manager import TSDFGlobalIntegrator, TSDFGlobalManager  # noqa: F401
