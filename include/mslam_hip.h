@@ -153,7 +153,9 @@ int mslam_gn_accumulate(int kind, const float* Twc, const float* K, int num_pose
 int mslam_gn_solve_retract(const float* Hs, const float* gs, int num_poses, int num_edges,
                            int num_points, float* Twc, float* dx, float delta_thresh, void* workspace,
                            size_t workspace_bytes, void* stream);
-/* status4 (device i32[4]) <- {done, iterations run, chol_fail, bits of last ||dx|| (f32)}. */
+/* status4 (device i32[4]) <- {done, iterations run, chol_fail, bits of last ||dx|| (f32)}.  chol_fail != 0: the
+ * factorisation of the most recent solve_retract() failed (dx = 0, poses untouched); it stays until the next solve
+ * that runs (a solve after `done` does not) and is 0 after one that succeeded and after begin(). */
 int mslam_gn_status(int* status4, int num_poses, int num_edges, int num_points, void* workspace,
                     size_t workspace_bytes, void* stream);
 

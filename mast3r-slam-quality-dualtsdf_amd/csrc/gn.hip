@@ -45,7 +45,9 @@ constexpr int kTile = 64;       // Cholesky trailing-update tile
 struct GnState {
   int done;        // ||dx|| < delta_thresh reached: later launches are no-ops
   int iters;       // GN iterations actually executed
-  int chol_fail;   // current factorisation hit a non-positive pivot (Eigen: info() != Success)
+  int chol_fail;   // 1: the factorisation in flight hit a non-positive pivot (Eigen: info() != Success), set by chol_step
+                   // and consumed by gn_finish; 2: the most recent finished solve failed (what mslam_gn_status reports);
+                   // 0: it succeeded.  A later solve's chol_step overwrites a 2 with 1, its gn_finish a 2 with 0.
   float last_norm;
 };
 
@@ -911,7 +913,7 @@ __global__ __launch_bounds__(256) void gn_finish_kernel(GnState* __restrict__ st
   const int t = threadIdx.x;
   const int n = N * 7;
   __shared__ float red[256];
-  const bool fail = st->chol_fail != 0;
+  const bool fail = st->chol_fail == 1;  // 2 is the previous solve's record, not this factorisation's
   float ss = 0.0f;
   for (int k = t; k < n; k += 256) {
     const float d = fail ? 0.0f : -(float)xs[k];  // "NOTE: Accounting for negative here!" :1208-1209
@@ -934,7 +936,7 @@ __global__ __launch_bounds__(256) void gn_finish_kernel(GnState* __restrict__ st
     const float nrm = sqrtf(red[0]);
     st->last_norm = nrm;
     st->iters += 1;
-    st->chol_fail = 0;
+    st->chol_fail = fail ? 2 : 0;
     if (nrm < delta_thresh) st->done = 1;
   }
 }

@@ -5,6 +5,10 @@ Bars (SURVEY §8 tolerance table):
   dx, updated Twc    abs <= 1e-5 after ONE iteration (fp64 solve both sides); <= 2e-4 after the full
                      loop (fp32 rounding of Hs feeds a 10-step nonlinear iteration)
   Sim3 ops           abs <= 2e-6
+
+These bars do not see the weak residual family (distance | log depth: 1e-7 of the blocks at the production sigmas), the
+chunked stream away from two shapes, or the loop state: tests/test_gn_blocks_gpu.py and tests/test_gn_loop_gpu.py hold the
+same kernels to the float64 reference of tests/gn_ref.py there.
 """
 import numpy as np
 import pytest
