@@ -677,6 +677,48 @@ int mslam_mesh_align_step_indexed(const float* src, int n, const float* vertices
                                   void* state, int32_t* nearest, float* moved, double* dist2, double* closest,
                                   double* log_row, void* stream);
 
+/* Point clouds: a cloud index, the exact nearest neighbour and the voxel downsample (no counterpart in the reference,
+ * DESIGN.md "Point clouds"; the definition is tests/cloud_numpy.py).  points f32[N,3]; a point is valid when its three
+ * coordinates are finite.  An invalid point is never a nearest neighbour and is never fused.  The points are never copied
+ * or permuted; all arithmetic is f64 on the f32 inputs in one fixed order; no atomics.
+ *   mslam_cloud_index_boxes   `order` i32[N] is the caller's stable sort of the points' Morton keys
+ *                             (mslam_mesh_index_point_keys over the box of the VALID points, INT64_MAX put in for an
+ *                             invalid point, so those come last).  Into the workspace (>= mslam_cloud_index_bytes(N),
+ *                             MSLAM_ENOMEM with the needed size in mslam_last_error when short): f64 boxes lo.xyz, hi.xyz
+ *                             of the tiles of 128 consecutive points in `order`, then of the groups of 32 tiles;
+ *                             (+inf, -inf) for an empty one.  An entry of `order` outside [0, N) is skipped, not followed.
+ *   mslam_cloud_distance      dist2 f64[n], nearest i32[n]: per query the smallest squared distance dx dx + dy dy + dz dz
+ *                             (the f64 differences of the f32 inputs, in that order, uncontracted) to a valid point, and
+ *                             the lowest ORIGINAL index of a point at it, whatever order the tiles are visited in; +inf
+ *                             and -1 for a query with a non-finite coordinate and for a cloud without a valid point.
+ *                             order == NULL: the plain scan, tiles of the input order, no culling (`index` is not
+ *                             read).  Otherwise `index` is the workspace above (only read): a tile whose box cannot beat
+ *                             the block's current bests is skipped, and with levels = 2 a whole group first; the same
+ *                             bits.  A point that `order` does not name is not seen.  skip_counts (may be NULL):
+ *                             i32[4 * ceil(n / 256)], per wave the tile scans it skipped, a skipped group counting as
+ *                             all of its tiles.
+ *   mslam_cloud_voxel_keys    keys i64[N]: the packed voxel key of the global TSDF for the cell size voxel_size,
+ *                             floor(f32 coordinate / f32 voxel_size) per axis in [-2^20, 2^20), 21 bits each, x highest;
+ *                             INT64_MAX for an invalid or out-of-range point.  (The one cell whose three indices are all
+ *                             2^20 - 1 has that very bit pattern and counts as out of range.)
+ *   mslam_cloud_voxel_reduce  the caller sorts the keys (stable) -> sorted_keys i64[N] and perm i64[N] (the original
+ *                             index of each sorted slot), and lists the slots where a new key other than INT64_MAX
+ *                             begins -> starts i64[M].  One entry per voxel, in key order: centroid f32[M,3], the f64 sum
+ *                             of the members in sorted order (within a voxel: original index order) divided by the count
+ *                             and rounded once; count i32[M]; first i32[M], the lowest original index; with colors
+ *                             u8[N,3], color u8[M,3] = (2 sum + count) / (2 count) in integers (NULL together).  An
+ *                             entry of perm outside [0, N) is skipped.  The same bits on every call. */
+size_t mslam_cloud_index_bytes(int num_points);
+int mslam_cloud_index_boxes(const float* points, int num_points, const int32_t* order, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int mslam_cloud_distance(const float* queries, int n, const float* points, int num_points, const int32_t* order,
+                         const void* index, size_t index_bytes, int levels, int32_t* skip_counts, double* dist2,
+                         int32_t* nearest, void* stream);
+int mslam_cloud_voxel_keys(const float* points, int num_points, double voxel_size, int64_t* keys, void* stream);
+int mslam_cloud_voxel_reduce(const float* points, const uint8_t* colors, int num_points, const int64_t* sorted_keys,
+                             const int64_t* perm, const int64_t* starts, int num_voxels, float* centroid,
+                             int32_t* count, int32_t* first, uint8_t* color, void* stream);
+
 /* Mesh textures: keyframe images baked into a per-face atlas, and the shading of a ray cast (no counterpart in the
  * reference, DESIGN.md "Mesh textures"; the definition is tests/texture_numpy.py).  The atlas is a pure function of
  * (F, texels = R >= 4): face f is half f & 1 of cell f >> 1, a cell is R + 1 texels wide and R high, the cells lie

@@ -1,0 +1,353 @@
+// Point clouds: a cloud index, the exact nearest neighbour of a point in a cloud, and the voxel downsample.  Semantics
+// in DESIGN.md "Point clouds"; tests/cloud_numpy.py states the same definitions, operation by operation, in numpy.
+// Everything is f64 on the f32 inputs in one fixed order and the build has -ffp-contract=off, so a * b + c below is two
+// roundings, as in numpy.
+//
+// A point is VALID when its three coordinates are finite.  An invalid point is never anyone's nearest neighbour and is
+// never fused into a voxel; a query with a non-finite coordinate has no neighbour (+inf, -1).
+//
+//   index     the caller sorts the Morton keys of the valid points (mslam_mesh_index_point_keys over the box of the valid
+//             points, INT64_MAX for an invalid one) -> order i32[N]; cd_box_kernel writes the f64 boxes of the tiles of
+//             128 consecutive points IN `order`, cd_group_kernel the boxes of the groups of 32 tiles above them.  The
+//             points are never copied or permuted.
+//   distance  cd_scan: one query per thread, 256 per block, the tiles staged through LDS as f64, the skip test and the
+//             tie rule of md_scan (mesh_tri.h).  The invariant there holds here in its simplest form: a point of a tile
+//             lies IN the tile's box exactly (f32 values in f64), so its squared distance is at least the box's lb2 up
+//             to the roundings of the two sums, far inside the slack (1 + 2^-20) and 2^-27 S^2 of the test.  A skipped
+//             tile therefore holds only points strictly farther than a real point: neither the minimum nor a tie, and
+//             the output is that of the plain ascending scan, lowest ORIGINAL index on ties, bit for bit.
+//   voxels    cd_voxel_key_kernel: world_to_key of tsdf_table.h per point.  The caller sorts the keys (stable), flags the
+//             segment heads and lists them; cd_voxel_reduce_kernel then walks one voxel per thread in sorted order, which
+//             within a voxel is original index order.  A voxel that holds a large share of the cloud serialises.
+// No atomics, no waiting between blocks, every loop bounded by a tile or point count.
+#include "mesh_tri.h"
+#include "tsdf_table.h"
+
+namespace mslam {
+
+constexpr int kCdPointDoubles = 4;      // x, y, z, tag: 0 invalid, else 1 + the original index (exact in a double)
+
+__device__ __forceinline__ bool cd_finite(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
+
+// Slot i of the tiles: point i itself, or with an index order[i], range-checked before it is followed (n: no point).
+__device__ __forceinline__ int cd_slot_point(const int32_t* __restrict__ order, int i, int n) {
+  if (!order || i >= n) return i;
+  const int j = order[i];
+  return (unsigned)j < (unsigned)n ? j : n;
+}
+
+// Point j as p[0..2] f64 and p[3] = 1 + j; all zeros for j >= n or an invalid point
+__device__ __forceinline__ bool cd_load_point(const float* __restrict__ points, int j, int n, double* p) {
+  p[0] = p[1] = p[2] = p[3] = 0.0;
+  if (j >= n) return false;
+  const float x = points[3 * (size_t)j], y = points[3 * (size_t)j + 1], z = points[3 * (size_t)j + 2];
+  if (!cd_finite(x, y, z)) return false;
+  p[0] = (double)x, p[1] = (double)y, p[2] = (double)z, p[3] = (double)j + 1.0;
+  return true;
+}
+
+// box[6 * tile + ...] = lo.xyz, hi.xyz over the valid points of the tile; (+inf, -inf) for a tile without one
+__global__ __launch_bounds__(64) void cd_box_kernel(const float* __restrict__ points, int n,
+                                                    const int32_t* __restrict__ order, double* __restrict__ box) {
+  const int tile = blockIdx.x, lane = threadIdx.x;
+  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (int k = lane; k < kMdTile; k += kWave) {
+    double p[kCdPointDoubles];
+    if (cd_load_point(points, cd_slot_point(order, tile * kMdTile + k, n), n, p)) {
+#pragma unroll
+      for (int d = 0; d < 3; d++) {
+        lo[d] = fmin(lo[d], p[d]);
+        hi[d] = fmax(hi[d], p[d]);
+      }
+    }
+  }
+#pragma unroll
+  for (int d = 0; d < 3; d++) {
+    for (int off = 32; off > 0; off >>= 1) {
+      lo[d] = fmin(lo[d], __shfl_down(lo[d], off, kWave));
+      hi[d] = fmax(hi[d], __shfl_down(hi[d], off, kWave));
+    }
+    if (lane == 0) {
+      box[6 * (size_t)tile + d] = lo[d];
+      box[6 * (size_t)tile + 3 + d] = hi[d];
+    }
+  }
+}
+
+// gbox[6 * group + c]: min (c < 3) or max of component c over the boxes of the group's tiles
+__global__ __launch_bounds__(256) void cd_group_kernel(const double* __restrict__ box, int ntiles, int ngroups,
+                                                       double* __restrict__ gbox) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= 6 * ngroups) return;
+  const int g = i / 6, c = i % 6;
+  const int t1 = min(ntiles, (g + 1) * kMdGroup);
+  double x = c < 3 ? INFINITY : -INFINITY;
+  for (int t = g * kMdGroup; t < t1; t++) {
+    const double y = box[6 * (size_t)t + c];
+    x = c < 3 ? fmin(x, y) : fmax(x, y);
+  }
+  gbox[i] = x;
+}
+
+template <bool kIndexed>
+__device__ __forceinline__ void cd_stage(const float* __restrict__ points, int n, const int32_t* __restrict__ order,
+                                         int tile, int tid, double* s_pts) {
+  cd_load_point(points, cd_slot_point(kIndexed ? order : nullptr, tile * kMdTile + tid, n), n,
+                s_pts + tid * kCdPointDoubles);
+}
+
+__device__ __forceinline__ double cd_dist2(double px, double py, double pz, const double* q) {
+  const double dx = px - q[0], dy = py - q[1], dz = pz - q[2];
+  return md_dot(dx, dy, dz, dx, dy, dz);
+}
+
+// The nearest valid point of the cloud to this lane's query p: md_scan of mesh_tri.h with points in the place of faces.
+// Every thread of the block calls it, also one without a query (`has` false): it reaches the same barriers and never
+// keeps a tile in.  kIndexed: the tiles follow `order`, they are culled by `box` and, when given, `gbox`, and ties go to
+// the lowest original index; otherwise the plain ascending scan, where neither is read.  The block first stages its home
+// tile, the one whose box is nearest to the block's first query q0 (which tile it is changes no output), and every lane
+// takes its starting bound ub from that tile's points: the value of a real point.
+template <bool kIndexed>
+__device__ __forceinline__ MdNearest cd_scan(double px, double py, double pz, bool has, double q0x, double q0y,
+                                             double q0z, const float* __restrict__ points, int n,
+                                             const int32_t* __restrict__ order, const double* __restrict__ box,
+                                             const double* __restrict__ gbox, double* s_pts, int* s_home) {
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  const int ntiles = (n + kMdTile - 1) / kMdTile;
+  const bool cull = kIndexed;
+  double best = INFINITY, ub = INFINITY;
+  int best_j = -1, n_skipped = 0;
+
+  if (cull && __syncthreads_or(has)) {
+    if (wave == 0) {
+      double m = INFINITY, s2;
+      int mt = -1;
+      for (int t = lane; t < ntiles; t += kWave) {
+        const double lb2 = md_box_lb2(q0x, q0y, q0z, box + 6 * (size_t)t, &s2);
+        if (lb2 < m) m = lb2, mt = t;
+      }
+      for (int off = 32; off > 0; off >>= 1) {
+        const double om = __shfl_down(m, off, kWave);
+        const int ot = __shfl_down(mt, off, kWave);
+        if (ot >= 0 && (mt < 0 || om < m || (om == m && ot < mt))) m = om, mt = ot;
+      }
+      if (lane == 0) *s_home = mt;
+    }
+    __syncthreads();
+    const int home = *s_home;
+    if (home >= 0) {
+      if (tid < kMdTile) cd_stage<kIndexed>(points, n, order, home, tid, s_pts);
+      __syncthreads();
+      if (has) {
+        const int cnt = min(kMdTile, n - home * kMdTile);
+        for (int k = 0; k < cnt; k++) {
+          const double* q = s_pts + k * kCdPointDoubles;
+          if (q[3] != 0.0) ub = fmin(ub, cd_dist2(px, py, pz, q));
+        }
+      }
+    }
+  }
+
+  // without an index: one "group" of all tiles, and the loops below are the plain tile loop
+  const int ngroups = kIndexed ? (ntiles + kMdGroup - 1) / kMdGroup : 1;
+  for (int g = 0; g < ngroups; g++) {
+    const int t0 = kIndexed ? g * kMdGroup : 0, t1 = kIndexed ? min(ntiles, t0 + kMdGroup) : ntiles;
+    if (kIndexed && gbox) {
+      bool lane_skips = !has;
+      if (has) {
+        double s2;
+        const double lb2 = md_box_lb2(px, py, pz, gbox + 6 * (size_t)g, &s2);
+        lane_skips = lb2 > fmin(best, ub) * (1.0 + 0x1p-20) + 0x1p-27 * s2;
+      }
+      // also the barrier between the last tile's reads and the next staging
+      if (__syncthreads_and(lane_skips)) {
+        n_skipped += t1 - t0;
+        continue;
+      }
+    }
+    for (int tile = t0; tile < t1; tile++) {
+      bool lane_skips = !has;
+      if (cull && has) {
+        double s2;
+        const double lb2 = md_box_lb2(px, py, pz, box + 6 * (size_t)tile, &s2);
+        lane_skips = lb2 > fmin(best, ub) * (1.0 + 0x1p-20) + 0x1p-27 * s2;
+      }
+      const bool wave_skips = cull && __all(lane_skips);
+      // also the barrier between the last tile's reads and this tile's staging
+      if (__syncthreads_and(cull && lane_skips)) {
+        n_skipped++;
+        continue;
+      }
+      if (tid < kMdTile) cd_stage<kIndexed>(points, n, order, tile, tid, s_pts);
+      __syncthreads();
+      if (wave_skips) {
+        n_skipped++;
+        continue;
+      }
+      if (!has) continue;                                   // no barrier below: the lane only idles through the tile
+      const int cnt = min(kMdTile, n - tile * kMdTile);
+      for (int k = 0; k < cnt; k++) {
+        const double* q = s_pts + k * kCdPointDoubles;      // one address for the whole wave: an LDS broadcast
+        if (q[3] != 0.0) {
+          const double d = cd_dist2(px, py, pz, q);
+          const int j = (int)q[3] - 1;
+          if (d < best || (d == best && j < best_j)) best = d, best_j = j;
+        }
+      }
+    }
+  }
+  return {best, best_j, n_skipped};
+}
+
+template <bool kIndexed>
+__global__ __launch_bounds__(kMdBlock) void cd_distance_kernel(const float* __restrict__ queries, int n,
+                                                               const float* __restrict__ points, int num_points,
+                                                               const int32_t* __restrict__ order,
+                                                               const double* __restrict__ box,
+                                                               const double* __restrict__ gbox,
+                                                               int32_t* __restrict__ skipped,
+                                                               double* __restrict__ dist2,
+                                                               int32_t* __restrict__ nearest) {
+  __shared__ double s_pts[kMdTile * kCdPointDoubles];
+  __shared__ int s_home;
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  const size_t i0 = (size_t)blockIdx.x * kMdBlock, i = i0 + tid;
+  const bool in_range = i < (size_t)n;
+  float qx = 0.0f, qy = 0.0f, qz = 0.0f;
+  if (in_range) qx = queries[3 * i], qy = queries[3 * i + 1], qz = queries[3 * i + 2];
+  const bool has = in_range && cd_finite(qx, qy, qz);
+  const MdNearest r = cd_scan<kIndexed>((double)qx, (double)qy, (double)qz, has, (double)queries[3 * i0],
+                                        (double)queries[3 * i0 + 1], (double)queries[3 * i0 + 2], points, num_points,
+                                        order, box, gbox, s_pts, &s_home);
+  if (in_range) {
+    dist2[i] = has ? r.dist2 : INFINITY;
+    nearest[i] = has ? r.face : -1;
+  }
+  if (skipped && lane == 0) skipped[4 * (size_t)blockIdx.x + wave] = r.skipped;
+}
+
+__global__ __launch_bounds__(256) void cd_voxel_key_kernel(const float* __restrict__ points, int n, float voxel_size,
+                                                           int64_t* __restrict__ keys) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float x = points[3 * (size_t)i], y = points[3 * (size_t)i + 1], z = points[3 * (size_t)i + 2];
+  uint64_t key = 0;
+  keys[i] = cd_finite(x, y, z) && world_to_key(x, y, z, voxel_size, key) ? (int64_t)key : INT64_MAX;
+}
+
+// One voxel per thread: the members are the sorted slots from starts[v] while the key stays the same.  perm[slot] is the
+// member's original index, range-checked before it is followed.
+__global__ __launch_bounds__(256) void cd_voxel_reduce_kernel(const float* __restrict__ points,
+                                                              const uint8_t* __restrict__ colors, int n,
+                                                              const int64_t* __restrict__ sorted_keys,
+                                                              const int64_t* __restrict__ perm,
+                                                              const int64_t* __restrict__ starts, int num_voxels,
+                                                              float* __restrict__ centroid, int32_t* __restrict__ count,
+                                                              int32_t* __restrict__ first,
+                                                              uint8_t* __restrict__ color) {
+  const int v = blockIdx.x * 256 + threadIdx.x;
+  if (v >= num_voxels) return;
+  const int64_t s = starts[v];
+  double sum[3] = {0.0, 0.0, 0.0};
+  uint64_t csum[3] = {0, 0, 0};
+  int cnt = 0, lowest = INT32_MAX;
+  if (s >= 0 && s < (int64_t)n) {
+    const int64_t key = sorted_keys[s];
+    for (int64_t k = s; k < (int64_t)n && sorted_keys[k] == key; k++) {
+      const int64_t j = perm[k];
+      if ((uint64_t)j >= (uint64_t)n) continue;
+#pragma unroll
+      for (int d = 0; d < 3; d++) sum[d] += (double)points[3 * (size_t)j + d];
+      if (colors) {
+#pragma unroll
+        for (int d = 0; d < 3; d++) csum[d] += colors[3 * (size_t)j + d];
+      }
+      cnt++;
+      lowest = min(lowest, (int)j);
+    }
+  }
+#pragma unroll
+  for (int d = 0; d < 3; d++) centroid[3 * (size_t)v + d] = cnt ? (float)(sum[d] / (double)cnt) : 0.0f;
+  count[v] = cnt;
+  first[v] = cnt ? lowest : -1;
+  if (color) {
+#pragma unroll
+    for (int d = 0; d < 3; d++)
+      color[3 * (size_t)v + d] = cnt ? (uint8_t)((2 * csum[d] + (uint64_t)cnt) / (2 * (uint64_t)cnt)) : 0;
+  }
+}
+
+}  // namespace mslam
+
+using namespace mslam;
+
+extern "C" size_t mslam_cloud_index_bytes(int num_points) { return num_points > 0 ? md_index_bytes(num_points) : 0; }
+
+extern "C" int mslam_cloud_index_boxes(const float* points, int num_points, const int32_t* order, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+  MSLAM_REQUIRE(num_points >= 0, "cloud_index_boxes: negative size");
+  if (num_points == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(points && order && workspace, "cloud_index_boxes: null pointer");
+  if (workspace_bytes < md_index_bytes(num_points))
+    return md_too_small("cloud_index_boxes", "workspace", workspace_bytes, md_index_bytes(num_points));
+  hipStream_t s = (hipStream_t)stream;
+  const int ntiles = (int)blocks_for(num_points, kMdTile), ngroups = md_groups(num_points);
+  double* box = (double*)workspace;
+  hipLaunchKernelGGL(cd_box_kernel, dim3(ntiles), dim3(kWave), 0, s, points, num_points, order, box);
+  hipLaunchKernelGGL(cd_group_kernel, dim3(blocks_for(6 * ngroups, 256)), dim3(256), 0, s, (const double*)box, ntiles,
+                     ngroups, box + 6 * (size_t)ntiles);
+  MSLAM_LAUNCH_CHECK("cloud_index_boxes");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_cloud_distance(const float* queries, int n, const float* points, int num_points,
+                                    const int32_t* order, const void* index, size_t index_bytes, int levels,
+                                    int32_t* skip_counts, double* dist2, int32_t* nearest, void* stream) {
+  MSLAM_REQUIRE(n >= 0 && num_points >= 0, "cloud_distance: negative size");
+  MSLAM_REQUIRE(levels == 1 || levels == 2, "cloud_distance: levels must be 1 (tiles) or 2 (tiles and groups)");
+  if (n == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(queries && dist2 && nearest, "cloud_distance: null pointer");
+  MSLAM_REQUIRE(num_points == 0 || points, "cloud_distance: null pointer");
+  const bool indexed = order != nullptr && num_points > 0;
+  if (indexed) {
+    MSLAM_REQUIRE(index, "cloud_distance: an order needs its index");
+    if (index_bytes < md_index_bytes(num_points))
+      return md_too_small("cloud_distance", "index", index_bytes, md_index_bytes(num_points));
+  }
+  const double* box = indexed ? (const double*)index : nullptr;
+  const double* gbox = indexed && levels == 2 ? md_index_gbox(index, num_points) : nullptr;
+  hipLaunchKernelGGL(indexed ? cd_distance_kernel<true> : cd_distance_kernel<false>, dim3(blocks_for(n, kMdBlock)),
+                     dim3(kMdBlock), 0, (hipStream_t)stream, queries, n, points, num_points, order, box, gbox,
+                     skip_counts, dist2, nearest);
+  MSLAM_LAUNCH_CHECK("cloud_distance");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_cloud_voxel_keys(const float* points, int num_points, double voxel_size, int64_t* keys,
+                                      void* stream) {
+  MSLAM_REQUIRE(num_points >= 0, "cloud_voxel_keys: negative size");
+  MSLAM_REQUIRE((float)voxel_size > 0.0f && (float)voxel_size < INFINITY,
+                "cloud_voxel_keys: the voxel size must be positive and finite in float32");
+  if (num_points == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(points && keys, "cloud_voxel_keys: null pointer");
+  hipLaunchKernelGGL(cd_voxel_key_kernel, dim3(blocks_for(num_points, 256)), dim3(256), 0, (hipStream_t)stream, points,
+                     num_points, (float)voxel_size, keys);
+  MSLAM_LAUNCH_CHECK("cloud_voxel_keys");
+  return MSLAM_OK;
+}
+
+extern "C" int mslam_cloud_voxel_reduce(const float* points, const uint8_t* colors, int num_points,
+                                        const int64_t* sorted_keys, const int64_t* perm, const int64_t* starts,
+                                        int num_voxels, float* centroid, int32_t* count, int32_t* first, uint8_t* color,
+                                        void* stream) {
+  MSLAM_REQUIRE(num_points >= 0 && num_voxels >= 0, "cloud_voxel_reduce: negative size");
+  MSLAM_REQUIRE(num_voxels <= num_points, "cloud_voxel_reduce: more voxels than points");
+  if (num_voxels == 0) return MSLAM_OK;
+  MSLAM_REQUIRE(!colors == !color, "cloud_voxel_reduce: colors and color go together");
+  MSLAM_REQUIRE(points && sorted_keys && perm && starts && centroid && count && first,
+                "cloud_voxel_reduce: null pointer");
+  hipLaunchKernelGGL(cd_voxel_reduce_kernel, dim3(blocks_for(num_voxels, 256)), dim3(256), 0, (hipStream_t)stream,
+                     points, colors, num_points, sorted_keys, perm, starts, num_voxels, centroid, count, first, color);
+  MSLAM_LAUNCH_CHECK("cloud_voxel_reduce");
+  return MSLAM_OK;
+}

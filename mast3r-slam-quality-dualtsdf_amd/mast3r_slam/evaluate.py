@@ -197,6 +197,63 @@ def load_mesh(filename):
     return vertices, face["i"].astype(np.int32).reshape(-1, 3)
 
 
+def load_ply_points(filename):
+    """Reads the points of a binary little-endian PLY with a vertex element - what save_ply and save_mesh write, or a
+    laser scan - with or without faces -> (points f32[N,3], colors u8[N,3] or None) numpy.  The vertex element must
+    come first and needs float x, y, z; `colors` are its uchar red, green, blue when all three are present; its other
+    properties are skipped by their declared sizes, and every element after it is left unread.  With load_mesh's
+    refusals: files that are no PLY, ASCII or big-endian files, list properties on vertices, x, y, z of another type,
+    and files that end inside the vertex element raise ValueError."""
+    what = "load_ply_points"
+    with open(filename, "rb") as fh:
+        data = fh.read()
+    end = data.find(b"end_header\n")
+    if not data.startswith(b"ply") or end < 0:
+        raise ValueError(f"{what}: {filename} is not a PLY file")
+    lines = data[:end].decode("ascii", "replace").split("\n")
+    body = end + len(b"end_header\n")
+    if not any(ln.split() == ["format", "binary_little_endian", "1.0"] for ln in lines):
+        raise ValueError(f"{what}: {filename} is not binary_little_endian 1.0 (ASCII and big-endian are not read)")
+    elements = []                                        # [name, count, [property words]]
+    for ln in lines:
+        w = ln.split()
+        if w[:1] == ["element"]:
+            elements.append([w[1], int(w[2]), []])
+        elif w[:1] == ["property"]:
+            if not elements:
+                raise ValueError(f"{what}: property before any element")
+            elements[-1][2].append(w[1:])
+    if not elements or elements[0][0] != "vertex":
+        raise ValueError(f"{what}: expected a vertex element first")
+    _, n_v, vprops = elements[0]
+    fields = []
+    for w in vprops:
+        if w[0] == "list" or w[0] not in _PLY_SIZES:
+            raise ValueError(f"{what}: unsupported vertex property '{' '.join(w)}'")
+        is_xyz = w[1] in ("x", "y", "z")
+        if is_xyz and w[0] not in ("float", "float32"):
+            raise ValueError(f"{what}: vertex {w[1]} must be float, got {w[0]}")
+        is_rgb = w[1] in ("red", "green", "blue") and w[0] in ("uchar", "uint8")
+        fields.append((w[1], "<f4" if is_xyz else "u1" if is_rgb else f"V{_PLY_SIZES[w[0]]}"))
+    if not {"x", "y", "z"} <= {name for name, _ in fields}:
+        raise ValueError(f"{what}: the vertex element has no float x, y, z")
+    vdt = np.dtype(fields)
+    if len(data) < body + n_v * vdt.itemsize:
+        raise ValueError(f"{what}: the file ends inside the vertex element")
+    vert = np.frombuffer(data, vdt, n_v, body)
+    points = np.stack([vert["x"], vert["y"], vert["z"]], 1).astype(np.float32).reshape(-1, 3)
+    colors = None
+    if all(vdt.fields.get(c, (None,))[0] == np.dtype("u1") for c in ("red", "green", "blue")):
+        colors = np.stack([vert["red"], vert["green"], vert["blue"]], 1).astype(np.uint8).reshape(-1, 3)
+    return points, colors
+
+
+def save_cloud_metrics(savedir, filename, metrics):
+    """The dict of tsdf.compare_clouds / SlamSystem.evaluate_cloud as JSON with sorted keys, in the form of
+    save_mesh_metrics.  Returns the path."""
+    return save_mesh_metrics(savedir, filename, metrics)
+
+
 def trajectory_ate(est_xyz, gt_xyz, with_scale=True, device="cuda:0"):
     """Absolute trajectory error of the positions est_xyz (K x 3) against gt_xyz (K x 3), numpy arrays or tensors, after
     the best similarity (tsdf.fit_sim3 on `device`; `with_scale=False`: the best rigid motion) -> (rmse, T): the root

@@ -447,6 +447,74 @@ class SlamSystem:
         return compare_meshes(mesh, (gt_vertices, gt_faces), n_samples=n_samples, threshold=threshold,
                               _validate_pred=False, **kw)
 
+    def keyframe_cloud(self, conf_threshold=None, voxel=None, colors=True):
+        """The map as a point cloud at this point of the run, on the device: what evaluate.save_reconstruction gathers -
+        for every keyframe the world points T_WC.act(X_canon) (with calibration: X_canon constrained to the pixel rays
+        first) of the pixels whose average confidence is > `conf_threshold` (default tracking.C_conf of the config), in
+        keyframe order -> (points f32[N,3], colors u8[N,3] or None).  `voxel`: the cloud is then thinned by
+        tsdf.downsample_cloud on that grid (centroids and mean colours, in key order).  `colors=False`: no colours.
+        Drains the backend first, so the poses are the ones it has solved."""
+        from mast3r_slam.geometry import constrain_points_to_ray
+
+        self.drain()
+        if conf_threshold is None:
+            conf_threshold = float(config["tracking"]["C_conf"])
+        pts, cols = [], []
+        for i in range(len(self.keyframes)):
+            kf = self.keyframes[i]
+            X = kf.X_canon
+            if config["use_calib"]:
+                X = constrain_points_to_ray(kf.img_shape.flatten()[:2], X[None], kf.K).squeeze(0)
+            pW = kf.T_WC.act(X).reshape(-1, 3).to(device=self.device, dtype=torch.float32)
+            keep = kf.get_average_conf().to(device=self.device, dtype=torch.float32).reshape(-1) > conf_threshold
+            pts.append(pW[keep])
+            if colors:
+                cols.append((kf.uimg * 255).to(torch.uint8).reshape(-1, 3).to(self.device)[keep])
+        points = torch.cat(pts).contiguous() if pts else torch.zeros((0, 3), dtype=torch.float32, device=self.device)
+        color = (torch.cat(cols).contiguous() if cols else torch.zeros((0, 3), dtype=torch.uint8,
+                                                                        device=self.device)) if colors else None
+        if voxel is not None:
+            from mast3r_slam.tsdf import downsample_cloud
+
+            points, color, _ = downsample_cloud(points, voxel, color)
+        return points, color
+
+    def evaluate_cloud(self, gt_points, threshold=None, voxel=None, align=None, init=None, gt_positions=None,
+                       align_kw=None, index=None, conf_threshold=None):
+        """Quality of the map's point cloud (self.keyframe_cloud(conf_threshold)) against a ground-truth cloud gt_points
+        f32[N,3] (a numpy array or a device tensor; a laser scan needs no faces): the dict of tsdf.compare_clouds
+        (DESIGN.md "Point clouds").  `threshold` and `voxel` default to the global TSDF's voxel size (the config's when
+        the global TSDF is off): both clouds are thinned on the map's own grid and a point counts as right within one
+        cell; voxel=0 scores the raw clouds.  `align`, `init` ("trajectory" with `gt_positions` for
+        self.align_trajectory), `align_kw` and `index` (None or True) as in evaluate_mesh, with tsdf.align_clouds in the
+        place of align_meshes."""
+        from mast3r_slam.tsdf import compare_clouds
+
+        vs = float(self.tsdf_manager.volume.voxel_size if self.tsdf_manager is not None
+                   else config["tsdf_global"]["voxel_size"])
+        threshold = vs if threshold is None else float(threshold)
+        voxel = vs if voxel is None else float(voxel)
+        kw = {}
+        if align is not None:
+            kw["align"] = align
+            if isinstance(align, str):
+                kw["align_kw"] = dict(align_kw or {})
+                if isinstance(init, str):
+                    if init != "trajectory" or gt_positions is None:
+                        raise ValueError("SlamSystem.evaluate_cloud: init='trajectory' needs gt_positions")
+                    init = self.align_trajectory(gt_positions)
+                if init is not None:
+                    kw["align_kw"]["init"] = init
+            elif init is not None or align_kw:
+                raise ValueError("SlamSystem.evaluate_cloud: init and align_kw go with align='icp' only")
+        elif init is not None or align_kw:
+            raise ValueError("SlamSystem.evaluate_cloud: init and align_kw go with align='icp' only")
+        points, _ = self.keyframe_cloud(conf_threshold, colors=False)
+        gt = torch.as_tensor(gt_points, dtype=torch.float32).to(points.device).reshape(-1, 3).contiguous()
+        if index is not None and index is not False:
+            kw["index"] = index
+        return compare_clouds(points, gt, threshold=threshold, voxel=voxel if voxel > 0.0 else None, **kw)
+
     def evaluate_depth(self, gt_vertices, gt_faces, align=None, near=0.05, far=10.0, index=None):
         """The "Depth L1" figure of dense-SLAM evaluations: for every keyframe, the view of the global TSDF
         (TSDFVolume.render) against the view of a ground-truth mesh (tsdf.render_mesh; gt_vertices f32[V,3], gt_faces
