@@ -3,8 +3,8 @@
 // colour only if it is in the table, so the owner rule of a sharded table, overflow handling and kMaxProbe carry over
 // with no second hash.  Semantics in DESIGN.md "Colour"; tests/color_numpy.py states the same in numpy.
 //
-//   fuse      one thread per (band position, point): the point's ray walk is restated from tsdf_emit_kernel
-//             (csrc/tsdf_global.hip, same f32 operations in the same order: this TU is built with -ffp-contract=off too),
+//   fuse      one thread per (band position, point): the point's ray walk is shared with tsdf_emit_kernel
+//             (csrc/tsdf_walk.h: one statement of the f32 operations; this TU is built with -ffp-contract=off too),
 //             thread j looks at sample k0 + j only.  In-band samples find their voxel (read only) and add
 //             wq = rint(w * 2^20) and wq * c8 (c8 = rint(255 c), 8 bit) to the voxel's four words.
 //   The sums are INTEGERS: the result does not depend on the order of arrival, so colour is bit-identical for any
@@ -16,38 +16,29 @@
 //   sample are added by four neighbouring lanes after a quad exchange, so one wave instruction carries 16 segments of
 //   32 contiguous bytes instead of 64 single words in 64 rows; the adds are non-returning device-scope
 //   global_atomic_add_x2.
-//   sample    one thread per point: trilinear colour on the mesh's and the view's lattice (g = p / vs - 0.5), corners
-//             without colour contribute the default colour.  Serves mesh vertices, view pixels and sample_color().
+//   sample    one thread per point: trilinear colour on the mesh's and the view's lattice (tsdf_table.h lattice_cell),
+//             corners without colour contribute the default colour.  Serves mesh vertices, view pixels and
+//             sample_color().
 #include "common.h"
-#include "tsdf_table.h"
+#include "tsdf_walk.h"
 
 namespace mslam {
 
 constexpr double kColorWeightScale = 1048576.0;   // 2^20 units per unit of weight
 constexpr int kColorWords = 4;
 
-// One sample of one point, exactly as tsdf_emit_kernel sees it: returns the weight in fixed point (0: nothing to add)
-// and the slot of its voxel.
-__device__ __forceinline__ unsigned long long color_sample(const TsdfTable& t, float o0, float o1, float o2, float d0,
-                                                           float d1, float d2, float L, float maxd, float lstep, int num,
-                                                           int k, double cf, float vs, float truncf, uint64_t& slot) {
-  float dist;
-  if (num == 1) dist = 0.0f;
-  else if (k == num - 1) dist = maxd;
-  else dist = (float)k * lstep;
-  const float sdf = L - dist;
-  if (fabsf(sdf) > truncf) return 0ull;
-  const float s0 = o0 + dist * d0, s1 = o1 + dist * d1, s2 = o2 + dist * d2;
-  const float e = -fabsf(sdf) / truncf;
-  const double w = cf * exp((double)e);
-  if (!(w > 0.0)) return 0ull;
-  uint64_t key;
-  if (!world_to_key(s0, s1, s2, vs, key)) return 0ull;   // tsdf_table.h: the key function of the emit pass
-  const int64_t s = table_find(t, key);     // not in this table (another shard owns it, or the insert overflowed)
+// Sample k of a point's walk: its weight in fixed point (0: nothing to add) and the slot of its voxel.  `step` tells a
+// sample behind the band from the rest.
+__device__ __forceinline__ unsigned long long color_sample(const TsdfTable& t, const RayWalk& ray, int k, double cf,
+                                                           float vs, float truncf, uint64_t& slot, WalkStep& step) {
+  WalkSample smp;
+  step = walk_sample(ray, k, cf, vs, truncf, smp);
+  if (step != kSampleOk) return 0ull;
+  const int64_t s = table_find(t, smp.key);   // not in this table (another shard owns it, or the insert overflowed)
   if (s < 0) return 0ull;
   slot = (uint64_t)s;
   // weights beyond 2^53 units are not confidences any more; the bound only keeps the conversion defined
-  return (unsigned long long)rint(fmin(w * kColorWeightScale, 9007199254740992.0));
+  return (unsigned long long)rint(fmin(smp.w * kColorWeightScale, 9007199254740992.0));
 }
 
 __global__ __launch_bounds__(256) void color_fuse_kernel(void* base, uint64_t cap, unsigned long long* __restrict__ color,
@@ -64,32 +55,23 @@ __global__ __launch_bounds__(256) void color_fuse_kernel(void* base, uint64_t ca
   uint64_t slot = 0;
   uint32_t c8 = 0;
   if (j < band) {
-    const float o0 = origin[0], o1 = origin[1], o2 = origin[2];
-    const float r0 = points[3 * (size_t)i] - o0, r1 = points[3 * (size_t)i + 1] - o1, r2 = points[3 * (size_t)i + 2] - o2;
-    const float sq = (float)(((double)(r0 * r0) + (double)(r1 * r1)) + (double)(r2 * r2));
-    const float L = sqrtf(sq);
-    const float maxd = L + truncf;
-    if (isfinite(L) && !(L < 1.0e-4f) && maxd / stepf < 1048576.0f) {
-      const float d0 = r0 / L, d1 = r1 / L, d2 = r2 / L;
-      int num = (int)(maxd / stepf);
-      if (num < 1) num = 1;
-      const float lstep = num > 1 ? maxd / (float)(num - 1) : 0.0f;
-      int k0 = num > 1 ? (int)((L - truncf) / lstep) - 2 : 0;
-      if (k0 < 0) k0 = 0;
+    RayWalk ray;
+    if (walk_begin(points, (size_t)i, origin, stepf, truncf, ray) == kWalkOk) {   // no ray, or one the emit pass dropped
       const double cf = conf[i];
       const float cr = rgb[3 * (size_t)i], cg = rgb[3 * (size_t)i + 1], cb = rgb[3 * (size_t)i + 2];
       auto q8 = [](float c) { return (uint32_t)rintf(255.0f * fminf(fmaxf(c, 0.0f), 1.0f)); };   // NaN -> 0
       c8 = q8(cr) | (q8(cg) << 8) | (q8(cb) << 16);
-      const int k = k0 + j;
-      if (k < num) wq = color_sample(t, o0, o1, o2, d0, d1, d2, L, maxd, lstep, num, k, cf, vs, truncf, slot);
+      const int k = ray.k0 + j;
+      WalkStep step;
+      if (k < ray.num) wq = color_sample(t, ray, k, cf, vs, truncf, slot, step);
       if (j == band - 1) {
         // Samples past the last band position.  The in-band samples are a contiguous run that starts at most three
         // positions after k0 and is shorter than 2 trunc / step + 2, so usually none is left; the exact end point
         // (dist = maxd, k = num - 1) is the one that can lie further out.  Whatever is left is added here, one by one.
-        for (int kk = k + 1; kk < num; kk++) {
-          if (kk < num - 1 && L - (float)kk * lstep < -truncf) kk = num - 1;   // past the band: only the end point is left
+        for (int kk = k + 1; kk < ray.num; kk++) {
           uint64_t s2 = 0;
-          const unsigned long long w2 = color_sample(t, o0, o1, o2, d0, d1, d2, L, maxd, lstep, num, kk, cf, vs, truncf, s2);
+          const unsigned long long w2 = color_sample(t, ray, kk, cf, vs, truncf, s2, step);
+          if (step == kSampleBehind && kk < ray.num - 1) kk = ray.num - 2;   // past the band: only the end point is left
           if (w2 == 0ull) continue;
           unsigned long long* dst = color + s2 * kColorWords;
           atomicAdd(dst, w2);
@@ -158,8 +140,6 @@ __global__ __launch_bounds__(256) void color_load_kernel(void* base, uint64_t ca
   for (int c = 0; c < kColorWords; c++) color[(uint64_t)s * kColorWords + c] = sums[(size_t)i * kColorWords + c];
 }
 
-__device__ __forceinline__ double color_lerp(double a, double b, double f) { return a + f * (b - a); }
-
 __global__ __launch_bounds__(256) void color_sample_kernel(void* base, uint64_t cap,
                                                            const unsigned long long* __restrict__ color,
                                                            const float* __restrict__ pts, int n, int image_w, double vs,
@@ -167,69 +147,43 @@ __global__ __launch_bounds__(256) void color_sample_kernel(void* base, uint64_t 
                                                            uint8_t* __restrict__ out_count) {
   const TsdfTable t = table_carve(base, cap);
   size_t i;
-  if (image_w > 0) {     // the points are the pixels of an image with rows of image_w: 16x16 per block, 8x8 per wave
-    const int h = n / image_w;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int px = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
-    const int py = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
-    if (px >= image_w || py >= h) return;
+  if (image_w > 0) {     // the points are the pixels of an image with rows of image_w
+    int px, py;
+    pixel_tile(px, py);
+    if (px >= image_w || py >= n / image_w) return;
     i = (size_t)py * image_w + px;
   } else {
     i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (size_t)n) return;
   }
   const double dflt[3] = {dr, dg, db};
+  const double p[3] = {(double)pts[3 * i], (double)pts[3 * i + 1], (double)pts[3 * i + 2]};
   double b[3], f[3];
-  bool ok = true;
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-    const double g = (double)pts[3 * i + a] / vs - 0.5;
-    b[a] = floor(g);
-    f[a] = g - b[a];
-    ok = ok && fabs(b[a]) < (double)kKeyBias;    // false for a non-finite point too
-  }
-  double v[8][3];
+  const bool ok = lattice_cell(p, vs, b, f);    // false for a non-finite point too
+  double v[3][8];   // channel, corner
   int count = 0;
 #pragma unroll
   for (int c = 0; c < 8; c++) {
     int64_t s = -1;
     uint64_t key;
-    if (ok && pack_key((long long)b[0] + (c & 1), (long long)b[1] + ((c >> 1) & 1), (long long)b[2] + ((c >> 2) & 1), key))
+    if (ok && pack_key((long long)b[0] + corner_offset(c, 0), (long long)b[1] + corner_offset(c, 1),
+                       (long long)b[2] + corner_offset(c, 2), key))
       s = table_find(t, key);
+    // a corner has colour when its voxel is in the table and something was fused into it: not the valid-voxel rule
     const unsigned long long sw = s >= 0 ? color[(uint64_t)s * kColorWords] : 0ull;
     if (sw > 0ull) {
       const double den = 255.0 * (double)sw;
 #pragma unroll
-      for (int a = 0; a < 3; a++) v[c][a] = (double)color[(uint64_t)s * kColorWords + 1 + a] / den;
+      for (int a = 0; a < 3; a++) v[a][c] = (double)color[(uint64_t)s * kColorWords + 1 + a] / den;
       count++;
     } else {
 #pragma unroll
-      for (int a = 0; a < 3; a++) v[c][a] = dflt[a];
+      for (int a = 0; a < 3; a++) v[a][c] = dflt[a];
     }
   }
 #pragma unroll
-  for (int a = 0; a < 3; a++) {
-    double r = dflt[a];
-    if (ok) {
-      const double c00 = color_lerp(v[0][a], v[1][a], f[0]), c10 = color_lerp(v[2][a], v[3][a], f[0]);
-      const double c01 = color_lerp(v[4][a], v[5][a], f[0]), c11 = color_lerp(v[6][a], v[7][a], f[0]);
-      r = color_lerp(color_lerp(c00, c10, f[1]), color_lerp(c01, c11, f[1]), f[2]);
-    }
-    out_rgb[3 * i + a] = (float)r;
-  }
+  for (int a = 0; a < 3; a++) out_rgb[3 * i + a] = (float)(ok ? trilerp(v[a], f) : dflt[a]);
   out_count[i] = (uint8_t)count;
-}
-
-static bool color_cap_ok(uint64_t capacity) {
-  return capacity >= 1024 && (capacity & (capacity - 1)) == 0 && capacity <= (1ull << 32);
-}
-
-// band positions per point: tsdf_global.hip max_band_for (the most samples a point can have in band) plus the up to
-// three out-of-band samples the walk starts early with, plus one
-static int color_band_for(double voxel_size, double trunc, double step_scale) {
-  double step = voxel_size * step_scale;
-  if (step < 1.0e-4) step = 1.0e-4;
-  return (int)(2.0 * trunc / step) + 8;
 }
 
 }  // namespace mslam
@@ -237,13 +191,13 @@ static int color_band_for(double voxel_size, double trunc, double step_scale) {
 using namespace mslam;
 
 extern "C" size_t mslam_tsdf_color_bytes(uint64_t capacity) {
-  if (!color_cap_ok(capacity)) return 0;
+  if (!table_cap_ok(capacity)) return 0;
   return (size_t)capacity * kColorWords * sizeof(unsigned long long);
 }
 
 extern "C" int mslam_tsdf_color_init(void* color, size_t color_bytes, uint64_t capacity, void* stream) {
   MSLAM_REQUIRE(color, "tsdf_color_init: null buffer");
-  MSLAM_REQUIRE(color_cap_ok(capacity), "tsdf_color_init: capacity must be a power of two in [2^10, 2^32]");
+  MSLAM_REQUIRE(table_cap_ok(capacity), "tsdf_color_init: capacity must be a power of two in [2^10, 2^32]");
   MSLAM_REQUIRE(color_bytes >= mslam_tsdf_color_bytes(capacity), "tsdf_color_init: buffer too small for %llu slots",
                 (unsigned long long)capacity);
   return check_hip(hipMemsetAsync(color, 0, mslam_tsdf_color_bytes(capacity), (hipStream_t)stream), "tsdf_color_init");
@@ -255,17 +209,17 @@ extern "C" int mslam_tsdf_integrate_color(void* table, uint64_t capacity, void* 
   MSLAM_REQUIRE(n_points >= 0, "tsdf_integrate_color: negative point count");
   if (n_points == 0) return MSLAM_OK;
   MSLAM_REQUIRE(table && color && points_world && conf && rgb && cam_origin, "tsdf_integrate_color: null pointer");
-  MSLAM_REQUIRE(color_cap_ok(capacity), "tsdf_integrate_color: bad capacity");
+  MSLAM_REQUIRE(table_cap_ok(capacity), "tsdf_integrate_color: bad capacity");
   MSLAM_REQUIRE(voxel_size > 0 && trunc > 0, "tsdf_integrate_color: voxel_size and trunc must be positive");
-  double step = voxel_size * step_scale;
-  if (step < 1.0e-4) step = 1.0e-4;
-  const int band = color_band_for(voxel_size, trunc, step_scale);
+  // band positions per point: the most samples a point can have in band, plus the up to three out-of-band samples the
+  // walk starts early with, plus one
+  const int band = max_band_for(voxel_size, trunc, step_scale) + 4;
   const long long threads = (long long)band * n_points;
-  const long long blocks = (threads + 255) / 256;
-  MSLAM_REQUIRE(blocks < (1ll << 31), "tsdf_integrate_color: %lld x %d samples exceed the grid", (long long)n_points, band);
-  hipLaunchKernelGGL(color_fuse_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, table, capacity,
-                     (unsigned long long*)color, points_world, conf, rgb, cam_origin, n_points, band, (float)voxel_size,
-                     (float)step, (float)trunc);
+  MSLAM_REQUIRE(threads <= 256ll * 0x7FFFFFFF, "tsdf_integrate_color: %lld x %d samples exceed the grid",
+                (long long)n_points, band);
+  hipLaunchKernelGGL(color_fuse_kernel, dim3(blocks_for(threads, 256)), dim3(256), 0, (hipStream_t)stream, table,
+                     capacity, (unsigned long long*)color, points_world, conf, rgb, cam_origin, n_points, band,
+                     (float)voxel_size, (float)integrate_step(voxel_size, step_scale), (float)trunc);
   MSLAM_LAUNCH_CHECK("tsdf_integrate_color");
   return MSLAM_OK;
 }
@@ -274,9 +228,9 @@ extern "C" int mslam_tsdf_color_rehash(void* old_table, uint64_t old_capacity, c
                                        uint64_t new_capacity, void* new_color, void* stream) {
   MSLAM_REQUIRE(old_table && new_table && old_color && new_color && old_table != new_table && old_color != new_color,
                 "tsdf_color_rehash: bad buffers");
-  MSLAM_REQUIRE(color_cap_ok(old_capacity) && color_cap_ok(new_capacity) && new_capacity >= old_capacity,
+  MSLAM_REQUIRE(table_cap_ok(old_capacity) && table_cap_ok(new_capacity) && new_capacity >= old_capacity,
                 "tsdf_color_rehash: capacities must be powers of two, new >= old");
-  hipLaunchKernelGGL(color_rehash_kernel, dim3((unsigned)((old_capacity + 255) / 256)), dim3(256), 0,
+  hipLaunchKernelGGL(color_rehash_kernel, dim3(blocks_for(old_capacity, 256)), dim3(256), 0,
                      (hipStream_t)stream, old_table, old_capacity, (const unsigned long long*)old_color, new_table,
                      new_capacity, (unsigned long long*)new_color);
   MSLAM_LAUNCH_CHECK("tsdf_color_rehash");
@@ -288,8 +242,8 @@ extern "C" int mslam_tsdf_color_dump(void* table, uint64_t capacity, const void*
   MSLAM_REQUIRE(n >= 0, "tsdf_color_dump: negative count");
   if (n == 0) return MSLAM_OK;
   MSLAM_REQUIRE(table && color && keys && sums, "tsdf_color_dump: null pointer");
-  MSLAM_REQUIRE(color_cap_ok(capacity), "tsdf_color_dump: bad capacity");
-  hipLaunchKernelGGL(color_dump_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, table,
+  MSLAM_REQUIRE(table_cap_ok(capacity), "tsdf_color_dump: bad capacity");
+  hipLaunchKernelGGL(color_dump_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, table,
                      capacity, (const unsigned long long*)color, keys, n, (unsigned long long*)sums);
   MSLAM_LAUNCH_CHECK("tsdf_color_dump");
   return MSLAM_OK;
@@ -300,8 +254,8 @@ extern "C" int mslam_tsdf_color_load(void* table, uint64_t capacity, void* color
   MSLAM_REQUIRE(n >= 0, "tsdf_color_load: negative count");
   if (n == 0) return MSLAM_OK;
   MSLAM_REQUIRE(table && color && keys && sums, "tsdf_color_load: null pointer");
-  MSLAM_REQUIRE(color_cap_ok(capacity), "tsdf_color_load: bad capacity");
-  hipLaunchKernelGGL(color_load_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, table,
+  MSLAM_REQUIRE(table_cap_ok(capacity), "tsdf_color_load: bad capacity");
+  hipLaunchKernelGGL(color_load_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, table,
                      capacity, (unsigned long long*)color, keys, (const unsigned long long*)sums, n);
   MSLAM_LAUNCH_CHECK("tsdf_color_load");
   return MSLAM_OK;
@@ -313,12 +267,12 @@ extern "C" int mslam_tsdf_color_sample(void* table, uint64_t capacity, const voi
   MSLAM_REQUIRE(n >= 0, "tsdf_color_sample: negative count");
   if (n == 0) return MSLAM_OK;
   MSLAM_REQUIRE(table && color && points && out_rgb && out_count, "tsdf_color_sample: null pointer");
-  MSLAM_REQUIRE(color_cap_ok(capacity), "tsdf_color_sample: bad capacity");
+  MSLAM_REQUIRE(table_cap_ok(capacity), "tsdf_color_sample: bad capacity");
   MSLAM_REQUIRE(voxel_size > 0.0, "tsdf_color_sample: voxel_size must be positive");
   MSLAM_REQUIRE(image_w >= 0 && (image_w == 0 || n % image_w == 0), "tsdf_color_sample: %d points are not rows of %d",
                 n, image_w);
-  const dim3 grid = image_w > 0 ? dim3((unsigned)((image_w + 15) / 16), (unsigned)((n / image_w + 15) / 16))
-                                : dim3((unsigned)((n + 255) / 256));
+  const dim3 grid = image_w > 0 ? dim3(blocks_for(image_w, 16), blocks_for(n / image_w, 16))
+                                : dim3(blocks_for(n, 256));
   hipLaunchKernelGGL(color_sample_kernel, grid, dim3(256), 0, (hipStream_t)stream, table, capacity,
                      (const unsigned long long*)color, points, n, image_w, voxel_size, default_r, default_g, default_b,
                      out_rgb, out_count);

@@ -19,10 +19,11 @@
 //   scatter one thread per record moves it into its voxel's segment (arrival order is arbitrary)
 //   replay  one thread per touched voxel applies its records in increasing sequence number
 // All fp32 steps that feed the integer key are the reference's float32 operations in the same order
-// (TU built with -ffp-contract=off), so keys are bit-exact.
+// (TU built with -ffp-contract=off), so keys are bit-exact.  They live in csrc/tsdf_walk.h, shared with the colour
+// fuse (csrc/tsdf_color.hip), which must find the voxels the emit pass makes.
 #include "common.h"
 #include "sim3.h"
-#include "tsdf_table.h"
+#include "tsdf_walk.h"
 
 namespace mslam {
 
@@ -97,53 +98,28 @@ __global__ __launch_bounds__(256) void tsdf_emit_kernel(void* base, uint64_t cap
   TsdfTable t = table_carve(base, cap);
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const float o0 = origin[0], o1 = origin[1], o2 = origin[2];
-  const float r0 = points[3 * i] - o0, r1 = points[3 * i + 1] - o1, r2 = points[3 * i + 2] - o2;
-  // np.linalg.norm: sqrt(sdot) with float products accumulated in double (OpenBLAS), rounded once
-  const float sq = (float)(((double)(r0 * r0) + (double)(r1 * r1)) + (double)(r2 * r2));
-  const float L = sqrtf(sq);
-  if (!isfinite(L) || L < 1.0e-4f) return;
+  RayWalk ray;
+  const WalkBegin begun = walk_begin(points, (size_t)i, origin, stepf, truncf, ray);
+  if (begun == kWalkNoRay) return;
   if (shard_id == 0) atomicAdd(&t.hdr->fused, 1u);
-  const float d0 = r0 / L, d1 = r1 / L, d2 = r2 / L;
-  const float maxd = L + truncf;
-  // A ray of more than 2^20 samples (15 km at the default 1.5 cm step) only occurs when a pose has diverged; the
-  // reference would spend minutes in np.linspace there.  The point is dropped and reported (overflow code 3).
-  if (!(maxd / stepf < 1048576.0f)) { t.hdr->overflow = 3; return; }
-  int num = (int)(maxd / stepf);
-  if (num < 1) num = 1;
-  const float lstep = num > 1 ? maxd / (float)(num - 1) : 0.0f;
+  if (begun == kWalkTooLong) { t.hdr->overflow = 3; return; }   // the point is dropped and reported
   const double cf = conf[i];
-  // the in-band samples (|L - dist| <= trunc) are a contiguous index range; start a little early
-  int k0 = num > 1 ? (int)((L - truncf) / lstep) - 2 : 0;
-  if (k0 < 0) k0 = 0;
   int emitted = 0;
-  for (int k = k0; k < num; k++) {
-    float dist;
-    if (num == 1) dist = 0.0f;
-    else if (k == num - 1) dist = maxd;
-    else dist = (float)k * lstep;
-    const float sdf = L - dist;
-    if (fabsf(sdf) > truncf) {
-      if (sdf < 0.0f && k < num - 1) { k = num - 2; }  // past the band: only the exact end point is left
-      continue;
-    }
-    const float s0 = o0 + dist * d0, s1 = o1 + dist * d1, s2 = o2 + dist * d2;
-    float tv = sdf / truncf;
-    tv = fminf(fmaxf(tv, -1.0f), 1.0f);
-    const float e = -fabsf(sdf) / truncf;
-    const double w = cf * exp((double)e);
-    if (!(w > 0.0)) continue;  // `if weight <= 0.0: return` (NaN weights fall through in python; not emitted here)
-    uint64_t key;
-    if (!world_to_key(s0, s1, s2, vs, key)) { t.hdr->overflow = 1; continue; }
-    if (num_shards > 1 && (int)((mix64(key) >> 40) % (uint64_t)num_shards) != shard_id) continue;
-    const int64_t slot = table_insert(t, key);
+  for (int k = ray.k0; k < ray.num; k++) {
+    WalkSample smp;
+    const WalkStep step = walk_sample(ray, k, cf, vs, truncf, smp);
+    if (step == kSampleBehind && k < ray.num - 1) k = ray.num - 2;   // past the band: only the exact end point is left
+    if (step == kSampleNoKey) t.hdr->overflow = 1;
+    if (step != kSampleOk) continue;
+    if (num_shards > 1 && (int)((mix64(smp.key) >> 40) % (uint64_t)num_shards) != shard_id) continue;
+    const int64_t slot = table_insert(t, smp.key);
     if (slot < 0) { t.hdr->overflow = 1; continue; }
     const uint32_t r = atomicAdd(&t.hdr->n_records, 1u);
     if (r >= max_rec || emitted >= max_band) { t.hdr->overflow = 2; continue; }
     S.rec_seq[r] = (uint32_t)i * (uint32_t)max_band + (uint32_t)emitted;
     S.rec_slot[r] = (uint32_t)slot;
-    S.rec_tsdf[r] = tv;
-    S.rec_w[r] = w;
+    S.rec_tsdf[r] = smp.tv;
+    S.rec_w[r] = smp.w;
     emitted++;
     if (atomicAdd(&t.cnt[slot], 1u) == 0u) S.touched[atomicAdd(&t.hdr->n_touched, 1u)] = (uint32_t)slot;
   }
@@ -170,7 +146,21 @@ __global__ __launch_bounds__(256) void tsdf_scatter_kernel(void* base, uint64_t 
   S.seg_w[pos] = S.rec_w[i];
 }
 
-// one thread per touched voxel: apply its samples in the reference's order (global_volume.py:74-88)
+// the reference's running average of one voxel (global_volume.py:74-88)
+__device__ __forceinline__ void voxel_update(double& tsdf, double& weight, uint8_t& state, double tv, double w,
+                                             double max_weight) {
+  if (state == 0) {  // first touch: stored as given, not averaged, not clamped
+    tsdf = tv; weight = w; state = 1;
+  } else {
+    double total = weight + w;
+    if (total > max_weight) total = max_weight;
+    tsdf = (tsdf * weight + tv * w) / (total > 1.0e-9 ? total : 1.0e-9);
+    weight = total;
+    state = 2;
+  }
+}
+
+// one thread per touched voxel: apply its samples in the reference's order
 constexpr uint32_t kSortMax = 48;
 
 __global__ __launch_bounds__(256) void tsdf_replay_kernel(void* base, uint64_t cap, IntegrateScratch S,
@@ -184,19 +174,6 @@ __global__ __launch_bounds__(256) void tsdf_replay_kernel(void* base, uint64_t c
   const uint32_t L = t.cnt[slot], o = t.off[slot];
   double tsdf = t.tsdf[slot], weight = t.weight[slot];
   uint8_t state = t.state[slot];
-  auto apply = [&](uint32_t j) {
-    const double tv = (double)S.seg_tsdf[o + j];
-    const double w = S.seg_w[o + j];
-    if (state == 0) {  // first touch: stored as given, not averaged, not clamped
-      tsdf = tv; weight = w; state = 1;
-    } else {
-      double total = weight + w;
-      if (total > max_weight) total = max_weight;
-      tsdf = (tsdf * weight + tv * w) / (total > 1.0e-9 ? total : 1.0e-9);
-      weight = total;
-      state = 2;
-    }
-  };
   if (L <= kSortMax) {
     // the usual case (a voxel sees ~10 samples of a keyframe): sequence numbers are read ONCE, insertion-sorted in
     // this thread's LDS row, then the records are applied in that order
@@ -208,7 +185,8 @@ __global__ __launch_bounds__(256) void tsdf_replay_kernel(void* base, uint64_t c
       while (k > 0 && sq[k - 1] > v) { sq[k] = sq[k - 1]; sp[k] = sp[k - 1]; k--; }
       sq[k] = v; sp[k] = (uint8_t)r;
     }
-    for (uint32_t r = 0; r < L; r++) apply(sp[r]);
+    for (uint32_t r = 0; r < L; r++)
+      voxel_update(tsdf, weight, state, (double)S.seg_tsdf[o + sp[r]], S.seg_w[o + sp[r]], max_weight);
   } else {
     // a voxel close to the camera collects hundreds of samples of one keyframe: handed to tsdf_replay_big_kernel (one
     // wave per voxel)
@@ -238,17 +216,6 @@ __global__ __launch_bounds__(64) void tsdf_replay_big_kernel(void* base, uint64_
     const uint32_t L = t.cnt[slot], o = t.off[slot];
     double tsdf = t.tsdf[slot], weight = t.weight[slot];
     uint8_t state = t.state[slot];
-    auto apply = [&](double tv, double w) {
-      if (state == 0) {
-        tsdf = tv; weight = w; state = 1;
-      } else {
-        double total = weight + w;
-        if (total > max_weight) total = max_weight;
-        tsdf = (tsdf * weight + tv * w) / (total > 1.0e-9 ? total : 1.0e-9);
-        weight = total;
-        state = 2;
-      }
-    };
     if (L <= kBigMax) {
       for (uint32_t r = lane; r < L; r += 64) b_seq[r] = S.seg_seq[o + r];
       __syncthreads();
@@ -261,7 +228,7 @@ __global__ __launch_bounds__(64) void tsdf_replay_big_kernel(void* base, uint64_
       }
       __syncthreads();
       if (lane == 0)
-        for (uint32_t r = 0; r < L; r++) apply((double)b_tsdf[r], b_w[r]);
+        for (uint32_t r = 0; r < L; r++) voxel_update(tsdf, weight, state, (double)b_tsdf[r], b_w[r], max_weight);
     } else if (lane == 0) {
       long long last = -1;
       for (uint32_t r = 0; r < L; r++) {
@@ -271,7 +238,7 @@ __global__ __launch_bounds__(64) void tsdf_replay_big_kernel(void* base, uint64_
           if ((long long)sv > last && sv < best) { best = sv; bj = j; }
         }
         last = best;
-        apply((double)S.seg_tsdf[o + bj], S.seg_w[o + bj]);
+        voxel_update(tsdf, weight, state, (double)S.seg_tsdf[o + bj], S.seg_w[o + bj], max_weight);
       }
     }
     if (lane == 0) {
@@ -285,7 +252,9 @@ __global__ __launch_bounds__(64) void tsdf_replay_big_kernel(void* base, uint64_
 // ---------------------------------------------------------------------------------------------
 // query + gradient (global_volume.py:93-128)
 // ---------------------------------------------------------------------------------------------
-// One voxel as the query sees it: state 0 = absent (not in the table, key out of range, or never fused).
+// One voxel as the query sees it: state 0 = absent (not in the table, key out of range, or never fused).  The query's
+// gate is the reference's `weight < min_weight` on these values (they may come from a look-up of other shards' tables,
+// and a NaN weight passes it), not voxel_valid of tsdf_table.h.
 struct VoxelVal { int state; double w, v; };
 
 __device__ __forceinline__ void voxel_keys7(float px, float py, float pz, float vs, uint64_t (&keys)[7], bool (&ok)[7]) {
@@ -547,28 +516,21 @@ __global__ __launch_bounds__(256) void tsdf_dump_kernel(void* base, uint64_t cap
 
 __global__ void tsdf_dump_begin_kernel(TsdfHeader* h) { h->dump_cursor = 0; }
 
-static int max_band_for(double voxel_size, double trunc, double step_scale) {
-  double step = voxel_size * step_scale;
-  if (step < 1.0e-4) step = 1.0e-4;
-  return (int)(2.0 * trunc / step) + 4;
-}
-
 }  // namespace mslam
 
 using namespace mslam;
 
 extern "C" size_t mslam_tsdf_table_bytes(uint64_t capacity) {
-  if (capacity == 0 || (capacity & (capacity - 1)) != 0) return 0;
+  if (!table_cap_ok(capacity)) return 0;
   return table_bytes(capacity);
 }
 
 extern "C" int mslam_tsdf_table_init(void* table, size_t table_bytes_, uint64_t capacity, void* stream) {
   MSLAM_REQUIRE(table, "tsdf_table_init: null table");
-  MSLAM_REQUIRE(capacity >= 1024 && (capacity & (capacity - 1)) == 0 && capacity <= (1ull << 32),
-                "tsdf_table_init: capacity must be a power of two in [2^10, 2^32]");
+  MSLAM_REQUIRE(table_cap_ok(capacity), "tsdf_table_init: capacity must be a power of two in [2^10, 2^32]");
   MSLAM_REQUIRE(table_bytes_ >= table_bytes(capacity), "tsdf_table_init: buffer too small for %llu slots",
                 (unsigned long long)capacity);
-  hipLaunchKernelGGL(tsdf_init_kernel, dim3((unsigned)((capacity + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(tsdf_init_kernel, dim3(blocks_for(capacity, 256)), dim3(256), 0, (hipStream_t)stream,
                      table, capacity);
   MSLAM_LAUNCH_CHECK("tsdf_table_init");
   return MSLAM_OK;
@@ -577,10 +539,9 @@ extern "C" int mslam_tsdf_table_init(void* table, size_t table_bytes_, uint64_t 
 extern "C" int mslam_tsdf_rehash(void* old_table, uint64_t old_capacity, void* new_table, uint64_t new_capacity,
                                  void* stream) {
   MSLAM_REQUIRE(old_table && new_table && old_table != new_table, "tsdf_rehash: bad tables");
-  MSLAM_REQUIRE(new_capacity >= old_capacity && (new_capacity & (new_capacity - 1)) == 0 &&
-                    (old_capacity & (old_capacity - 1)) == 0,
+  MSLAM_REQUIRE(table_cap_ok(old_capacity) && table_cap_ok(new_capacity) && new_capacity >= old_capacity,
                 "tsdf_rehash: capacities must be powers of two, new >= old");
-  hipLaunchKernelGGL(tsdf_rehash_kernel, dim3((unsigned)((old_capacity + 255) / 256)), dim3(256), 0,
+  hipLaunchKernelGGL(tsdf_rehash_kernel, dim3(blocks_for(old_capacity, 256)), dim3(256), 0,
                      (hipStream_t)stream, old_table, old_capacity, new_table, new_capacity);
   MSLAM_LAUNCH_CHECK("tsdf_rehash");
   return MSLAM_OK;
@@ -600,6 +561,7 @@ extern "C" int mslam_tsdf_integrate(void* table, uint64_t capacity, const float*
   MSLAM_REQUIRE(n_points >= 0, "tsdf_integrate: negative point count");
   if (n_points == 0) return MSLAM_OK;
   MSLAM_REQUIRE(table && points_world && conf && cam_origin && workspace, "tsdf_integrate: null pointer");
+  MSLAM_REQUIRE(table_cap_ok(capacity), "tsdf_integrate: bad capacity");
   MSLAM_REQUIRE(num_shards >= 1 && shard_id >= 0 && shard_id < num_shards, "tsdf_integrate: bad shard %d/%d",
                 shard_id, num_shards);
   MSLAM_REQUIRE(voxel_size > 0 && trunc > 0, "tsdf_integrate: voxel_size and trunc must be positive");
@@ -612,14 +574,12 @@ extern "C" int mslam_tsdf_integrate(void* table, uint64_t capacity, const float*
     return MSLAM_ENOMEM;
   }
   hipStream_t s = (hipStream_t)stream;
-  double step = voxel_size * step_scale;
-  if (step < 1.0e-4) step = 1.0e-4;
   TsdfTable t = table_carve(table, capacity);
   hipLaunchKernelGGL(tsdf_begin_kernel, dim3(1), dim3(1), 0, s, t.hdr);
-  hipLaunchKernelGGL(tsdf_emit_kernel, dim3((n_points + 255) / 256), dim3(256), 0, s, table, capacity, points_world,
-                     conf, cam_origin, n_points, (float)voxel_size, (float)step, (float)trunc, max_band, shard_id,
-                     num_shards, S, (uint32_t)max_rec);
-  const unsigned rec_blocks = (unsigned)((max_rec + 255) / 256);
+  hipLaunchKernelGGL(tsdf_emit_kernel, dim3(blocks_for(n_points, 256)), dim3(256), 0, s, table, capacity, points_world,
+                     conf, cam_origin, n_points, (float)voxel_size, (float)integrate_step(voxel_size, step_scale),
+                     (float)trunc, max_band, shard_id, num_shards, S, (uint32_t)max_rec);
+  const unsigned rec_blocks = blocks_for(max_rec, 256);
   hipLaunchKernelGGL(tsdf_alloc_kernel, dim3(rec_blocks), dim3(256), 0, s, table, capacity, S);
   hipLaunchKernelGGL(tsdf_scatter_kernel, dim3(rec_blocks), dim3(256), 0, s, table, capacity, S, (uint32_t)max_rec);
   hipLaunchKernelGGL(tsdf_replay_kernel, dim3(rec_blocks), dim3(256), 0, s, table, capacity, S, max_weight);
@@ -630,6 +590,7 @@ extern "C" int mslam_tsdf_integrate(void* table, uint64_t capacity, const float*
 
 extern "C" int mslam_tsdf_header(void* table, uint64_t capacity, uint32_t* out8_host, void* stream) {
   MSLAM_REQUIRE(table && out8_host, "tsdf_header: null pointer");
+  MSLAM_REQUIRE(table_cap_ok(capacity), "tsdf_header: bad capacity");
   TsdfTable t = table_carve(table, capacity);
   TsdfHeader h;
   int rc = check_hip(hipMemcpyAsync(&h, t.hdr, sizeof(h), hipMemcpyDeviceToHost, (hipStream_t)stream), "tsdf_header");
@@ -645,10 +606,11 @@ extern "C" int mslam_tsdf_header(void* table, uint64_t capacity, uint32_t* out8_
 extern "C" int mslam_tsdf_dump(void* table, uint64_t capacity, int64_t* keys, double* tsdf, double* weight,
                                uint32_t max_out, void* stream) {
   MSLAM_REQUIRE(table && keys && tsdf && weight, "tsdf_dump: null pointer");
+  MSLAM_REQUIRE(table_cap_ok(capacity), "tsdf_dump: bad capacity");
   TsdfTable t = table_carve(table, capacity);
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(tsdf_dump_begin_kernel, dim3(1), dim3(1), 0, s, t.hdr);
-  hipLaunchKernelGGL(tsdf_dump_kernel, dim3((unsigned)((capacity + 255) / 256)), dim3(256), 0, s, table, capacity,
+  hipLaunchKernelGGL(tsdf_dump_kernel, dim3(blocks_for(capacity, 256)), dim3(256), 0, s, table, capacity,
                      keys, tsdf, weight, max_out);
   MSLAM_LAUNCH_CHECK("tsdf_dump");
   return MSLAM_OK;
@@ -659,7 +621,8 @@ extern "C" int mslam_tsdf_query(void* table, uint64_t capacity, const float* poi
   MSLAM_REQUIRE(n >= 0, "tsdf_query: negative count");
   if (n == 0) return MSLAM_OK;
   MSLAM_REQUIRE(table && points && value && grad && status, "tsdf_query: null pointer");
-  hipLaunchKernelGGL(tsdf_query_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, table, capacity,
+  MSLAM_REQUIRE(table_cap_ok(capacity), "tsdf_query: bad capacity");
+  hipLaunchKernelGGL(tsdf_query_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, table, capacity,
                      points, n, (float)voxel_size, voxel_size, min_weight, value, grad, status);
   MSLAM_LAUNCH_CHECK("tsdf_query");
   return MSLAM_OK;
@@ -672,7 +635,8 @@ static int pose_step_impl(void* table, uint64_t capacity, const double* lookup, 
   MSLAM_REQUIRE(n >= 0, "%s: negative count", what);
   MSLAM_REQUIRE((table || lookup) && workspace && (n == 0 || (points && conf)), "%s: null pointer", what);
   MSLAM_REQUIRE(!(update_pose || points_in_camera_frame) || pose, "%s: pose required", what);
-  int nblk = (n + 255) / 256;
+  MSLAM_REQUIRE(table_cap_ok(capacity), "%s: bad capacity", what);
+  int nblk = (int)blocks_for(n, 256);
   if (nblk > 64) nblk = 64;
   if (nblk < 1) nblk = 1;
   MSLAM_REQUIRE(workspace_bytes >= sizeof(double) * 36 * 64, "%s: workspace needs %zu bytes", what,
@@ -702,7 +666,8 @@ extern "C" int mslam_tsdf_lookup7(void* table, uint64_t capacity, const float* p
   MSLAM_REQUIRE(n >= 0, "tsdf_lookup7: negative count");
   if (n == 0) return MSLAM_OK;
   MSLAM_REQUIRE(table && points && out, "tsdf_lookup7: null pointer");
-  hipLaunchKernelGGL(tsdf_lookup7_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, table, capacity,
+  MSLAM_REQUIRE(table_cap_ok(capacity), "tsdf_lookup7: bad capacity");
+  hipLaunchKernelGGL(tsdf_lookup7_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, table, capacity,
                      points, n, pose, (float)voxel_size, out);
   MSLAM_LAUNCH_CHECK("tsdf_lookup7");
   return MSLAM_OK;
@@ -713,7 +678,7 @@ extern "C" int mslam_tsdf_query_lookup(const double* lookup, int n, double voxel
   MSLAM_REQUIRE(n >= 0, "tsdf_query_lookup: negative count");
   if (n == 0) return MSLAM_OK;
   MSLAM_REQUIRE(lookup && value && grad && status, "tsdf_query_lookup: null pointer");
-  hipLaunchKernelGGL(tsdf_query_lookup_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, lookup, n,
+  hipLaunchKernelGGL(tsdf_query_lookup_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, lookup, n,
                      voxel_size, min_weight, value, grad, status);
   MSLAM_LAUNCH_CHECK("tsdf_query_lookup");
   return MSLAM_OK;
@@ -725,6 +690,7 @@ extern "C" int mslam_tsdf_pose_step_lookup(const double* lookup, const float* po
                                            double* H_out, double* b_out, int* used_out, void* workspace,
                                            size_t workspace_bytes, void* stream) {
   MSLAM_REQUIRE(lookup, "tsdf_pose_step_lookup: null lookup");
+  // no table is read: the capacity only has to pass the check
   return pose_step_impl(nullptr, 1024, lookup, points, conf, n, pose, points_in_camera_frame, voxel_size, min_weight,
                         lambda, damping, update_pose, H_out, b_out, used_out, workspace, workspace_bytes, stream,
                         "tsdf_pose_step_lookup");

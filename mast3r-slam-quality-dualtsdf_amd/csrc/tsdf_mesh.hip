@@ -39,18 +39,6 @@ static MeshScratch mesh_carve(void* base, uint64_t cap) {
   return s;
 }
 
-__device__ __forceinline__ bool voxel_valid(const TsdfTable& t, int64_t slot, double min_weight) {
-  return slot >= 0 && t.state[slot] != 0 && t.weight[slot] >= min_weight;
-}
-
-// slot of the valid voxel at (x, y, z), or -1 (absent, unfused, light, or outside the key range)
-__device__ __forceinline__ int64_t find_valid(const TsdfTable& t, long long x, long long y, long long z, double min_weight) {
-  uint64_t key;
-  if (!pack_key(x, y, z, key)) return -1;
-  const int64_t s = table_find(t, key);
-  return voxel_valid(t, s, min_weight) ? s : -1;
-}
-
 __global__ __launch_bounds__(256) void mesh_keys_kernel(void* base, uint64_t cap, double min_weight,
                                                         int64_t* __restrict__ sort_keys) {
   const TsdfTable t = table_carve(base, cap);
@@ -68,14 +56,15 @@ __global__ __launch_bounds__(256) void mesh_rank_kernel(uint64_t cap, const int6
   if (sorted[i] != kNoKey) S.rank[order[i]] = (uint32_t)i;
 }
 
-// the 8 cube corners of key (x, y, z): slot of corner c = x + 2y + 4z offsets, -1 when absent / invalid
+// the 8 cube corners of key (x, y, z) in the lattice's corner order (tsdf_table.h corner_offset): slot of corner c, -1
+// when absent / invalid
 __device__ __forceinline__ bool cube_slots(const TsdfTable& t, int64_t own_slot, long long x, long long y, long long z,
                                            double min_weight, int64_t (&cs)[8]) {
   cs[0] = own_slot;
   bool full = true;
 #pragma unroll
   for (int c = 1; c < 8; c++) {
-    cs[c] = find_valid(t, x + (c & 1), y + ((c >> 1) & 1), z + ((c >> 2) & 1), min_weight);
+    cs[c] = find_valid(t, x + corner_offset(c, 0), y + corner_offset(c, 1), z + corner_offset(c, 2), min_weight);
     full = full && cs[c] >= 0;
   }
   return full;
@@ -218,22 +207,20 @@ __global__ __launch_bounds__(256) void tsdf_load_kernel(void* base, uint64_t cap
   t.tsdf[slot] = tsdf[i]; t.weight[slot] = weight[i]; t.state[slot] = 2;
 }
 
-static unsigned blocks_for(uint64_t n) { return (unsigned)((n + 255) / 256); }
-
 }  // namespace mslam
 
 using namespace mslam;
 
 extern "C" size_t mslam_tsdf_mesh_workspace_bytes(uint64_t capacity) {
-  if (capacity == 0 || (capacity & (capacity - 1)) != 0) return 0;
+  if (!table_cap_ok(capacity)) return 0;
   return mesh_carve(nullptr, capacity).bytes;
 }
 
 extern "C" int mslam_tsdf_mesh_keys(void* table, uint64_t capacity, double min_weight, int64_t* sort_keys,
                                     void* stream) {
   MSLAM_REQUIRE(table && sort_keys, "tsdf_mesh_keys: null pointer");
-  MSLAM_REQUIRE(capacity >= 1024 && (capacity & (capacity - 1)) == 0, "tsdf_mesh_keys: bad capacity");
-  hipLaunchKernelGGL(mesh_keys_kernel, dim3(blocks_for(capacity)), dim3(256), 0, (hipStream_t)stream, table, capacity,
+  MSLAM_REQUIRE(table_cap_ok(capacity), "tsdf_mesh_keys: bad capacity");
+  hipLaunchKernelGGL(mesh_keys_kernel, dim3(blocks_for(capacity, 256)), dim3(256), 0, (hipStream_t)stream, table, capacity,
                      min_weight, sort_keys);
   MSLAM_LAUNCH_CHECK("tsdf_mesh_keys");
   return MSLAM_OK;
@@ -243,12 +230,11 @@ extern "C" int mslam_tsdf_mesh_count(void* table, uint64_t capacity, double min_
                                      const int64_t* sorted_keys, const int64_t* order, int32_t* counts,
                                      void* workspace, size_t workspace_bytes, void* stream) {
   MSLAM_REQUIRE(table && sorted_keys && order && counts && workspace, "tsdf_mesh_count: null pointer");
-  MSLAM_REQUIRE(capacity >= 1024 && (capacity & (capacity - 1)) == 0 && capacity <= (1ull << 32),
-                "tsdf_mesh_count: bad capacity");
+  MSLAM_REQUIRE(table_cap_ok(capacity), "tsdf_mesh_count: bad capacity");
   const MeshScratch S = mesh_carve(workspace, capacity);
   MSLAM_REQUIRE(workspace_bytes >= S.bytes, "tsdf_mesh_count: workspace needs %zu bytes", S.bytes);
   hipStream_t s = (hipStream_t)stream;
-  const unsigned nb = blocks_for(capacity);
+  const unsigned nb = blocks_for(capacity, 256);
   hipLaunchKernelGGL(mesh_rank_kernel, dim3(nb), dim3(256), 0, s, capacity, sorted_keys, order, S);
   hipLaunchKernelGGL(mesh_classify_kernel, dim3(nb), dim3(256), 0, s, table, capacity, min_weight, level, sorted_keys,
                      order, S, counts + capacity);
@@ -266,12 +252,11 @@ extern "C" int mslam_tsdf_mesh_emit(void* table, uint64_t capacity, double voxel
   if (n_vertices == 0 && n_faces == 0) return MSLAM_OK;
   MSLAM_REQUIRE(table && sorted_keys && order && vbase && fbase && workspace && vertices && normals && faces,
                 "tsdf_mesh_emit: null pointer");
-  MSLAM_REQUIRE(capacity >= 1024 && (capacity & (capacity - 1)) == 0 && capacity <= (1ull << 32),
-                "tsdf_mesh_emit: bad capacity");
+  MSLAM_REQUIRE(table_cap_ok(capacity), "tsdf_mesh_emit: bad capacity");
   const MeshScratch S = mesh_carve(workspace, capacity);
   MSLAM_REQUIRE(workspace_bytes >= S.bytes, "tsdf_mesh_emit: workspace needs %zu bytes", S.bytes);
   hipStream_t s = (hipStream_t)stream;
-  const unsigned nb = blocks_for(capacity);
+  const unsigned nb = blocks_for(capacity, 256);
   hipLaunchKernelGGL(mesh_vertices_kernel, dim3(nb), dim3(256), 0, s, table, capacity, voxel_size, min_weight, level,
                      sorted_keys, order, S, vbase, n_vertices, vertices, normals);
   hipLaunchKernelGGL(mesh_faces_kernel, dim3(nb), dim3(256), 0, s, table, capacity, min_weight, sorted_keys, order, S,
@@ -285,8 +270,8 @@ extern "C" int mslam_tsdf_load(void* table, uint64_t capacity, const int64_t* ke
   MSLAM_REQUIRE(n >= 0, "tsdf_load: negative count");
   if (n == 0) return MSLAM_OK;
   MSLAM_REQUIRE(table && keys && tsdf && weight, "tsdf_load: null pointer");
-  MSLAM_REQUIRE(capacity >= 1024 && (capacity & (capacity - 1)) == 0, "tsdf_load: bad capacity");
-  hipLaunchKernelGGL(tsdf_load_kernel, dim3(blocks_for((uint64_t)n)), dim3(256), 0, (hipStream_t)stream, table,
+  MSLAM_REQUIRE(table_cap_ok(capacity), "tsdf_load: bad capacity");
+  hipLaunchKernelGGL(tsdf_load_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, (hipStream_t)stream, table,
                      capacity, keys, tsdf, weight, n);
   MSLAM_LAUNCH_CHECK("tsdf_load");
   return MSLAM_OK;

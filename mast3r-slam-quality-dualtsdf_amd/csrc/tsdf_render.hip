@@ -57,56 +57,30 @@ __global__ __launch_bounds__(256) void render_blocks_kernel(void* base, uint64_t
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= cap) return;
   const uint64_t k = t.keys[i];
-  if (k == kEmptyKey || t.state[i] == 0 || !(t.weight[i] >= min_weight)) return;
+  if (k == kEmptyKey || !voxel_valid(t, (int64_t)i, min_weight)) return;
   long long x, y, z;
   unpack_key(k, x, y, z);
   const uint64_t bk = pack_block(x >> kBlockShift, y >> kBlockShift, z >> kBlockShift);
-  uint64_t s = mix64(bk) & (B.cap - 1);
-  const uint64_t limit = B.cap < kMaxProbe ? B.cap : kMaxProbe;
-  for (uint64_t probe = 0; probe < limit; probe++) {
-    uint64_t cur = B.keys[s];                 // most voxels find their block already there: no atomic
-    if (cur == kEmptyKey)
-      cur = atomicCAS((unsigned long long*)&B.keys[s], (unsigned long long)kEmptyKey, (unsigned long long)bk);
-    if (cur == kEmptyKey || cur == bk) return;
-    s = (s + 1) & (B.cap - 1);
-  }
-  B.hdr->overflow = 1u;
+  bool inserted;
+  // most voxels find their block already there: read first, no atomic
+  if (probe_insert<kInsertReadFirst>(B.keys, B.cap, bk, inserted) < 0) B.hdr->overflow = 1u;
 }
 
-__device__ __forceinline__ bool block_marked(const BlockSet& B, uint64_t bk) {
-  uint64_t s = mix64(bk) & (B.cap - 1);
-  const uint64_t limit = B.cap < kMaxProbe ? B.cap : kMaxProbe;
-  for (uint64_t probe = 0; probe < limit; probe++) {
-    const uint64_t k = B.keys[s];
-    if (k == bk) return true;
-    if (k == kEmptyKey) return false;
-    s = (s + 1) & (B.cap - 1);
-  }
-  return false;   // not reached when the set did not overflow (an insert that probed this far raised the flag)
-}
+// a miss after kMaxProbe slots is not reached when the set did not overflow (an insert that probed this far raised the flag)
+__device__ __forceinline__ bool block_marked(const BlockSet& B, uint64_t bk) { return probe_find(B.keys, B.cap, bk) >= 0; }
 
 struct Ray {
   double o[3], d[3];
   double near, step, vs;
 };
 
-// sample k: cell base (as doubles, integral) and the fractions inside it; false when the position is not finite or
-// outside the key range (such a sample is invalid)
+// sample k: its cell on the sample lattice (tsdf_table.h lattice_cell); false when the position is not finite or outside
+// the key range (such a sample is invalid)
 __device__ __forceinline__ bool sample_cell(const Ray& r, int k, double (&b)[3], double (&f)[3]) {
   const double tk = r.near + (double)k * r.step;
-  bool ok = true;
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-    const double p = r.o[a] + tk * r.d[a];
-    const double g = p / r.vs - 0.5;
-    b[a] = floor(g);
-    f[a] = g - b[a];
-    ok = ok && fabs(b[a]) < (double)kKeyBias;
-  }
-  return ok;
+  const double p[3] = {r.o[0] + tk * r.d[0], r.o[1] + tk * r.d[1], r.o[2] + tk * r.d[2]};
+  return lattice_cell(p, r.vs, b, f);
 }
-
-__device__ __forceinline__ double lerp(double a, double b, double f) { return a + f * (b - a); }
 
 struct Cell {
   int x, y, z;
@@ -121,20 +95,14 @@ __device__ __forceinline__ void cell_load(const TsdfTable& t, double min_weight,
 #pragma unroll
   for (int i = 0; i < 8; i++) {
     if (!c.valid) break;                     // one missing corner settles it: the sample is invalid
-    uint64_t key;
-    int64_t s = -1;
     // base is inside the key range; base + 1 may step out of it at the upper end
-    if (pack_key(x + (i & 1), y + ((i >> 1) & 1), z + ((i >> 2) & 1), key)) s = table_find(t, key);
-    if (s >= 0 && t.state[s] != 0 && t.weight[s] >= min_weight) c.v[i] = t.tsdf[s];
+    const int64_t s = find_valid(t, x + corner_offset(i, 0), y + corner_offset(i, 1), z + corner_offset(i, 2), min_weight);
+    if (s >= 0) c.v[i] = t.tsdf[s];
     else c.valid = false;
   }
 }
 
-__device__ __forceinline__ double cell_value(const Cell& c, const double (&f)[3]) {
-  const double c00 = lerp(c.v[0], c.v[1], f[0]), c10 = lerp(c.v[2], c.v[3], f[0]);
-  const double c01 = lerp(c.v[4], c.v[5], f[0]), c11 = lerp(c.v[6], c.v[7], f[0]);
-  return lerp(lerp(c00, c10, f[1]), lerp(c01, c11, f[1]), f[2]);
-}
+__device__ __forceinline__ double cell_value(const Cell& c, const double (&f)[3]) { return trilerp(c.v, f); }
 
 // analytic gradient of the trilinear interpolant
 __device__ __forceinline__ void cell_gradient(const Cell& c, const double (&f)[3], double vs, double (&g)[3]) {
@@ -177,10 +145,8 @@ __global__ __launch_bounds__(256) void render_kernel(void* base, uint64_t cap, c
                                                      double step, int skip, BlockSet B, float* __restrict__ range,
                                                      float* __restrict__ normal, uint8_t* __restrict__ hit) {
   const TsdfTable t = table_carve(base, cap);
-  // 16x16 pixels per block, 8x8 per wave
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int px = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
-  const int py = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+  int px, py;
+  pixel_tile(px, py);
   if (px >= w || py >= h) return;
   const size_t i = (size_t)py * w + px;
 
@@ -263,14 +229,14 @@ __global__ __launch_bounds__(256) void render_kernel(void* base, uint64_t cap, c
 using namespace mslam;
 
 extern "C" size_t mslam_tsdf_render_workspace_bytes(uint64_t capacity) {
-  if (capacity == 0 || (capacity & (capacity - 1)) != 0) return 0;
+  if (!table_cap_ok(capacity)) return 0;
   return blocks_carve(nullptr, capacity).bytes;
 }
 
 extern "C" int mslam_tsdf_render_blocks(void* table, uint64_t capacity, double min_weight, void* workspace,
                                         size_t workspace_bytes, void* stream) {
   MSLAM_REQUIRE(table && workspace, "tsdf_render_blocks: null pointer");
-  MSLAM_REQUIRE(capacity >= 1024 && (capacity & (capacity - 1)) == 0, "tsdf_render_blocks: bad capacity");
+  MSLAM_REQUIRE(table_cap_ok(capacity), "tsdf_render_blocks: bad capacity");
   const BlockSet B = blocks_carve(workspace, capacity);
   MSLAM_REQUIRE(workspace_bytes >= B.bytes, "tsdf_render_blocks: workspace needs %zu bytes", B.bytes);
   hipStream_t s = (hipStream_t)stream;
@@ -278,7 +244,7 @@ extern "C" int mslam_tsdf_render_blocks(void* table, uint64_t capacity, double m
   if (rc) return rc;
   rc = check_hip(hipMemsetAsync(B.keys, 0xFF, B.cap * 8, s), "tsdf_render_blocks memset");
   if (rc) return rc;
-  hipLaunchKernelGGL(render_blocks_kernel, dim3((unsigned)((capacity + 255) / 256)), dim3(256), 0, s, table, capacity,
+  hipLaunchKernelGGL(render_blocks_kernel, dim3(blocks_for(capacity, 256)), dim3(256), 0, s, table, capacity,
                      min_weight, B);
   MSLAM_LAUNCH_CHECK("tsdf_render_blocks");
   return MSLAM_OK;
@@ -291,12 +257,12 @@ extern "C" int mslam_tsdf_render(void* table, uint64_t capacity, const float* ra
   MSLAM_REQUIRE(h >= 0 && w >= 0 && (int64_t)h * w < (1ll << 31), "tsdf_render: bad image size");
   if (h == 0 || w == 0) return MSLAM_OK;
   MSLAM_REQUIRE(table && rays && pose8 && workspace && range && normal && hit, "tsdf_render: null pointer");
-  MSLAM_REQUIRE(capacity >= 1024 && (capacity & (capacity - 1)) == 0, "tsdf_render: bad capacity");
+  MSLAM_REQUIRE(table_cap_ok(capacity), "tsdf_render: bad capacity");
   MSLAM_REQUIRE(voxel_size > 0.0 && step > 0.0 && far > near && far - near < INFINITY, "tsdf_render: bad march");
   MSLAM_REQUIRE((far - near) / step < (double)kMaxSamples, "tsdf_render: more than 2^30 samples per ray");
   const BlockSet B = blocks_carve(const_cast<void*>(workspace), capacity);
   MSLAM_REQUIRE(workspace_bytes >= B.bytes, "tsdf_render: workspace needs %zu bytes", B.bytes);
-  hipLaunchKernelGGL(render_kernel, dim3((unsigned)((w + 15) / 16), (unsigned)((h + 15) / 16)), dim3(256), 0,
+  hipLaunchKernelGGL(render_kernel, dim3(blocks_for(w, 16), blocks_for(h, 16)), dim3(256), 0,
                      (hipStream_t)stream, table, capacity, rays, h, w, pose8, voxel_size, min_weight, level, near, far,
                      step, skip, B, range, normal, hit);
   MSLAM_LAUNCH_CHECK("tsdf_render");

@@ -1,5 +1,8 @@
-// Layout of the global-TSDF voxel hash and its probe helpers, shared by csrc/tsdf_global.hip (integrate / query /
-// pose) and csrc/tsdf_mesh.hip (mesh extraction, loading).
+// The global-TSDF voxel hash and every rule of reading it, each stated once: layout and capacity rule, keys, the bounded
+// probe, what a valid voxel is, the sample lattice with its corner order and trilinear blend, and the pixel tile of the
+// image-shaped kernels.  Used by csrc/tsdf_global.hip (integrate / query / pose), tsdf_color.hip (colour fuse and
+// sample), tsdf_render.hip (ray cast), tsdf_mesh.hip (mesh extraction, loading), tsdf_walk.h (the ray walk of a fused
+// point) and cloud.hip (world_to_key).
 #pragma once
 #include "common.h"
 
@@ -7,6 +10,12 @@ namespace mslam {
 
 constexpr uint64_t kEmptyKey = ~0ull;
 constexpr int kKeyBias = 1 << 20;  // coordinates in [-2^20, 2^20)
+
+// Every table is made by mslam_tsdf_table_init, which refuses any other capacity: an entry point that checks this
+// refuses nothing that worked before, and no kernel masks with cap - 1 on a number that is not a power of two.
+static inline bool table_cap_ok(uint64_t capacity) {
+  return capacity >= 1024 && (capacity & (capacity - 1)) == 0 && capacity <= (1ull << 32);
+}
 
 struct TsdfHeader {
   uint64_t capacity;     // slots (power of two)
@@ -98,29 +107,95 @@ __device__ __forceinline__ bool world_to_key(float px, float py, float pz, float
 // scanning a multi-million-slot table.
 constexpr uint64_t kMaxProbe = 1024;
 
-__device__ __forceinline__ int64_t table_find(const TsdfTable& t, uint64_t key) {
-  uint64_t s = mix64(key) & (t.cap - 1);
-  const uint64_t limit = t.cap < kMaxProbe ? t.cap : kMaxProbe;
+// The probe over a raw key array of `cap` slots (a power of two): the slot that holds `key`, or -1.  kFind only reads
+// and stops at the first empty slot.  kInsert claims the first empty slot with a 64-bit CAS.  kInsertReadFirst reads
+// the slot and goes to the CAS only when it saw it empty: for a set whose inserts mostly find their key already there
+// (the block set of the ray cast) most probes then cost no atomic.
+enum ProbeMode { kFind, kInsert, kInsertReadFirst };
+
+template <ProbeMode kMode>
+__device__ __forceinline__ int64_t probe_slot(uint64_t* keys, uint64_t cap, uint64_t key, bool& inserted) {
+  uint64_t s = mix64(key) & (cap - 1);
+  const uint64_t limit = cap < kMaxProbe ? cap : kMaxProbe;
   for (uint64_t probe = 0; probe < limit; probe++) {
-    const uint64_t k = t.keys[s];
+    uint64_t k = kMode == kInsert ? kEmptyKey : keys[s];
+    if (kMode != kFind && k == kEmptyKey) {
+      k = atomicCAS((unsigned long long*)&keys[s], (unsigned long long)kEmptyKey, (unsigned long long)key);
+      if (k == kEmptyKey) { inserted = true; return (int64_t)s; }
+    }
     if (k == key) return (int64_t)s;
-    if (k == kEmptyKey) return -1;
-    s = (s + 1) & (t.cap - 1);
+    if (kMode == kFind && k == kEmptyKey) return -1;
+    s = (s + 1) & (cap - 1);
   }
   return -1;
 }
 
+__device__ __forceinline__ int64_t probe_find(uint64_t* keys, uint64_t cap, uint64_t key) {
+  bool inserted;
+  return probe_slot<kFind>(keys, cap, key, inserted);
+}
+
+// `inserted` is set when this call claimed the slot and left alone otherwise
+template <ProbeMode kMode = kInsert>
+__device__ __forceinline__ int64_t probe_insert(uint64_t* keys, uint64_t cap, uint64_t key, bool& inserted) {
+  static_assert(kMode != kFind, "probe_insert inserts");
+  return probe_slot<kMode>(keys, cap, key, inserted);
+}
+
+__device__ __forceinline__ int64_t table_find(const TsdfTable& t, uint64_t key) { return probe_find(t.keys, t.cap, key); }
+
 __device__ __forceinline__ int64_t table_insert(const TsdfTable& t, uint64_t key) {
-  uint64_t s = mix64(key) & (t.cap - 1);
-  const uint64_t limit = t.cap < kMaxProbe ? t.cap : kMaxProbe;
-  for (uint64_t probe = 0; probe < limit; probe++) {
-    const uint64_t prev = atomicCAS((unsigned long long*)&t.keys[s], (unsigned long long)kEmptyKey,
-                                    (unsigned long long)key);
-    if (prev == kEmptyKey) { atomicAdd(&t.hdr->count, 1u); return (int64_t)s; }
-    if (prev == key) return (int64_t)s;
-    s = (s + 1) & (t.cap - 1);
+  bool inserted = false;
+  const int64_t s = probe_insert(t.keys, t.cap, key, inserted);
+  if (inserted) atomicAdd(&t.hdr->count, 1u);
+  return s;
+}
+
+// A voxel that the mesh, the view and the block set count: present, fused, and heavy enough.
+__device__ __forceinline__ bool voxel_valid(const TsdfTable& t, int64_t slot, double min_weight) {
+  return slot >= 0 && t.state[slot] != 0 && t.weight[slot] >= min_weight;
+}
+
+// slot of the valid voxel at (x, y, z), or -1 (absent, unfused, light, or outside the key range)
+__device__ __forceinline__ int64_t find_valid(const TsdfTable& t, long long x, long long y, long long z, double min_weight) {
+  uint64_t key;
+  if (!pack_key(x, y, z, key)) return -1;
+  const int64_t s = table_find(t, key);
+  return voxel_valid(t, s, min_weight) ? s : -1;
+}
+
+// The sample lattice of the mesh, the view and the colour: voxel values sit at the voxel centres, so a point p lies in
+// the cell whose base corner is b = floor(p / vs - 0.5) (integral, as doubles) at the fractions f = p / vs - 0.5 - b.
+// False when the point is not finite or the base is outside the key range; b + 1 may still step out of it.
+__device__ __forceinline__ bool lattice_cell(const double (&p)[3], double vs, double (&b)[3], double (&f)[3]) {
+  bool ok = true;
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    const double g = p[a] / vs - 0.5;
+    b[a] = floor(g);
+    f[a] = g - b[a];
+    ok = ok && fabs(b[a]) < (double)kKeyBias;
   }
-  return -1;
+  return ok;
+}
+
+// corner c = dx + 2 dy + 4 dz of a cell or a cube: its offset from the base along `axis`
+__device__ __forceinline__ int corner_offset(int c, int axis) { return (c >> axis) & 1; }
+
+__device__ __forceinline__ double lerp(double a, double b, double f) { return a + f * (b - a); }
+
+__device__ __forceinline__ double trilerp(const double (&v)[8], const double (&f)[3]) {
+  const double c00 = lerp(v[0], v[1], f[0]), c10 = lerp(v[2], v[3], f[0]);
+  const double c01 = lerp(v[4], v[5], f[0]), c11 = lerp(v[6], v[7], f[0]);
+  return lerp(lerp(c00, c10, f[1]), lerp(c01, c11, f[1]), f[2]);
+}
+
+// Image-shaped launches: 16x16 pixels per 256-thread block, 8x8 per wave (2x2 waves), so that a wave's rays or points
+// probe neighbouring voxels.  The grid is blocks_for(w, 16) x blocks_for(h, 16).
+__device__ __forceinline__ void pixel_tile(int& px, int& py) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  px = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
+  py = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
 }
 
 }  // namespace mslam

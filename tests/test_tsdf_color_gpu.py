@@ -15,6 +15,7 @@ from mast3r_slam import synthetic
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import color_numpy as C  # noqa: E402
 import render_numpy as R  # noqa: E402
+import tsdf_global_refs as G  # noqa: E402
 from mesh_support import POSES, VS, _rays, _room, _vol, color_checks  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -101,6 +102,47 @@ def test_order_independent_bit_for_bit(device):
         sums = np.concatenate([p[1] for p in parts])
         o = np.lexsort((keys[:, 2], keys[:, 1], keys[:, 0]))
         same((keys[o], sums[o]), f"{n} shards")
+
+
+BAND_CASES = sorted(name for name in G.CASES if name.startswith("band_"))
+
+
+@pytest.mark.parametrize("name", BAND_CASES)
+def test_color_walk_visits_the_emit_walks_voxels(device, name):
+    """The colour fuse finds its voxels by the keys the emit pass made them with (csrc/tsdf_walk.h): on the band-edge
+    sweeps (coarse step, the clamped 1e-4 step, a band thinner than a voxel, negative and corner origins) every voxel of
+    the volume must have colour, unsharded and as two shards, and the shards' union must be the unsharded volume.
+    Set equality is the right assertion because no in-band weight rounds to zero units: the smallest confidence is
+    above 5e-5 and exp(-|sdf| / trunc) >= 1 / e in band, so a sample adds at least 5e-5 / e * 2^20 = 19 units; checked
+    below from ray_samples before the GPU is asked."""
+    from mast3r_slam.tsdf import TSDFVolume
+
+    p, c, o, vs, tr, mw, ss = G.CASES[name]()
+    units = []
+    for point, conf in zip(p, c):
+        rs = G.ray_samples(point, o, vs, tr, ss)
+        if rs is not None and len(rs[2]):
+            units.append(float((conf * np.exp(rs[2].astype(np.float64))).min()) * 2.0 ** 20)
+    print(f"{name}: {len(p)} rays, {len(units)} with in-band samples, smallest weight {min(units):.0f} units")
+    assert len(units) > len(p) // 2 and min(units) >= 19.0
+    rgb = np.random.default_rng(len(p)).uniform(0.0, 1.0, (len(p), 3)).astype(np.float32)
+
+    def fused(**kw):
+        vol = TSDFVolume(vs, tr, mw, 1.0e-3, capacity=1 << 16, device=device, color=True, **kw)
+        vol.integrate(p, c, o, step_scale=ss, colors=rgb, return_fused=False)
+        assert vol.maintain()[0] > 0            # raises if a sample was dropped
+        keys, sums = vol.voxel_color_sums()
+        assert np.array_equal(keys, vol.voxels()[0])
+        dark = int((sums[:, 0] == 0).sum())
+        assert dark == 0, f"{name} {kw}: {dark} of {len(keys)} voxels have no colour"
+        return keys, sums
+
+    keys, sums = fused()
+    parts = [fused(shard_id=r, num_shards=2) for r in range(2)]
+    assert all(0 < len(k) < len(keys) for k, _ in parts)
+    uk, us = np.concatenate([k for k, _ in parts]), np.concatenate([s for _, s in parts])
+    order = np.lexsort((uk[:, 2], uk[:, 1], uk[:, 0]))
+    assert np.array_equal(uk[order], keys) and np.array_equal(us[order], sums)
 
 
 def test_tsdf_untouched(device):
