@@ -7,15 +7,16 @@
 // never fused into a voxel; a query with a non-finite coordinate has no neighbour (+inf, -1).
 //
 //   index     the caller sorts the Morton keys of the valid points (mslam_mesh_index_point_keys over the box of the valid
-//             points, INT64_MAX for an invalid one) -> order i32[N]; cd_box_kernel writes the f64 boxes of the tiles of
-//             128 consecutive points IN `order`, cd_group_kernel the boxes of the groups of 32 tiles above them.  The
+//             points, INT64_MAX for an invalid one) -> order i32[N]; md_build_index<MdPoint> of mesh_tri.h writes the f64
+//             boxes of the tiles of 128 consecutive points IN `order` and of the groups of 32 tiles above them.  The
 //             points are never copied or permuted.
-//   distance  cd_scan: one query per thread, 256 per block, the tiles staged through LDS as f64, the skip test and the
-//             tie rule of md_scan (mesh_tri.h).  The invariant there holds here in its simplest form: a point of a tile
-//             lies IN the tile's box exactly (f32 values in f64), so its squared distance is at least the box's lb2 up
-//             to the roundings of the two sums, far inside the slack (1 + 2^-20) and 2^-27 S^2 of the test.  A skipped
-//             tile therefore holds only points strictly farther than a real point: neither the minimum nor a tie, and
-//             the output is that of the plain ascending scan, lowest ORIGINAL index on ties, bit for bit.
+//   distance  md_scan<MdPoint, .> of mesh_tri.h, the scan the mesh tools run over triangles: one query per thread, 256
+//             per block, the tiles staged through LDS as f64, its skip test and its tie rule.  The invariant there holds
+//             here in its simplest form: a point of a tile lies IN the tile's box exactly (f32 values in f64), so its
+//             squared distance is at least the box's lb2 up to the roundings of the two sums, far inside the slack
+//             (1 + 2^-20) and 2^-27 S^2 of the test.  A skipped tile therefore holds only points strictly farther than
+//             a real point: neither the minimum nor a tie, and the output is that of the plain ascending scan, lowest
+//             ORIGINAL index on ties, bit for bit.  A lane without a query idles through the tiles the block scans.
 //   voxels    cd_voxel_key_kernel: world_to_key of tsdf_table.h per point.  The caller sorts the keys (stable), flags the
 //             segment heads and lists them; cd_voxel_reduce_kernel then walks one voxel per thread in sorted order, which
 //             within a voxel is original index order.  A voxel that holds a large share of the cloud serialises.
@@ -25,180 +26,36 @@
 
 namespace mslam {
 
-constexpr int kCdPointDoubles = 4;      // x, y, z, tag: 0 invalid, else 1 + the original index (exact in a double)
-
 __device__ __forceinline__ bool cd_finite(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 
-// Slot i of the tiles: point i itself, or with an index order[i], range-checked before it is followed (n: no point).
-__device__ __forceinline__ int cd_slot_point(const int32_t* __restrict__ order, int i, int n) {
-  if (!order || i >= n) return i;
-  const int j = order[i];
-  return (unsigned)j < (unsigned)n ? j : n;
-}
-
-// Point j as p[0..2] f64 and p[3] = 1 + j; all zeros for j >= n or an invalid point
-__device__ __forceinline__ bool cd_load_point(const float* __restrict__ points, int j, int n, double* p) {
-  p[0] = p[1] = p[2] = p[3] = 0.0;
-  if (j >= n) return false;
-  const float x = points[3 * (size_t)j], y = points[3 * (size_t)j + 1], z = points[3 * (size_t)j + 2];
-  if (!cd_finite(x, y, z)) return false;
-  p[0] = (double)x, p[1] = (double)y, p[2] = (double)z, p[3] = (double)j + 1.0;
-  return true;
-}
-
-// box[6 * tile + ...] = lo.xyz, hi.xyz over the valid points of the tile; (+inf, -inf) for a tile without one
-__global__ __launch_bounds__(64) void cd_box_kernel(const float* __restrict__ points, int n,
-                                                    const int32_t* __restrict__ order, double* __restrict__ box) {
-  const int tile = blockIdx.x, lane = threadIdx.x;
-  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-  for (int k = lane; k < kMdTile; k += kWave) {
-    double p[kCdPointDoubles];
-    if (cd_load_point(points, cd_slot_point(order, tile * kMdTile + k, n), n, p)) {
-#pragma unroll
-      for (int d = 0; d < 3; d++) {
-        lo[d] = fmin(lo[d], p[d]);
-        hi[d] = fmax(hi[d], p[d]);
-      }
-    }
+// What a tile of a cloud holds (the trait md_scan, md_box_kernel and md_build_index of mesh_tri.h ask for): a slot is
+// x, y, z and the tag, 0 for an invalid point, else 1 + the original index (exact in a double).
+struct MdPoint {
+  struct Src {
+    const float* points;
+    int n;
+  };
+  static constexpr int kDoubles = 4;
+  static __host__ __device__ __forceinline__ int count(const Src s) { return s.n; }
+  // Point j as p[0..2] f64 and p[3] = 1 + j; all zeros for j >= n or an invalid point
+  static __device__ __forceinline__ bool load(const Src s, int j, double* p) {
+    p[0] = p[1] = p[2] = p[3] = 0.0;
+    if (j >= s.n) return false;
+    const float x = s.points[3 * (size_t)j], y = s.points[3 * (size_t)j + 1], z = s.points[3 * (size_t)j + 2];
+    if (!cd_finite(x, y, z)) return false;
+    p[0] = (double)x, p[1] = (double)y, p[2] = (double)z, p[3] = (double)j + 1.0;
+    return true;
   }
-#pragma unroll
-  for (int d = 0; d < 3; d++) {
-    for (int off = 32; off > 0; off >>= 1) {
-      lo[d] = fmin(lo[d], __shfl_down(lo[d], off, kWave));
-      hi[d] = fmax(hi[d], __shfl_down(hi[d], off, kWave));
-    }
-    if (lane == 0) {
-      box[6 * (size_t)tile + d] = lo[d];
-      box[6 * (size_t)tile + 3 + d] = hi[d];
-    }
+  static __device__ __forceinline__ double dist2(double px, double py, double pz, const double* q) {
+    const double dx = px - q[0], dy = py - q[1], dz = pz - q[2];
+    return md_dot(dx, dy, dz, dx, dy, dz);
   }
-}
+};
 
-// gbox[6 * group + c]: min (c < 3) or max of component c over the boxes of the group's tiles
-__global__ __launch_bounds__(256) void cd_group_kernel(const double* __restrict__ box, int ntiles, int ngroups,
-                                                       double* __restrict__ gbox) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= 6 * ngroups) return;
-  const int g = i / 6, c = i % 6;
-  const int t1 = min(ntiles, (g + 1) * kMdGroup);
-  double x = c < 3 ? INFINITY : -INFINITY;
-  for (int t = g * kMdGroup; t < t1; t++) {
-    const double y = box[6 * (size_t)t + c];
-    x = c < 3 ? fmin(x, y) : fmax(x, y);
-  }
-  gbox[i] = x;
-}
-
-template <bool kIndexed>
-__device__ __forceinline__ void cd_stage(const float* __restrict__ points, int n, const int32_t* __restrict__ order,
-                                         int tile, int tid, double* s_pts) {
-  cd_load_point(points, cd_slot_point(kIndexed ? order : nullptr, tile * kMdTile + tid, n), n,
-                s_pts + tid * kCdPointDoubles);
-}
-
-__device__ __forceinline__ double cd_dist2(double px, double py, double pz, const double* q) {
-  const double dx = px - q[0], dy = py - q[1], dz = pz - q[2];
-  return md_dot(dx, dy, dz, dx, dy, dz);
-}
-
-// The nearest valid point of the cloud to this lane's query p: md_scan of mesh_tri.h with points in the place of faces.
-// Every thread of the block calls it, also one without a query (`has` false): it reaches the same barriers and never
-// keeps a tile in.  kIndexed: the tiles follow `order`, they are culled by `box` and, when given, `gbox`, and ties go to
-// the lowest original index; otherwise the plain ascending scan, where neither is read.  The block first stages its home
-// tile, the one whose box is nearest to the block's first query q0 (which tile it is changes no output), and every lane
-// takes its starting bound ub from that tile's points: the value of a real point.
-template <bool kIndexed>
-__device__ __forceinline__ MdNearest cd_scan(double px, double py, double pz, bool has, double q0x, double q0y,
-                                             double q0z, const float* __restrict__ points, int n,
-                                             const int32_t* __restrict__ order, const double* __restrict__ box,
-                                             const double* __restrict__ gbox, double* s_pts, int* s_home) {
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  const int ntiles = (n + kMdTile - 1) / kMdTile;
-  const bool cull = kIndexed;
-  double best = INFINITY, ub = INFINITY;
-  int best_j = -1, n_skipped = 0;
-
-  if (cull && __syncthreads_or(has)) {
-    if (wave == 0) {
-      double m = INFINITY, s2;
-      int mt = -1;
-      for (int t = lane; t < ntiles; t += kWave) {
-        const double lb2 = md_box_lb2(q0x, q0y, q0z, box + 6 * (size_t)t, &s2);
-        if (lb2 < m) m = lb2, mt = t;
-      }
-      for (int off = 32; off > 0; off >>= 1) {
-        const double om = __shfl_down(m, off, kWave);
-        const int ot = __shfl_down(mt, off, kWave);
-        if (ot >= 0 && (mt < 0 || om < m || (om == m && ot < mt))) m = om, mt = ot;
-      }
-      if (lane == 0) *s_home = mt;
-    }
-    __syncthreads();
-    const int home = *s_home;
-    if (home >= 0) {
-      if (tid < kMdTile) cd_stage<kIndexed>(points, n, order, home, tid, s_pts);
-      __syncthreads();
-      if (has) {
-        const int cnt = min(kMdTile, n - home * kMdTile);
-        for (int k = 0; k < cnt; k++) {
-          const double* q = s_pts + k * kCdPointDoubles;
-          if (q[3] != 0.0) ub = fmin(ub, cd_dist2(px, py, pz, q));
-        }
-      }
-    }
-  }
-
-  // without an index: one "group" of all tiles, and the loops below are the plain tile loop
-  const int ngroups = kIndexed ? (ntiles + kMdGroup - 1) / kMdGroup : 1;
-  for (int g = 0; g < ngroups; g++) {
-    const int t0 = kIndexed ? g * kMdGroup : 0, t1 = kIndexed ? min(ntiles, t0 + kMdGroup) : ntiles;
-    if (kIndexed && gbox) {
-      bool lane_skips = !has;
-      if (has) {
-        double s2;
-        const double lb2 = md_box_lb2(px, py, pz, gbox + 6 * (size_t)g, &s2);
-        lane_skips = lb2 > fmin(best, ub) * (1.0 + 0x1p-20) + 0x1p-27 * s2;
-      }
-      // also the barrier between the last tile's reads and the next staging
-      if (__syncthreads_and(lane_skips)) {
-        n_skipped += t1 - t0;
-        continue;
-      }
-    }
-    for (int tile = t0; tile < t1; tile++) {
-      bool lane_skips = !has;
-      if (cull && has) {
-        double s2;
-        const double lb2 = md_box_lb2(px, py, pz, box + 6 * (size_t)tile, &s2);
-        lane_skips = lb2 > fmin(best, ub) * (1.0 + 0x1p-20) + 0x1p-27 * s2;
-      }
-      const bool wave_skips = cull && __all(lane_skips);
-      // also the barrier between the last tile's reads and this tile's staging
-      if (__syncthreads_and(cull && lane_skips)) {
-        n_skipped++;
-        continue;
-      }
-      if (tid < kMdTile) cd_stage<kIndexed>(points, n, order, tile, tid, s_pts);
-      __syncthreads();
-      if (wave_skips) {
-        n_skipped++;
-        continue;
-      }
-      if (!has) continue;                                   // no barrier below: the lane only idles through the tile
-      const int cnt = min(kMdTile, n - tile * kMdTile);
-      for (int k = 0; k < cnt; k++) {
-        const double* q = s_pts + k * kCdPointDoubles;      // one address for the whole wave: an LDS broadcast
-        if (q[3] != 0.0) {
-          const double d = cd_dist2(px, py, pz, q);
-          const int j = (int)q[3] - 1;
-          if (d < best || (d == best && j < best_j)) best = d, best_j = j;
-        }
-      }
-    }
-  }
-  return {best, best_j, n_skipped};
-}
-
+// The nearest valid point of the cloud to each query.  A query with a non-finite coordinate is a lane without a point
+// (`has` false) to md_scan.  kIndexed: the tiles follow `order`, they are culled by `box` and, when given, `gbox`, every
+// lane takes its starting bound from the block's home tile, and ties go to the lowest original index; otherwise the
+// plain ascending scan, where none of the three is read.
 template <bool kIndexed>
 __global__ __launch_bounds__(kMdBlock) void cd_distance_kernel(const float* __restrict__ queries, int n,
                                                                const float* __restrict__ points, int num_points,
@@ -208,7 +65,7 @@ __global__ __launch_bounds__(kMdBlock) void cd_distance_kernel(const float* __re
                                                                int32_t* __restrict__ skipped,
                                                                double* __restrict__ dist2,
                                                                int32_t* __restrict__ nearest) {
-  __shared__ double s_pts[kMdTile * kCdPointDoubles];
+  __shared__ double s_pts[kMdTile * MdPoint::kDoubles];
   __shared__ int s_home;
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
   const size_t i0 = (size_t)blockIdx.x * kMdBlock, i = i0 + tid;
@@ -216,9 +73,10 @@ __global__ __launch_bounds__(kMdBlock) void cd_distance_kernel(const float* __re
   float qx = 0.0f, qy = 0.0f, qz = 0.0f;
   if (in_range) qx = queries[3 * i], qy = queries[3 * i + 1], qz = queries[3 * i + 2];
   const bool has = in_range && cd_finite(qx, qy, qz);
-  const MdNearest r = cd_scan<kIndexed>((double)qx, (double)qy, (double)qz, has, (double)queries[3 * i0],
-                                        (double)queries[3 * i0 + 1], (double)queries[3 * i0 + 2], points, num_points,
-                                        order, box, gbox, s_pts, &s_home);
+  const MdNearest r = md_scan<MdPoint, kIndexed>((double)qx, (double)qy, (double)qz, has, (double)queries[3 * i0],
+                                                 (double)queries[3 * i0 + 1], (double)queries[3 * i0 + 2],
+                                                 {points, num_points}, kIndexed, box, s_pts, &s_home, INFINITY, true,
+                                                 order, gbox);
   if (in_range) {
     dist2[i] = has ? r.dist2 : INFINITY;
     nearest[i] = has ? r.face : -1;
@@ -288,16 +146,8 @@ extern "C" int mslam_cloud_index_boxes(const float* points, int num_points, cons
   MSLAM_REQUIRE(num_points >= 0, "cloud_index_boxes: negative size");
   if (num_points == 0) return MSLAM_OK;
   MSLAM_REQUIRE(points && order && workspace, "cloud_index_boxes: null pointer");
-  if (workspace_bytes < md_index_bytes(num_points))
-    return md_too_small("cloud_index_boxes", "workspace", workspace_bytes, md_index_bytes(num_points));
-  hipStream_t s = (hipStream_t)stream;
-  const int ntiles = (int)blocks_for(num_points, kMdTile), ngroups = md_groups(num_points);
-  double* box = (double*)workspace;
-  hipLaunchKernelGGL(cd_box_kernel, dim3(ntiles), dim3(kWave), 0, s, points, num_points, order, box);
-  hipLaunchKernelGGL(cd_group_kernel, dim3(blocks_for(6 * ngroups, 256)), dim3(256), 0, s, (const double*)box, ntiles,
-                     ngroups, box + 6 * (size_t)ntiles);
-  MSLAM_LAUNCH_CHECK("cloud_index_boxes");
-  return MSLAM_OK;
+  return md_build_index<MdPoint>({points, num_points}, order, workspace, workspace_bytes, "cloud_index_boxes",
+                                 (hipStream_t)stream);
 }
 
 extern "C" int mslam_cloud_distance(const float* queries, int n, const float* points, int num_points,

@@ -120,9 +120,9 @@ __global__ __launch_bounds__(kMdBlock) void ma_step_kernel(const float* __restri
       warm = true;
     }
   }
-  const MdNearest r = md_scan<kIndexed>(px, py, pz, has, (double)(float)y0[0], (double)(float)y0[1],
-                                        (double)(float)y0[2], vert, faces, nf, nv, cull, box, s_tri, &s_home, ub, !warm,
-                                        order, gbox);
+  const MdNearest r = md_scan<MdTri, kIndexed>(px, py, pz, has, (double)(float)y0[0], (double)(float)y0[1],
+                                               (double)(float)y0[2], {vert, faces, nf, nv}, cull, box, s_tri, &s_home, ub,
+                                               !warm, order, gbox);
   const double best = r.dist2;
   const int best_f = r.face;
 
@@ -350,7 +350,7 @@ extern "C" int mslam_mesh_align_init(const float* T0, const float* vertices, con
     return md_too_small("mesh_align_init", "workspace", workspace_bytes, md_box_bytes(num_faces));
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(ma_init_kernel, dim3(1), dim3(kWave), 0, s, T0, (double*)state);
-  if (num_faces > 0) md_launch_boxes(vertices, faces, num_faces, num_vertices, nullptr, (double*)workspace, s);
+  if (num_faces > 0) md_launch_boxes<MdTri>({vertices, faces, num_faces, num_vertices}, nullptr, (double*)workspace, s);
   MSLAM_LAUNCH_CHECK("mesh_align_init");
   return MSLAM_OK;
 }

@@ -80,9 +80,9 @@ __global__ __launch_bounds__(kMdBlock) void md_distance_kernel(const float* __re
   double px = 0.0, py = 0.0, pz = 0.0;
   if (has) px = (double)points[3 * i], py = (double)points[3 * i + 1], pz = (double)points[3 * i + 2];
   const MdNearest r =
-      md_scan<kIndexed>(px, py, pz, has, (double)points[3 * i0], (double)points[3 * i0 + 1],
-                        (double)points[3 * i0 + 2], vert, faces, nf, nv, cull, box, s_tri, &s_home, INFINITY, true, order,
-                        gbox);
+      md_scan<MdTri, kIndexed>(px, py, pz, has, (double)points[3 * i0], (double)points[3 * i0 + 1],
+                               (double)points[3 * i0 + 2], {vert, faces, nf, nv}, cull, box, s_tri, &s_home, INFINITY, true,
+                               order, gbox);
   if (has) {
     dist2[i] = r.dist2;
     nearest[i] = r.face;
@@ -139,7 +139,7 @@ static int md_distance_impl(const char* what, bool indexed, const float* points,
     const size_t box_bytes = md_box_bytes(num_faces), count_bytes = skip == 2 ? md_count_bytes(n) : 0;
     if (workspace_bytes < box_bytes + count_bytes)
       return md_too_small(what, "workspace", workspace_bytes, box_bytes + count_bytes);
-    md_launch_boxes(vertices, faces, num_faces, num_vertices, nullptr, (double*)workspace, s);
+    md_launch_boxes<MdTri>({vertices, faces, num_faces, num_vertices}, nullptr, (double*)workspace, s);
     if (count_bytes) skip_counts = (int32_t*)((char*)workspace + box_bytes);
     if (num_faces <= kMdTile) {                  // one tile: it is scanned whatever its box says, so scan it once
       if (count_bytes) {

@@ -7,8 +7,8 @@
 //            bits over the box of the mesh's vertices (`bounds`, formed by the caller); INT64_MAX for an invalid face
 //            (md_load_tri's rule).  The same kernel, without faces, keys points: that is how queries are sorted.
 //   (caller)   a stable sort of the keys -> order i32[F].  Stable: the index is the same bits on every build.
-//   boxes    the f64 boxes of the tiles of 128 consecutive faces IN `order` (md_box_kernel of mesh_tri.h, every entry of
-//            `order` range-checked before it is followed), then the boxes of the groups of 32 tiles above them.
+//   boxes    the f64 boxes of the tiles of 128 consecutive faces IN `order`, every entry of `order` range-checked before
+//            it is followed, then the boxes of the groups of 32 tiles above them (md_build_index of mesh_tri.h).
 // The faces are never copied or permuted: the scans stage tile t through order[128 t + k].  No atomics; nothing is
 // written but the keys and the boxes.
 #include "mesh_tri.h"
@@ -63,22 +63,6 @@ __global__ __launch_bounds__(256) void mi_keys_kernel(const float* __restrict__ 
   keys[i] = mi_morton(c, bounds);
 }
 
-// gbox[6 * group + c]: min (c < 3) or max of component c over the boxes of the group's tiles.  An empty tile's
-// (+inf, -inf) changes nothing, and a group of empty tiles keeps it.
-__global__ __launch_bounds__(256) void mi_group_kernel(const double* __restrict__ box, int ntiles, int ngroups,
-                                                       double* __restrict__ gbox) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= 6 * ngroups) return;
-  const int g = i / 6, c = i % 6;
-  const int t1 = min(ntiles, (g + 1) * kMdGroup);
-  double x = c < 3 ? INFINITY : -INFINITY;
-  for (int t = g * kMdGroup; t < t1; t++) {
-    const double y = box[6 * (size_t)t + c];
-    x = c < 3 ? fmin(x, y) : fmax(x, y);
-  }
-  gbox[i] = x;
-}
-
 }  // namespace mslam
 
 using namespace mslam;
@@ -112,14 +96,6 @@ extern "C" int mslam_mesh_index_boxes(const float* vertices, const int32_t* face
   MSLAM_REQUIRE(num_faces >= 0 && num_vertices >= 0, "mesh_index_boxes: negative size");
   if (num_faces == 0) return MSLAM_OK;
   MSLAM_REQUIRE(faces && order && workspace && (vertices || num_vertices == 0), "mesh_index_boxes: null pointer");
-  if (workspace_bytes < md_index_bytes(num_faces))
-    return md_too_small("mesh_index_boxes", "workspace", workspace_bytes, md_index_bytes(num_faces));
-  hipStream_t s = (hipStream_t)stream;
-  const int ntiles = (int)blocks_for(num_faces, kMdTile), ngroups = md_groups(num_faces);
-  double* box = (double*)workspace;
-  md_launch_boxes(vertices, faces, num_faces, num_vertices, order, box, s);
-  hipLaunchKernelGGL(mi_group_kernel, dim3(blocks_for(6 * ngroups, 256)), dim3(256), 0, s, (const double*)box, ntiles,
-                     ngroups, box + 6 * (size_t)ntiles);
-  MSLAM_LAUNCH_CHECK("mesh_index_boxes");
-  return MSLAM_OK;
+  return md_build_index<MdTri>({vertices, faces, num_faces, num_vertices}, order, workspace, workspace_bytes,
+                               "mesh_index_boxes", (hipStream_t)stream);
 }

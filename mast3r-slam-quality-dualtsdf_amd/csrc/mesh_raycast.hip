@@ -196,7 +196,7 @@ __global__ __launch_bounds__(kMdBlock) void rc_kernel(const float* __restrict__ 
         n_skipped++;
         continue;
       }
-      if (tid < kMdTile) md_stage<kIndexed>(vert, faces, nf, nv, order, tile, tid, s_tri);
+      if (tid < kMdTile) md_stage<MdTri, kIndexed>({vert, faces, nf, nv}, order, tile, tid, s_tri);
       __syncthreads();
       if (wave_skips) {
         n_skipped++;
@@ -261,7 +261,7 @@ extern "C" int mslam_mesh_raycast_boxes(const float* vertices, const int32_t* fa
   MSLAM_REQUIRE(faces && workspace && (vertices || num_vertices == 0), "mesh_raycast_boxes: null pointer");
   if (workspace_bytes < md_box_bytes(num_faces))
     return md_too_small("mesh_raycast_boxes", "workspace", workspace_bytes, md_box_bytes(num_faces));
-  md_launch_boxes(vertices, faces, num_faces, num_vertices, nullptr, (double*)workspace, (hipStream_t)stream);
+  md_launch_boxes<MdTri>({vertices, faces, num_faces, num_vertices}, nullptr, (double*)workspace, (hipStream_t)stream);
   MSLAM_LAUNCH_CHECK("mesh_raycast_boxes");
   return MSLAM_OK;
 }

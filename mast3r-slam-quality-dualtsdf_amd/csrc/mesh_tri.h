@@ -1,7 +1,8 @@
 // Triangle helpers shared by the mesh-quality kernels (mesh_distance.hip) and the mesh-alignment kernels
 // (mesh_align.hip): the validity rule, the closest point of a triangle by Voronoi regions, the per-tile boxes, the
-// distance from a point to a box, and md_scan, the one culled nearest-face scan that md_distance_kernel and
-// ma_step_kernel both call.  Semantics in DESIGN.md "Mesh quality"; tests/meshdist_numpy.py states the same
+// distance from a point to a box, and md_scan, the one culled nearest-element scan that md_distance_kernel and
+// ma_step_kernel call over triangles (MdTri) and cd_distance_kernel of cloud.hip over points (MdPoint), with the index
+// builder md_build_index beside it.  Semantics in DESIGN.md "Mesh quality"; tests/meshdist_numpy.py states the same
 // definitions, operation by operation, in numpy.  Everything is f64 on the f32 inputs and the build has
 // -ffp-contract=off, so a * b + c below is two roundings, as in numpy.
 //
@@ -142,27 +143,48 @@ __device__ __forceinline__ double md_dist2(double px, double py, double pz, cons
   return md_dot(rx, ry, rz, rx, ry, rz);
 }
 
-// Slot i of the tiles: face i itself, or with an index order[i], range-checked before it is followed (nf: no face).
-__device__ __forceinline__ int md_slot_face(const int32_t* __restrict__ order, int i, int nf) {
-  if (!order || i >= nf) return i;
+// WHAT A TILE HOLDS is a stateless trait type Prim: MdTri here, MdPoint in cloud.hip.  It names a source struct Src and
+// count(src), its elements; kDoubles, the f64 words of a slot, the last of them the valid tag (0: invalid);
+// load(src, i, t), which fills slot t from element i (all zeros and false for i >= count or an invalid element); and
+// dist2(px, py, pz, t).  Static inline functions, no state, no callables: md_scan<MdTri, .> is the text a scan written
+// for triangles alone would be (DESIGN.md "Where the walk lives").
+struct MdTri {
+  struct Src {
+    const float* vert;
+    const int32_t* faces;
+    int nf, nv;
+  };
+  static constexpr int kDoubles = kMdTriDoubles;
+  static __host__ __device__ __forceinline__ int count(const Src s) { return s.nf; }
+  static __device__ __forceinline__ bool load(const Src s, int f, double* t) {
+    return md_load_tri(s.vert, s.faces, f, s.nf, s.nv, t);
+  }
+  static __device__ __forceinline__ double dist2(double px, double py, double pz, const double* t) {
+    return md_dist2(px, py, pz, t);
+  }
+};
+
+// Slot i of the tiles: element i itself, or with an index order[i], range-checked before it is followed (n: none).
+__device__ __forceinline__ int md_slot(const int32_t* __restrict__ order, int i, int n) {
+  if (!order || i >= n) return i;
   const int f = order[i];
-  return (unsigned)f < (unsigned)nf ? f : nf;
+  return (unsigned)f < (unsigned)n ? f : n;
 }
 
-// box[6 * tile + ...] = lo.xyz, hi.xyz over the vertices of the tile's valid faces; (+inf, -inf) for a tile without one.
-// `order`, when given, names the faces of the tiles (md_slot_face).  static: one copy per translation unit that
-// includes this header.
-static __global__ __launch_bounds__(64) void md_box_kernel(const float* __restrict__ vert,
-                                                           const int32_t* __restrict__ faces, int nf, int nv,
+// box[6 * tile + ...] = lo.xyz, hi.xyz over the coordinates of the tile's valid elements (a face's three corners, a
+// point); (+inf, -inf) for a tile without one.  `order`, when given, names the elements of the tiles (md_slot).
+// static: one copy per translation unit that includes this header.
+template <class Prim>
+static __global__ __launch_bounds__(64) void md_box_kernel(const typename Prim::Src src,
                                                            const int32_t* __restrict__ order,
                                                            double* __restrict__ box) {
-  const int tile = blockIdx.x, lane = threadIdx.x;
+  const int tile = blockIdx.x, lane = threadIdx.x, n = Prim::count(src);
   double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
   for (int k = lane; k < kMdTile; k += kWave) {
-    double t[kMdTriDoubles];
-    if (md_load_tri(vert, faces, md_slot_face(order, tile * kMdTile + k, nf), nf, nv, t)) {
+    double t[Prim::kDoubles];
+    if (Prim::load(src, md_slot(order, tile * kMdTile + k, n), t)) {
 #pragma unroll
-      for (int j = 0; j < 9; j++) {
+      for (int j = 0; j < Prim::kDoubles - 1; j++) {
         lo[j % 3] = fmin(lo[j % 3], t[j]);
         hi[j % 3] = fmax(hi[j % 3], t[j]);
       }
@@ -179,6 +201,22 @@ static __global__ __launch_bounds__(64) void md_box_kernel(const float* __restri
       box[6 * (size_t)tile + 3 + d] = hi[d];
     }
   }
+}
+
+// gbox[6 * group + c]: min (c < 3) or max of component c over the boxes of the group's tiles.  An empty tile's
+// (+inf, -inf) changes nothing, and a group of empty tiles keeps it.
+static __global__ __launch_bounds__(256) void md_group_kernel(const double* __restrict__ box, int ntiles, int ngroups,
+                                                              double* __restrict__ gbox) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= 6 * ngroups) return;
+  const int g = i / 6, c = i % 6;
+  const int t1 = min(ntiles, (g + 1) * kMdGroup);
+  double x = c < 3 ? INFINITY : -INFINITY;
+  for (int t = g * kMdGroup; t < t1; t++) {
+    const double y = box[6 * (size_t)t + c];
+    x = c < 3 ? fmin(x, y) : fmax(x, y);
+  }
+  gbox[i] = x;
 }
 
 // Squared distance from p to the box b, and the square of the largest coordinate magnitude of either
@@ -200,18 +238,18 @@ struct MdNearest {
   int skipped;    // the tiles this lane's wave did not scan
 };
 
-// Slot `tid` of `tile` into LDS.  kIndexed: the face is order[128 tile + tid] and t[9] of a valid face is 1 + its
+// Slot `tid` of `tile` into LDS.  kIndexed: the element is order[128 tile + tid] and the tag of a valid one is 1 + its
 // original index (exact in a double), which the scans read back for the tie rule.
-template <bool kIndexed>
-__device__ __forceinline__ void md_stage(const float* __restrict__ vert, const int32_t* __restrict__ faces, int nf,
-                                         int nv, const int32_t* __restrict__ order, int tile, int tid, double* s_tri) {
-  const int f = md_slot_face(kIndexed ? order : nullptr, tile * kMdTile + tid, nf);
-  double* t = s_tri + tid * kMdTriDoubles;
-  if (md_load_tri(vert, faces, f, nf, nv, t) && kIndexed) t[9] = (double)f + 1.0;
+template <class Prim, bool kIndexed>
+__device__ __forceinline__ void md_stage(const typename Prim::Src src, const int32_t* __restrict__ order, int tile,
+                                         int tid, double* s_tri) {
+  const int f = md_slot(kIndexed ? order : nullptr, tile * kMdTile + tid, Prim::count(src));
+  double* t = s_tri + tid * Prim::kDoubles;
+  if (Prim::load(src, f, t) && kIndexed) t[Prim::kDoubles - 1] = (double)f + 1.0;
 }
 
-// The nearest valid face of the mesh to this lane's point p.  Every thread of the block calls it, also one without a
-// point (`has` false): it reaches the same barriers and never keeps a tile in.
+// The nearest valid element (face of the mesh, point of the cloud) to this lane's point p.  Every thread of the block
+// calls it, also one without a point (`has` false): it reaches the same barriers and never keeps a tile in.
 // `cull` 0 is the plain ascending scan.  With `cull` the two parameters that may differ per lane, neither of which
 // changes an output bit, are
 //   ub         the lane's starting bound: +inf, or md_dist2(p, any valid face), which is the value of a real face
@@ -221,15 +259,15 @@ __device__ __forceinline__ void md_stage(const float* __restrict__ vert, const i
 //              no output), and those lanes take ub from its faces.
 // kIndexed (see the header comment): the tiles follow `order`, ties go to the lowest original index, and `gbox`, when
 // given, holds the boxes of the groups of kMdGroup tiles.  Without it `order` and `gbox` are not read.
-// s_tri: kMdTile * kMdTriDoubles doubles of LDS; s_home: one LDS word.
-template <bool kIndexed>
+// s_tri: kMdTile * Prim::kDoubles doubles of LDS; s_home: one LDS word.
+template <class Prim, bool kIndexed>
 __device__ __forceinline__ MdNearest md_scan(double px, double py, double pz, bool has, double q0x, double q0y,
-                                             double q0z, const float* __restrict__ vert,
-                                             const int32_t* __restrict__ faces, int nf, int nv, int cull,
+                                             double q0z, const typename Prim::Src src, int cull,
                                              const double* __restrict__ box, double* s_tri, int* s_home, double ub,
                                              bool need_home, const int32_t* __restrict__ order = nullptr,
                                              const double* __restrict__ gbox = nullptr) {
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  const int nf = Prim::count(src);
   const int ntiles = (nf + kMdTile - 1) / kMdTile;
   double best = INFINITY;
   int best_f = -1, n_skipped = 0;
@@ -252,13 +290,17 @@ __device__ __forceinline__ MdNearest md_scan(double px, double py, double pz, bo
     __syncthreads();
     const int home = *s_home;
     if (home >= 0) {
-      if (tid < kMdTile) md_stage<kIndexed>(vert, faces, nf, nv, order, home, tid, s_tri);
+      // before the staging branch, not inside `if (need_home)`: formed there, home * kMdTile is merged with the
+      // staging's copy of it at the join of a divergent branch, and the loop below runs on vector counters (DESIGN.md
+      // "Where the walk lives")
+      const int cnt = min(kMdTile, nf - home * kMdTile);
+      if (tid < kMdTile) md_stage<Prim, kIndexed>(src, order, home, tid, s_tri);
       __syncthreads();
       if (need_home) {
-        const int cnt = min(kMdTile, nf - home * kMdTile);
         for (int k = 0; k < cnt; k++) {
-          const double* t = s_tri + k * kMdTriDoubles;
-          if (t[9] != 0.0) ub = fmin(ub, md_dist2(px, py, pz, t));     // fmin: a NaN distance never becomes the bound
+          const double* t = s_tri + k * Prim::kDoubles;
+          // fmin: a NaN distance never becomes the bound
+          if (t[Prim::kDoubles - 1] != 0.0) ub = fmin(ub, Prim::dist2(px, py, pz, t));
         }
       }
     }
@@ -294,7 +336,7 @@ __device__ __forceinline__ MdNearest md_scan(double px, double py, double pz, bo
         n_skipped++;
         continue;
       }
-      if (tid < kMdTile) md_stage<kIndexed>(vert, faces, nf, nv, order, tile, tid, s_tri);
+      if (tid < kMdTile) md_stage<Prim, kIndexed>(src, order, tile, tid, s_tri);
       __syncthreads();
       if (wave_skips) {
         n_skipped++;
@@ -302,11 +344,11 @@ __device__ __forceinline__ MdNearest md_scan(double px, double py, double pz, bo
       }
       const int cnt = min(kMdTile, nf - tile * kMdTile);
       for (int k = 0; k < cnt; k++) {
-        const double* t = s_tri + k * kMdTriDoubles;       // one address for the whole wave: an LDS broadcast
-        if (t[9] != 0.0) {
-          const double d = md_dist2(px, py, pz, t);
+        const double* t = s_tri + k * Prim::kDoubles;       // one address for the whole wave: an LDS broadcast
+        if (t[Prim::kDoubles - 1] != 0.0) {
+          const double d = Prim::dist2(px, py, pz, t);
           if (kIndexed) {
-            const int f = (int)t[9] - 1;
+            const int f = (int)t[Prim::kDoubles - 1] - 1;
             if (d < best || (d == best && f < best_f)) best = d, best_f = f;
           } else if (d < best) {
             best = d, best_f = tile * kMdTile + k;
@@ -329,11 +371,11 @@ inline const double* md_index_gbox(const void* index, int nf) {
   return (const double*)((const char*)index + md_box_bytes(nf));
 }
 
-// The boxes of the tiles of nf > 0 faces -> box; `order` null: the tiles of the caller's face order
-inline void md_launch_boxes(const float* vert, const int32_t* faces, int nf, int nv, const int32_t* order, double* box,
-                            hipStream_t stream) {
-  hipLaunchKernelGGL(md_box_kernel, dim3(blocks_for(nf, kMdTile)), dim3(kWave), 0, stream, vert, faces, nf, nv, order,
-                     box);
+// The boxes of the tiles of the > 0 elements of src -> box; `order` null: the tiles of the caller's element order
+template <class Prim>
+inline void md_launch_boxes(const typename Prim::Src src, const int32_t* order, double* box, hipStream_t stream) {
+  hipLaunchKernelGGL(md_box_kernel<Prim>, dim3(blocks_for(Prim::count(src), kMdTile)), dim3(kWave), 0, stream, src,
+                     order, box);
 }
 
 // The error of entry point `what` whose `thing` ("workspace", "index") is too small
@@ -347,6 +389,20 @@ inline int md_launched(const char* what) {
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) set_error("%s launch: %s", what, hipGetErrorString(e));
   return e == hipSuccess ? MSLAM_OK : MSLAM_EHIP;
+}
+
+// An index's workspace of entry point `what` filled for the > 0 elements of src in `order`: the size check, the tile
+// boxes, the group boxes above them, the launch check.
+template <class Prim>
+inline int md_build_index(const typename Prim::Src src, const int32_t* order, void* workspace, size_t workspace_bytes,
+                          const char* what, hipStream_t stream) {
+  const int n = Prim::count(src), ntiles = (int)blocks_for(n, kMdTile), ngroups = md_groups(n);
+  if (workspace_bytes < md_index_bytes(n)) return md_too_small(what, "workspace", workspace_bytes, md_index_bytes(n));
+  double* box = (double*)workspace;
+  md_launch_boxes<Prim>(src, order, box, stream);
+  hipLaunchKernelGGL(md_group_kernel, dim3(blocks_for(6 * ngroups, 256)), dim3(256), 0, stream, (const double*)box,
+                     ntiles, ngroups, box + 6 * (size_t)ntiles);
+  return md_launched(what);
 }
 
 }  // namespace mslam

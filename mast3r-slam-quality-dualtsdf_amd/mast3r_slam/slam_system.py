@@ -385,6 +385,22 @@ class SlamSystem:
         est = torch.stack(centres).to(device=self.device, dtype=torch.float32) if n else gt.new_zeros((0, 3))
         return fit_sim3(est, gt)[0]
 
+    def _alignment_kw(self, what, align, init, gt_positions, align_kw):
+        """The align / align_kw keywords of compare_meshes and compare_clouds from evaluate_mesh's and evaluate_cloud's
+        arguments: with align="icp", `init` joins align_kw, "trajectory" as self.align_trajectory(gt_positions)."""
+        if not isinstance(align, str):
+            if init is not None or align_kw:
+                raise ValueError(f"{what}: init and align_kw go with align='icp' only")
+            return {} if align is None else dict(align=align)
+        align_kw = dict(align_kw or {})
+        if isinstance(init, str):
+            if init != "trajectory" or gt_positions is None:
+                raise ValueError(f"{what}: init='trajectory' needs gt_positions")
+            init = self.align_trajectory(gt_positions)
+        if init is not None:
+            align_kw["init"] = init
+        return dict(align=align, align_kw=align_kw)
+
     def evaluate_mesh(self, gt_vertices, gt_faces, n_samples=200_000, threshold=None, align=None, init=None,
                       gt_positions=None, align_kw=None, observed=False, gt_K=None, index=None, **extract_kw):
         """Quality of the global TSDF's mesh at this point of the run against a ground-truth mesh (gt_vertices f32[V,3],
@@ -412,21 +428,7 @@ class SlamSystem:
 
         if threshold is None:
             threshold = float(self.tsdf_manager.cfg.get("mesh_eval_threshold", 0.05))
-        kw = {}
-        if align is not None:
-            kw["align"] = align
-            if isinstance(align, str):
-                kw["align_kw"] = dict(align_kw or {})
-                if isinstance(init, str):
-                    if init != "trajectory" or gt_positions is None:
-                        raise ValueError("SlamSystem.evaluate_mesh: init='trajectory' needs gt_positions")
-                    init = self.align_trajectory(gt_positions)
-                if init is not None:
-                    kw["align_kw"]["init"] = init
-            elif init is not None or align_kw:
-                raise ValueError("SlamSystem.evaluate_mesh: init and align_kw go with align='icp' only")
-        elif init is not None or align_kw:
-            raise ValueError("SlamSystem.evaluate_mesh: init and align_kw go with align='icp' only")
+        kw = self._alignment_kw("SlamSystem.evaluate_mesh", align, init, gt_positions, align_kw)
         mesh = self.extract_mesh(**extract_kw)
         dev = mesh[0].device
         gt_vertices = torch.as_tensor(gt_vertices, dtype=torch.float32).to(dev)
@@ -494,21 +496,7 @@ class SlamSystem:
                    else config["tsdf_global"]["voxel_size"])
         threshold = vs if threshold is None else float(threshold)
         voxel = vs if voxel is None else float(voxel)
-        kw = {}
-        if align is not None:
-            kw["align"] = align
-            if isinstance(align, str):
-                kw["align_kw"] = dict(align_kw or {})
-                if isinstance(init, str):
-                    if init != "trajectory" or gt_positions is None:
-                        raise ValueError("SlamSystem.evaluate_cloud: init='trajectory' needs gt_positions")
-                    init = self.align_trajectory(gt_positions)
-                if init is not None:
-                    kw["align_kw"]["init"] = init
-            elif init is not None or align_kw:
-                raise ValueError("SlamSystem.evaluate_cloud: init and align_kw go with align='icp' only")
-        elif init is not None or align_kw:
-            raise ValueError("SlamSystem.evaluate_cloud: init and align_kw go with align='icp' only")
+        kw = self._alignment_kw("SlamSystem.evaluate_cloud", align, init, gt_positions, align_kw)
         points, _ = self.keyframe_cloud(conf_threshold, colors=False)
         gt = torch.as_tensor(gt_points, dtype=torch.float32).to(points.device).reshape(-1, 3).contiguous()
         if index is not None and index is not False:
@@ -529,7 +517,7 @@ class SlamSystem:
         if self.tsdf_manager is None:
             raise RuntimeError("SlamSystem.evaluate_depth: the global TSDF is disabled (tsdf_global.enabled = False)")
         from mast3r_slam.tsdf import render_mesh
-        from mast3r_slam.tsdf.mesh_index import _index_arg
+        from mast3r_slam.tsdf.mesh_index import MeshIndex, _index_arg
         from mast3r_slam.tsdf.mesh_raycast import compose_sim3
 
         self.drain()
@@ -538,7 +526,7 @@ class SlamSystem:
             raise RuntimeError("SlamSystem.evaluate_depth: no keyframe yet")
         gt = (torch.as_tensor(gt_vertices, dtype=torch.float32).to(self.device),
               torch.as_tensor(gt_faces, dtype=torch.int32).to(self.device))
-        index = _index_arg(index, *gt, "SlamSystem.evaluate_depth")
+        index = _index_arg(MeshIndex, index, "SlamSystem.evaluate_depth", *gt)
         T = None if align is None else torch.as_tensor(getattr(align, "data", align)).detach().double().cpu().reshape(8)
         a_scale = 1.0 if T is None else float(T[7])
         diffs, n_pixels = [], 0

@@ -8,13 +8,15 @@ finite.  An invalid point is never anyone's nearest neighbour, is never fused in
 """
 import math
 
-import numpy as np
 import torch
 
 import mslam_hip as _m
 
 from ._mesh_args import _points_arg, _sim3_arg
-from .mesh_align import DEGENERATE, LOG_DOUBLES, OK, STATE_BYTES, _read_state
+from .mesh_align import (DEGENERATE, LOG_DOUBLES, OK, STATE_BYTES, _alignment_arg, _icp_args, _icp_run,
+                         _read_state)
+from .mesh_index import _index_arg, _sorted_scan, _SpatialIndex
+from .mesh_metrics import _fscore_chamfer
 
 _NONE = torch.iinfo(torch.int64).max
 
@@ -23,7 +25,7 @@ def _valid(points):
     return torch.isfinite(points).all(1)
 
 
-class CloudIndex:
+class CloudIndex(_SpatialIndex):
     """The index of the cloud `points` f32[N,3] (a device tensor), built once and passed as `index=` to cloud_distance,
     align_clouds and compare_clouds for that same tensor.  It keeps the tensor (never copied or permuted), `order`
     i32[N] - the valid points by the Morton code of their place in the box of the valid points, invalid points last,
@@ -36,7 +38,6 @@ class CloudIndex:
         self.p = _points_arg(points, "points", what)
         self.N = int(self.p.shape[0])
         dev = self.device = self.p.device
-        L, st = _m.lib(), _m.stream_ptr()
         if self.N:
             ok = _valid(self.p)
             inf = torch.tensor(math.inf, dtype=torch.float32, device=dev)
@@ -46,24 +47,7 @@ class CloudIndex:
         else:
             self.bounds = torch.zeros(6, dtype=torch.float32, device=dev)
             keys = torch.empty(0, dtype=torch.int64, device=dev)
-        self.order = torch.sort(keys, stable=True)[1].to(torch.int32)
-        self.ws_bytes = int(L.mslam_cloud_index_bytes(self.N))
-        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev) if self.ws_bytes else None
-        _m.check(L.mslam_cloud_index_boxes(_m.ptr(self.p), self.N, _m.ptr(self.order), _m.ptr(self.ws), self.ws_bytes,
-                                           st), "cloud_index_boxes")
-
-    def point_keys(self, points):
-        """keys i64[n] of the points f32[n,3] (contiguous, on the index's device): their Morton codes in the box of the
-        cloud's valid points, a point outside it in the nearest cell."""
-        n = int(points.shape[0])
-        keys = torch.empty(n, dtype=torch.int64, device=self.device)
-        _m.check(_m.lib().mslam_mesh_index_point_keys(_m.ptr(points), n, _m.ptr(self.bounds), _m.ptr(keys),
-                                                      _m.stream_ptr()), "mesh_index_point_keys")
-        return keys
-
-    def query_order(self, points):
-        """i64[n]: the points' indices in the order of their keys (stable)."""
-        return torch.sort(self.point_keys(points), stable=True)[1]
+        self._build(keys, self.N, "cloud_index", (_m.ptr(self.p), self.N))
 
     def check(self, points, what):
         """Raises ValueError unless the index was built for this very tensor: the same shape and data pointer."""
@@ -74,35 +58,18 @@ class CloudIndex:
         return self
 
 
-def _cloud_index_arg(index, points, what):
-    """index=None / True / a CloudIndex -> None or a CloudIndex checked against the cloud."""
-    if index is None or index is False:
-        return None
-    if index is True:
-        return CloudIndex(points)
-    if not isinstance(index, CloudIndex):
-        raise TypeError(f"{what}: index must be None, True or a CloudIndex, got {type(index).__name__}")
-    return index.check(points, what)
-
-
 def _distance2(queries, points, index=None, sort_queries=True, levels=2):
     """(dist2 f64[n], nearest i32[n]) of the checked arguments."""
-    n, N, dev = int(queries.shape[0]), int(points.shape[0]), queries.device
-    dist2 = torch.empty(n, dtype=torch.float64, device=dev)
-    nearest = torch.empty(n, dtype=torch.int32, device=dev)
-    L = _m.lib()
-    if index is None:
-        _m.check(L.mslam_cloud_distance(_m.ptr(queries), n, _m.ptr(points), N, 0, 0, 0, 1, 0, _m.ptr(dist2),
-                                        _m.ptr(nearest), _m.stream_ptr()), "cloud_distance")
-        return dist2, nearest
-    perm = index.query_order(queries) if sort_queries and n > 1 else None
-    q = queries if perm is None else queries[perm].contiguous()
-    _m.check(L.mslam_cloud_distance(_m.ptr(q), n, _m.ptr(points), N, _m.ptr(index.order), _m.ptr(index.ws),
-                                    index.ws_bytes, levels, 0, _m.ptr(dist2), _m.ptr(nearest), _m.stream_ptr()),
-             "cloud_distance")
-    if perm is None:
-        return dist2, nearest
-    return torch.empty_like(dist2).index_copy_(0, perm, dist2), torch.empty_like(nearest).index_copy_(0, perm, nearest)
+    n, N = int(queries.shape[0]), int(points.shape[0])
+    # without an index: no order, no boxes, and levels 1, which the plain scan does not read
+    order, ws, ws_bytes, levels = (0, 0, 0, 1) if index is None else (_m.ptr(index.order), _m.ptr(index.ws),
+                                                                      index.ws_bytes, levels)
+
+    def scan(q, dist2, nearest):
+        _m.check(_m.lib().mslam_cloud_distance(_m.ptr(q), n, _m.ptr(points), N, order, ws, ws_bytes, levels, 0,
+                                               _m.ptr(dist2), _m.ptr(nearest), _m.stream_ptr()), "cloud_distance")
+
+    return _sorted_scan(queries, index, sort_queries, scan)
 
 
 def cloud_distance(queries, points, index=None, sort_queries=True):
@@ -116,7 +83,7 @@ def cloud_distance(queries, points, index=None, sort_queries=True):
     clouds")."""
     what = "cloud_distance"
     queries = _points_arg(queries, "queries", what)
-    index = _cloud_index_arg(index, points, what)
+    index = _index_arg(CloudIndex, index, what, points)
     points = _points_arg(points, "points", what)
     if queries.device != points.device:
         raise ValueError(f"{what}: queries and points are on different devices")
@@ -170,6 +137,8 @@ def downsample_cloud(points, voxel, colors=None, return_first=False):
     return (centroid, color, count, first) if return_first else (centroid, color, count)
 
 
+# not merged with mesh_align.transform_mesh: this one is an elementwise f64 sum in a stated order, that one a matmul,
+# they round differently and tests pin the bits of each
 def transform_cloud(points, T, _normalise=True):
     """The points f32[n,3] moved by the Sim3 T [t(3), q(xyzw), s]: s (R p) + t per coordinate in f64, rounded once to
     f32.  Elementwise torch ops on the points' device, one multiply or add each; the quaternion is normalised first
@@ -199,7 +168,7 @@ def stride_sample(points, n_samples):
 def align_clouds(pred, gt, init=None, n_samples=20000, max_iters=50, trim=math.inf, with_scale=True, tol=1e-6,
                  check_every=5, index=None, _trace=None):
     """Trimmed point-to-point ICP of the cloud `pred` onto the cloud `gt` (f32[N,3] device tensors): the Sim3 T with
-    T(pred) ~ gt.  The arguments, the returned dict and the stop rule are align_meshes'.
+    T(pred) ~ gt.  The arguments, the returned dict and the stop rule are align_meshes' (mesh_align._icp_args, _icp_run).
 
     The source sample is stride_sample(pred, n_samples), drawn once.  Every iteration moves it by the current T (f64,
     rounded once to f32), finds each moved point's nearest neighbour in gt (cloud_distance; `index`: None, True or a
@@ -215,20 +184,11 @@ def align_clouds(pred, gt, init=None, n_samples=20000, max_iters=50, trim=math.i
     within trim under the T that iteration started from, and their RMSE), history (numpy f64[iterations, 4]: inliers,
     rmse, scale after the solve, status)."""
     what = "align_clouds"
-    max_iters, check_every = int(max_iters), int(check_every)
-    if max_iters < 1 or check_every < 1:
-        raise ValueError(f"{what}: max_iters and check_every must be >= 1, got {max_iters} and {check_every}")
-    if not float(tol) >= 0.0:
-        raise ValueError(f"{what}: tol must be >= 0, got {tol}")
-    trims = [float(t) for t in trim] if isinstance(trim, (list, tuple, np.ndarray)) else [float(trim)] * max_iters
-    if len(trims) != max_iters:
-        raise ValueError(f"{what}: a trim sequence needs one value per iteration ({max_iters}), got {len(trims)}")
-    if not all(t >= 0.0 for t in trims):
-        raise ValueError(f"{what}: trim must be >= 0 (+inf keeps every pair)")
+    max_iters, check_every, trims = _icp_args(what, max_iters, check_every, tol, trim)
     if int(n_samples) < 1:
         raise ValueError(f"{what}: n_samples must be >= 1, got {n_samples}")
     pred = _points_arg(pred, "pred", what)
-    index = _cloud_index_arg(index, gt, what)
+    index = _index_arg(CloudIndex, index, what, gt)
     gt = _points_arg(gt, "gt", what)
     if pred.device != gt.device:
         raise ValueError(f"{what}: pred and gt are on different devices")
@@ -246,8 +206,9 @@ def align_clouds(pred, gt, init=None, n_samples=20000, max_iters=50, trim=math.i
     fit_log = torch.zeros(LOG_DOUBLES, dtype=torch.float64, device=dev)
     log = torch.zeros((max_iters, 4), dtype=torch.float64, device=dev)
     inf = torch.tensor(math.inf, dtype=torch.float64, device=dev)
-    converged, hist, it = False, None, 0
-    for it in range(max_iters):
+
+    def step(it):
+        nonlocal T
         moved = transform_cloud(src, T, _normalise=False)
         dist2, nearest = _distance2(moved, gt, index)
         has = nearest >= 0
@@ -271,14 +232,9 @@ def align_clouds(pred, gt, init=None, n_samples=20000, max_iters=50, trim=math.i
         if _trace is not None:
             _trace.append(dict(T_before=T_before, moved=moved, dist2=dist2, nearest=nearest, weights=w, dst=dst,
                                fit_log=fit_log.clone(), T=T, status=status.clone()))
-        if (it + 1) % check_every == 0 or it + 1 == max_iters:
-            hist = log[:it + 1].cpu().numpy()                              # the one host read of this stretch
-            if hist[it, 3] != OK:
-                break
-            if it >= 1 and abs(hist[it, 1] - hist[it - 1, 1]) <= float(tol) * hist[it - 1, 1]:
-                converged = True
-                break
-    return dict(T=T, iterations=it + 1, converged=converged, rmse=float(hist[it, 1]), inliers=int(hist[it, 0]),
+
+    iterations, converged, hist = _icp_run(step, log, max_iters, check_every, tol)
+    return dict(T=T, iterations=iterations, converged=converged, rmse=float(hist[-1, 1]), inliers=int(hist[-1, 0]),
                 history=hist)
 
 
@@ -334,8 +290,6 @@ def compare_clouds(pred, gt, threshold=0.05, voxel=None, max_dist=None, align=No
         raise ValueError(f"{what}: max_dist must be >= 0, got {max_dist}")
     if voxel is not None and isinstance(index, CloudIndex):
         raise ValueError(f"{what}: voxel= thins gt into a new tensor; pass index=True with it")
-    if align is None and align_kw:
-        raise ValueError(f"{what}: align_kw goes with align='icp' only")
     pred = _points_arg(pred, "pred", what)
     gt_given = gt
     gt = _points_arg(gt, "gt", what)
@@ -344,19 +298,9 @@ def compare_clouds(pred, gt, threshold=0.05, voxel=None, max_dist=None, align=No
     if voxel is not None:
         pred, gt = downsample_cloud(pred, voxel)[0], downsample_cloud(gt, voxel)[0]
         gt_given = gt
-    g_index = _cloud_index_arg(index, gt_given, what)
-    alignment = None
-    if align is not None:
-        if isinstance(align, str):
-            if align != "icp":
-                raise ValueError(f"{what}: align must be None, a Sim3 or 'icp', got {align!r}")
-            res = align_clouds(pred, gt, index=g_index, **(align_kw or {}))
-            T, alignment = res["T"], dict(rmse=res["rmse"], iterations=res["iterations"])
-        else:
-            if align_kw:
-                raise ValueError(f"{what}: align_kw goes with align='icp' only")
-            T, alignment = _sim3_arg(align, what, pred.device, torch.float64), dict(rmse=None, iterations=None)
-        alignment["T"] = T.tolist()
+    g_index = _index_arg(CloudIndex, index, what, gt_given)
+    T, alignment = _alignment_arg(what, align, align_kw, lambda **kw: align_clouds(pred, gt, index=g_index, **kw))
+    if T is not None:
         pred = transform_cloud(pred, T)
     p_index = CloudIndex(pred) if g_index is not None else None
     figures = _direction(pred, gt, g_index, threshold, limit) + _direction(gt, pred, p_index, threshold, limit)
@@ -366,8 +310,7 @@ def compare_clouds(pred, gt, threshold=0.05, voxel=None, max_dist=None, align=No
         raise ValueError(f"{what}: a cloud has no valid point ({int(n_pred)} in pred, {int(n_gt)} in gt)")
     out = dict(accuracy=acc, accuracy_median=acc_med, accuracy_rmse=acc_rms, completion=comp,
                completion_median=comp_med, completion_rmse=comp_rms, precision=prec, recall=rec,
-               fscore=2.0 * prec * rec / (prec + rec) if prec + rec > 0.0 else 0.0, chamfer=0.5 * (acc + comp),
-               n_pred=int(n_pred), n_gt=int(n_gt), threshold=threshold, voxel=None if voxel is None else float(voxel),
+               **_fscore_chamfer(prec, rec, acc, comp), n_pred=int(n_pred), n_gt=int(n_gt), threshold=threshold, voxel=None if voxel is None else float(voxel),
                max_dist=None if max_dist is None else limit, accuracy_outliers=int(acc_out),
                completion_outliers=int(comp_out))
     if alignment is not None:

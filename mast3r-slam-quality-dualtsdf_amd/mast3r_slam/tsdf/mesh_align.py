@@ -13,7 +13,7 @@ import torch
 import mslam_hip as _m
 
 from ._mesh_args import _mesh_arg, _pair, _points_arg, _sample, _sim3_arg
-from .mesh_index import _index_arg
+from .mesh_index import MeshIndex, _index_arg
 
 STATE_BYTES, LOG_DOUBLES, OK, DEGENERATE = (_m.header_constants()["MSLAM_MESH_ALIGN_" + k] for k in (
     "STATE_BYTES", "LOG_DOUBLES", "OK", "DEGENERATE"))
@@ -68,6 +68,8 @@ def fit_sim3(src, dst, weights=None, with_scale=True):
     return T64, T32
 
 
+# not merged with cloud.transform_cloud: that one is an elementwise f64 sum in a stated order, this one a matmul, they
+# round differently and tests pin the bits of each
 def transform_mesh(vertices, T, normals=None):
     """The vertices f32[V,3] moved by the Sim3 T (s R v + t, in f64, stored f32) and, when given, the normals rotated
     (R n): torch ops on the vertices' device.  Returns the vertices, or (vertices, normals)."""
@@ -84,6 +86,57 @@ def transform_mesh(vertices, T, normals=None):
     if normals is None:
         return moved
     return moved, (normals.to(torch.float64) @ R.T).to(normals.dtype)
+
+
+def _icp_args(what, max_iters, check_every, tol, trim):
+    """(max_iters, check_every, trims) of align_meshes' and align_clouds' loop arguments, checked; trims: one float
+    per iteration."""
+    max_iters, check_every = int(max_iters), int(check_every)
+    if max_iters < 1 or check_every < 1:
+        raise ValueError(f"{what}: max_iters and check_every must be >= 1, got {max_iters} and {check_every}")
+    if not float(tol) >= 0.0:
+        raise ValueError(f"{what}: tol must be >= 0, got {tol}")
+    trims = [float(t) for t in trim] if isinstance(trim, (list, tuple, np.ndarray)) else [float(trim)] * max_iters
+    if len(trims) != max_iters:
+        raise ValueError(f"{what}: a trim sequence needs one value per iteration ({max_iters}), got {len(trims)}")
+    if not all(t >= 0.0 for t in trims):
+        raise ValueError(f"{what}: trim must be >= 0 (+inf keeps every pair)")
+    return max_iters, check_every, trims
+
+
+def _icp_run(step, log, max_iters, check_every, tol):
+    """The ICP loop and its stop rule -> (iterations, converged, history).  step(it) runs iteration `it` and leaves its
+    (inliers, rmse, scale, status) in log[it, :4], a tensor of max_iters rows.  The log is read every `check_every`
+    iterations and after the last; at a read the loop stops when the latest status is not OK, or, from the second
+    iteration on, when the RMSE of the last two iterations differs by at most `tol` relative.  So `iterations` is a
+    multiple of check_every or max_iters, and history (numpy f64[iterations, 4]) is the log up to there."""
+    converged, hist, it = False, None, 0
+    for it in range(max_iters):
+        step(it)
+        if (it + 1) % check_every == 0 or it + 1 == max_iters:
+            hist = log[:it + 1, :4].cpu().numpy()                      # the one host read of this stretch
+            if hist[it, 3] != OK:
+                break
+            if it >= 1 and abs(hist[it, 1] - hist[it - 1, 1]) <= float(tol) * hist[it - 1, 1]:
+                converged = True
+                break
+    return it + 1, converged, hist
+
+
+def _alignment_arg(what, align, align_kw, icp):
+    """compare_meshes' and compare_clouds' `align` -> (T, alignment): (None, None) for None; a Sim3 itself; for "icp"
+    the T of icp(**align_kw), align_meshes or align_clouds bound to the pair.  alignment: the dict the figures gain."""
+    if not isinstance(align, str):
+        if align_kw:
+            raise ValueError(f"{what}: align_kw goes with align='icp' only")
+        if align is None:
+            return None, None
+        T = _sim3_arg(align, what, None, torch.float64)
+        return T, dict(rmse=None, iterations=None, T=T.tolist())
+    if align != "icp":
+        raise ValueError(f"{what}: align must be None, a Sim3 or 'icp', got {align!r}")
+    res = icp(**(align_kw or {}))
+    return res["T"], dict(rmse=res["rmse"], iterations=res["iterations"], T=res["T"].tolist())
 
 
 def align_meshes(pred, gt, init=None, n_samples=20000, max_iters=50, trim=math.inf, with_scale=True, seed=0, tol=1e-6,
@@ -110,17 +163,8 @@ def align_meshes(pred, gt, init=None, n_samples=20000, max_iters=50, trim=math.i
     iteration: the pairs within trim under the T that iteration started from, and their RMSE), history (numpy
     f64[iterations, 4]: inliers, rmse, scale after the solve, status)."""
     what = "align_meshes"
-    max_iters, check_every = int(max_iters), int(check_every)
-    if max_iters < 1 or check_every < 1:
-        raise ValueError(f"{what}: max_iters and check_every must be >= 1, got {max_iters} and {check_every}")
-    if not float(tol) >= 0.0:
-        raise ValueError(f"{what}: tol must be >= 0, got {tol}")
-    trims = [float(t) for t in trim] if isinstance(trim, (list, tuple, np.ndarray)) else [float(trim)] * max_iters
-    if len(trims) != max_iters:
-        raise ValueError(f"{what}: a trim sequence needs one value per iteration ({max_iters}), got {len(trims)}")
-    if not all(t >= 0.0 for t in trims):
-        raise ValueError(f"{what}: trim must be >= 0 (+inf keeps every pair)")
-    index = _index_arg(index, *_pair(gt, "gt"), what)
+    max_iters, check_every, trims = _icp_args(what, max_iters, check_every, tol, trim)
+    index = _index_arg(MeshIndex, index, what, *_pair(gt, "gt"))
     pv, pf, pV, pF = _mesh_arg(*_pair(pred, "pred"), True, what)
     gv, gf, gV, gF = _mesh_arg(*_pair(gt, "gt"), True, what)
     if pv.device != gv.device:
@@ -142,8 +186,8 @@ def align_meshes(pred, gt, init=None, n_samples=20000, max_iters=50, trim=math.i
                                          _m.ptr(state), st), "mesh_align_init")
     else:
         _m.check(L.mslam_mesh_align_init_indexed(_m.ptr(T0), _m.ptr(state), st), "mesh_align_init_indexed")
-    converged, hist, it = False, None, 0
-    for it in range(max_iters):
+
+    def step(it):
         if index is None:
             _m.check(L.mslam_mesh_align_step(_m.ptr(src), n, _m.ptr(gv), _m.ptr(gf), gF, gV, trims[it],
                                              1 if with_scale else 0, 0, _m.ptr(ws), ws_bytes, _m.ptr(state),
@@ -155,12 +199,7 @@ def align_meshes(pred, gt, init=None, n_samples=20000, max_iters=50, trim=math.i
                                                      1 if with_scale else 0, 0, _m.ptr(ws), ws_bytes, _m.ptr(state),
                                                      _m.ptr(nearest), _m.ptr(moved), _m.ptr(dist2), 0,
                                                      _m.ptr(log[it]), st), "mesh_align_step_indexed")
-        if (it + 1) % check_every == 0 or it + 1 == max_iters:
-            hist = log[:it + 1, :4].cpu().numpy()                      # the one host read of this stretch
-            if hist[it, 3] != OK:
-                break
-            if it >= 1 and abs(hist[it, 1] - hist[it - 1, 1]) <= float(tol) * hist[it - 1, 1]:
-                converged = True
-                break
-    return dict(T=_read_state(state)[0], iterations=it + 1, converged=converged, rmse=float(hist[it, 1]),
-                inliers=int(hist[it, 0]), history=hist)
+
+    iterations, converged, hist = _icp_run(step, log, max_iters, check_every, tol)
+    return dict(T=_read_state(state)[0], iterations=iterations, converged=converged, rmse=float(hist[-1, 1]),
+                inliers=int(hist[-1, 0]), history=hist)

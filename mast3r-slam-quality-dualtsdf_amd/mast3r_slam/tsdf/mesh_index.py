@@ -12,7 +12,37 @@ import mslam_hip as _m
 from ._mesh_args import _mesh_arg, _pair
 
 
-class MeshIndex:
+class _SpatialIndex:
+    """What MeshIndex and CloudIndex (cloud.py) share: `device`, `bounds` f32[6] (the box the Morton keys are taken in),
+    `order` i32[n] (the elements by key, from a stable sort), and `ws` / `ws_bytes`, the workspace of the boxes of the
+    128-element tiles in that order and of the groups of 32 tiles.  A subclass checks its arguments, sets `device` and
+    `bounds`, forms its elements' keys and calls _build; it keeps its own `check`."""
+
+    def _build(self, keys, n, name, source):
+        """`order` from the keys i64[n], then the workspace: mslam_<name>_bytes(n) and mslam_<name>_boxes(*source, order,
+        workspace, bytes, stream)."""
+        L = _m.lib()
+        self.order = torch.sort(keys, stable=True)[1].to(torch.int32)
+        self.ws_bytes = int(getattr(L, f"mslam_{name}_bytes")(n))
+        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=self.device) if self.ws_bytes else None
+        _m.check(getattr(L, f"mslam_{name}_boxes")(*source, _m.ptr(self.order), _m.ptr(self.ws), self.ws_bytes,
+                                                   _m.stream_ptr()), f"{name}_boxes")
+
+    def point_keys(self, points):
+        """keys i64[n] of the points f32[n,3] (contiguous, on the index's device): their Morton codes in `bounds`, a
+        point outside it in the nearest cell.  Sorting queries by them makes neighbours of the lanes of a wave."""
+        n = int(points.shape[0])
+        keys = torch.empty(n, dtype=torch.int64, device=self.device)
+        _m.check(_m.lib().mslam_mesh_index_point_keys(_m.ptr(points), n, _m.ptr(self.bounds), _m.ptr(keys),
+                                                      _m.stream_ptr()), "mesh_index_point_keys")
+        return keys
+
+    def query_order(self, points):
+        """i64[n]: the points' indices in the order of their keys (stable)."""
+        return torch.sort(self.point_keys(points), stable=True)[1]
+
+
+class MeshIndex(_SpatialIndex):
     """The index of the mesh (vertices f32[V,3], faces i32[F,3], device tensors), built once and passed as `index=` to
     mesh_distance, compare_meshes, align_meshes, render_mesh and observed_points for that same mesh.  It keeps the two
     tensors (they are never copied or permuted), `order` i32[F] - the faces by the Morton code of their centroids,
@@ -26,31 +56,13 @@ class MeshIndex:
         self.pointers = (vertices.data_ptr(), faces.data_ptr()) if self.shapes else None
         self.v, self.f, self.V, self.F = _mesh_arg(vertices, faces, validate, what)
         dev = self.device = self.v.device
-        L, st = _m.lib(), _m.stream_ptr()
         # the box of the vertices: plumbing, like the sort below
         self.bounds = torch.cat((self.v.amin(0), self.v.amax(0))).contiguous() if self.V else torch.zeros(
             6, dtype=torch.float32, device=dev)
         keys = torch.empty(self.F, dtype=torch.int64, device=dev)
-        _m.check(L.mslam_mesh_index_keys(_m.ptr(self.v), self.V, _m.ptr(self.f), self.F, _m.ptr(self.bounds),
-                                         _m.ptr(keys), st), "mesh_index_keys")
-        self.order = torch.sort(keys, stable=True)[1].to(torch.int32)
-        self.ws_bytes = int(L.mslam_mesh_index_bytes(self.F))
-        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev) if self.ws_bytes else None
-        _m.check(L.mslam_mesh_index_boxes(_m.ptr(self.v), _m.ptr(self.f), self.F, self.V, _m.ptr(self.order),
-                                          _m.ptr(self.ws), self.ws_bytes, st), "mesh_index_boxes")
-
-    def point_keys(self, points):
-        """keys i64[n] of the points f32[n,3] (contiguous, on the index's device): their Morton codes in the mesh's box,
-        a point outside it in the nearest cell.  Sorting queries by them makes neighbours of the lanes of a wave."""
-        n = int(points.shape[0])
-        keys = torch.empty(n, dtype=torch.int64, device=self.device)
-        _m.check(_m.lib().mslam_mesh_index_point_keys(_m.ptr(points), n, _m.ptr(self.bounds), _m.ptr(keys),
-                                                      _m.stream_ptr()), "mesh_index_point_keys")
-        return keys
-
-    def query_order(self, points):
-        """i64[n]: the points' indices in the order of their keys (stable)."""
-        return torch.sort(self.point_keys(points), stable=True)[1]
+        _m.check(_m.lib().mslam_mesh_index_keys(_m.ptr(self.v), self.V, _m.ptr(self.f), self.F, _m.ptr(self.bounds),
+                                                _m.ptr(keys), _m.stream_ptr()), "mesh_index_keys")
+        self._build(keys, self.F, "mesh_index", (_m.ptr(self.v), _m.ptr(self.f), self.F, self.V))
 
     def check(self, vertices, faces, what):
         """Raises ValueError unless the index was built for these very tensors: the same shapes and data pointers."""
@@ -68,12 +80,27 @@ def build_mesh_index(mesh, validate=True):
     return MeshIndex(*_pair(mesh, "mesh"), validate=validate)
 
 
-def _index_arg(index, vertices, faces, what):
-    """index=None / True / a MeshIndex -> None or a MeshIndex checked against the mesh."""
+def _index_arg(cls, index, what, *tensors):
+    """index=None / True / an index of class `cls` (MeshIndex, CloudIndex) -> None or one checked against `tensors`,
+    the mesh's vertices and faces or the cloud's points."""
     if index is None or index is False:
         return None
     if index is True:
-        return MeshIndex(vertices, faces)
-    if not isinstance(index, MeshIndex):
-        raise TypeError(f"{what}: index must be None, True or a MeshIndex, got {type(index).__name__}")
-    return index.check(vertices, faces, what)
+        return cls(*tensors)
+    if not isinstance(index, cls):
+        raise TypeError(f"{what}: index must be None, True or a {cls.__name__}, got {type(index).__name__}")
+    return index.check(*tensors, what)
+
+
+def _sorted_scan(queries, index, sort_queries, scan):
+    """(dist2 f64[n], nearest i32[n]) from scan(q, dist2, nearest), the call that fills them for the queries q f32[n,3].
+    With an index and `sort_queries`, q is the queries in the order of their Morton keys and the results are scattered
+    back."""
+    n, dev = int(queries.shape[0]), queries.device
+    dist2 = torch.empty(n, dtype=torch.float64, device=dev)
+    nearest = torch.empty(n, dtype=torch.int32, device=dev)
+    perm = index.query_order(queries) if index is not None and sort_queries and n > 1 else None
+    scan(queries if perm is None else queries[perm].contiguous(), dist2, nearest)
+    if perm is None:
+        return dist2, nearest
+    return torch.empty_like(dist2).index_copy_(0, perm, dist2), torch.empty_like(nearest).index_copy_(0, perm, nearest)

@@ -12,9 +12,9 @@ import torch
 
 import mslam_hip as _m
 
-from ._mesh_args import _areas, _mesh_arg, _pair, _points_arg, _sample, _sim3_arg
-from .mesh_align import align_meshes, transform_mesh
-from .mesh_index import _index_arg
+from ._mesh_args import _areas, _mesh_arg, _pair, _points_arg, _sample
+from .mesh_align import _alignment_arg, align_meshes, transform_mesh
+from .mesh_index import MeshIndex, _index_arg, _sorted_scan
 
 
 def face_areas(vertices, faces, _validate=True):
@@ -35,28 +35,29 @@ def sample_mesh(vertices, faces, n, seed=0, _validate=True):
 def _distance2(points, vertices, faces, V, F, skip, index=None, sort_queries=True):
     """(dist2 f64[n], nearest i32[n]).  `index`: a MeshIndex of this mesh - the scan runs over its tiles, and with
     `sort_queries` on the points in the order of their Morton keys, the results scattered back."""
-    n = int(points.shape[0])
-    dev = points.device
-    dist2 = torch.empty(n, dtype=torch.float64, device=dev)
-    nearest = torch.empty(n, dtype=torch.int32, device=dev)
-    L = _m.lib()
-    if index is not None:
-        perm = index.query_order(points) if sort_queries and n > 1 else None
-        pts = points if perm is None else points[perm].contiguous()
-        _m.check(L.mslam_mesh_distance_indexed(_m.ptr(pts), n, _m.ptr(vertices), _m.ptr(faces), F, V,
-                                               _m.ptr(index.order), _m.ptr(index.ws), index.ws_bytes, 2, 0,
-                                               _m.ptr(dist2), _m.ptr(nearest), _m.stream_ptr()),
-                 "mesh_distance_indexed")
-        if perm is None:
-            return dist2, nearest
-        return torch.empty_like(dist2).index_copy_(0, perm, dist2), torch.empty_like(nearest).index_copy_(0, perm,
-                                                                                                       nearest)
-    ws_bytes = int(L.mslam_mesh_distance_workspace_bytes(F)) if skip and F else 0
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-    _m.check(L.mslam_mesh_distance(_m.ptr(points), n, _m.ptr(vertices), _m.ptr(faces), F, V, 1 if ws_bytes else 0,
-                                   _m.ptr(ws), ws_bytes, _m.ptr(dist2), _m.ptr(nearest), _m.stream_ptr()),
-             "mesh_distance")
-    return dist2, nearest
+    L, n = _m.lib(), int(points.shape[0])
+    ws_bytes = int(L.mslam_mesh_distance_workspace_bytes(F)) if index is None and skip and F else 0
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=points.device) if ws_bytes else None
+
+    def scan(pts, dist2, nearest):
+        if index is not None:
+            _m.check(L.mslam_mesh_distance_indexed(_m.ptr(pts), n, _m.ptr(vertices), _m.ptr(faces), F, V,
+                                                   _m.ptr(index.order), _m.ptr(index.ws), index.ws_bytes, 2, 0,
+                                                   _m.ptr(dist2), _m.ptr(nearest), _m.stream_ptr()),
+                     "mesh_distance_indexed")
+        else:
+            _m.check(L.mslam_mesh_distance(_m.ptr(pts), n, _m.ptr(vertices), _m.ptr(faces), F, V, 1 if ws_bytes else 0,
+                                           _m.ptr(ws), ws_bytes, _m.ptr(dist2), _m.ptr(nearest), _m.stream_ptr()),
+                     "mesh_distance")
+
+    return _sorted_scan(points, index, sort_queries, scan)
+
+
+def _fscore_chamfer(precision, recall, accuracy, completion):
+    """The two figures compare_meshes and compare_clouds derive from the other four, as dict entries: the harmonic mean
+    of precision and recall (0 when both are 0) and the mean of accuracy and completion."""
+    return dict(fscore=2.0 * precision * recall / (precision + recall) if precision + recall > 0.0 else 0.0,
+                chamfer=0.5 * (accuracy + completion))
 
 
 def mesh_distance(points, vertices, faces, skip=True, _validate=True, index=None, sort_queries=True):
@@ -68,7 +69,7 @@ def mesh_distance(points, vertices, faces, skip=True, _validate=True, index=None
     tiles and group boxes, and with `sort_queries` the points are scanned in the order of their Morton keys and the
     results scattered back; the same bits again, for faces in any order (DESIGN.md "Mesh index")."""
     points = _points_arg(points, "points", "mesh_distance")
-    index = _index_arg(index, vertices, faces, "mesh_distance")
+    index = _index_arg(MeshIndex, index, "mesh_distance", vertices, faces)
     vertices, faces, V, F = _mesh_arg(vertices, faces, _validate, "mesh_distance")
     if points.device != vertices.device:
         raise ValueError("mesh_distance: points and mesh are on different devices")
@@ -102,25 +103,13 @@ def compare_meshes(pred, gt, n_samples=200_000, threshold=0.05, seed=0, skip=Tru
     observed-part cull run over it, so their speed does not depend on the order of gt's faces.  The dict is the same,
     value for value."""
     n = int(n_samples)
-    index = _index_arg(index, *_pair(gt, "gt"), "compare_meshes")
+    index = _index_arg(MeshIndex, index, "compare_meshes", *_pair(gt, "gt"))
     threshold = float(threshold)
-    alignment = None
-    if align is not None:
+    T, alignment = _alignment_arg("compare_meshes", align, align_kw,
+                                  lambda **kw: align_meshes(_pair(pred, "pred"), gt, index=index, **kw))
+    if T is not None:
         pvert, pfaces = _pair(pred, "pred")
-        if isinstance(align, str):
-            if align != "icp":
-                raise ValueError(f"compare_meshes: align must be None, a Sim3 or 'icp', got {align!r}")
-            res = align_meshes((pvert, pfaces), gt, index=index, **(align_kw or {}))
-            T, alignment = res["T"], dict(rmse=res["rmse"], iterations=res["iterations"])
-        else:
-            if align_kw:
-                raise ValueError("compare_meshes: align_kw goes with align='icp' only")
-            T, alignment = _sim3_arg(align, "compare_meshes", pvert.device, torch.float64), dict(rmse=None,
-                                                                                               iterations=None)
-        alignment["T"] = T.tolist()
         pred = (transform_mesh(pvert, T), pfaces)
-    elif align_kw:
-        raise ValueError("compare_meshes: align_kw goes with align='icp' only")
     pv, pf, pV, pF = _mesh_arg(*_pair(pred, "pred"), _validate_pred, "compare_meshes")
     gv, gf, gV, gF = _mesh_arg(*_pair(gt, "gt"), True, "compare_meshes")
     p_pts, _, p_area = _sample(pv, pf, pV, pF, n, seed, "compare_meshes (pred)")
@@ -128,7 +117,7 @@ def compare_meshes(pred, gt, n_samples=200_000, threshold=0.05, seed=0, skip=Tru
     n_obs = n
     if observed is not None:
         seen = _observed_samples(g_pts, _pair(gt, "gt") if index is not None else (gv, gf), observed,
-                                 T if align is not None else None, bool(skip), index)
+                                 T, bool(skip), index)
         g_pts = g_pts[seen]
         n_obs = int(g_pts.shape[0])                                               # a host read
         if n_obs == 0:
@@ -140,8 +129,8 @@ def compare_meshes(pred, gt, n_samples=200_000, threshold=0.05, seed=0, skip=Tru
         out += [d.sum() / m, 0.5 * (s[(m - 1) // 2] + s[m // 2]), (d <= threshold).sum().to(torch.float64) / m]
     acc, acc_med, prec, comp, comp_med, rec = torch.stack(out).tolist()          # the one host read of the figures
     out = dict(accuracy=acc, accuracy_median=acc_med, completion=comp, completion_median=comp_med, precision=prec,
-               recall=rec, fscore=2.0 * prec * rec / (prec + rec) if prec + rec > 0.0 else 0.0,
-               chamfer=0.5 * (acc + comp), n_samples=n, threshold=threshold, pred_area=p_area, gt_area=g_area)
+               recall=rec, **_fscore_chamfer(prec, rec, acc, comp), n_samples=n, threshold=threshold, pred_area=p_area,
+               gt_area=g_area)
     if alignment is not None:
         out["alignment"] = alignment
     if observed is not None:

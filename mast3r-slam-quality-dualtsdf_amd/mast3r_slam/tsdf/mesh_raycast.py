@@ -11,7 +11,7 @@ import mslam_hip as _m
 
 from ._mesh_args import _mesh_arg, _pair, _points_arg
 from .global_volume import _render_args
-from .mesh_index import _index_arg
+from .mesh_index import MeshIndex, _index_arg
 
 
 class _Caster:
@@ -19,7 +19,7 @@ class _Caster:
     a MeshIndex of the mesh) the tiles and group boxes are the index's."""
 
     def __init__(self, vertices, faces, validate, skip, what, index=None):
-        self.index = _index_arg(index, vertices, faces, what)
+        self.index = _index_arg(MeshIndex, index, what, vertices, faces)
         self.v, self.f, self.V, self.F = _mesh_arg(vertices, faces, validate, what)
         self.device = self.v.device
         L = _m.lib()
