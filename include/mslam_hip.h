@@ -719,6 +719,37 @@ int mslam_cloud_voxel_reduce(const float* points, const uint8_t* colors, int num
                              const int64_t* perm, const int64_t* starts, int num_voxels, float* centroid,
                              int32_t* count, int32_t* first, uint8_t* color, void* stream);
 
+/* Point clouds: the k nearest neighbours and normals (no counterpart in the reference, DESIGN.md "Point clouds"; the
+ * definition is tests/cloud_knn_numpy.py; csrc/cloud_knn.hip).
+ *   mslam_cloud_knn      dist2 f64[n,k], neighbors i32[n,k], 1 <= k <= MSLAM_CLOUD_KNN_MAX_K: row i holds the k smallest
+ *                        valid points of the cloud under the total order (dist2, original index), ascending, dist2 the
+ *                        sum of mslam_cloud_distance.  exclude (i32[n], may be NULL): the point with index exclude[i] is
+ *                        left out of row i - by index, so a duplicate of it elsewhere stays, at distance 0; an entry
+ *                        outside [0, N) excludes nothing.  Slots beyond the points that qualify hold (+inf, -1), and so
+ *                        does the row of a query with a non-finite coordinate.  order, index, index_bytes, levels and
+ *                        skip_counts as mslam_cloud_distance: the same bits in the three forms, and k = 1 without
+ *                        exclude is mslam_cloud_distance's output.  `order` names no point twice.
+ *   mslam_cloud_normals  one normal per point from row i of neighbors i32[N,k] (the k-NN of the cloud in itself without
+ *                        exclude; entries outside [0, N) are no neighbours), all in f64: count i32[N] = m, the entries
+ *                        that are neighbours (0 for an invalid point); the centroid (the sum in list order / m) and the
+ *                        covariance (the six sums of products of the differences from it, in list order, each / m);
+ *                        its eigenvectors by cyclic Jacobi; normals f32[N,3] the unit eigenvector of the smallest
+ *                        eigenvalue, turned towards the viewpoint (viewpoints f32[3] with viewpoint_stride 0, f32[N,3]
+ *                        with 3; exactly perpendicular: not turned) or, with viewpoints NULL, so that its component of
+ *                        largest magnitude is positive; curvature f32[N] = max(l_min, 0) / (l0 + l1 + l2).  m < 3 or
+ *                        a middle eigenvalue <= 2^-40 of the largest: normal (0, 0, 0) and curvature NaN.  moments
+ *                        (may be NULL, for tests): f64[N, MSLAM_CLOUD_NORMALS_MOMENTS] - the centroid, the covariance
+ *                        xx xy xz yy yz zz, the three eigenvalues in the order of their columns, and the oriented
+ *                        normal before its rounding to f32. */
+#define MSLAM_CLOUD_KNN_MAX_K 32
+#define MSLAM_CLOUD_NORMALS_MOMENTS 15
+int mslam_cloud_knn(const float* queries, int n, const float* points, int num_points, int k, const int32_t* exclude,
+                    const int32_t* order, const void* index, size_t index_bytes, int levels, int32_t* skip_counts,
+                    double* dist2, int32_t* neighbors, void* stream);
+int mslam_cloud_normals(const float* points, int num_points, const int32_t* neighbors, int k, const float* viewpoints,
+                        int viewpoint_stride, float* normals, float* curvature, int32_t* count, double* moments,
+                        void* stream);
+
 /* Mesh textures: keyframe images baked into a per-face atlas, and the shading of a ray cast (no counterpart in the
  * reference, DESIGN.md "Mesh textures"; the definition is tests/texture_numpy.py).  The atlas is a pure function of
  * (F, texels = R >= 4): face f is half f & 1 of cell f >> 1, a cell is R + 1 texels wide and R high, the cells lie

@@ -103,6 +103,30 @@ def save_ply(filename, points, colors):
     _write_ply(filename, pcd)
 
 
+def save_cloud(filename, points, colors=None, normals=None):
+    """A point cloud (SlamSystem.keyframe_cloud's tensors, or numpy arrays) as binary little-endian PLY: x, y, z float
+    [, nx, ny, nz float][, red, green, blue uchar] per vertex, the layout load_ply_points reads."""
+    host = lambda a, dtype: np.ascontiguousarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a, dtype)
+    points = host(points, np.float32).reshape(-1, 3)
+    fields = [("x", "f4"), ("y", "f4"), ("z", "f4")]
+    if normals is not None:
+        normals = host(normals, np.float32).reshape(-1, 3)
+        fields += [("nx", "f4"), ("ny", "f4"), ("nz", "f4")]
+    if colors is not None:
+        colors = host(colors, np.uint8).reshape(-1, 3)
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    for name, a in (("normals", normals), ("colors", colors)):
+        if a is not None and len(a) != len(points):
+            raise ValueError(f"save_cloud: {name} must be ({len(points)},3), got {a.shape}")
+    pcd = np.empty(len(points), dtype=fields)
+    pcd["x"], pcd["y"], pcd["z"] = points.T
+    if normals is not None:
+        pcd["nx"], pcd["ny"], pcd["nz"] = normals.T
+    if colors is not None:
+        pcd["red"], pcd["green"], pcd["blue"] = colors.T
+    _write_ply(filename, pcd)
+
+
 def save_mesh(filename, vertices, faces, normals=None, colors=None):
     """Triangle mesh as binary little-endian PLY: `element vertex` (x, y, z [, nx, ny, nz] float [, red, green, blue]
     uchar = rint(255 c) of `colors` in [0, 1]) and `element face` (`property list uchar int vertex_indices`).  Arrays may

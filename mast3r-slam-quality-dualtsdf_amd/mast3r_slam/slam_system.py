@@ -449,19 +449,22 @@ class SlamSystem:
         return compare_meshes(mesh, (gt_vertices, gt_faces), n_samples=n_samples, threshold=threshold,
                               _validate_pred=False, **kw)
 
-    def keyframe_cloud(self, conf_threshold=None, voxel=None, colors=True):
+    def keyframe_cloud(self, conf_threshold=None, voxel=None, colors=True, outliers=None, normals=None):
         """The map as a point cloud at this point of the run, on the device: what evaluate.save_reconstruction gathers -
         for every keyframe the world points T_WC.act(X_canon) (with calibration: X_canon constrained to the pixel rays
         first) of the pixels whose average confidence is > `conf_threshold` (default tracking.C_conf of the config), in
         keyframe order -> (points f32[N,3], colors u8[N,3] or None).  `voxel`: the cloud is then thinned by
         tsdf.downsample_cloud on that grid (centroids and mean colours, in key order).  `colors=False`: no colours.
-        Drains the backend first, so the poses are the ones it has solved."""
+        Drains the backend first, so the poses are the ones it has solved.  `outliers`: a dict of keyword arguments for
+        tsdf.cloud_outliers, applied after `voxel`; the points it drops leave the cloud.  `normals`: k - a third return
+        value, tsdf.cloud_normals(points, k) turned towards the camera centre of the keyframe each point came from
+        (after thinning: the keyframe of the cell's lowest-index member).  With both None the pair is what it was."""
         from mast3r_slam.geometry import constrain_points_to_ray
 
         self.drain()
         if conf_threshold is None:
             conf_threshold = float(config["tracking"]["C_conf"])
-        pts, cols = [], []
+        pts, cols, source = [], [], []
         for i in range(len(self.keyframes)):
             kf = self.keyframes[i]
             X = kf.X_canon
@@ -470,26 +473,50 @@ class SlamSystem:
             pW = kf.T_WC.act(X).reshape(-1, 3).to(device=self.device, dtype=torch.float32)
             keep = kf.get_average_conf().to(device=self.device, dtype=torch.float32).reshape(-1) > conf_threshold
             pts.append(pW[keep])
+            if normals is not None:
+                source.append((i, kf.T_WC.data.reshape(8)[:3].to(device=self.device, dtype=torch.float32)))
             if colors:
                 cols.append((kf.uimg * 255).to(torch.uint8).reshape(-1, 3).to(self.device)[keep])
         points = torch.cat(pts).contiguous() if pts else torch.zeros((0, 3), dtype=torch.float32, device=self.device)
         color = (torch.cat(cols).contiguous() if cols else torch.zeros((0, 3), dtype=torch.uint8,
                                                                         device=self.device)) if colors else None
-        if voxel is not None:
-            from mast3r_slam.tsdf import downsample_cloud
+        if outliers is None and normals is None:
+            if voxel is not None:
+                from mast3r_slam.tsdf import downsample_cloud
 
-            points, color, _ = downsample_cloud(points, voxel, color)
-        return points, color
+                points, color, _ = downsample_cloud(points, voxel, color)
+            return points, color
+        from mast3r_slam.tsdf import cloud_normals, downsample_cloud, filter_cloud
+
+        # the keyframe of every point, carried through the thinning and the filter
+        kf_of = (torch.cat([torch.full((int(p.shape[0]),), i, dtype=torch.int64, device=self.device)
+                            for p, (i, _) in zip(pts, source)]) if source else
+                 torch.zeros(0, dtype=torch.int64, device=self.device))
+        if voxel is not None:
+            points, color, _, first = downsample_cloud(points, voxel, color, return_first=True)
+            if normals is not None:
+                kf_of = kf_of[first.long()]
+        if outliers is not None:
+            points, color, kept = filter_cloud(points, color, **dict(outliers))
+            if normals is not None:
+                kf_of = kf_of[kept]
+        if normals is None:
+            return points, color
+        centres = (torch.stack([c for _, c in source]) if source else
+                   torch.zeros((0, 3), dtype=torch.float32, device=self.device))
+        viewpoint = centres[kf_of].contiguous() if int(points.shape[0]) else None
+        return points, color, cloud_normals(points, normals, viewpoint=viewpoint)[0]
 
     def evaluate_cloud(self, gt_points, threshold=None, voxel=None, align=None, init=None, gt_positions=None,
-                       align_kw=None, index=None, conf_threshold=None):
+                       align_kw=None, index=None, conf_threshold=None, outliers=None, normals=None):
         """Quality of the map's point cloud (self.keyframe_cloud(conf_threshold)) against a ground-truth cloud gt_points
         f32[N,3] (a numpy array or a device tensor; a laser scan needs no faces): the dict of tsdf.compare_clouds
         (DESIGN.md "Point clouds").  `threshold` and `voxel` default to the global TSDF's voxel size (the config's when
         the global TSDF is off): both clouds are thinned on the map's own grid and a point counts as right within one
         cell; voxel=0 scores the raw clouds.  `align`, `init` ("trajectory" with `gt_positions` for
         self.align_trajectory), `align_kw` and `index` (None or True) as in evaluate_mesh, with tsdf.align_clouds in the
-        place of align_meshes."""
+        place of align_meshes.  `outliers`: a dict for tsdf.cloud_outliers, applied to the map's raw cloud first
+        (keyframe_cloud); `normals`: k, for compare_clouds' normal-consistency figures."""
         from mast3r_slam.tsdf import compare_clouds
 
         vs = float(self.tsdf_manager.volume.voxel_size if self.tsdf_manager is not None
@@ -497,10 +524,12 @@ class SlamSystem:
         threshold = vs if threshold is None else float(threshold)
         voxel = vs if voxel is None else float(voxel)
         kw = self._alignment_kw("SlamSystem.evaluate_cloud", align, init, gt_positions, align_kw)
-        points, _ = self.keyframe_cloud(conf_threshold, colors=False)
+        points, _ = self.keyframe_cloud(conf_threshold, colors=False, outliers=outliers)
         gt = torch.as_tensor(gt_points, dtype=torch.float32).to(points.device).reshape(-1, 3).contiguous()
         if index is not None and index is not False:
             kw["index"] = index
+        if normals is not None:
+            kw["normals"] = normals
         return compare_clouds(points, gt, threshold=threshold, voxel=voxel if voxel > 0.0 else None, **kw)
 
     def evaluate_depth(self, gt_vertices, gt_faces, align=None, near=0.05, far=10.0, index=None):

@@ -10,8 +10,8 @@ from .mesh_raycast import observed_points, render_mesh  # noqa: F401
 from .mesh_index import MeshIndex, build_mesh_index  # noqa: F401
 from .mesh_texture import (MeshTexture, atlas_classes, atlas_layout, bake_texture, render_mesh_color,  # noqa: F401
                            sized_layout)
-from .cloud import (CloudIndex, align_clouds, cloud_distance, compare_clouds, downsample_cloud,  # noqa: F401
-                    transform_cloud)
+from .cloud import (CloudIndex, align_clouds, cloud_distance, cloud_knn, cloud_normals, cloud_outliers,  # noqa: F401
+                    compare_clouds, downsample_cloud, filter_cloud, transform_cloud)
 from .image_metrics import image_metrics  # noqa: F401
 from .tsdf_optimizer import TSDFPoseOptimizer  # noqa: F401
 from .global_manager import TSDFGlobalIntegrator, TSDFGlobalManager  # noqa: F401

@@ -1,13 +1,16 @@
 """Point clouds on the device: a spatial index, the exact nearest neighbour of points in a cloud, the voxel downsample,
 trimmed point-to-point ICP and the accuracy / completion / precision / recall / F-score / Chamfer figures between two
 clouds - what scores the product's own output (evaluate.save_reconstruction's cloud) against a scan without faces.
+Below them the k nearest neighbours under a total order, and what stands on them: normals, the statistical and the
+radius outlier rule, the normal-consistency figures of compare_clouds.
 
-No counterpart in the reference.  The kernels are csrc/cloud.hip (DESIGN.md "Point clouds"); the numpy statement of the
-same definitions is tests/cloud_numpy.py.  A cloud is points f32[N,3]; a point is valid when its three coordinates are
+No counterpart in the reference.  The kernels are csrc/cloud.hip and csrc/cloud_knn.hip (DESIGN.md "Point clouds"); the
+numpy statements of the same definitions are tests/cloud_numpy.py and tests/cloud_knn_numpy.py.  A cloud is points f32[N,3]; a point is valid when its three coordinates are
 finite.  An invalid point is never anyone's nearest neighbour, is never fused into a voxel and enters no figure.
 """
 import math
 
+import numpy as np
 import torch
 
 import mslam_hip as _m
@@ -238,11 +241,12 @@ def align_clouds(pred, gt, init=None, n_samples=20000, max_iters=50, trim=math.i
                 history=hist)
 
 
-def _direction(queries, points, index, threshold, max_dist):
+def _direction(queries, points, index, threshold, max_dist, scan=None):
     """The figures of one direction as 0-d f64 device tensors: mean, median, rmse over the valid queries within
-    max_dist, the share of the valid queries within threshold, the valid queries beyond max_dist, the valid queries."""
+    max_dist, the share of the valid queries within threshold, the valid queries beyond max_dist, the valid queries.
+    `scan`: the (dist2, nearest) of _distance2 for these arguments, when the caller holds it."""
     dev = queries.device
-    dist2 = _distance2(queries, points, index)[0]
+    dist2 = (_distance2(queries, points, index) if scan is None else scan)[0]
     d = torch.sqrt(dist2)
     ok = _valid(queries)
     kept = ok & (d <= max_dist)
@@ -262,7 +266,8 @@ def _direction(queries, points, index, threshold, max_dist):
     return [mean, median, rmse, within, (ok & ~(d <= max_dist)).sum().to(torch.float64), n_ok]
 
 
-def compare_clouds(pred, gt, threshold=0.05, voxel=None, max_dist=None, align=None, align_kw=None, index=None):
+def compare_clouds(pred, gt, threshold=0.05, voxel=None, max_dist=None, align=None, align_kw=None, index=None,
+                   normals=None):
     """Quality of the cloud `pred` against the ground-truth cloud `gt` (f32[N,3] device tensors, one frame): the figure
     set of compare_meshes, from the points themselves.  Returns Python numbers: accuracy / accuracy_median /
     accuracy_rmse (every valid pred point to its nearest gt point: mean, median, root mean square), completion /
@@ -282,8 +287,15 @@ def compare_clouds(pred, gt, threshold=0.05, voxel=None, max_dist=None, align=No
 
     `index`: None - plain scans, every pair is measured; True - a CloudIndex of each cloud is built; a CloudIndex of
     `gt` (without `voxel`, which makes a new tensor) - that one and a new one of pred.  The dict is the same, value for
-    value."""
+    value.
+
+    `normals`: None, or k - cloud_normals(., k) of both clouds after thinning and alignment, and the dict gains
+    normal_consistency_accuracy / normal_consistency_completion (the mean of |n_query . n_nearest| over a direction's
+    pairs within `max_dist` whose two normals are non-zero; NaN without one), normal_consistency (their mean) and
+    n_normal_pairs (the pairs of both directions)."""
     what = "compare_clouds"
+    if normals is not None:
+        normals = _k_arg(normals, what, "normals")
     threshold = float(threshold)
     limit = math.inf if max_dist is None else float(max_dist)
     if not limit >= 0.0:
@@ -303,9 +315,20 @@ def compare_clouds(pred, gt, threshold=0.05, voxel=None, max_dist=None, align=No
     if T is not None:
         pred = transform_cloud(pred, T)
     p_index = CloudIndex(pred) if g_index is not None else None
-    figures = _direction(pred, gt, g_index, threshold, limit) + _direction(gt, pred, p_index, threshold, limit)
+    if normals is None:
+        figures = _direction(pred, gt, g_index, threshold, limit) + _direction(gt, pred, p_index, threshold, limit)
+        consistency = []
+    else:
+        # the normals' own k-NN is always indexed: the same bits as the plain scan, and not quadratic
+        n_pred_, n_gt_ = (cloud_normals(c, normals, index=ix if ix is not None else True)[0]
+                          for c, ix in ((pred, p_index), (gt, g_index)))
+        acc_scan, comp_scan = _distance2(pred, gt, g_index), _distance2(gt, pred, p_index)
+        figures = (_direction(pred, gt, g_index, threshold, limit, acc_scan)
+                   + _direction(gt, pred, p_index, threshold, limit, comp_scan))
+        consistency = (_normal_consistency(acc_scan, n_pred_, n_gt_, limit)
+                       + _normal_consistency(comp_scan, n_gt_, n_pred_, limit))
     (acc, acc_med, acc_rms, prec, acc_out, n_pred, comp, comp_med, comp_rms, rec, comp_out,
-     n_gt) = torch.stack(figures).tolist()                                    # the one host read of the figures
+     n_gt, *consistency) = torch.stack(figures + consistency).tolist()       # the one host read of the figures
     if n_pred == 0 or n_gt == 0:
         raise ValueError(f"{what}: a cloud has no valid point ({int(n_pred)} in pred, {int(n_gt)} in gt)")
     out = dict(accuracy=acc, accuracy_median=acc_med, accuracy_rmse=acc_rms, completion=comp,
@@ -315,4 +338,191 @@ def compare_clouds(pred, gt, threshold=0.05, voxel=None, max_dist=None, align=No
                completion_outliers=int(comp_out))
     if alignment is not None:
         out["alignment"] = alignment
+    if normals is not None:
+        nc_acc, pairs_acc, nc_comp, pairs_comp = consistency
+        out.update(normal_consistency_accuracy=nc_acc, normal_consistency_completion=nc_comp,
+                   normal_consistency=0.5 * (nc_acc + nc_comp), n_normal_pairs=int(pairs_acc + pairs_comp))
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# k nearest neighbours, normals, outliers (csrc/cloud_knn.hip; the statement is tests/cloud_knn_numpy.py)
+# ----------------------------------------------------------------------------------------------------------------------
+MAX_K = _m.header_constants()["MSLAM_CLOUD_KNN_MAX_K"]
+
+
+def _k_arg(k, what, name="k"):
+    if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= MAX_K:
+        raise ValueError(f"{what}: {name} must be an integer in [1, {MAX_K}], got {k!r}")
+    return int(k)
+
+
+def _knn2(queries, points, k, index=None, sort_queries=True, exclude=None, levels=2):
+    """(dist2 f64[n,k], neighbors i32[n,k]) of the checked arguments; `exclude`: None or i32[n] on the device."""
+    n, N, dev = int(queries.shape[0]), int(points.shape[0]), queries.device
+    order, ws, ws_bytes, levels = (0, 0, 0, 1) if index is None else (_m.ptr(index.order), _m.ptr(index.ws),
+                                                                      index.ws_bytes, levels)
+    dist2 = torch.empty((n, k), dtype=torch.float64, device=dev)
+    neighbors = torch.empty((n, k), dtype=torch.int32, device=dev)
+    perm = index.query_order(queries) if index is not None and sort_queries and n > 1 else None
+    q = queries if perm is None else queries[perm].contiguous()
+    ex = exclude if perm is None or exclude is None else exclude[perm].contiguous()
+    _m.check(_m.lib().mslam_cloud_knn(_m.ptr(q), n, _m.ptr(points), N, k, _m.ptr(ex), order, ws, ws_bytes, levels, 0,
+                                      _m.ptr(dist2), _m.ptr(neighbors), _m.stream_ptr()), "cloud_knn")
+    if perm is None:
+        return dist2, neighbors
+    return torch.empty_like(dist2).index_copy_(0, perm, dist2), torch.empty_like(neighbors).index_copy_(0, perm, neighbors)
+
+
+def _self(points):
+    return torch.arange(int(points.shape[0]), dtype=torch.int32, device=points.device)
+
+
+def cloud_knn(queries, points, k, index=None, sort_queries=True, exclude=None):
+    """The k nearest neighbours, 1 <= k <= 32, of the queries f32[n,3] in the cloud `points` f32[N,3] -> (distance
+    f64[n,k], neighbors i32[n,k]) device tensors.  Row i holds the k smallest valid points under the total order
+    (squared distance, index), ascending - the squared distance is cloud_distance's f64 sum - so a tie goes to the
+    lower index; slots beyond the points that qualify hold +inf and -1, and so does the row of a query with a non-finite
+    coordinate.  `exclude`: None; i32[n], the point with index exclude[i] is left out of row i (an entry outside [0, N)
+    excludes nothing); "self" - `queries` is `points` and every point is left out of its own row.  Exclusion is by
+    index: a duplicate of the query at another index stays a neighbour, at distance 0.  `index`, `sort_queries`: as in
+    cloud_distance; the same bits in every form, and k = 1 without `exclude` is cloud_distance (DESIGN.md "Point
+    clouds")."""
+    what = "cloud_knn"
+    k = _k_arg(k, what)
+    same = queries is points or (torch.is_tensor(queries) and torch.is_tensor(points)
+                                 and queries.shape == points.shape and queries.data_ptr() == points.data_ptr())
+    queries = _points_arg(queries, "queries", what)
+    index = _index_arg(CloudIndex, index, what, points)
+    points = _points_arg(points, "points", what)
+    if queries.device != points.device:
+        raise ValueError(f"{what}: queries and points are on different devices")
+    if isinstance(exclude, str):
+        if exclude != "self" or not same:
+            raise ValueError(f"{what}: exclude='self' needs queries to be the points tensor itself")
+        exclude = _self(points)
+    elif exclude is not None:
+        if not torch.is_tensor(exclude) or tuple(exclude.shape) != (int(queries.shape[0]),):
+            raise ValueError(f"{what}: exclude must be None, 'self' or an i32[{int(queries.shape[0])}] device tensor")
+        _m.require_dtype(exclude, torch.int32, "exclude")
+        _m.ptr(exclude)
+        if exclude.device != points.device:
+            raise ValueError(f"{what}: exclude and points are on different devices")
+        exclude = exclude.contiguous()
+    dist2, neighbors = _knn2(queries, points, k, index, sort_queries, exclude)
+    return torch.sqrt(dist2), neighbors
+
+
+def _normals(points, neighbors, k, viewpoint, what):
+    """mslam_cloud_normals of the checked points and their neighbour rows -> (normals, curvature, count)."""
+    N, dev = int(points.shape[0]), points.device
+    vp, stride = None, 0
+    if viewpoint is not None:
+        vp = viewpoint if torch.is_tensor(viewpoint) else torch.as_tensor(np.asarray(viewpoint, np.float32))
+        vp = vp.detach().to(device=dev, dtype=torch.float32).contiguous()
+        if tuple(vp.shape) == (N, 3) and N != 1:
+            stride = 3
+        elif vp.numel() == 3:
+            vp = vp.reshape(3)
+        else:
+            raise ValueError(f"{what}: viewpoint must be 3 numbers or ({N},3), got {tuple(vp.shape)}")
+    normals = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    curvature = torch.empty(N, dtype=torch.float32, device=dev)
+    count = torch.empty(N, dtype=torch.int32, device=dev)
+    _m.check(_m.lib().mslam_cloud_normals(_m.ptr(points), N, _m.ptr(neighbors), k, _m.ptr(vp), stride, _m.ptr(normals),
+                                          _m.ptr(curvature), _m.ptr(count), 0, _m.stream_ptr()), "cloud_normals")
+    return normals, curvature, count
+
+
+def cloud_normals(points, k=16, viewpoint=None, index=True):
+    """A normal per point of the cloud `points` f32[N,3] from its k nearest neighbours in the cloud, itself included
+    (cloud_knn without exclusion) -> (normals f32[N,3], curvature f32[N], count i32[N]) device tensors.  The normal is
+    the unit eigenvector of the smallest eigenvalue of the neighbourhood's covariance (f64, cyclic Jacobi), the
+    curvature the surface variation l_min / (l0 + l1 + l2), the count the neighbours found.  Fewer than 3 neighbours,
+    coincident or collinear ones (the middle eigenvalue <= 2^-40 of the largest) and an invalid point: the normal is
+    (0, 0, 0) and the curvature NaN.  `viewpoint`: 3 numbers, or f32[N,3] with one per point - the normal is turned
+    towards it (not when exactly perpendicular); None - turned so that its largest component is positive.  `index`:
+    None, True or a CloudIndex of the tensor; the same bits (DESIGN.md "Point clouds")."""
+    what = "cloud_normals"
+    k = _k_arg(k, what)
+    index = _index_arg(CloudIndex, index, what, points)
+    points = _points_arg(points, "points", what)
+    neighbors = _knn2(points, points, k, index)[1]
+    return _normals(points, neighbors, k, viewpoint, what)
+
+
+def cloud_outliers(points, k=16, std_ratio=2.0, radius=None, min_neighbors=None, index=True):
+    """Which points of the cloud `points` f32[N,3] to keep -> (keep bool[N] device tensor, dict).
+
+    The statistical rule (Open3D's and PCL's; `std_ratio` None: off): mean_i is the mean distance from point i to its k
+    nearest neighbours other than itself (cloud_knn with exclude="self"; the sum in list order over the m_i found,
+    divided by m_i; a valid point with m_i >= 1), mu and sigma the mean and the SAMPLE standard deviation (divisor
+    M - 1; 0 when M < 2) of the mean_i over those M points, in f64 on the device; a point is kept when mean_i <= mu +
+    std_ratio * sigma.  The radius rule (`radius` and `min_neighbors` <= 32 together): a point is kept when its
+    min_neighbors-th neighbour lies within `radius` (squared distance <= radius^2 in f64).  With both, both must hold;
+    an invalid point is never kept.  The dict: mu, sigma, threshold (NaN without the statistical rule), kept, n_valid -
+    one host read - and mean_distance f64[N] (a device tensor; NaN where undefined; None without the rule)."""
+    what = "cloud_outliers"
+    if (radius is None) != (min_neighbors is None):
+        raise ValueError(f"{what}: radius and min_neighbors go together")
+    if std_ratio is None and radius is None:
+        raise ValueError(f"{what}: no rule: give std_ratio, or radius and min_neighbors")
+    if std_ratio is not None and not float(std_ratio) >= 0.0:
+        raise ValueError(f"{what}: std_ratio must be >= 0, got {std_ratio}")
+    if radius is not None and not float(radius) >= 0.0:
+        raise ValueError(f"{what}: radius must be >= 0, got {radius}")
+    index = _index_arg(CloudIndex, index, what, points)
+    points = _points_arg(points, "points", what)
+    N, dev = int(points.shape[0]), points.device
+    ok = _valid(points)
+    keep = ok.clone()
+    nan = torch.full((), math.nan, dtype=torch.float64, device=dev)
+    mu = sigma = thr = nan
+    mean = None
+    if std_ratio is not None:
+        k = _k_arg(k, what)
+        dist2, nb = _knn2(points, points, k, index, exclude=_self(points))
+        d, has = torch.sqrt(dist2), nb >= 0
+        total = torch.zeros(N, dtype=torch.float64, device=dev)
+        for j in range(k):                                                   # the sum in list order
+            total = total + torch.where(has[:, j], d[:, j], torch.zeros_like(total))
+        m = has.sum(1)
+        scored = ok & (m >= 1)
+        mean = torch.where(scored, total / m.to(torch.float64), nan)
+        M = scored.sum().to(torch.float64)
+        zero = torch.zeros_like(total)
+        mu = torch.where(scored, mean, zero).sum() / M
+        dev2 = torch.where(scored, (mean - mu) * (mean - mu), zero).sum()
+        sigma = torch.where(M >= 2.0, torch.sqrt(dev2 / (M - 1.0)), torch.zeros_like(mu))
+        thr = mu + float(std_ratio) * sigma
+        keep &= scored & (mean <= thr)
+    if radius is not None:
+        mn = _k_arg(min_neighbors, what, "min_neighbors")
+        r2 = _knn2(points, points, mn, index, exclude=_self(points))[0][:, mn - 1]
+        keep &= r2 <= float(radius) * float(radius)
+    mu_, sigma_, thr_, kept, n_valid = torch.stack(
+        [mu, sigma, thr, keep.sum().to(torch.float64), ok.sum().to(torch.float64)]).tolist()      # the host read
+    return keep, dict(mu=mu_, sigma=sigma_, threshold=thr_, kept=int(kept), n_valid=int(n_valid), mean_distance=mean)
+
+
+def filter_cloud(points, colors=None, **outlier_kw):
+    """The cloud without the points cloud_outliers(points, **outlier_kw) drops, in the original order -> (points
+    f32[M,3], colors u8[M,3] or None, kept_indices i64[M])."""
+    keep = cloud_outliers(points, **outlier_kw)[0]
+    if colors is not None:
+        colors = _colors_arg(colors, int(points.shape[0]), "filter_cloud")
+    idx = torch.nonzero(keep).reshape(-1)
+    return points[idx].contiguous(), None if colors is None else colors[idx].contiguous(), idx
+
+
+def _normal_consistency(scan, n_query, n_points, max_dist):
+    """[mean of |n_query . n_nearest| over the pairs within max_dist whose two normals are non-zero (NaN without one),
+    the pairs] as 0-d f64 device tensors, from the (dist2, nearest) of one direction."""
+    dist2, nearest = scan
+    j = nearest.clamp_min(0).long()
+    a, b = n_query.to(torch.float64), n_points.to(torch.float64)[j] if int(n_points.shape[0]) else torch.zeros_like(
+        n_query, dtype=torch.float64)
+    pair = (nearest >= 0) & (torch.sqrt(dist2) <= max_dist) & (a != 0.0).any(1) & (b != 0.0).any(1)
+    dot = torch.abs((a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2])
+    pairs = pair.sum().to(torch.float64)
+    return [torch.where(pair, dot, torch.zeros_like(dot)).sum() / pairs, pairs]
