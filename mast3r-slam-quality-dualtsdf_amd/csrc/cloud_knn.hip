@@ -15,22 +15,24 @@
 // under the total order; kn_offer is then one fully unrolled compare-and-shift pass, every index a constant, so nothing
 // is indexed at run time and nothing goes to scratch (the resource table is in DESIGN.md).
 //
-// WHY CULLING STAYS EXACT.  The invariant of mesh_tri.h, read with the k-th best in the place of the best.  A point of
-// a tile lies in the tile's box exactly, so its dist2 is at least the box's lb2 up to the roundings of the two sums.  A
-// tile (or a group of 32) is skipped only when every lane with a query has
+// WHY CULLING STAYS EXACT.  The invariant of mesh_tri.h, read with the k-th best in the place of the best: md_walk
+// compares a box with the policy's bound(), and KnList's is the list's last entry.  A point of a tile lies in the
+// tile's box exactly, so its dist2 is at least the box's lb2 up to the roundings of the two sums.  A tile (or a group
+// of 32) is skipped only when every lane with a query has
 //     lb2 > kth (1 + 2^-20) + 2^-27 S^2 ,
 // kth = +inf while the lane's list is not full.  Every point of a skipped tile is then strictly beyond the lane's
 // current k-th best, which only shrinks: the point is neither in the final list nor tied with its last entry.
 //
 // THE HOME TILE.  The set of the k smallest under a total order, and their order, do not depend on the order of the
 // visit.  So with an index the block first scans its home tile - the tile whose box is nearest to the block's first
-// query, found as in md_scan - as an ordinary tile, which fills the lists with near points, and the walk passes over
-// that tile when it reaches it: every point is still offered at most once.  Which tile it is changes no output bit.
-// There is no separate upper bound: the list's last entry is the bound.
+// query, md_home_tile - as an ordinary tile, which fills the lists with near points, and hands it to the walk as
+// `done`: the walk passes over that tile when it reaches it, so every point is still offered at most once.  Which tile
+// it is changes no output bit.  There is no separate upper bound: the list's last entry is the bound.
 //
-// The walk is md_scan's: one query per thread, 256 per block, tiles of 128 points staged through LDS as f64 by
-// md_stage<MdPoint, .>, one __syncthreads_and per tile that is also the barrier before the next staging; a lane without
-// a query idles through the barriers and never keeps a tile in.  MdPoint::load tags every valid slot with 1 + its
+// THE WALK is md_walk<MdPoint, kIndexed> of mesh_tri.h, md_scan's walk over a policy object: one query per thread,
+// 256 per block, tiles of 128 points staged through LDS as f64 by md_stage<MdPoint, .>, one __syncthreads_and per tile
+// that is also the barrier before the next staging; a lane without a query idles through the barriers and never keeps
+// a tile in.  The policy object is KnList below.  MdPoint::load tags every valid slot with 1 + its
 // original index, so the plain scan (order NULL: the tiles of the input order, nothing culled) applies the same total
 // order and there is one kernel body.  An `order` entry outside [0, N) is skipped (md_slot); a point that `order` does
 // not name is not seen, and `order` is taken to name no point twice.
@@ -62,19 +64,20 @@ __device__ __forceinline__ void kn_offer(double (&ld)[kCap], int (&li)[kCap], do
   if (below_this) ld[0] = c, li[0] = ci;
 }
 
-// The staged tile's `cnt` slots offered to this lane's list; `ex`: the original index left out (-1: none)
+// What a lane keeps (the policy md_walk of mesh_tri.h asks for): the sorted list, and `ex`, the original index left out
+// (-1: none).  kn_kernel builds the list in place, scans with it and stores from it.
 template <int kCap>
-__device__ __forceinline__ void kn_scan_tile(const double* s_pts, int cnt, double px, double py, double pz, int ex,
-                                             double (&ld)[kCap], int (&li)[kCap]) {
-  for (int s = 0; s < cnt; s++) {
-    const double* t = s_pts + s * MdPoint::kDoubles;      // one address for the whole wave: an LDS broadcast
-    if (t[3] != 0.0) {
-      const double d = MdPoint::dist2(px, py, pz, t);
-      const int f = (int)t[3] - 1;
-      if (f != ex && kn_less(d, f, ld[kCap - 1], li[kCap - 1])) kn_offer<kCap>(ld, li, d, f);
-    }
+struct KnList {
+  int ex;
+  double ld[kCap];
+  int li[kCap];
+  __device__ __forceinline__ double bound() const { return ld[kCap - 1]; }
+  template <bool kIndexed>
+  __device__ __forceinline__ void offer(double d, double tag, int) {
+    const int f = (int)tag - 1;
+    if (f != ex && kn_less(d, f, ld[kCap - 1], li[kCap - 1])) kn_offer<kCap>(ld, li, d, f);
   }
-}
+};
 
 template <int kCap, bool kIndexed>
 __global__ __launch_bounds__(kMdBlock) void kn_kernel(const float* __restrict__ queries, int n,
@@ -86,101 +89,47 @@ __global__ __launch_bounds__(kMdBlock) void kn_kernel(const float* __restrict__ 
                                                       int32_t* __restrict__ neighbors) {
   __shared__ double s_pts[kMdTile * MdPoint::kDoubles];
   __shared__ int s_home;
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  const int tid = threadIdx.x;
   const size_t i0 = (size_t)blockIdx.x * kMdBlock, i = i0 + tid;
   const bool in_range = i < (size_t)n;
   float qx = 0.0f, qy = 0.0f, qz = 0.0f;
   if (in_range) qx = queries[3 * i], qy = queries[3 * i + 1], qz = queries[3 * i + 2];
   const bool has = in_range && cd_finite(qx, qy, qz);
   const double px = (double)qx, py = (double)qy, pz = (double)qz;
-  const int ex = in_range && exclude ? exclude[i] : -1;
   const MdPoint::Src src = {points, num_points};
   const int ntiles = (num_points + kMdTile - 1) / kMdTile;
 
-  double ld[kCap];
-  int li[kCap];
+  // a lane without a query keeps (-inf, -1) throughout: nothing beats it, so the lane never inserts
+  KnList<kCap> list;
+  list.ex = in_range && exclude ? exclude[i] : -1;
 #pragma unroll
-  for (int s = 0; s < kCap; s++) ld[s] = s >= kCap - k ? INFINITY : -INFINITY, li[s] = -1;
-  int n_skipped = 0, home = -1;
+  for (int s = 0; s < kCap; s++) list.ld[s] = has && s >= kCap - k ? INFINITY : -INFINITY, list.li[s] = -1;
+  int home = -1;
 
   if (kIndexed && __syncthreads_or(has)) {
-    if (wave == 0) {
-      const double q0x = (double)queries[3 * i0], q0y = (double)queries[3 * i0 + 1], q0z = (double)queries[3 * i0 + 2];
-      double m = INFINITY, s2;
-      int mt = -1;
-      for (int t = lane; t < ntiles; t += kWave) {
-        const double lb2 = md_box_lb2(q0x, q0y, q0z, box + 6 * (size_t)t, &s2);
-        if (lb2 < m) m = lb2, mt = t;
-      }
-      for (int off = 32; off > 0; off >>= 1) {
-        const double om = __shfl_down(m, off, kWave);
-        const int ot = __shfl_down(mt, off, kWave);
-        if (ot >= 0 && (mt < 0 || om < m || (om == m && ot < mt))) m = om, mt = ot;
-      }
-      if (lane == 0) s_home = mt;
-    }
-    __syncthreads();
-    home = s_home;
+    home = md_home_tile((double)queries[3 * i0], (double)queries[3 * i0 + 1], (double)queries[3 * i0 + 2], box,
+                        ntiles, &s_home);
     if (home >= 0) {
-      const int cnt = min(kMdTile, num_points - home * kMdTile);
+      const int cnt = min(kMdTile, num_points - home * kMdTile);          // before the staging branch, as in md_scan
       if (tid < kMdTile) md_stage<MdPoint, kIndexed>(src, order, home, tid, s_pts);
       __syncthreads();
-      if (has) kn_scan_tile<kCap>(s_pts, cnt, px, py, pz, ex, ld, li);
+      md_offer_tile<MdPoint, kIndexed>(s_pts, home, cnt, px, py, pz, list);
     }
   }
-
-  // without an index: one "group" of all tiles, and the loops below are the plain tile loop
-  const int ngroups = kIndexed ? (ntiles + kMdGroup - 1) / kMdGroup : 1;
-  for (int g = 0; g < ngroups; g++) {
-    const int t0 = kIndexed ? g * kMdGroup : 0, t1 = kIndexed ? min(ntiles, t0 + kMdGroup) : ntiles;
-    if (kIndexed && gbox) {
-      bool lane_skips = !has;
-      if (has) {
-        double s2;
-        const double lb2 = md_box_lb2(px, py, pz, gbox + 6 * (size_t)g, &s2);
-        lane_skips = lb2 > ld[kCap - 1] * (1.0 + 0x1p-20) + 0x1p-27 * s2;
-      }
-      // also the barrier between the last tile's reads and the next staging
-      if (__syncthreads_and(lane_skips)) {
-        n_skipped += t1 - t0 - (home >= t0 && home < t1 ? 1 : 0);
-        continue;
-      }
-    }
-    for (int tile = t0; tile < t1; tile++) {
-      if (tile == home) continue;                    // scanned first, above; the same for the whole block
-      bool lane_skips = !has;
-      if (kIndexed && has) {
-        double s2;
-        const double lb2 = md_box_lb2(px, py, pz, box + 6 * (size_t)tile, &s2);
-        lane_skips = lb2 > ld[kCap - 1] * (1.0 + 0x1p-20) + 0x1p-27 * s2;
-      }
-      const bool wave_skips = kIndexed && __all(lane_skips);
-      // also the barrier between the last tile's reads and this tile's staging
-      if (__syncthreads_and(kIndexed && lane_skips)) {
-        n_skipped++;
-        continue;
-      }
-      if (tid < kMdTile) md_stage<MdPoint, kIndexed>(src, order, tile, tid, s_pts);
-      __syncthreads();
-      if (wave_skips) {
-        n_skipped++;
-        continue;
-      }
-      if (has) kn_scan_tile<kCap>(s_pts, min(kMdTile, num_points - tile * kMdTile), px, py, pz, ex, ld, li);
-    }
-  }
+  const int n_skipped =
+      md_walk<MdPoint, kIndexed>(px, py, pz, has, src, kIndexed, box, gbox, order, s_pts, ntiles, home, list);
 
   if (in_range) {
 #pragma unroll
     for (int s = 0; s < kCap; s++) {
       const int slot = s - (kCap - k);
       if (slot >= 0) {
-        dist2[i * (size_t)k + slot] = has ? ld[s] : INFINITY;
-        neighbors[i * (size_t)k + slot] = has ? li[s] : -1;
+        dist2[i * (size_t)k + slot] = has ? list.ld[s] : INFINITY;
+        neighbors[i * (size_t)k + slot] = has ? list.li[s] : -1;
       }
     }
   }
-  if (skipped && lane == 0) skipped[4 * (size_t)blockIdx.x + wave] = n_skipped;
+  if (skipped && (tid & (kWave - 1)) == 0) skipped[4 * (size_t)blockIdx.x + tid / kWave] = n_skipped;
 }
 
 // One rotation of the cyclic Jacobi sweep on the pair (P, Q): ma_jacobi4's, with constant indices
@@ -308,15 +257,6 @@ __global__ __launch_bounds__(256) void kn_normals_kernel(const float* __restrict
   count[i] = m;
 }
 
-template <int kCap>
-static void kn_launch(bool indexed, unsigned blocks, hipStream_t stream, const float* queries, int n,
-                      const float* points, int num_points, int k, const int32_t* exclude, const int32_t* order,
-                      const double* box, const double* gbox, int32_t* skipped, double* dist2, int32_t* neighbors) {
-  const auto kernel = indexed ? kn_kernel<kCap, true> : kn_kernel<kCap, false>;
-  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kMdBlock), 0, stream, queries, n, points, num_points, k, exclude, order,
-                     box, gbox, skipped, dist2, neighbors);
-}
-
 }  // namespace mslam
 
 using namespace mslam;
@@ -338,17 +278,13 @@ extern "C" int mslam_cloud_knn(const float* queries, int n, const float* points,
   }
   const double* box = indexed ? (const double*)index : nullptr;
   const double* gbox = indexed && levels == 2 ? md_index_gbox(index, num_points) : nullptr;
-  const unsigned blocks = blocks_for(n, kMdBlock);
-  const hipStream_t st = (hipStream_t)stream;
-  if (k <= 8)
-    kn_launch<8>(indexed, blocks, st, queries, n, points, num_points, k, exclude, order, box, gbox, skip_counts, dist2,
-                 neighbors);
-  else if (k <= 16)
-    kn_launch<16>(indexed, blocks, st, queries, n, points, num_points, k, exclude, order, box, gbox, skip_counts, dist2,
-                  neighbors);
-  else
-    kn_launch<32>(indexed, blocks, st, queries, n, points, num_points, k, exclude, order, box, gbox, skip_counts, dist2,
-                  neighbors);
+  // the smallest capacity that holds k, plain or indexed
+  static const decltype(&kn_kernel<8, false>) kernels[3][2] = {{kn_kernel<8, false>, kn_kernel<8, true>},
+                                                                 {kn_kernel<16, false>, kn_kernel<16, true>},
+                                                                 {kn_kernel<32, false>, kn_kernel<32, true>}};
+  const auto kernel = kernels[k <= 8 ? 0 : k <= 16 ? 1 : 2][indexed];
+  hipLaunchKernelGGL(kernel, dim3(blocks_for(n, kMdBlock)), dim3(kMdBlock), 0, (hipStream_t)stream, queries, n, points,
+                     num_points, k, exclude, order, box, gbox, skip_counts, dist2, neighbors);
   MSLAM_LAUNCH_CHECK("cloud_knn");
   return MSLAM_OK;
 }

@@ -1,10 +1,11 @@
 // Triangle helpers shared by the mesh-quality kernels (mesh_distance.hip) and the mesh-alignment kernels
 // (mesh_align.hip): the validity rule, the closest point of a triangle by Voronoi regions, the per-tile boxes, the
-// distance from a point to a box, and md_scan, the one culled nearest-element scan that md_distance_kernel and
-// ma_step_kernel call over triangles (MdTri) and cd_distance_kernel of cloud.hip over points (MdPoint), with the index
-// builder md_build_index beside it.  Semantics in DESIGN.md "Mesh quality"; tests/meshdist_numpy.py states the same
-// definitions, operation by operation, in numpy.  Everything is f64 on the f32 inputs and the build has
-// -ffp-contract=off, so a * b + c below is two roundings, as in numpy.
+// distance from a point to a box, the home-tile search md_home_tile, md_scan, the one culled nearest-element scan that
+// md_distance_kernel and ma_step_kernel call over triangles (MdTri) and cd_distance_kernel of cloud.hip over points
+// (MdPoint), md_walk, the same block-wide walk over groups and tiles keeping what a policy object says (kn_kernel of
+// cloud_knn.hip: the k best), and the index builder md_build_index.  Semantics in DESIGN.md "Mesh quality";
+// tests/meshdist_numpy.py states the same definitions, operation by operation, in numpy.  Everything is f64 on the f32
+// inputs and the build has -ffp-contract=off, so a * b + c below is two roundings, as in numpy.
 //
 // THE INVARIANT that makes culling exact.  md_dist2(p, f) is |p - q|^2 for a computed point q of face f: a vertex
 // itself, a + v (b - a) with a computed 0 <= v <= 1 (both ends of an edge region's division are ordered, and rounding
@@ -248,6 +249,107 @@ __device__ __forceinline__ void md_stage(const typename Prim::Src src, const int
   if (Prim::load(src, f, t) && kIndexed) t[Prim::kDoubles - 1] = (double)f + 1.0;
 }
 
+// The home tile of a block: the tile whose box is nearest to q0, the lowest on ties, -1 without a tile or with every
+// box at +inf (an infinite coordinate; a NaN one is at distance 0 along its axis).  Wave 0 searches, every thread of
+// the block calls and gets the same answer.  s_home: one LDS word.
+__device__ __forceinline__ int md_home_tile(double q0x, double q0y, double q0z, const double* __restrict__ box,
+                                            int ntiles, int* s_home) {
+  const int lane = threadIdx.x & (kWave - 1);
+  if (threadIdx.x / kWave == 0) {
+    double m = INFINITY, s2;
+    int mt = -1;
+    for (int t = lane; t < ntiles; t += kWave) {
+      const double lb2 = md_box_lb2(q0x, q0y, q0z, box + 6 * (size_t)t, &s2);
+      if (lb2 < m) m = lb2, mt = t;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+      const double om = __shfl_down(m, off, kWave);
+      const int ot = __shfl_down(mt, off, kWave);
+      if (ot >= 0 && (mt < 0 || om < m || (om == m && ot < mt))) m = om, mt = ot;
+    }
+    if (lane == 0) *s_home = mt;
+  }
+  __syncthreads();
+  return *s_home;
+}
+
+// WHAT A LANE KEEPS of the elements it meets is a policy object Acc, a local of the calling kernel: KnList of
+// cloud_knn.hip, the k best.  bound() is the value the skip test compares a box with: an element strictly beyond it
+// changes nothing the lane keeps.  offer<kIndexed>(d, tag, slot) takes an element at squared distance d from a valid
+// slot: `tag` is the slot's last word, 1 + the original index when tagged (md_stage), `slot` its place in the tiles.
+// A plain struct with inline members: no callables, nothing captured.  md_scan below is the same walk over one best
+// {best, ub, best_f}, written out: as a policy of md_walk it was measured and held for two of its three kernels
+// (DESIGN.md "Where the walk lives").
+
+// The `cnt` slots of the staged tile `tile` offered to this lane's acc
+template <class Prim, bool kIndexed, class Acc>
+__device__ __forceinline__ void md_offer_tile(const double* s_tri, int tile, int cnt, double px, double py, double pz,
+                                              Acc& acc) {
+  for (int k = 0; k < cnt; k++) {
+    const double* t = s_tri + k * Prim::kDoubles;           // one address for the whole wave: an LDS broadcast
+    if (t[Prim::kDoubles - 1] != 0.0)
+      acc.template offer<kIndexed>(Prim::dist2(px, py, pz, t), t[Prim::kDoubles - 1], tile * kMdTile + k);
+  }
+}
+
+// THE WALK over groups and tiles, block-wide: the group vote, the tile vote, the staging, and the one
+// __syncthreads_and at each vote that is also the barrier before the next staging.  Every thread of the block calls
+// it, also one without a point (`has` false): it reaches the same barriers and never keeps a tile in.  `cull` 0 votes
+// nothing away.  ntiles: the tiles of src.  `done`: a tile the caller has offered to acc already, passed over here and
+// counted neither as scanned nor as skipped, also when its group is voted away (-1: none; with the constant the test
+// and the subtraction fold away).  Returns the tiles this lane's wave did not scan.  s_tri: kMdTile * Prim::kDoubles
+// doubles of LDS.  Both vote sites are inlined into the calling kernel's own body (DESIGN.md "Where the walk lives").
+template <class Prim, bool kIndexed, class Acc>
+__device__ __forceinline__ int md_walk(double px, double py, double pz, bool has, const typename Prim::Src src,
+                                       int cull, const double* __restrict__ box, const double* __restrict__ gbox,
+                                       const int32_t* __restrict__ order, double* s_tri, int ntiles, int done,
+                                       Acc& acc) {
+  const int tid = threadIdx.x;
+  const int nf = Prim::count(src);
+  int n_skipped = 0;
+  // without an index: one "group" of all tiles, and the loops below are the plain tile loop
+  const int ngroups = kIndexed ? (ntiles + kMdGroup - 1) / kMdGroup : 1;
+  for (int g = 0; g < ngroups; g++) {
+    const int t0 = kIndexed ? g * kMdGroup : 0, t1 = kIndexed ? min(ntiles, t0 + kMdGroup) : ntiles;
+    if (kIndexed && cull && gbox) {
+      bool lane_skips = !has;
+      if (has) {
+        double s2;
+        const double lb2 = md_box_lb2(px, py, pz, gbox + 6 * (size_t)g, &s2);
+        lane_skips = lb2 > acc.bound() * (1.0 + 0x1p-20) + 0x1p-27 * s2;
+      }
+      // also the barrier between the last tile's reads and the next staging
+      if (__syncthreads_and(lane_skips)) {
+        n_skipped += t1 - t0 - (done >= t0 && done < t1 ? 1 : 0);
+        continue;
+      }
+    }
+    for (int tile = t0; tile < t1; tile++) {
+      if (tile == done) continue;                    // the same for the whole block
+      bool lane_skips = !has;
+      if (cull && has) {
+        double s2;
+        const double lb2 = md_box_lb2(px, py, pz, box + 6 * (size_t)tile, &s2);
+        lane_skips = lb2 > acc.bound() * (1.0 + 0x1p-20) + 0x1p-27 * s2;
+      }
+      const bool wave_skips = cull && __all(lane_skips);
+      // also the barrier between the last tile's reads and this tile's staging
+      if (__syncthreads_and(cull && lane_skips)) {
+        n_skipped++;
+        continue;
+      }
+      if (tid < kMdTile) md_stage<Prim, kIndexed>(src, order, tile, tid, s_tri);
+      __syncthreads();
+      if (wave_skips) {
+        n_skipped++;
+        continue;
+      }
+      md_offer_tile<Prim, kIndexed>(s_tri, tile, min(kMdTile, nf - tile * kMdTile), px, py, pz, acc);
+    }
+  }
+  return n_skipped;
+}
+
 // The nearest valid element (face of the mesh, point of the cloud) to this lane's point p.  Every thread of the block
 // calls it, also one without a point (`has` false): it reaches the same barriers and never keeps a tile in.
 // `cull` 0 is the plain ascending scan.  With `cull` the two parameters that may differ per lane, neither of which
@@ -266,29 +368,12 @@ __device__ __forceinline__ MdNearest md_scan(double px, double py, double pz, bo
                                              const double* __restrict__ box, double* s_tri, int* s_home, double ub,
                                              bool need_home, const int32_t* __restrict__ order = nullptr,
                                              const double* __restrict__ gbox = nullptr) {
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
+  const int tid = threadIdx.x;
   const int nf = Prim::count(src);
   const int ntiles = (nf + kMdTile - 1) / kMdTile;
-  double best = INFINITY;
-  int best_f = -1, n_skipped = 0;
 
   if (cull && __syncthreads_or(has && need_home)) {
-    if (wave == 0) {
-      double m = INFINITY, s2;
-      int mt = -1;
-      for (int t = lane; t < ntiles; t += kWave) {
-        const double lb2 = md_box_lb2(q0x, q0y, q0z, box + 6 * (size_t)t, &s2);
-        if (lb2 < m) m = lb2, mt = t;
-      }
-      for (int off = 32; off > 0; off >>= 1) {
-        const double om = __shfl_down(m, off, kWave);
-        const int ot = __shfl_down(mt, off, kWave);
-        if (ot >= 0 && (mt < 0 || om < m || (om == m && ot < mt))) m = om, mt = ot;
-      }
-      if (lane == 0) *s_home = mt;
-    }
-    __syncthreads();
-    const int home = *s_home;
+    const int home = md_home_tile(q0x, q0y, q0z, box, ntiles, s_home);
     if (home >= 0) {
       // before the staging branch, not inside `if (need_home)`: formed there, home * kMdTile is merged with the
       // staging's copy of it at the join of a divergent branch, and the loop below runs on vector counters (DESIGN.md
@@ -306,7 +391,10 @@ __device__ __forceinline__ MdNearest md_scan(double px, double py, double pz, bo
     }
   }
 
-  // without an index: one "group" of all tiles, and the loops below are the plain tile loop
+  // md_walk's loops with one best in the place of the policy object (why they are written out: DESIGN.md "Where the
+  // walk lives").  Without an index: one "group" of all tiles, and the loops below are the plain tile loop
+  double best = INFINITY;
+  int best_f = -1, n_skipped = 0;
   const int ngroups = kIndexed ? (ntiles + kMdGroup - 1) / kMdGroup : 1;
   for (int g = 0; g < ngroups; g++) {
     const int t0 = kIndexed ? g * kMdGroup : 0, t1 = kIndexed ? min(ntiles, t0 + kMdGroup) : ntiles;

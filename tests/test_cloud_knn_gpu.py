@@ -321,6 +321,48 @@ def test_culling(device):
                   f"{got[2][:waves].sum() / (waves * ntiles):.3f} (queries in input order)")
 
 
+@pytest.mark.parametrize("layout", ["first query (nan, 0, 0)", "home tile in the last group"])
+def test_home_tile_of_a_query_without_a_point(device, layout):
+    """33 tiles in two groups: 32 x 128 points in a 1 m box at the low corner (tiles 0..31, group 0) and 128 points in
+    a second box 10 m away (tile 32, group 1); one block of 64 queries whose first has a NaN, so the home tile is the
+    one nearest to a point that no lane searches for; k = 8, tiles and groups.  The walk passes over the home tile, and
+    a group that is voted away counts its tiles less the home tile when that lies in it: waves 1..3, which hold no
+    query and so skip whatever they meet, count every tile but the home tile, 32, whichever group the vote removes.
+      first query (nan, 0, 0)       the issue's layout: the other 63 queries lie in the far box.  The home tile lies in
+        group 0, which is met first, with nothing but the home tile's own points in the lists: its box is no farther
+        than they are, so the group is never voted away, and wave 0 counts only tiles of group 0 that all its lanes
+        skip one by one.  It reports 0, the count of the kernel when it had its own copy of the walk (31 was expected
+        there; DESIGN.md "Point clouds" has why no layout with the home tile in the first group can give it).
+      home tile in the last group   the far box lies at (10, 10, 10), the first query is (nan, 10.5, 10.5), whose y
+        and z pick tile 32, and the other 63 lie in the near box.  After group 0 every list is full within 3 m^2, group
+        1 is voted away, and it counts 1 - 1 = 0 tiles: wave 0 reports only tiles of group 0, at most 31.
+    In both layouts the counts with tiles alone, where no group is voted away, are the same."""
+    rng = np.random.default_rng(11)
+    issue = layout.startswith("first")
+    shift = np.array([10.0, 0.0, 0.0] if issue else [10.0, 10.0, 10.0])
+    near, far = rng.uniform(0, 1, (32 * T, 3)), rng.uniform(0, 1, (T, 3)) + shift
+    P = np.concatenate([far, near]).astype(np.float32)                     # the input order says nothing
+    Q = (rng.uniform(0.1, 0.9, (64, 3)) + (shift if issue else 0.0)).astype(np.float32)
+    Q[0] = (np.nan, 0.0, 0.0) if issue else (np.nan, 10.5, 10.5)
+    ix = _build(device, P)
+    assert len(ix["tile"]) == 33 and len(ix["group"]) == 2 and (ix["order"][:32 * T] >= T).all()
+    want = K.knn(Q, P, 8)
+    assert np.isposinf(want[0][0]).all() and (want[1][0] == -1).all()
+    assert ((want[1][1:] < T) == issue).all()                               # neighbours in the queries' own box
+    plain = _knn(device, ix, Q, 8, "plain")
+    _same(plain, want)
+    got = _knn(device, ix, Q, 8, 2)
+    _same(got, want)
+    assert got[0].tobytes() == plain[0].tobytes() and got[1].tobytes() == plain[1].tobytes()
+    print(f"{layout}: skip counts {got[2].tolist()}")
+    assert got[2].shape == (4,) and (got[2][1:] == 32).all(), got[2]
+    tiles = _knn(device, ix, Q, 8, 1)                                      # no group vote, the home tile passed over
+    _same(tiles, want)
+    assert np.array_equal(got[2], tiles[2]) and got[2][0] <= 31, (got[2], tiles[2])
+    if issue:
+        assert got[2][0] == 0, got[2]
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # normals
 # ----------------------------------------------------------------------------------------------------------------------
