@@ -428,10 +428,12 @@ int mslam_mesh_decimate_finish(const int32_t* faces, int num_faces, int num_vert
  *   mslam_mesh_holes_double   one round of pointer doubling from state_in to state_out (never the same buffer):
  *                             (p, m) -> (p of p, min(m, m of p)); a dart whose p is -1 keeps its m.  After r rounds with
  *                             2^r >= B, p >= 0 exactly on the cycles of next, and m is the cycle's smallest vertex.
- *   mslam_mesh_holes_labels   keys i32[B+1]: m for a dart on a cycle, INT32_MAX for any other, INT32_MAX in slot B.  The
- *                             caller sorts them; the runs below the last give loop_id i32[L], ascending, and length.
- *   mslam_mesh_holes_assign   dart_loop i32[B]: the position of the dart's m in loop_id, -1 off the cycles; start i32[L]:
- *                             the dart of each loop whose tail is the loop id (the caller presets -1).
+ *   mslam_mesh_holes_loop_labels  with flag NULL: keys i32[B+1]: m for a dart on a cycle, INT32_MAX for any other,
+ *                             INT32_MAX in slot B.  The caller sorts them; the runs below the last give loop_id i32[L],
+ *                             ascending, and length.
+ *   mslam_mesh_holes_loop_assign  with own = the linked state, loop_name = loop_id, and flag, loop_id and loop_head
+ *                             NULL: dart_loop i32[B]: the position of the dart's m in loop_id, -1 off the cycles;
+ *                             start i32[L]: the dart of each loop whose tail is the loop id (the caller presets -1).
  *   mslam_mesh_holes_measure  one lane per loop, walking from start along next: perimeter f64[L] (NaN when not walked),
  *                             centre f64[L,3] (the f64 mean of the tails) and fillable u8[L]: 3 <= n <= max_edges and
  *                             every dart's fan face (head, tail, centre) turns the way of the dart's own face.  A loop
@@ -448,9 +450,11 @@ int mslam_mesh_holes_link(const int32_t* tail, const int32_t* head, const int32_
                           const int64_t* tail_order, const int32_t* sorted_head, int num_darts, int num_vertices,
                           int32_t* state, void* stream);
 int mslam_mesh_holes_double(const int32_t* state_in, int32_t* state_out, int num_darts, void* stream);
-int mslam_mesh_holes_labels(const int32_t* state, int num_darts, int32_t* keys, void* stream);
-int mslam_mesh_holes_assign(const int32_t* state, const int32_t* tail, int num_darts, const int32_t* loop_id,
-                            int num_loops, int32_t* dart_loop, int32_t* start, void* stream);
+int mslam_mesh_holes_loop_labels(const int32_t* labelled, const uint8_t* flag, int num_darts, int32_t* keys,
+                                 void* stream);
+int mslam_mesh_holes_loop_assign(const int32_t* labelled, const int32_t* own, const uint8_t* flag, const int32_t* tail,
+                                 const int32_t* head, int num_darts, const int32_t* loop_name, int num_loops,
+                                 int32_t* dart_loop, int32_t* start, int32_t* loop_id, int32_t* loop_head, void* stream);
 int mslam_mesh_holes_measure(const float* vertices, const int32_t* faces, int num_faces, int num_vertices,
                              const int32_t* dart, const int32_t* tail, const int32_t* head, const int32_t* state,
                              int num_darts, const int32_t* start, const int32_t* length, int num_loops, int max_edges,
@@ -463,8 +467,9 @@ int mslam_mesh_holes_emit(const float* vertices, const float* colors, const int3
 
 /* Mesh holes, bow-tie mode (DESIGN.md "Mesh holes", tests/bowtie_numpy.py): boundary darts are paired across the hole
  * they bound, so that the rims of holes that meet in a vertex close.  Runs between mslam_mesh_holes_darts and
- * mslam_mesh_holes_measure in place of link .. assign; measure and emit read the paired state.  state, labelled, rank and
- * paired are i32[B,2], 8-byte aligned.  One lane per element, no atomics, every index read from memory is checked.
+ * mslam_mesh_holes_measure in place of link and double, and ahead of loop_labels and loop_assign (declared above, here
+ * with their flag); measure and emit read the paired state.  state, labelled, rank and paired are i32[B,2], 8-byte
+ * aligned.  One lane per element, no atomics, every index read from memory is checked.
  *   mslam_mesh_holes_dkeys        keys i64[3 F]: slot 3 f + c holds tail V + head of that directed edge of a counting
  *                                 face, INT64_MAX in the three slots of any other face.  The caller sorts them, stable,
  *                                 with the permutation (sorted_keys, key_order), gathers dart_key i64[B] = keys[dart] and
@@ -478,8 +483,9 @@ int mslam_mesh_holes_emit(const float* vertices, const float* colors, const int3
  *                                 fan, m the walk's smallest name.
  *   mslam_mesh_holes_rank_init    rank[d] = (fan[d], 1) on a closed walk, (-1, 1) when fan[d] is the walk's first dart
  *                                 (the one whose name is the label), (-1, 0) off the walks.
- *   mslam_mesh_holes_rank_double  one round of (p, c) -> (p of p, c + c of p), never in place: after r rounds with
- *                                 2^r >= B, c is the number of steps to the walk's first dart, n for that dart itself.
+ *   mslam_mesh_holes_rank_double  one round of (p, c) -> (p of p, c + c of p), never in place (mslam_mesh_holes_double
+ *                                 with a sum, saturating at B + 1, for the minimum): after r rounds with 2^r >= B, c is
+ *                                 the number of steps to the walk's first dart, n for that dart itself.
  *   mslam_mesh_holes_walk_keys    keys i64[B]: label B + (B - c), INT64_MAX off the walks.  Sorted by the caller with
  *                                 the permutation (walk_order): by walk, then by rank.
  *   mslam_mesh_holes_pair_keys    keys i64[B], slot j for the dart walk_order[j]: head B + label, INT64_MAX off the
@@ -491,10 +497,12 @@ int mslam_mesh_holes_emit(const float* vertices, const float* colors, const int3
  *   mslam_mesh_holes_tail_keys    keys i64[B]: label V + tail on a cycle of next, INT64_MAX elsewhere.  The caller sorts.
  *   mslam_mesh_holes_tail_flag    flag u8[B], zeroed by the caller: flag[label] = 1 when a sorted key equals the one
  *                                 before it: that cycle has a vertex as a tail twice and stays open.
- *   mslam_mesh_holes_loop_labels  mslam_mesh_holes_labels without the flagged cycles: the runs give loop_name i32[L],
- *                                 the smallest dart name of every loop, ascending, and the lengths.
- *   mslam_mesh_holes_loop_assign  dart_loop i32[B] as mslam_mesh_holes_assign; start, loop_id, loop_head i32[L]: the
- *                                 dart whose name is the loop's, its tail and its head. */
+ *   mslam_mesh_holes_loop_labels  with the flag: a dart whose m is outside [0, B) or flagged gets INT32_MAX too (only
+ *                                 a flag makes m an index; without one it is not held against B).  The runs give
+ *                                 loop_name i32[L], the smallest dart name of every loop, ascending, and the lengths.
+ *   mslam_mesh_holes_loop_assign  with own = paired and the flag: dart_loop i32[B] as above; start, loop_id, loop_head
+ *                                 i32[L]: the dart whose name (own[d] second entry) is the loop's, its tail and its
+ *                                 head.  loop_id and loop_head may each be NULL; tail and head are read only for them. */
 int mslam_mesh_holes_dkeys(const int32_t* faces, int num_faces, int num_vertices, int64_t* keys, void* stream);
 int mslam_mesh_holes_fan(const int32_t* faces, int num_faces, int num_vertices, const int32_t* dart,
                          const int32_t* head, int num_darts, const int64_t* sorted_keys, const int64_t* key_order,
@@ -514,12 +522,6 @@ int mslam_mesh_holes_tail_keys(const int32_t* labelled, const int32_t* tail, int
                                int64_t* keys, void* stream);
 int mslam_mesh_holes_tail_flag(const int64_t* sorted_keys, int num_darts, int num_vertices, uint8_t* flag,
                                void* stream);
-int mslam_mesh_holes_loop_labels(const int32_t* labelled, const uint8_t* flag, int num_darts, int32_t* keys,
-                                 void* stream);
-int mslam_mesh_holes_loop_assign(const int32_t* labelled, const int32_t* paired, const uint8_t* flag,
-                                 const int32_t* tail, const int32_t* head, int num_darts, const int32_t* loop_name,
-                                 int num_loops, int32_t* dart_loop, int32_t* start, int32_t* loop_id,
-                                 int32_t* loop_head, void* stream);
 
 /* Mesh quality: face areas, a surface sampler and the exact point-to-mesh distance (no counterpart in the reference,
  * DESIGN.md "Mesh quality").  vertices f32[V,3], faces i32[F,3]; every index is checked against [0, V) before use.  A

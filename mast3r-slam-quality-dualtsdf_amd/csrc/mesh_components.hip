@@ -25,7 +25,7 @@
 // stay connected through parent entries of indices below v (by induction over the index), so v keeps its connection to
 // everything parent[v] has ever held.  When the hook kernel has ended, no pair is pending, the parent links alone span
 // each component, every tree's root is its smallest index, and flatten reads it.
-#include "common.h"
+#include "mesh_topo.h"
 
 namespace mslam {
 
@@ -57,10 +57,6 @@ __device__ __forceinline__ void cc_unite(int32_t* parent, int a, int b) {
   }
 }
 
-__device__ __forceinline__ bool cc_in_range(int a, int b, int c, int nv) {
-  return (unsigned)a < (unsigned)nv && (unsigned)b < (unsigned)nv && (unsigned)c < (unsigned)nv;
-}
-
 __global__ __launch_bounds__(256) void cc_init_kernel(int nv, int32_t* __restrict__ root) {
   const int v = blockIdx.x * 256 + threadIdx.x;
   if (v < nv) root[v] = v;
@@ -71,7 +67,7 @@ __global__ __launch_bounds__(256) void cc_hook_kernel(const int32_t* __restrict_
   const int f = blockIdx.x * 256 + threadIdx.x;
   if (f >= nf) return;
   const int a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
-  if (!cc_in_range(a, b, c, nv)) return;     // the caller validates; never index outside the array
+  if (!tp_in_range(a, b, c, nv)) return;     // the caller validates; never index outside the array
   cc_unite(parent, a, b);
   cc_unite(parent, a, c);
 }
@@ -170,7 +166,7 @@ __global__ __launch_bounds__(256) void cc_emit_kernel(const float* __restrict__ 
   if (i < nf && keep_face[i]) {
     const int64_t o = fbase[i];
     const int a = faces[3 * (size_t)i], b = faces[3 * (size_t)i + 1], c = faces[3 * (size_t)i + 2];
-    if (o >= 0 && o < nf_out && cc_in_range(a, b, c, nv)) {
+    if (o >= 0 && o < nf_out && tp_in_range(a, b, c, nv)) {
       out_faces[3 * o] = (int32_t)vbase[a];       // a kept face's vertices are kept: they share its root
       out_faces[3 * o + 1] = (int32_t)vbase[b];
       out_faces[3 * o + 2] = (int32_t)vbase[c];

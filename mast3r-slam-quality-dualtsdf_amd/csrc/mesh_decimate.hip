@@ -21,16 +21,11 @@
 // is skipped.
 #include <math.h>
 
-#include "common.h"
+#include "mesh_topo.h"
 
 namespace mslam {
 
 constexpr int kDmState = MSLAM_MESH_DECIMATE_STATE;       // doubles per vertex: 10 quadric entries, then the area
-
-__device__ __forceinline__ bool dm_counts(int a, int b, int c, int nv) {
-  return (unsigned)a < (unsigned)nv && (unsigned)b < (unsigned)nv && (unsigned)c < (unsigned)nv && a != b && b != c &&
-         a != c;
-}
 
 // the finaliser of MurmurHash3 over u and the round: tests/decimate_numpy.py hash32
 __device__ __forceinline__ uint32_t dm_hash32(uint32_t u, uint32_t round) {
@@ -43,17 +38,12 @@ __device__ __forceinline__ uint32_t dm_hash32(uint32_t u, uint32_t round) {
   return x;
 }
 
-__device__ __forceinline__ void dm_pos(const float* __restrict__ vert, int v, double (&p)[3]) {
-  p[0] = (double)vert[3 * (size_t)v], p[1] = (double)vert[3 * (size_t)v + 1], p[2] = (double)vert[3 * (size_t)v + 2];
-}
-
 // (b - a) x (c - a)
 __device__ __forceinline__ void dm_cross(const double (&a)[3], const double (&b)[3], const double (&c)[3],
                                          double (&n)[3]) {
-  const double e1[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, e2[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
-  n[0] = e1[1] * e2[2] - e1[2] * e2[1];
-  n[1] = e1[2] * e2[0] - e1[0] * e2[2];
-  n[2] = e1[0] * e2[1] - e1[1] * e2[0];
+  double e1[3], e2[3];
+  tp_sub(b, a, e1), tp_sub(c, a, e2);
+  tp_cross(e1, e2, n);
 }
 
 __global__ __launch_bounds__(256) void dm_state_kernel(const float* __restrict__ vert,
@@ -70,11 +60,11 @@ __global__ __launch_bounds__(256) void dm_state_kernel(const float* __restrict__
     const int64_t f = pairs[j] - v * nf;
     if ((uint64_t)f >= (uint64_t)nf) continue;
     const int ia = faces[3 * f], ib = faces[3 * f + 1], ic = faces[3 * f + 2];
-    if (!dm_counts(ia, ib, ic, nv)) continue;
+    if (!tp_counts(ia, ib, ic, nv)) continue;
     double a[3], b[3], c[3], n[3];
-    dm_pos(vert, ia, a), dm_pos(vert, ib, b), dm_pos(vert, ic, c);
+    tp_point(vert, ia, a), tp_point(vert, ib, b), tp_point(vert, ic, c);
     dm_cross(a, b, c, n);
-    const double ln = sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+    const double ln = sqrt(tp_dot(n, n));
     if (!(ln > 0.0 && ln < (double)INFINITY)) continue;
     const double kx = n[0] / ln, ky = n[1] / ln, kz = n[2] / ln, area = 0.5 * ln;
     const double g[4] = {kx, ky, kz, -((kx * a[0] + ky * a[1]) + kz * a[2])};
@@ -124,7 +114,7 @@ __global__ __launch_bounds__(256) void dm_candidates_kernel(
       double q[kDmState], h[3];
 #pragma unroll
       for (int k = 0; k < kDmState; k++) q[k] = su[k] + state[kDmState * (int64_t)v + k];
-      dm_pos(vert, v, h);
+      tp_point(vert, v, h);
       const double x = h[0], y = h[1], z = h[2];
       const double r0 = ((q[0] * x + q[1] * y) + q[2] * z) + q[3];
       const double r1 = ((q[1] * x + q[4] * y) + q[5] * z) + q[6];
@@ -157,18 +147,18 @@ __global__ __launch_bounds__(256) void dm_candidates_kernel(
         const int64_t f = pairs[i] - u * nf;
         if ((uint64_t)f >= (uint64_t)nf) continue;
         const int t[3] = {faces[3 * f], faces[3 * f + 1], faces[3 * f + 2]};
-        if (!dm_counts(t[0], t[1], t[2], nv)) continue;
+        if (!tp_counts(t[0], t[1], t[2], nv)) continue;
         if (t[0] == v || t[1] == v || t[2] == v) continue;
         double p[3][3], w[3][3], o[3], n[3];
 #pragma unroll
         for (int d = 0; d < 3; d++) {
-          dm_pos(vert, t[d], p[d]);
+          tp_point(vert, t[d], p[d]);
 #pragma unroll
           for (int e = 0; e < 3; e++) w[d][e] = t[d] == (int)u ? h[e] : p[d][e];
         }
         dm_cross(p[0], p[1], p[2], o);
         dm_cross(w[0], w[1], w[2], n);
-        ok = (n[0] * o[0] + n[1] * o[1]) + n[2] * o[2] > 0.0;
+        ok = tp_dot(n, o) > 0.0;
       }
       if (!ok) continue;
       bestc = cv, bestv = v;
@@ -227,7 +217,7 @@ __global__ __launch_bounds__(256) void dm_finish_kernel(const int32_t* __restric
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < nf) {
     const int a = faces[3 * (size_t)i], b = faces[3 * (size_t)i + 1], c = faces[3 * (size_t)i + 2];
-    const bool ok = dm_counts(a, b, c, nv);
+    const bool ok = tp_counts(a, b, c, nv);
     keep_face[i] = ok ? 1 : 0;
     if (ok) referenced[a] = 1, referenced[b] = 1, referenced[c] = 1;      // every writer writes the same value
   }

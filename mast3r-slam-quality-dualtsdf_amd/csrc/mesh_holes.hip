@@ -16,11 +16,11 @@
 //            (ptr[ptr[d]], min(lab[d], lab[ptr[d]])), and stays when ptr[d] is none.  After r rounds ptr is the 2^r-th
 //            successor, or none if the chain ends before it, and lab the smallest tail on the way: with 2^r >= B a dart
 //            whose ptr is not none lies on a cycle and lab is the loop id.
-//   labels   one thread per boundary dart: the sort key lab, or INT32_MAX for an open dart, and one more INT32_MAX.
+//   loop_labels  one thread per boundary dart: the sort key lab, or INT32_MAX for an open dart, and one more INT32_MAX.
 //   (caller)   sorts them; unique_consecutive with counts gives the loop ids, ascending, and their lengths (one host read);
 //            the last run, less one, counts the open darts.
-//   assign   one thread per boundary dart: the number of its loop (binary search of lab in the loop ids) or -1, and the
-//            loop's first dart: the one whose tail is the loop id.
+//   loop_assign  one thread per boundary dart: the number of its loop (binary search of lab in the loop ids) or -1, and
+//            the loop's first dart: the one whose own label (here its tail) is the loop id.
 //   measure  one thread per loop: walks it from its first dart and writes the perimeter, the centre and whether the loop
 //            is fillable.  Loops longer than max_edges are walked only when all perimeters are asked for.
 //   (caller)   exclusive scans of the fillable flags and lengths give the bases (one host read: the new sizes).
@@ -29,24 +29,19 @@
 // its array before it is followed; a walk that meets a bad one stops and its loop is not fillable.
 #include <math.h>
 
-#include "common.h"
+#include "mesh_topo.h"
 
 namespace mslam {
 
 constexpr int64_t kMhNoKey = INT64_MAX;
 constexpr int32_t kMhNoLabel = INT32_MAX;
 
-__device__ __forceinline__ bool mh_counts(int a, int b, int c, int nv) {
-  return (unsigned)a < (unsigned)nv && (unsigned)b < (unsigned)nv && (unsigned)c < (unsigned)nv && a != b && b != c &&
-         a != c;
-}
-
 __global__ __launch_bounds__(256) void mh_keys_kernel(const int32_t* __restrict__ faces, int nf, int nv,
                                                       int64_t* __restrict__ keys) {
   const int f = blockIdx.x * 256 + threadIdx.x;
   if (f >= nf) return;
   const int a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
-  const bool ok = mh_counts(a, b, c, nv);
+  const bool ok = tp_counts(a, b, c, nv);
   int64_t* k = keys + 3 * (size_t)f;
   k[0] = ok ? (int64_t)min(a, b) * nv + max(a, b) : kMhNoKey;
   k[1] = ok ? (int64_t)min(b, c) * nv + max(b, c) : kMhNoKey;
@@ -80,23 +75,6 @@ __global__ __launch_bounds__(256) void mh_darts_kernel(const int32_t* __restrict
   head[i] = h;
 }
 
-// the first position of `sorted` (ascending, n entries) that is >= v
-__device__ __forceinline__ int mh_lower(const int32_t* __restrict__ sorted, int n, int v) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (sorted[mid] < v) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
-// the position of v in `sorted` when it occurs exactly once, else -1
-__device__ __forceinline__ int mh_once(const int32_t* __restrict__ sorted, int n, int v) {
-  const int p = mh_lower(sorted, n, v);
-  if (p >= n || sorted[p] != v) return -1;
-  return (p + 1 < n && sorted[p + 1] == v) ? -1 : p;
-}
-
 __global__ __launch_bounds__(256) void mh_link_kernel(const int32_t* __restrict__ tail,
                                                       const int32_t* __restrict__ head,
                                                       const int32_t* __restrict__ sorted_tail,
@@ -108,8 +86,8 @@ __global__ __launch_bounds__(256) void mh_link_kernel(const int32_t* __restrict_
   const int h = head[i];
   int nxt = -1;
   if ((unsigned)h < (unsigned)nv) {
-    const int p = mh_once(sorted_tail, nb, h);
-    if (p >= 0 && mh_once(sorted_head, nb, h) >= 0) {
+    const int p = tp_once(sorted_tail, nb, h);
+    if (p >= 0 && tp_once(sorted_head, nb, h) >= 0) {
       const int64_t j = tail_order[p];
       if ((uint64_t)j < (uint64_t)nb) nxt = (int)j;
     }
@@ -117,6 +95,17 @@ __global__ __launch_bounds__(256) void mh_link_kernel(const int32_t* __restrict_
   state[i] = make_int2(nxt, tail[i]);
 }
 
+// The combine step of a pointer doubling: what a dart's second entry becomes when its pointer jumps over `over`.
+struct MhMinLabel {                                      // the smallest label on the way
+  static __device__ __forceinline__ int join(int own, int over, int) { return min(own, over); }
+};
+struct MhSumSteps {                                      // the number of steps, saturating at B + 1
+  static __device__ __forceinline__ int join(int own, int over, int nb) {
+    return (int)min((int64_t)own + (int64_t)over, (int64_t)nb + 1);
+  }
+};
+
+template <class Join>
 __global__ __launch_bounds__(256) void mh_double_kernel(const int2* __restrict__ state_in, int2* __restrict__ state_out,
                                                         int nb) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -125,56 +114,54 @@ __global__ __launch_bounds__(256) void mh_double_kernel(const int2* __restrict__
   if ((unsigned)s.x < (unsigned)nb) {
     const int2 t = state_in[s.x];
     s.x = (unsigned)t.x < (unsigned)nb ? t.x : -1;
-    s.y = min(s.y, t.y);
+    s.y = Join::join(s.y, t.y, nb);
   } else {
     s.x = -1;
   }
   state_out[i] = s;
 }
 
-__global__ __launch_bounds__(256) void mh_labels_kernel(const int2* __restrict__ state, int nb,
-                                                        int32_t* __restrict__ keys) {
+// Is the dart with the doubled state s on a loop?  It lies on a cycle, and `flag` (null: no cycle is excluded) does not
+// exclude the cycle's label.  Only a flag makes the label an index, so only then is it held against [0, B): in plain mode
+// a label is a vertex and may well be >= B.
+__device__ __forceinline__ bool mh_on_loop(int2 s, const uint8_t* __restrict__ flag, int nb) {
+  return s.x >= 0 && (!flag || ((unsigned)s.y < (unsigned)nb && !flag[s.y]));
+}
+
+__global__ __launch_bounds__(256) void mh_loop_labels_kernel(const int2* __restrict__ labelled,
+                                                             const uint8_t* __restrict__ flag, int nb,
+                                                             int32_t* __restrict__ keys) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i > nb) return;
   int32_t k = kMhNoLabel;
   if (i < nb) {
-    const int2 s = state[i];
-    if (s.x >= 0) k = s.y;
+    const int2 s = labelled[i];
+    if (mh_on_loop(s, flag, nb)) k = s.y;
   }
   keys[i] = k;
 }
 
-__global__ __launch_bounds__(256) void mh_assign_kernel(const int2* __restrict__ state, const int32_t* __restrict__ tail,
-                                                        int nb, const int32_t* __restrict__ loop_id, int nl,
-                                                        int32_t* __restrict__ dart_loop, int32_t* __restrict__ start) {
+// `own`: the state before the doubling, whose second entry is the dart's own label (its tail, or its name in bow-tie
+// mode).  Labels on a cycle are distinct (a loop id is a simple vertex; names are distinct), so one dart writes start[l].
+__global__ __launch_bounds__(256) void mh_loop_assign_kernel(
+    const int2* __restrict__ labelled, const int2* __restrict__ own, const uint8_t* __restrict__ flag,
+    const int32_t* __restrict__ tail, const int32_t* __restrict__ head, int nb, const int32_t* __restrict__ loop_name,
+    int nl, int32_t* __restrict__ dart_loop, int32_t* __restrict__ start, int32_t* __restrict__ loop_id,
+    int32_t* __restrict__ loop_head) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= nb) return;
-  const int2 s = state[i];
+  const int2 s = labelled[i];
   int l = -1;
-  if (s.x >= 0) {
-    const int p = mh_lower(loop_id, nl, s.y);
-    if (p < nl && loop_id[p] == s.y) l = p;
+  if (mh_on_loop(s, flag, nb)) {
+    const int p = tp_lower(loop_name, nl, s.y);
+    if (p < nl && loop_name[p] == s.y) l = p;
   }
   dart_loop[i] = l;
-  if (l >= 0 && tail[i] == s.y) start[l] = i;          // one dart leaves the loop id: it is a simple vertex
-}
-
-__device__ __forceinline__ void mh_point(const float* __restrict__ v, int i, double (&p)[3]) {
-  p[0] = (double)v[3 * (size_t)i], p[1] = (double)v[3 * (size_t)i + 1], p[2] = (double)v[3 * (size_t)i + 2];
-}
-
-__device__ __forceinline__ void mh_sub(const double (&a)[3], const double (&b)[3], double (&r)[3]) {
-  r[0] = a[0] - b[0], r[1] = a[1] - b[1], r[2] = a[2] - b[2];
-}
-
-__device__ __forceinline__ void mh_cross(const double (&u)[3], const double (&v)[3], double (&r)[3]) {
-  r[0] = u[1] * v[2] - u[2] * v[1];
-  r[1] = u[2] * v[0] - u[0] * v[2];
-  r[2] = u[0] * v[1] - u[1] * v[0];
-}
-
-__device__ __forceinline__ double mh_dot(const double (&u)[3], const double (&v)[3]) {
-  return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2];
+  if (l >= 0 && own[i].y == s.y) {
+    start[l] = i;
+    if (loop_id) loop_id[l] = tail[i];
+    if (loop_head) loop_head[l] = head[i];
+  }
 }
 
 // tail and head of boundary dart d, both in [0, V); false for a dart outside [0, B) or a vertex outside [0, V)
@@ -203,10 +190,10 @@ __global__ __launch_bounds__(256) void mh_measure_kernel(
     ok = mh_ends(tail, head, d, nb, nv, a, b);
     if (!ok) break;
     double pa[3], pb[3], e[3];
-    mh_point(vert, a, pa);
-    mh_point(vert, b, pb);
-    mh_sub(pb, pa, e);
-    per = per + sqrt(mh_dot(e, e));
+    tp_point(vert, a, pa);
+    tp_point(vert, b, pb);
+    tp_sub(pb, pa, e);
+    per = per + sqrt(tp_dot(e, e));
 #pragma unroll
     for (int k = 0; k < 3; k++) s[k] = s[k] + pa[k];
     d = state[d].x;
@@ -223,20 +210,20 @@ __global__ __launch_bounds__(256) void mh_measure_kernel(
     const int f = dart[d] / 3;
     if ((unsigned)f >= (unsigned)nf) { fill = false; break; }
     const int i0 = faces[3 * (size_t)f], i1 = faces[3 * (size_t)f + 1], i2 = faces[3 * (size_t)f + 2];
-    if (!mh_counts(i0, i1, i2, nv)) { fill = false; break; }
+    if (!tp_counts(i0, i1, i2, nv)) { fill = false; break; }
     double pa[3], pb[3], q0[3], q1[3], q2[3], u[3], w[3], e1[3], e2[3], fan[3], own[3];
-    mh_point(vert, a, pa);
-    mh_point(vert, b, pb);
-    mh_point(vert, i0, q0);
-    mh_point(vert, i1, q1);
-    mh_point(vert, i2, q2);
-    mh_sub(pa, pb, u);
-    mh_sub(c, pb, w);
-    mh_cross(u, w, fan);
-    mh_sub(q1, q0, e1);
-    mh_sub(q2, q0, e2);
-    mh_cross(e1, e2, own);
-    fill = mh_dot(fan, own) > 0.0;                       // false for zero and for NaN
+    tp_point(vert, a, pa);
+    tp_point(vert, b, pb);
+    tp_point(vert, i0, q0);
+    tp_point(vert, i1, q1);
+    tp_point(vert, i2, q2);
+    tp_sub(pa, pb, u);
+    tp_sub(c, pb, w);
+    tp_cross(u, w, fan);
+    tp_sub(q1, q0, e1);
+    tp_sub(q2, q0, e2);
+    tp_cross(e1, e2, own);
+    fill = tp_dot(fan, own) > 0.0;                       // false for zero and for NaN
     d = state[d].x;
   }
   perimeter[l] = ok ? per : (double)NAN;
@@ -273,11 +260,11 @@ __global__ __launch_bounds__(256) void mh_emit_kernel(
     face[0] = ok ? b : 0, face[1] = ok ? a : 0, face[2] = ok ? vnew : 0;      // measure has walked this loop: ok
     if (!ok) continue;
     double x[3], y[3], e1[3], e2[3], nrm[3];
-    mh_point(vert, b, x);
-    mh_point(vert, a, y);
-    mh_sub(y, x, e1);
-    mh_sub(c, x, e2);
-    mh_cross(e1, e2, nrm);
+    tp_point(vert, b, x);
+    tp_point(vert, a, y);
+    tp_sub(y, x, e1);
+    tp_sub(c, x, e2);
+    tp_cross(e1, e2, nrm);
 #pragma unroll
     for (int k = 0; k < 3; k++) {
       s[k] = s[k] + nrm[k];
@@ -285,7 +272,7 @@ __global__ __launch_bounds__(256) void mh_emit_kernel(
     }
     d = state[d].x;
   }
-  const double ln = sqrt(mh_dot(s, s));
+  const double ln = sqrt(tp_dot(s, s));
   const bool unit = ln > 0.0 && ln < (double)INFINITY;
 #pragma unroll
   for (int k = 0; k < 3; k++) {
@@ -308,43 +295,28 @@ __global__ __launch_bounds__(256) void mh_emit_kernel(
 //   claim    one thread per boundary dart: state = (fan(d) when nobody else claims it, else none; name), name = the
 //            position of the dart's key among the sorted keys of the boundary darts.
 //   double   as above: ptr >= 0 exactly on the closed walks of fan, lab = the walk's smallest name.
-//   rank_init, rank_double   a second pointer doubling over (successor, steps), cut in front of the walk's first dart:
-//            steps becomes the distance to that dart along fan, n for the first dart itself, so n - steps is the rank.
+//   rank_init, rank_double   the same doubling kernel over (successor, steps), adding steps where double takes the
+//            minimum, cut in front of the walk's first dart: steps becomes the distance to that dart along fan, n for the
+//            first dart itself, so n - steps is the rank.
 //   walk_keys  label B + (B - steps): the order by (walk, rank).  (caller) sorts with the permutation.
 //   pair_keys  in that order, head B + label.  (caller) sorts, stable: runs of one (head, walk) by ascending rank.
 //   repair   one thread per sorted slot: the ends of its run by binary search, next(d_m) = fan(d_(m-1 mod k)).
 //   double   on (next, name): the cycles of next and their smallest names.
 //   tail_keys, tail_flag   label V + tail, sorted by the caller; a repeated key stores 1 to the flag of that label (many
 //            lanes may store the same byte; nobody reads it in that launch).
-//   loop_labels, loop_assign   as labels and assign, without the flagged cycles, the first dart found by its name.
+//   loop_labels, loop_assign   as above, with the flag: without the flagged cycles; a label is a name, so the first dart
+//            is found by its name, and its tail and head are the loop's id and head.
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void mh_dkeys_kernel(const int32_t* __restrict__ faces, int nf, int nv,
                                                        int64_t* __restrict__ keys) {
   const int f = blockIdx.x * 256 + threadIdx.x;
   if (f >= nf) return;
   const int a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
-  const bool ok = mh_counts(a, b, c, nv);
+  const bool ok = tp_counts(a, b, c, nv);
   int64_t* k = keys + 3 * (size_t)f;
   k[0] = ok ? (int64_t)a * nv + b : kMhNoKey;
   k[1] = ok ? (int64_t)b * nv + c : kMhNoKey;
   k[2] = ok ? (int64_t)c * nv + a : kMhNoKey;
-}
-
-// the first position of `sorted` (ascending, n entries) that is >= v
-__device__ __forceinline__ int64_t mh_lower64(const int64_t* __restrict__ sorted, int64_t n, int64_t v) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (sorted[mid] < v) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
-// the position of v in `sorted` when it occurs exactly once, else -1
-__device__ __forceinline__ int64_t mh_once64(const int64_t* __restrict__ sorted, int64_t n, int64_t v) {
-  const int64_t p = mh_lower64(sorted, n, v);
-  if (p >= n || sorted[p] != v) return -1;
-  return (p + 1 < n && sorted[p + 1] == v) ? -1 : p;
 }
 
 __global__ __launch_bounds__(256) void mh_fan_kernel(const int32_t* __restrict__ faces, int nf, int nv,
@@ -360,16 +332,16 @@ __global__ __launch_bounds__(256) void mh_fan_kernel(const int32_t* __restrict__
   int out = -1;
   if ((uint64_t)s < (uint64_t)n && (unsigned)v < (unsigned)nv) {
     const int64_t row = (int64_t)v * nv;
-    const int64_t bound = mh_lower64(sorted_keys, n, row + nv) - mh_lower64(sorted_keys, n, row);
+    const int64_t bound = tp_lower(sorted_keys, n, row + nv) - tp_lower(sorted_keys, n, row);
     for (int64_t step = 0; step < bound; step++) {
       const int64_t f = s / 3;
       const int c = (int)(s - 3 * f), c1 = c == 2 ? 0 : c + 1, c2 = c1 == 2 ? 0 : c1 + 1;
       const int w = faces[3 * f + c2];
       if (faces[3 * f + c1] != v || (unsigned)w >= (unsigned)nv) break;    // the edge after s in its face is v -> w
-      const int p = mh_once(dart, nb, (int)(3 * f + c1));
+      const int p = tp_once(dart, nb, (int)(3 * f + c1));
       if (p >= 0) { out = p; break; }
-      const int64_t q = mh_once64(sorted_keys, n, (int64_t)w * nv + v);
-      if (q < 0 || mh_once64(sorted_keys, n, row + w) < 0) break;
+      const int64_t q = tp_once(sorted_keys, n, (int64_t)w * nv + v);
+      if (q < 0 || tp_once(sorted_keys, n, row + w) < 0) break;
       s = key_order[q];
       if ((uint64_t)s >= (uint64_t)n) break;
     }
@@ -385,8 +357,8 @@ __global__ __launch_bounds__(256) void mh_claim_kernel(const int32_t* __restrict
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= nb) return;
   const int s = fan[i];
-  const bool mine = (unsigned)s < (unsigned)nb && mh_once(sorted_fan, nb, s) >= 0;
-  state[i] = make_int2(mine ? s : -1, (int)mh_lower64(sorted_dart_key, nb, dart_key[i]));
+  const bool mine = (unsigned)s < (unsigned)nb && tp_once(sorted_fan, nb, s) >= 0;
+  state[i] = make_int2(mine ? s : -1, (int)tp_lower(sorted_dart_key, (int64_t)nb, dart_key[i]));
 }
 
 __global__ __launch_bounds__(256) void mh_rank_init_kernel(const int2* __restrict__ state,
@@ -401,21 +373,6 @@ __global__ __launch_bounds__(256) void mh_rank_init_kernel(const int2* __restric
     if (state[s].y != labelled[i].y) r.x = s;             // the walk's first dart carries the label as its name
   }
   rank[i] = r;
-}
-
-__global__ __launch_bounds__(256) void mh_rank_double_kernel(const int2* __restrict__ rank_in,
-                                                             int2* __restrict__ rank_out, int nb) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= nb) return;
-  int2 r = rank_in[i];
-  if ((unsigned)r.x < (unsigned)nb) {
-    const int2 t = rank_in[r.x];
-    r.x = (unsigned)t.x < (unsigned)nb ? t.x : -1;
-    r.y = (int)min((int64_t)r.y + (int64_t)t.y, (int64_t)nb + 1);
-  } else {
-    r.x = -1;
-  }
-  rank_out[i] = r;
 }
 
 __global__ __launch_bounds__(256) void mh_walk_keys_kernel(const int2* __restrict__ labelled,
@@ -466,7 +423,7 @@ __global__ __launch_bounds__(256) void mh_repair_kernel(const int64_t* __restric
   const int64_t k = sorted_pair_keys[j];
   int nxt = -1;
   if (k != kMhNoKey) {
-    const int64_t lo = mh_lower64(sorted_pair_keys, nb, k), hi = mh_lower64(sorted_pair_keys, nb, k + 1);
+    const int64_t n = nb, lo = tp_lower(sorted_pair_keys, n, k), hi = tp_lower(sorted_pair_keys, n, k + 1);
     const int64_t prev = j == lo ? hi - 1 : (int64_t)j - 1;
     const int dp = prev >= 0 && prev < nb ? mh_slot_dart(pair_order, walk_order, prev, nb) : -1;
     if (dp >= 0) {
@@ -498,56 +455,29 @@ __global__ __launch_bounds__(256) void mh_tail_flag_kernel(const int64_t* __rest
   if ((uint64_t)l < (uint64_t)nb) flag[l] = 1;
 }
 
-__global__ __launch_bounds__(256) void mh_loop_labels_kernel(const int2* __restrict__ labelled,
-                                                             const uint8_t* __restrict__ flag, int nb,
-                                                             int32_t* __restrict__ keys) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i > nb) return;
-  int32_t k = kMhNoLabel;
-  if (i < nb) {
-    const int2 s = labelled[i];
-    if (s.x >= 0 && (unsigned)s.y < (unsigned)nb && !flag[s.y]) k = s.y;
-  }
-  keys[i] = k;
-}
-
-__global__ __launch_bounds__(256) void mh_loop_assign_kernel(
-    const int2* __restrict__ labelled, const int2* __restrict__ paired, const uint8_t* __restrict__ flag,
-    const int32_t* __restrict__ tail, const int32_t* __restrict__ head, int nb, const int32_t* __restrict__ loop_name,
-    int nl, int32_t* __restrict__ dart_loop, int32_t* __restrict__ start, int32_t* __restrict__ loop_id,
-    int32_t* __restrict__ loop_head) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= nb) return;
-  const int2 s = labelled[i];
-  int l = -1;
-  if (s.x >= 0 && (unsigned)s.y < (unsigned)nb && !flag[s.y]) {
-    const int p = mh_lower(loop_name, nl, s.y);
-    if (p < nl && loop_name[p] == s.y) l = p;
-  }
-  dart_loop[i] = l;
-  if (l >= 0 && paired[i].y == s.y) {                     // names are distinct: one dart of the loop has this one
-    start[l] = i;
-    loop_id[l] = tail[i];
-    loop_head[l] = head[i];
-  }
-}
-
 }  // namespace mslam
 
 using namespace mslam;
 
-#define MH_LAUNCH(kernel, count, ...) \
-  hipLaunchKernelGGL(kernel, dim3(blocks_for(count, 256)), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__)
+// What the entry points repeat, spelled once.  A state is i32[B,2], read and written as int2, hence 8-byte aligned.
+#define MH_STATE(p) reinterpret_cast<const int2*>(p)
+#define MH_STATE_OUT(p) reinterpret_cast<int2*>(p)
+#define MH_ALIGNED(p) ((uintptr_t)(p) % 8 == 0)
+#define MH_SIZES(name, ok) MSLAM_REQUIRE(ok, name ": negative size")
+#define MH_FACES(name, nf) MSLAM_REQUIRE((int64_t)(nf) * 3 < ((int64_t)1 << 31), name ": too many faces")
+// one thread per element in blocks of 256, the launch check, and the entry point's return
+#define MH_RUN(name, kernel, count, ...)                                                                     \
+  hipLaunchKernelGGL(kernel, dim3(blocks_for(count, 256)), dim3(256), 0, (hipStream_t)stream, __VA_ARGS__); \
+  MSLAM_LAUNCH_CHECK(name);                                                                                  \
+  return MSLAM_OK
 
 extern "C" int mslam_mesh_holes_keys(const int32_t* faces, int num_faces, int num_vertices, int64_t* keys,
                                      void* stream) {
-  MSLAM_REQUIRE(num_faces >= 0 && num_vertices >= 0, "mesh_holes_keys: negative size");
-  MSLAM_REQUIRE((int64_t)num_faces * 3 < ((int64_t)1 << 31), "mesh_holes_keys: too many faces");
+  MH_SIZES("mesh_holes_keys", num_faces >= 0 && num_vertices >= 0);
+  MH_FACES("mesh_holes_keys", num_faces);
   if (num_faces == 0) return MSLAM_OK;
   MSLAM_REQUIRE(faces && keys, "mesh_holes_keys: null pointer");
-  MH_LAUNCH(mh_keys_kernel, num_faces, faces, num_faces, num_vertices, keys);
-  MSLAM_LAUNCH_CHECK("mesh_holes_keys");
-  return MSLAM_OK;
+  MH_RUN("mesh_holes_keys", mh_keys_kernel, num_faces, faces, num_faces, num_vertices, keys);
 }
 
 extern "C" int mslam_mesh_holes_mark(const int64_t* sorted_keys, const int64_t* order, int64_t num_keys, uint8_t* flag,
@@ -555,66 +485,59 @@ extern "C" int mslam_mesh_holes_mark(const int64_t* sorted_keys, const int64_t* 
   MSLAM_REQUIRE(num_keys >= 0 && num_keys < ((int64_t)1 << 31), "mesh_holes_mark: size outside [0, 2^31)");
   if (num_keys == 0) return MSLAM_OK;
   MSLAM_REQUIRE(sorted_keys && order && flag, "mesh_holes_mark: null pointer");
-  MH_LAUNCH(mh_mark_kernel, num_keys, sorted_keys, order, num_keys, flag);
-  MSLAM_LAUNCH_CHECK("mesh_holes_mark");
-  return MSLAM_OK;
+  MH_RUN("mesh_holes_mark", mh_mark_kernel, num_keys, sorted_keys, order, num_keys, flag);
 }
 
 extern "C" int mslam_mesh_holes_darts(const int32_t* faces, int num_faces, int num_vertices, const int32_t* dart,
                                       int num_darts, int32_t* tail, int32_t* head, void* stream) {
-  MSLAM_REQUIRE(num_faces >= 0 && num_vertices >= 0 && num_darts >= 0, "mesh_holes_darts: negative size");
-  MSLAM_REQUIRE((int64_t)num_faces * 3 < ((int64_t)1 << 31), "mesh_holes_darts: too many faces");
+  MH_SIZES("mesh_holes_darts", num_faces >= 0 && num_vertices >= 0 && num_darts >= 0);
+  MH_FACES("mesh_holes_darts", num_faces);
   if (num_darts == 0) return MSLAM_OK;
   MSLAM_REQUIRE(dart && tail && head && (faces || num_faces == 0), "mesh_holes_darts: null pointer");
-  MH_LAUNCH(mh_darts_kernel, num_darts, faces, num_faces, num_vertices, dart, num_darts, tail, head);
-  MSLAM_LAUNCH_CHECK("mesh_holes_darts");
-  return MSLAM_OK;
+  MH_RUN("mesh_holes_darts", mh_darts_kernel, num_darts, faces, num_faces, num_vertices, dart, num_darts, tail, head);
 }
 
 extern "C" int mslam_mesh_holes_link(const int32_t* tail, const int32_t* head, const int32_t* sorted_tail,
                                      const int64_t* tail_order, const int32_t* sorted_head, int num_darts,
                                      int num_vertices, int32_t* state, void* stream) {
-  MSLAM_REQUIRE(num_darts >= 0 && num_vertices >= 0, "mesh_holes_link: negative size");
+  MH_SIZES("mesh_holes_link", num_darts >= 0 && num_vertices >= 0);
   if (num_darts == 0) return MSLAM_OK;
   MSLAM_REQUIRE(tail && head && sorted_tail && tail_order && sorted_head && state, "mesh_holes_link: null pointer");
-  MSLAM_REQUIRE((uintptr_t)state % 8 == 0, "mesh_holes_link: state must be 8-byte aligned");
-  MH_LAUNCH(mh_link_kernel, num_darts, tail, head, sorted_tail, tail_order, sorted_head, num_darts, num_vertices,
-            reinterpret_cast<int2*>(state));
-  MSLAM_LAUNCH_CHECK("mesh_holes_link");
-  return MSLAM_OK;
+  MSLAM_REQUIRE(MH_ALIGNED(state), "mesh_holes_link: state must be 8-byte aligned");
+  MH_RUN("mesh_holes_link", mh_link_kernel, num_darts, tail, head, sorted_tail, tail_order, sorted_head, num_darts,
+         num_vertices, MH_STATE_OUT(state));
 }
 
 extern "C" int mslam_mesh_holes_double(const int32_t* state_in, int32_t* state_out, int num_darts, void* stream) {
-  MSLAM_REQUIRE(num_darts >= 0, "mesh_holes_double: negative size");
+  MH_SIZES("mesh_holes_double", num_darts >= 0);
   if (num_darts == 0) return MSLAM_OK;
   MSLAM_REQUIRE(state_in && state_out && state_in != state_out, "mesh_holes_double: null pointer or out == in");
-  MSLAM_REQUIRE((uintptr_t)state_in % 8 == 0 && (uintptr_t)state_out % 8 == 0,
-                "mesh_holes_double: states must be 8-byte aligned");
-  MH_LAUNCH(mh_double_kernel, num_darts, reinterpret_cast<const int2*>(state_in), reinterpret_cast<int2*>(state_out),
-            num_darts);
-  MSLAM_LAUNCH_CHECK("mesh_holes_double");
-  return MSLAM_OK;
+  MSLAM_REQUIRE(MH_ALIGNED(state_in) && MH_ALIGNED(state_out), "mesh_holes_double: states must be 8-byte aligned");
+  MH_RUN("mesh_holes_double", mh_double_kernel<MhMinLabel>, num_darts, MH_STATE(state_in), MH_STATE_OUT(state_out),
+         num_darts);
 }
 
-extern "C" int mslam_mesh_holes_labels(const int32_t* state, int num_darts, int32_t* keys, void* stream) {
-  MSLAM_REQUIRE(num_darts >= 0 && num_darts < INT32_MAX, "mesh_holes_labels: size outside [0, 2^31 - 1)");
-  MSLAM_REQUIRE(keys && (state || num_darts == 0), "mesh_holes_labels: null pointer");
-  MSLAM_REQUIRE((uintptr_t)state % 8 == 0, "mesh_holes_labels: state must be 8-byte aligned");
-  MH_LAUNCH(mh_labels_kernel, (int64_t)num_darts + 1, reinterpret_cast<const int2*>(state), num_darts, keys);
-  MSLAM_LAUNCH_CHECK("mesh_holes_labels");
-  return MSLAM_OK;
+extern "C" int mslam_mesh_holes_loop_labels(const int32_t* labelled, const uint8_t* flag, int num_darts, int32_t* keys,
+                                            void* stream) {
+  MSLAM_REQUIRE(num_darts >= 0 && num_darts < INT32_MAX, "mesh_holes_loop_labels: size outside [0, 2^31 - 1)");
+  MSLAM_REQUIRE(keys && (labelled || num_darts == 0), "mesh_holes_loop_labels: null pointer");
+  MSLAM_REQUIRE(MH_ALIGNED(labelled), "mesh_holes_loop_labels: state must be 8-byte aligned");
+  MH_RUN("mesh_holes_loop_labels", mh_loop_labels_kernel, (int64_t)num_darts + 1, MH_STATE(labelled), flag, num_darts,
+         keys);
 }
 
-extern "C" int mslam_mesh_holes_assign(const int32_t* state, const int32_t* tail, int num_darts, const int32_t* loop_id,
-                                       int num_loops, int32_t* dart_loop, int32_t* start, void* stream) {
-  MSLAM_REQUIRE(num_darts >= 0 && num_loops >= 0, "mesh_holes_assign: negative size");
+extern "C" int mslam_mesh_holes_loop_assign(const int32_t* labelled, const int32_t* own, const uint8_t* flag,
+                                            const int32_t* tail, const int32_t* head, int num_darts,
+                                            const int32_t* loop_name, int num_loops, int32_t* dart_loop, int32_t* start,
+                                            int32_t* loop_id, int32_t* loop_head, void* stream) {
+  MH_SIZES("mesh_holes_loop_assign", num_darts >= 0 && num_loops >= 0);
   if (num_darts == 0) return MSLAM_OK;
-  MSLAM_REQUIRE(state && tail && dart_loop && (num_loops == 0 || (loop_id && start)), "mesh_holes_assign: null pointer");
-  MSLAM_REQUIRE((uintptr_t)state % 8 == 0, "mesh_holes_assign: state must be 8-byte aligned");
-  MH_LAUNCH(mh_assign_kernel, num_darts, reinterpret_cast<const int2*>(state), tail, num_darts, loop_id, num_loops,
-            dart_loop, start);
-  MSLAM_LAUNCH_CHECK("mesh_holes_assign");
-  return MSLAM_OK;
+  MSLAM_REQUIRE(labelled && own && dart_loop && (num_loops == 0 || (loop_name && start)) && (tail || !loop_id) &&
+                    (head || !loop_head),
+                "mesh_holes_loop_assign: null pointer");
+  MSLAM_REQUIRE(MH_ALIGNED(labelled) && MH_ALIGNED(own), "mesh_holes_loop_assign: states must be 8-byte aligned");
+  MH_RUN("mesh_holes_loop_assign", mh_loop_assign_kernel, num_darts, MH_STATE(labelled), MH_STATE(own), flag, tail,
+         head, num_darts, loop_name, num_loops, dart_loop, start, loop_id, loop_head);
 }
 
 extern "C" int mslam_mesh_holes_measure(const float* vertices, const int32_t* faces, int num_faces, int num_vertices,
@@ -622,19 +545,15 @@ extern "C" int mslam_mesh_holes_measure(const float* vertices, const int32_t* fa
                                         const int32_t* state, int num_darts, const int32_t* start,
                                         const int32_t* length, int num_loops, int max_edges, int all_perimeters,
                                         double* perimeter, double* centre, uint8_t* fillable, void* stream) {
-  MSLAM_REQUIRE(num_faces >= 0 && num_vertices >= 0 && num_darts >= 0 && num_loops >= 0,
-                "mesh_holes_measure: negative size");
-  MSLAM_REQUIRE((int64_t)num_faces * 3 < ((int64_t)1 << 31), "mesh_holes_measure: too many faces");
+  MH_SIZES("mesh_holes_measure", num_faces >= 0 && num_vertices >= 0 && num_darts >= 0 && num_loops >= 0);
+  MH_FACES("mesh_holes_measure", num_faces);
   if (num_loops == 0) return MSLAM_OK;
   MSLAM_REQUIRE(start && length && perimeter && centre && fillable, "mesh_holes_measure: null pointer");
   MSLAM_REQUIRE(num_darts == 0 || (vertices && faces && dart && tail && head && state),
                 "mesh_holes_measure: null pointer");
-  MSLAM_REQUIRE((uintptr_t)state % 8 == 0, "mesh_holes_measure: state must be 8-byte aligned");
-  MH_LAUNCH(mh_measure_kernel, num_loops, vertices, faces, num_faces, num_vertices, dart, tail, head,
-            reinterpret_cast<const int2*>(state), num_darts, start, length, num_loops, max_edges, all_perimeters,
-            perimeter, centre, fillable);
-  MSLAM_LAUNCH_CHECK("mesh_holes_measure");
-  return MSLAM_OK;
+  MSLAM_REQUIRE(MH_ALIGNED(state), "mesh_holes_measure: state must be 8-byte aligned");
+  MH_RUN("mesh_holes_measure", mh_measure_kernel, num_loops, vertices, faces, num_faces, num_vertices, dart, tail, head,
+         MH_STATE(state), num_darts, start, length, num_loops, max_edges, all_perimeters, perimeter, centre, fillable);
 }
 
 extern "C" int mslam_mesh_holes_emit(const float* vertices, const float* colors, const int32_t* tail,
@@ -643,9 +562,8 @@ extern "C" int mslam_mesh_holes_emit(const float* vertices, const float* colors,
                                      const int64_t* face_base, int num_loops, int num_vertices, int num_faces,
                                      int new_vertices, int new_faces, const double* centre, float* out_vertices,
                                      float* out_normals, float* out_colors, int32_t* out_faces, void* stream) {
-  MSLAM_REQUIRE(num_darts >= 0 && num_loops >= 0 && num_vertices >= 0 && num_faces >= 0 && new_vertices >= 0 &&
-                    new_faces >= 0,
-                "mesh_holes_emit: negative size");
+  MH_SIZES("mesh_holes_emit", num_darts >= 0 && num_loops >= 0 && num_vertices >= 0 && num_faces >= 0 &&
+                                  new_vertices >= 0 && new_faces >= 0);
   MSLAM_REQUIRE((int64_t)num_vertices + new_vertices < ((int64_t)1 << 31) &&
                     ((int64_t)num_faces + new_faces) * 3 < ((int64_t)1 << 31),
                 "mesh_holes_emit: the output leaves the int32 index range");
@@ -654,160 +572,111 @@ extern "C" int mslam_mesh_holes_emit(const float* vertices, const float* colors,
                     centre && out_vertices && out_normals && out_faces,
                 "mesh_holes_emit: null pointer");
   MSLAM_REQUIRE((colors == nullptr) == (out_colors == nullptr), "mesh_holes_emit: colors and out_colors go together");
-  MSLAM_REQUIRE((uintptr_t)state % 8 == 0, "mesh_holes_emit: state must be 8-byte aligned");
-  MH_LAUNCH(mh_emit_kernel, num_loops, vertices, colors, tail, head, reinterpret_cast<const int2*>(state), num_darts,
-            start, length, fillable, vertex_base, face_base, num_loops, num_vertices, num_faces, new_vertices,
-            new_faces, centre, out_vertices, out_normals, out_colors, out_faces);
-  MSLAM_LAUNCH_CHECK("mesh_holes_emit");
-  return MSLAM_OK;
+  MSLAM_REQUIRE(MH_ALIGNED(state), "mesh_holes_emit: state must be 8-byte aligned");
+  MH_RUN("mesh_holes_emit", mh_emit_kernel, num_loops, vertices, colors, tail, head, MH_STATE(state), num_darts, start,
+         length, fillable, vertex_base, face_base, num_loops, num_vertices, num_faces, new_vertices, new_faces, centre,
+         out_vertices, out_normals, out_colors, out_faces);
 }
 
 // ---- bow-tie mode ----------------------------------------------------------------------------------------------------
-#define MH_STATE(p) reinterpret_cast<const int2*>(p)
-#define MH_ALIGNED(p) ((uintptr_t)(p) % 8 == 0)
-
 extern "C" int mslam_mesh_holes_dkeys(const int32_t* faces, int num_faces, int num_vertices, int64_t* keys,
                                       void* stream) {
-  MSLAM_REQUIRE(num_faces >= 0 && num_vertices >= 0, "mesh_holes_dkeys: negative size");
-  MSLAM_REQUIRE((int64_t)num_faces * 3 < ((int64_t)1 << 31), "mesh_holes_dkeys: too many faces");
+  MH_SIZES("mesh_holes_dkeys", num_faces >= 0 && num_vertices >= 0);
+  MH_FACES("mesh_holes_dkeys", num_faces);
   if (num_faces == 0) return MSLAM_OK;
   MSLAM_REQUIRE(faces && keys, "mesh_holes_dkeys: null pointer");
-  MH_LAUNCH(mh_dkeys_kernel, num_faces, faces, num_faces, num_vertices, keys);
-  MSLAM_LAUNCH_CHECK("mesh_holes_dkeys");
-  return MSLAM_OK;
+  MH_RUN("mesh_holes_dkeys", mh_dkeys_kernel, num_faces, faces, num_faces, num_vertices, keys);
 }
 
 extern "C" int mslam_mesh_holes_fan(const int32_t* faces, int num_faces, int num_vertices, const int32_t* dart,
                                     const int32_t* head, int num_darts, const int64_t* sorted_keys,
                                     const int64_t* key_order, int32_t* fan, void* stream) {
-  MSLAM_REQUIRE(num_faces >= 0 && num_vertices >= 0 && num_darts >= 0, "mesh_holes_fan: negative size");
-  MSLAM_REQUIRE((int64_t)num_faces * 3 < ((int64_t)1 << 31), "mesh_holes_fan: too many faces");
+  MH_SIZES("mesh_holes_fan", num_faces >= 0 && num_vertices >= 0 && num_darts >= 0);
+  MH_FACES("mesh_holes_fan", num_faces);
   if (num_darts == 0) return MSLAM_OK;
   MSLAM_REQUIRE(dart && head && fan && (num_faces == 0 || (faces && sorted_keys && key_order)),
                 "mesh_holes_fan: null pointer");
-  MH_LAUNCH(mh_fan_kernel, num_darts, faces, num_faces, num_vertices, dart, head, num_darts, sorted_keys, key_order,
-            fan);
-  MSLAM_LAUNCH_CHECK("mesh_holes_fan");
-  return MSLAM_OK;
+  MH_RUN("mesh_holes_fan", mh_fan_kernel, num_darts, faces, num_faces, num_vertices, dart, head, num_darts, sorted_keys,
+         key_order, fan);
 }
 
 extern "C" int mslam_mesh_holes_claim(const int32_t* fan, const int32_t* sorted_fan, const int64_t* dart_key,
                                       const int64_t* sorted_dart_key, int num_darts, int32_t* state, void* stream) {
-  MSLAM_REQUIRE(num_darts >= 0, "mesh_holes_claim: negative size");
+  MH_SIZES("mesh_holes_claim", num_darts >= 0);
   if (num_darts == 0) return MSLAM_OK;
   MSLAM_REQUIRE(fan && sorted_fan && dart_key && sorted_dart_key && state, "mesh_holes_claim: null pointer");
   MSLAM_REQUIRE(MH_ALIGNED(state), "mesh_holes_claim: state must be 8-byte aligned");
-  MH_LAUNCH(mh_claim_kernel, num_darts, fan, sorted_fan, dart_key, sorted_dart_key, num_darts,
-            reinterpret_cast<int2*>(state));
-  MSLAM_LAUNCH_CHECK("mesh_holes_claim");
-  return MSLAM_OK;
+  MH_RUN("mesh_holes_claim", mh_claim_kernel, num_darts, fan, sorted_fan, dart_key, sorted_dart_key, num_darts,
+         MH_STATE_OUT(state));
 }
 
 extern "C" int mslam_mesh_holes_rank_init(const int32_t* state, const int32_t* labelled, int num_darts, int32_t* rank,
                                           void* stream) {
-  MSLAM_REQUIRE(num_darts >= 0, "mesh_holes_rank_init: negative size");
+  MH_SIZES("mesh_holes_rank_init", num_darts >= 0);
   if (num_darts == 0) return MSLAM_OK;
   MSLAM_REQUIRE(state && labelled && rank, "mesh_holes_rank_init: null pointer");
   MSLAM_REQUIRE(MH_ALIGNED(state) && MH_ALIGNED(labelled) && MH_ALIGNED(rank),
                 "mesh_holes_rank_init: states must be 8-byte aligned");
-  MH_LAUNCH(mh_rank_init_kernel, num_darts, MH_STATE(state), MH_STATE(labelled), num_darts,
-            reinterpret_cast<int2*>(rank));
-  MSLAM_LAUNCH_CHECK("mesh_holes_rank_init");
-  return MSLAM_OK;
+  MH_RUN("mesh_holes_rank_init", mh_rank_init_kernel, num_darts, MH_STATE(state), MH_STATE(labelled), num_darts,
+         MH_STATE_OUT(rank));
 }
 
 extern "C" int mslam_mesh_holes_rank_double(const int32_t* rank_in, int32_t* rank_out, int num_darts, void* stream) {
-  MSLAM_REQUIRE(num_darts >= 0, "mesh_holes_rank_double: negative size");
+  MH_SIZES("mesh_holes_rank_double", num_darts >= 0);
   if (num_darts == 0) return MSLAM_OK;
   MSLAM_REQUIRE(rank_in && rank_out && rank_in != rank_out, "mesh_holes_rank_double: null pointer or out == in");
   MSLAM_REQUIRE(MH_ALIGNED(rank_in) && MH_ALIGNED(rank_out), "mesh_holes_rank_double: states must be 8-byte aligned");
-  MH_LAUNCH(mh_rank_double_kernel, num_darts, MH_STATE(rank_in), reinterpret_cast<int2*>(rank_out), num_darts);
-  MSLAM_LAUNCH_CHECK("mesh_holes_rank_double");
-  return MSLAM_OK;
+  MH_RUN("mesh_holes_rank_double", mh_double_kernel<MhSumSteps>, num_darts, MH_STATE(rank_in), MH_STATE_OUT(rank_out),
+         num_darts);
 }
 
 extern "C" int mslam_mesh_holes_walk_keys(const int32_t* labelled, const int32_t* rank, int num_darts, int64_t* keys,
                                           void* stream) {
-  MSLAM_REQUIRE(num_darts >= 0, "mesh_holes_walk_keys: negative size");
+  MH_SIZES("mesh_holes_walk_keys", num_darts >= 0);
   if (num_darts == 0) return MSLAM_OK;
   MSLAM_REQUIRE(labelled && rank && keys, "mesh_holes_walk_keys: null pointer");
   MSLAM_REQUIRE(MH_ALIGNED(labelled) && MH_ALIGNED(rank), "mesh_holes_walk_keys: states must be 8-byte aligned");
-  MH_LAUNCH(mh_walk_keys_kernel, num_darts, MH_STATE(labelled), MH_STATE(rank), num_darts, keys);
-  MSLAM_LAUNCH_CHECK("mesh_holes_walk_keys");
-  return MSLAM_OK;
+  MH_RUN("mesh_holes_walk_keys", mh_walk_keys_kernel, num_darts, MH_STATE(labelled), MH_STATE(rank), num_darts, keys);
 }
 
 extern "C" int mslam_mesh_holes_pair_keys(const int32_t* labelled, const int32_t* head,
                                           const int64_t* sorted_walk_keys, const int64_t* walk_order, int num_darts,
                                           int num_vertices, int64_t* keys, void* stream) {
-  MSLAM_REQUIRE(num_darts >= 0 && num_vertices >= 0, "mesh_holes_pair_keys: negative size");
+  MH_SIZES("mesh_holes_pair_keys", num_darts >= 0 && num_vertices >= 0);
   if (num_darts == 0) return MSLAM_OK;
   MSLAM_REQUIRE(labelled && head && sorted_walk_keys && walk_order && keys, "mesh_holes_pair_keys: null pointer");
   MSLAM_REQUIRE(MH_ALIGNED(labelled), "mesh_holes_pair_keys: state must be 8-byte aligned");
-  MH_LAUNCH(mh_pair_keys_kernel, num_darts, MH_STATE(labelled), head, sorted_walk_keys, walk_order, num_darts,
-            num_vertices, keys);
-  MSLAM_LAUNCH_CHECK("mesh_holes_pair_keys");
-  return MSLAM_OK;
+  MH_RUN("mesh_holes_pair_keys", mh_pair_keys_kernel, num_darts, MH_STATE(labelled), head, sorted_walk_keys, walk_order,
+         num_darts, num_vertices, keys);
 }
 
 extern "C" int mslam_mesh_holes_repair(const int64_t* sorted_pair_keys, const int64_t* pair_order,
                                        const int64_t* walk_order, const int32_t* state, int num_darts, int32_t* paired,
                                        void* stream) {
-  MSLAM_REQUIRE(num_darts >= 0, "mesh_holes_repair: negative size");
+  MH_SIZES("mesh_holes_repair", num_darts >= 0);
   if (num_darts == 0) return MSLAM_OK;
   MSLAM_REQUIRE(sorted_pair_keys && pair_order && walk_order && state && paired && state != paired,
                 "mesh_holes_repair: null pointer or out == in");
   MSLAM_REQUIRE(MH_ALIGNED(state) && MH_ALIGNED(paired), "mesh_holes_repair: states must be 8-byte aligned");
-  MH_LAUNCH(mh_repair_kernel, num_darts, sorted_pair_keys, pair_order, walk_order, MH_STATE(state), num_darts,
-            reinterpret_cast<int2*>(paired));
-  MSLAM_LAUNCH_CHECK("mesh_holes_repair");
-  return MSLAM_OK;
+  MH_RUN("mesh_holes_repair", mh_repair_kernel, num_darts, sorted_pair_keys, pair_order, walk_order, MH_STATE(state),
+         num_darts, MH_STATE_OUT(paired));
 }
 
 extern "C" int mslam_mesh_holes_tail_keys(const int32_t* labelled, const int32_t* tail, int num_darts, int num_vertices,
                                           int64_t* keys, void* stream) {
-  MSLAM_REQUIRE(num_darts >= 0 && num_vertices >= 0, "mesh_holes_tail_keys: negative size");
+  MH_SIZES("mesh_holes_tail_keys", num_darts >= 0 && num_vertices >= 0);
   if (num_darts == 0) return MSLAM_OK;
   MSLAM_REQUIRE(labelled && tail && keys, "mesh_holes_tail_keys: null pointer");
   MSLAM_REQUIRE(MH_ALIGNED(labelled), "mesh_holes_tail_keys: state must be 8-byte aligned");
-  MH_LAUNCH(mh_tail_keys_kernel, num_darts, MH_STATE(labelled), tail, num_darts, num_vertices, keys);
-  MSLAM_LAUNCH_CHECK("mesh_holes_tail_keys");
-  return MSLAM_OK;
+  MH_RUN("mesh_holes_tail_keys", mh_tail_keys_kernel, num_darts, MH_STATE(labelled), tail, num_darts, num_vertices,
+         keys);
 }
 
 extern "C" int mslam_mesh_holes_tail_flag(const int64_t* sorted_keys, int num_darts, int num_vertices, uint8_t* flag,
                                           void* stream) {
-  MSLAM_REQUIRE(num_darts >= 0 && num_vertices >= 0, "mesh_holes_tail_flag: negative size");
+  MH_SIZES("mesh_holes_tail_flag", num_darts >= 0 && num_vertices >= 0);
   if (num_darts == 0) return MSLAM_OK;
   MSLAM_REQUIRE(num_vertices > 0, "mesh_holes_tail_flag: darts without vertices");
   MSLAM_REQUIRE(sorted_keys && flag, "mesh_holes_tail_flag: null pointer");
-  MH_LAUNCH(mh_tail_flag_kernel, num_darts, sorted_keys, num_darts, num_vertices, flag);
-  MSLAM_LAUNCH_CHECK("mesh_holes_tail_flag");
-  return MSLAM_OK;
-}
-
-extern "C" int mslam_mesh_holes_loop_labels(const int32_t* labelled, const uint8_t* flag, int num_darts, int32_t* keys,
-                                            void* stream) {
-  MSLAM_REQUIRE(num_darts >= 0 && num_darts < INT32_MAX, "mesh_holes_loop_labels: size outside [0, 2^31 - 1)");
-  MSLAM_REQUIRE(keys && ((labelled && flag) || num_darts == 0), "mesh_holes_loop_labels: null pointer");
-  MSLAM_REQUIRE(MH_ALIGNED(labelled), "mesh_holes_loop_labels: state must be 8-byte aligned");
-  MH_LAUNCH(mh_loop_labels_kernel, (int64_t)num_darts + 1, MH_STATE(labelled), flag, num_darts, keys);
-  MSLAM_LAUNCH_CHECK("mesh_holes_loop_labels");
-  return MSLAM_OK;
-}
-
-extern "C" int mslam_mesh_holes_loop_assign(const int32_t* labelled, const int32_t* paired, const uint8_t* flag,
-                                            const int32_t* tail, const int32_t* head, int num_darts,
-                                            const int32_t* loop_name, int num_loops, int32_t* dart_loop, int32_t* start,
-                                            int32_t* loop_id, int32_t* loop_head, void* stream) {
-  MSLAM_REQUIRE(num_darts >= 0 && num_loops >= 0, "mesh_holes_loop_assign: negative size");
-  if (num_darts == 0) return MSLAM_OK;
-  MSLAM_REQUIRE(labelled && paired && flag && tail && head && dart_loop &&
-                    (num_loops == 0 || (loop_name && start && loop_id && loop_head)),
-                "mesh_holes_loop_assign: null pointer");
-  MSLAM_REQUIRE(MH_ALIGNED(labelled) && MH_ALIGNED(paired), "mesh_holes_loop_assign: states must be 8-byte aligned");
-  MH_LAUNCH(mh_loop_assign_kernel, num_darts, MH_STATE(labelled), MH_STATE(paired), flag, tail, head, num_darts,
-            loop_name, num_loops, dart_loop, start, loop_id, loop_head);
-  MSLAM_LAUNCH_CHECK("mesh_holes_loop_assign");
-  return MSLAM_OK;
+  MH_RUN("mesh_holes_tail_flag", mh_tail_flag_kernel, num_darts, sorted_keys, num_darts, num_vertices, flag);
 }

@@ -20,7 +20,7 @@
 // memory is checked against its array before it is followed; an element that fails is skipped.
 #include <math.h>
 
-#include "common.h"
+#include "mesh_topo.h"
 
 namespace mslam {
 
@@ -53,7 +53,7 @@ __global__ __launch_bounds__(256) void ms_faces_kernel(const int32_t* __restrict
   if (f >= nf) return;
   const int a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
   int ca = -1, cb = -1, cc = -1;
-  if ((unsigned)a < (unsigned)nv && (unsigned)b < (unsigned)nv && (unsigned)c < (unsigned)nv) {
+  if (tp_in_range(a, b, c, nv)) {
     ca = cluster[a], cb = cluster[b], cc = cluster[c];
   }
   const bool ok = (unsigned)ca < (unsigned)nc && (unsigned)cb < (unsigned)nc && (unsigned)cc < (unsigned)nc;
@@ -150,16 +150,12 @@ __global__ __launch_bounds__(64) void ms_solve_kernel(
       const int64_t f = pairs[j] - (int64_t)cl * nf;
       if ((uint64_t)f >= (uint64_t)nf) continue;
       const int ia = faces[3 * f], ib = faces[3 * f + 1], ic = faces[3 * f + 2];
-      if (!((unsigned)ia < (unsigned)nv && (unsigned)ib < (unsigned)nv && (unsigned)ic < (unsigned)nv)) continue;
-      double a[3], e1[3], e2[3];
-#pragma unroll
-      for (int d = 0; d < 3; d++) {
-        a[d] = (double)vert[3 * (size_t)ia + d];
-        e1[d] = (double)vert[3 * (size_t)ib + d] - a[d];
-        e2[d] = (double)vert[3 * (size_t)ic + d] - a[d];
-      }
-      const double nx = e1[1] * e2[2] - e1[2] * e2[1], ny = e1[2] * e2[0] - e1[0] * e2[2],
-                   nz = e1[0] * e2[1] - e1[1] * e2[0];
+      if (!tp_in_range(ia, ib, ic, nv)) continue;
+      double a[3], pb[3], pc[3], e1[3], e2[3], nn[3];
+      tp_point(vert, ia, a), tp_point(vert, ib, pb), tp_point(vert, ic, pc);
+      tp_sub(pb, a, e1), tp_sub(pc, a, e2);
+      tp_cross(e1, e2, nn);
+      const double nx = nn[0], ny = nn[1], nz = nn[2];
       if (nx == 0.0 && ny == 0.0 && nz == 0.0) continue;       // mslam_mesh_face_areas' validity rule
       const double ln = sqrt(nx * nx + ny * ny + nz * nz), w = 0.5 * ln;
       const double u[3] = {nx / ln, ny / ln, nz / ln};

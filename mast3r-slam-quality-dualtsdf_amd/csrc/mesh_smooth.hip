@@ -18,23 +18,18 @@
 // that fails is skipped.
 #include <math.h>
 
-#include "common.h"
+#include "mesh_topo.h"
 
 namespace mslam {
 
 constexpr int64_t kSmNone = INT64_MAX;
-
-__device__ __forceinline__ bool sm_counts(int a, int b, int c, int nv) {
-  return (unsigned)a < (unsigned)nv && (unsigned)b < (unsigned)nv && (unsigned)c < (unsigned)nv && a != b && b != c &&
-         a != c;
-}
 
 __global__ __launch_bounds__(256) void sm_edges_kernel(const int32_t* __restrict__ faces, int nf, int nv,
                                                        int64_t* __restrict__ keys) {
   const int f = blockIdx.x * 256 + threadIdx.x;
   if (f >= nf) return;
   const int a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
-  const bool ok = sm_counts(a, b, c, nv);
+  const bool ok = tp_counts(a, b, c, nv);
   int64_t* k = keys + 6 * (size_t)f;
   k[0] = ok ? (int64_t)a * nv + b : kSmNone;
   k[1] = ok ? (int64_t)b * nv + a : kSmNone;
@@ -49,7 +44,7 @@ __global__ __launch_bounds__(256) void sm_faces_kernel(const int32_t* __restrict
   const int f = blockIdx.x * 256 + threadIdx.x;
   if (f >= nf) return;
   const int a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
-  const bool ok = sm_counts(a, b, c, nv);
+  const bool ok = tp_counts(a, b, c, nv);
   pairs[3 * (size_t)f] = ok ? (int64_t)a * nf + f : kSmNone;
   pairs[3 * (size_t)f + 1] = ok ? (int64_t)b * nf + f : kSmNone;
   pairs[3 * (size_t)f + 2] = ok ? (int64_t)c * nf + f : kSmNone;
@@ -123,20 +118,16 @@ __global__ __launch_bounds__(256) void sm_normals_kernel(const float* __restrict
     const int64_t f = pairs[j] - v * nf;
     if ((uint64_t)f >= (uint64_t)nf) continue;
     const int ia = faces[3 * f], ib = faces[3 * f + 1], ic = faces[3 * f + 2];
-    if (!sm_counts(ia, ib, ic, nv)) continue;
-    double e1[3], e2[3];
+    if (!tp_counts(ia, ib, ic, nv)) continue;
+    double a[3], b[3], c[3], e1[3], e2[3], fn[3];
+    tp_point(vert, ia, a), tp_point(vert, ib, b), tp_point(vert, ic, c);
+    tp_sub(b, a, e1), tp_sub(c, a, e2);
+    tp_cross(e1, e2, fn);
 #pragma unroll
-    for (int d = 0; d < 3; d++) {
-      const double a = (double)vert[3 * (size_t)ia + d];
-      e1[d] = (double)vert[3 * (size_t)ib + d] - a;
-      e2[d] = (double)vert[3 * (size_t)ic + d] - a;
-    }
-    s[0] += e1[1] * e2[2] - e1[2] * e2[1];
-    s[1] += e1[2] * e2[0] - e1[0] * e2[2];
-    s[2] += e1[0] * e2[1] - e1[1] * e2[0];
+    for (int d = 0; d < 3; d++) s[d] += fn[d];
     n++;
   }
-  const double ln = sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]);
+  const double ln = sqrt(tp_dot(s, s));
   const bool unit = ln > 0.0 && ln < (double)INFINITY;      // false when the sum is zero, infinite or NaN
 #pragma unroll
   for (int d = 0; d < 3; d++) {

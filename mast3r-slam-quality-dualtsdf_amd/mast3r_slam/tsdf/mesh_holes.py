@@ -3,7 +3,8 @@
 No counterpart in the reference.  The kernels are csrc/mesh_holes.hip (DESIGN.md "Mesh holes"); the numpy statement of
 the same definitions is tests/holes_numpy.py.  torch sorts and scans, the kernels do the rest.  Works on any welded mesh,
 not only on what extract_mesh returns.  `bowties=True` pairs the boundary darts across the hole they bound, so that holes
-which meet in a vertex are loops of their own (_pair, _named_loops; tests/bowtie_numpy.py); it adds no host read.
+which meet in a vertex are loops of their own (_pair, _tail_flag; tests/bowtie_numpy.py); it adds no host read.  Both
+modes share one tracer: _trace, with _double and _loops.
 """
 import operator
 
@@ -50,59 +51,42 @@ def _rounds(B):
     return (B - 1).bit_length() + 1                         # ceil(log2 B) + 1
 
 
-def _double(state, rounds):
-    """`rounds` rounds of pointer doubling; `state` is left as it is."""
+def _double(state, rounds, entry="mesh_holes_double"):
+    """`rounds` rounds of the pointer doubling `entry` (the labels' minimum, or mesh_holes_rank_double's sum of steps),
+    between two spare buffers; `state` is left as it is."""
     B = int(state.shape[0])
+    fn = getattr(_m.lib(), "mslam_" + entry)
     buf = [state, torch.empty_like(state), torch.empty_like(state)]
     cur = 0
     for _ in range(rounds):
         nxt = 1 if cur != 1 else 2
-        _m.check(_m.lib().mslam_mesh_holes_double(_m.ptr(buf[cur]), _m.ptr(buf[nxt]), B, _m.stream_ptr()),
-                 "mesh_holes_double")
+        _m.check(fn(_m.ptr(buf[cur]), _m.ptr(buf[nxt]), B, _m.stream_ptr()), entry)
         cur = nxt
     return buf[cur]
 
 
-def _loops(labelled, tail):
-    """(loop_id i32[L], length i32[L], dart_loop i32[B], start i32[L], n_open i64[]).  One host read: L."""
-    B, dev = int(tail.shape[0]), tail.device
+def _loops(state, labelled, flag=None, tail=None, head=None):
+    """The loops among the cycles of `state`'s successors, `labelled` = _double(state): (loop_id i32[L], loop_head i32[L]
+    or None, length i32[L], dart_loop i32[B], start i32[L], n_open i64[]).  One host read: L.  Plain mode: a cycle's
+    label is its smallest tail and its loop's id.  Bow-tie mode passes `flag` (_tail_flag: the cycles that stay open),
+    `tail` and `head`: a label is a dart's name, and loop_id and loop_head are the tail and the head of that dart."""
+    B, dev = int(state.shape[0]), state.device
     L, stream = _m.lib(), _m.stream_ptr()
     keys = torch.empty(B + 1, dtype=torch.int32, device=dev)
-    _m.check(L.mslam_mesh_holes_labels(_m.ptr(labelled), B, _m.ptr(keys), stream), "mesh_holes_labels")
+    _m.check(L.mslam_mesh_holes_loop_labels(_m.ptr(labelled), _m.ptr(flag), B, _m.ptr(keys), stream),
+             "mesh_holes_loop_labels")
     runs, counts = torch.unique_consecutive(torch.sort(keys)[0], return_counts=True)
-    loop_id, length = runs[:-1].contiguous(), counts[:-1].to(torch.int32)         # the last run: the open darts, and one
-    nl = int(loop_id.shape[0])
+    loop_name, length = runs[:-1].contiguous(), counts[:-1].to(torch.int32)       # the last run: the open darts, and one
+    nl = int(loop_name.shape[0])
     dart_loop = torch.empty(B, dtype=torch.int32, device=dev)
-    start = torch.full((nl,), -1, dtype=torch.int32, device=dev)
-    _m.check(L.mslam_mesh_holes_assign(_m.ptr(labelled), _m.ptr(tail), B, _m.ptr(loop_id), nl, _m.ptr(dart_loop),
-                                       _m.ptr(start), stream), "mesh_holes_assign")
-    return loop_id, length, dart_loop, start, counts[-1] - 1
-
-
-def _trace(faces, V, F):
-    """The boundary of a mesh whose face indices lie in [0, V): dict of device tensors.  Two host reads."""
-    dev = faces.device
-    i32 = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
-    dart, tail, head = _darts(faces, V, F) if F and V else (i32(0), i32(0), i32(0))
-    B = int(dart.shape[0])
-    if B == 0:
-        return dict(dart=dart, tail=tail, head=head, state=torch.zeros((0, 2), dtype=torch.int32, device=dev),
-                    loop_id=i32(0), length=i32(0), dart_loop=i32(0), start=i32(0),
-                    n_open=torch.zeros((), dtype=torch.int64, device=dev))
-    state = _link(tail, head, V)
-    loop_id, length, dart_loop, start, n_open = _loops(_double(state, _rounds(B)), tail)
-    return dict(dart=dart, tail=tail, head=head, state=state, loop_id=loop_id, length=length, dart_loop=dart_loop,
-                start=start, n_open=n_open)
-
-
-def _double_ranks(rank, rounds):
-    """`rounds` rounds of the (successor, steps) doubling."""
-    B = int(rank.shape[0])
-    buf = [rank, torch.empty_like(rank)]
-    for r in range(rounds):
-        _m.check(_m.lib().mslam_mesh_holes_rank_double(_m.ptr(buf[r & 1]), _m.ptr(buf[~r & 1]), B, _m.stream_ptr()),
-                 "mesh_holes_rank_double")
-    return buf[rounds & 1]
+    named = flag is not None
+    unset = lambda: torch.full((nl,), -1, dtype=torch.int32, device=dev)
+    start = unset()
+    loop_id, loop_head = (unset(), unset()) if named else (None, None)
+    _m.check(L.mslam_mesh_holes_loop_assign(_m.ptr(labelled), _m.ptr(state), _m.ptr(flag), _m.ptr(tail), _m.ptr(head),
+                                            B, _m.ptr(loop_name), nl, _m.ptr(dart_loop), _m.ptr(start), _m.ptr(loop_id),
+                                            _m.ptr(loop_head), stream), "mesh_holes_loop_assign")
+    return loop_id if named else loop_name, loop_head, length, dart_loop, start, counts[-1] - 1
 
 
 def _pair(faces, V, F, dart, tail, head):
@@ -127,7 +111,7 @@ def _pair(faces, V, F, dart, tail, head):
     rank = pairs()
     _m.check(L.mslam_mesh_holes_rank_init(_m.ptr(state), _m.ptr(labelled), B, _m.ptr(rank), stream),
              "mesh_holes_rank_init")
-    rank = _double_ranks(rank, rounds)
+    rank = _double(rank, rounds, "mesh_holes_rank_double")  # (successor, steps)
     walk_keys = i64(B)
     _m.check(L.mslam_mesh_holes_walk_keys(_m.ptr(labelled), _m.ptr(rank), B, _m.ptr(walk_keys), stream),
              "mesh_holes_walk_keys")
@@ -142,46 +126,39 @@ def _pair(faces, V, F, dart, tail, head):
     return paired
 
 
-def _named_loops(paired, tail, head, V):
-    """(loop_id, loop_head, length i32[L], dart_loop i32[B], start i32[L], n_open i64[]) of the cycles of bow-tie mode's
-    next on which no vertex is a tail twice.  One host read: L."""
+def _tail_flag(labelled, tail, V):
+    """flag u8[B], by label: 1 for the cycles of bow-tie mode's next on which a vertex is a tail twice; they stay open."""
     B, dev = int(tail.shape[0]), tail.device
     L, stream = _m.lib(), _m.stream_ptr()
-    labelled = _double(paired, _rounds(B))
     tail_keys = torch.empty(B, dtype=torch.int64, device=dev)
     _m.check(L.mslam_mesh_holes_tail_keys(_m.ptr(labelled), _m.ptr(tail), B, V, _m.ptr(tail_keys), stream),
              "mesh_holes_tail_keys")
     tail_keys = torch.sort(tail_keys)[0]
     flag = torch.zeros(B, dtype=torch.uint8, device=dev)
     _m.check(L.mslam_mesh_holes_tail_flag(_m.ptr(tail_keys), B, V, _m.ptr(flag), stream), "mesh_holes_tail_flag")
-    keys = torch.empty(B + 1, dtype=torch.int32, device=dev)
-    _m.check(L.mslam_mesh_holes_loop_labels(_m.ptr(labelled), _m.ptr(flag), B, _m.ptr(keys), stream),
-             "mesh_holes_loop_labels")
-    runs, counts = torch.unique_consecutive(torch.sort(keys)[0], return_counts=True)
-    loop_name, length = runs[:-1].contiguous(), counts[:-1].to(torch.int32)
-    nl = int(loop_name.shape[0])
-    dart_loop = torch.empty(B, dtype=torch.int32, device=dev)
-    start, loop_id, loop_head = (torch.full((nl,), -1, dtype=torch.int32, device=dev) for _ in range(3))
-    _m.check(L.mslam_mesh_holes_loop_assign(_m.ptr(labelled), _m.ptr(paired), _m.ptr(flag), _m.ptr(tail), _m.ptr(head),
-                                            B, _m.ptr(loop_name), nl, _m.ptr(dart_loop), _m.ptr(start), _m.ptr(loop_id),
-                                            _m.ptr(loop_head), stream), "mesh_holes_loop_assign")
-    return loop_id, loop_head, length, dart_loop, start, counts[-1] - 1
+    return flag
 
 
-def _trace_bowties(faces, V, F):
-    """_trace in bow-tie mode: the same dict plus loop_head; `state` holds bow-tie mode's next.  Two host reads."""
+def _trace(faces, V, F, bowties=False):
+    """The boundary of a mesh whose face indices lie in [0, V): dict of device tensors; in bow-tie mode `state` holds that
+    mode's next and the dict has loop_head too.  Two host reads."""
     dev = faces.device
     i32 = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
     dart, tail, head = _darts(faces, V, F) if F and V else (i32(0), i32(0), i32(0))
     B = int(dart.shape[0])
     if B == 0:
-        return dict(dart=dart, tail=tail, head=head, state=torch.zeros((0, 2), dtype=torch.int32, device=dev),
-                    loop_id=i32(0), loop_head=i32(0), length=i32(0), dart_loop=i32(0), start=i32(0),
-                    n_open=torch.zeros((), dtype=torch.int64, device=dev))
-    state = _pair(faces, V, F, dart, tail, head)
-    loop_id, loop_head, length, dart_loop, start, n_open = _named_loops(state, tail, head, V)
-    return dict(dart=dart, tail=tail, head=head, state=state, loop_id=loop_id, loop_head=loop_head, length=length,
-                dart_loop=dart_loop, start=start, n_open=n_open)
+        state, n_open = torch.zeros((0, 2), dtype=torch.int32, device=dev), torch.zeros((), dtype=torch.int64, device=dev)
+        loop_id, loop_head, length, dart_loop, start = (i32(0) for _ in range(5))
+    else:
+        state = _pair(faces, V, F, dart, tail, head) if bowties else _link(tail, head, V)
+        labelled = _double(state, _rounds(B))
+        named = (_tail_flag(labelled, tail, V), tail, head) if bowties else ()
+        loop_id, loop_head, length, dart_loop, start, n_open = _loops(state, labelled, *named)
+    tr = dict(dart=dart, tail=tail, head=head, state=state, loop_id=loop_id, length=length, dart_loop=dart_loop,
+              start=start, n_open=n_open)
+    if bowties:
+        tr["loop_head"] = loop_head
+    return tr
 
 
 def _measure(verts, faces, V, F, tr, max_edges, all_perimeters):
@@ -244,7 +221,7 @@ def mesh_boundaries(faces, num_vertices, vertices=None, bowties=False, _validate
     else:
         faces, V, F = _faces_arg(faces, num_vertices, _validate, what)
         _m.ptr(faces)
-    tr = _trace_bowties(faces, V, F) if bowties else _trace(faces, V, F)
+    tr = _trace(faces, V, F, bowties)
     perimeter = None
     if vertices is not None:
         perimeter = _measure(verts, faces, V, F, tr, 0, True)[0]
@@ -296,7 +273,7 @@ def fill_holes(mesh, max_edges, return_info=False, bowties=False, _validate=True
         _check_finite(what, vlo, vhi, finite)
         _check_face_range(what, flo, fhi, V)
     dev = verts.device
-    tr = _trace_bowties(faces, V, F) if bowties else _trace(faces, V, F)
+    tr = _trace(faces, V, F, bowties)
     nl = int(tr["loop_id"].shape[0])
     perimeter, centre, fillable = _measure(verts, faces, V, F, tr, 0 if off else max_edges, return_info)
     out, filled = mesh, fillable.bool()

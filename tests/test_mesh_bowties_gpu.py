@@ -361,9 +361,10 @@ def test_room(device):
 # ----------------------------------------------------------------------------------------------------------------------
 # the C entry points of the pairing, operands in guarded allocations
 # ----------------------------------------------------------------------------------------------------------------------
-def _raw(device, mesh, spoil=None):
+def _raw(device, mesh, spoil=None, variants=False):
     """dkeys .. loop_assign through the C entry points.  `spoil`: a function that changes the numpy copy of the fan
-    successors before they are claimed."""
+    successors before they are claimed.  `variants`: the loops are found three more times, without a flag, without a flag
+    and the loop_id and loop_head outputs, and with the flag but without those outputs: got["variants"]."""
     import mslam_hip as _m
     from mast3r_slam.tsdf.mesh_holes import _darts, _rounds
     from mesh_support import Operands
@@ -429,22 +430,33 @@ def _raw(device, mesh, spoil=None):
     stail = put(torch.sort(tail_keys)[0], np.int64)
     flag = ops.put(np.zeros(B, np.uint8), np.uint8)
     _m.check(L.mslam_mesh_holes_tail_flag(_m.ptr(stail), B, nv, _m.ptr(flag), st), "tail_flag")
-    lab = ops.out(i32, (B + 1,))
-    _m.check(L.mslam_mesh_holes_loop_labels(_m.ptr(labelled2), _m.ptr(flag), B, _m.ptr(lab), st), "loop_labels")
-    runs, counts = torch.unique_consecutive(torch.sort(lab)[0], return_counts=True)
-    loop_name, length = put(runs[:-1], np.int32), counts[:-1].cpu().numpy()
-    nl = int(loop_name.shape[0])
-    dart_loop = ops.out(i32, (B,))
-    start, loop_id, loop_head = (ops.out(i32, (nl,)) for _ in range(3))
-    _m.check(L.mslam_mesh_holes_loop_assign(_m.ptr(labelled2), _m.ptr(paired), _m.ptr(flag), _m.ptr(tail),
-                                            _m.ptr(head), B, _m.ptr(loop_name), nl, _m.ptr(dart_loop), _m.ptr(start),
-                                            _m.ptr(loop_id), _m.ptr(loop_head), st), "loop_assign")
+    h = lambda t: t.cpu().numpy()
+
+    def find(flag, names=True):
+        """loop_labels .. loop_assign; `flag` and, with names=False, the loop_id and loop_head outputs may be None."""
+        lab = ops.out(i32, (B + 1,))
+        _m.check(L.mslam_mesh_holes_loop_labels(_m.ptr(labelled2), _m.ptr(flag), B, _m.ptr(lab), st), "loop_labels")
+        runs, counts = torch.unique_consecutive(torch.sort(lab)[0], return_counts=True)
+        loop_name, length = put(runs[:-1], np.int32), counts[:-1].cpu().numpy()
+        nl = int(loop_name.shape[0])
+        dart_loop, start = ops.out(i32, (B,)), ops.out(i32, (nl,))
+        loop_id, loop_head = (ops.out(i32, (nl,)), ops.out(i32, (nl,))) if names else (None, None)
+        _m.check(L.mslam_mesh_holes_loop_assign(_m.ptr(labelled2), _m.ptr(paired), _m.ptr(flag), _m.ptr(tail),
+                                                _m.ptr(head), B, _m.ptr(loop_name), nl, _m.ptr(dart_loop),
+                                                _m.ptr(start), _m.ptr(loop_id), _m.ptr(loop_head), st), "loop_assign")
+        out = dict(lab=h(lab), dart_loop=h(dart_loop), start=h(start), loop_length=length, n_open=int(counts[-1]) - 1)
+        if names:
+            out.update(loop_id=h(loop_id), loop_head=h(loop_head))
+        return out
+
+    got = find(flag)
+    if variants:
+        got["variants"] = dict(null_flag=find(None), null_flag_no_names=find(None, False), no_names=find(flag, False))
     ops.check()
     assert np.array_equal(f.cpu().numpy(), F)
-    h = lambda t: t.cpu().numpy()
-    return dict(keys=h(keys), rotated=rotated, fan=h(state)[:, 0], name=h(state)[:, 1], nxt=h(paired)[:, 0],
-                flag=h(flag), dart_loop=h(dart_loop), start=h(start), loop_id=h(loop_id), loop_head=h(loop_head),
-                loop_length=length, n_open=int(counts[-1]) - 1)
+    got.update(keys=h(keys), rotated=rotated, fan=h(state)[:, 0], name=h(state)[:, 1], nxt=h(paired)[:, 0],
+               flag=h(flag))
+    return got
 
 
 def _raw_against(got, tr):
@@ -517,6 +529,20 @@ def test_entry_points_with_broken_successors(device):
     assert got["loop_length"].tolist() == [len(tr["walks"][l]) for l in keep]
     assert got["start"].tolist() == [tr["walks"][l][0] for l in keep]
     assert np.array_equal(got["nxt"][~broken], tr["nxt"][~broken])
+
+
+def test_null_flag_is_a_zero_flag(device):
+    """Where both are defined (labels that are dart names), loop_labels and loop_assign without a flag are those with an
+    all-zero flag, and the loop_id and loop_head outputs may be left out; _raw checks the guards and the outputs."""
+    mesh = BT.hole_pairs(3)
+    got = _raw(device, mesh, variants=True)
+    assert not got["flag"].any() and len(got["start"]) >= 5
+    _raw_against(got, BT.trace(mesh[2], len(mesh[0])))
+    for name, other in got["variants"].items():
+        assert set(other) == {"lab", "dart_loop", "start", "loop_length", "n_open"} | (
+            {"loop_id", "loop_head"} if name == "null_flag" else set()), name
+        for k, v in other.items():
+            assert np.array_equal(v, got[k]), (name, k)
 
 
 def test_entry_points_reject_bad_arguments(device):

@@ -207,8 +207,10 @@ def test_entry_points_exist_without_a_device():
     # fill_holes of the five export functions, and the shape of their signatures: test_mesh_chain_cpu.py
     assert config["tsdf_global"]["mesh_fill_holes"] == 0
     declared = mslam_hip.exported_symbols()
-    for s in ("keys", "mark", "darts", "link", "double", "labels", "assign", "measure", "emit"):
+    for s in ("keys", "mark", "darts", "link", "double", "loop_labels", "loop_assign", "measure", "emit"):
         assert "mslam_mesh_holes_" + s in declared and hasattr(mslam_hip.lib(), "mslam_mesh_holes_" + s), s
+    for s in ("labels", "assign"):                                  # one loop finder serves both modes
+        assert "mslam_mesh_holes_" + s not in declared and not hasattr(mslam_hip.lib(), "mslam_mesh_holes_" + s), s
     mesh = (torch.zeros(3, 3), torch.zeros(3, 3), torch.tensor([[0, 1, 2]], dtype=torch.int32))
     for off in (None, 0, -1):
         assert tsdf.fill_holes(mesh, off) is mesh

@@ -236,13 +236,13 @@ def _raw(device, mesh, max_edges, spoil=None):
         _m.check(L.mslam_mesh_holes_double(_m.ptr(buf[cur]), _m.ptr(buf[nxt]), B, st), "double")
         cur = nxt
     lab = ops.out(i32, (B + 1,))
-    _m.check(L.mslam_mesh_holes_labels(_m.ptr(buf[cur]), B, _m.ptr(lab), st), "labels")
+    _m.check(L.mslam_mesh_holes_loop_labels(_m.ptr(buf[cur]), 0, B, _m.ptr(lab), st), "labels")
     runs, counts = torch.unique_consecutive(torch.sort(lab)[0], return_counts=True)
     loop_id, length = put(runs[:-1], np.int32), put(counts[:-1], np.int32)
     nl = int(loop_id.shape[0])
     dart_loop, start = ops.out(i32, (B,)), ops.out(i32, (nl,))
-    _m.check(L.mslam_mesh_holes_assign(_m.ptr(buf[cur]), _m.ptr(tail), B, _m.ptr(loop_id), nl, _m.ptr(dart_loop),
-                                       _m.ptr(start), st), "assign")
+    _m.check(L.mslam_mesh_holes_loop_assign(_m.ptr(buf[cur]), _m.ptr(state), 0, 0, 0, B, _m.ptr(loop_id), nl,
+                                            _m.ptr(dart_loop), _m.ptr(start), 0, 0, st), "assign")
     walked = state
     if spoil is not None:
         s = state.cpu().numpy().copy()
@@ -360,6 +360,34 @@ def test_entry_points_empty(device):
     assert L.mslam_mesh_holes_double(_m.ptr(s), _m.ptr(s), 4, _m.stream_ptr()) == einval
     assert L.mslam_mesh_holes_double(_m.ptr(s), _m.ptr(s.clone()), -1, _m.stream_ptr()) == einval
     assert L.mslam_mesh_holes_keys(0, 3, 3, 0, _m.stream_ptr()) == einval
+    k = torch.zeros(5, dtype=torch.int32, device=device)
+    for B in (4, -1):                                                # a null `labelled`, and a negative count
+        state = 0 if B > 0 else _m.ptr(s)
+        assert L.mslam_mesh_holes_loop_labels(state, 0, B, _m.ptr(k), _m.stream_ptr()) == einval
+        assert L.mslam_mesh_holes_loop_assign(state, _m.ptr(s), 0, 0, 0, B, _m.ptr(k), 1, _m.ptr(k), _m.ptr(k), 0, 0,
+                                              _m.stream_ptr()) == einval
+
+
+def _open_octahedron():
+    """An octahedron whose vertices are numbered so that one face is (3, 4, 5), without that face: B = 3, and the id of
+    the only loop, vertex 3, is not below B.  Plain mode's labels are vertices; only bow-tie mode's are dart names."""
+    P = np.array([[-1, 0, 0], [0, -1, 0], [0, 0, -1], [1, 0, 0], [0, 1, 0], [0, 0, 1]], np.float32)
+    F = []
+    for sx, sy, sz in np.ndindex(2, 2, 2):                          # 1: the positive end of the axis
+        f = [3 * sx, 1 + 3 * sy, 2 + 3 * sz]
+        F.append(f if (sx + sy + sz) % 2 else f[::-1])              # wound outwards
+    assert F[-1] == [3, 4, 5]
+    return H.with_attributes(P, F[:-1])
+
+
+def test_loop_id_not_below_the_dart_count(device):
+    mesh = _open_octahedron()
+    want = H.fill(mesh, 16, return_info=True)
+    info = want[-1]
+    assert info["n_boundary_edges"] == 3 and info["n_open"] == 0 and info["loop_filled"].tolist() == [True]
+    assert info["loop_id"].tolist() == [3] and info["loop_length"].tolist() == [3]
+    out = _check(mesh, device, 16, "open octahedron", want=want)
+    assert out[2].shape[0] == 10 and out[-1]["dart_loop"].tolist() == [0, 0, 0]
 
 
 # ----------------------------------------------------------------------------------------------------------------------

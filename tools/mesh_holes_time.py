@@ -71,7 +71,7 @@ def measure(verts, faces, label):
     print(f"  (a) dart_table_ms {timed(lambda: MH._darts(faces, V, F), args.reps)}", flush=True)
     print(f"  (b) link_ms {timed(lambda: MH._link(tail, head, V), args.reps)}", flush=True)
     print(f"  (b) doubling_{rounds}_rounds_ms {timed(lambda: MH._double(state, rounds), args.reps)}", flush=True)
-    print(f"  (c) loops_ms {timed(lambda: MH._loops(labelled, tail), args.reps)}", flush=True)
+    print(f"  (c) loops_ms {timed(lambda: MH._loops(state, labelled), args.reps)}", flush=True)
     print(f"  (d) measure_capped_ms "
           f"{timed(lambda: MH._measure(verts, faces, V, F, tr, args.max_edges, False), args.reps)}", flush=True)
     print(f"  (d) measure_every_perimeter_ms "
@@ -111,9 +111,14 @@ def bowties(verts, faces, label):
         return torch.sort(keys, stable=True)
 
     paired = MH._pair(faces, V, F, dart, tail, head)
+
+    def named_loops():
+        labelled = MH._double(paired, MH._rounds(B))
+        return MH._loops(paired, labelled, MH._tail_flag(labelled, tail, V), tail, head)
+
     print(f"  (f) {label} directed_keys_sort_ms {timed(directed, args.reps)}", flush=True)
     print(f"  (f) {label} pair_ms {timed(lambda: MH._pair(faces, V, F, dart, tail, head), args.reps)}", flush=True)
-    print(f"  (f) {label} named_loops_ms {timed(lambda: MH._named_loops(paired, tail, head, V), args.reps)}", flush=True)
+    print(f"  (f) {label} named_loops_ms {timed(named_loops, args.reps)}", flush=True)
 
 
 def quality(mesh, gt, label):
