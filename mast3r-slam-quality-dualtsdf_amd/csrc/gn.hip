@@ -1291,6 +1291,16 @@ __global__ void sim3_act_kernel(const float* __restrict__ T, const float* __rest
   Y[i * 3] = y[0]; Y[i * 3 + 1] = y[1]; Y[i * 3 + 2] = y[2];
 }
 
+// sim3_unit with the norm taken in double: every component is q_i / |q| rounded once to float, so | |q| - 1 | <= 2^-24.
+// The float32 form loses up to 5 x 2^-24 (2.1 observed).  Sim3.exp uses this one: it builds a rotation from nothing, so
+// the norm error is all its own.  inv, * and retr keep sim3_unit, whose bits the running system's poses depend on.
+__device__ __forceinline__ Sim3f sim3_unit_f64(Sim3f T) {
+  const double x = T.q[0], y = T.q[1], z = T.q[2], w = T.q[3];
+  const double inv = 1.0 / sqrt(x * x + y * y + z * z + w * w);
+  T.q[0] = (float)(x * inv); T.q[1] = (float)(y * inv); T.q[2] = (float)(z * inv); T.q[3] = (float)(w * inv);
+  return T;
+}
+
 __global__ void sim3_unary_kernel(int op, const float* __restrict__ A, const float* __restrict__ B,
                                   float* __restrict__ O, int n, int bcast_a, int bcast_b) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1305,7 +1315,8 @@ __global__ void sim3_unary_kernel(int op, const float* __restrict__ A, const flo
   } else {  // retr: exp(A=xi) * B
     R = sim3_retr(A + 7 * (bcast_a ? 0 : i), sim3_load(B + 8 * (bcast_b ? 0 : i)));
   }
-  sim3_store(O + 8 * i, sim3_unit(R));   // lietorch normalises the quaternion of every group element it constructs
+  // lietorch normalises the quaternion of every group element it constructs
+  sim3_store(O + 8 * i, op == 2 ? sim3_unit_f64(R) : sim3_unit(R));
 }
 }  // namespace mslam
 

@@ -66,8 +66,10 @@ class Sim3:
 
     # -- group ops ---------------------------------------------------------------------------
     def _binary(self, op, a, b):
-        a2 = a.reshape(-1, a.shape[-1]).contiguous()
-        b2 = b.reshape(-1, 8).contiguous()
+        """op(a, b) row by row; a batch of one broadcasts against the other's and the result takes the larger one's
+        shape.  The kernels read float32: any other dtype is converted, the result is float32."""
+        a2 = a.reshape(-1, a.shape[-1]).contiguous().float()
+        b2 = b.reshape(-1, 8).contiguous().float()
         n = max(a2.shape[0], b2.shape[0])
         if a2.shape[0] not in (1, n) or b2.shape[0] not in (1, n):
             raise RuntimeError(f"Sim3: cannot broadcast batch sizes {a2.shape[0]} and {b2.shape[0]}")
@@ -79,7 +81,7 @@ class Sim3:
         return Sim3(out.reshape(*lead, 8))
 
     def inv(self):
-        flat = self.data.reshape(-1, 8).contiguous()
+        flat = self.data.reshape(-1, 8).contiguous().float()
         out = torch.empty_like(flat)
         rc = _m.lib().mslam_sim3_op(0, _m.ptr(flat), 0, _m.ptr(out), flat.shape[0], 0, 0, _m.stream_ptr())
         _m.check(rc, "Sim3.inv")
@@ -90,12 +92,19 @@ class Sim3:
 
     def retr(self, xi):
         """exp(xi) * self  (left retraction; lietorch's .retr, tracker.py:247)."""
-        return self._binary(3, xi.float(), self.data)
+        return self._binary(3, xi, self.data)
 
     def act(self, X):
-        """s*R*X + t.  self.data (...,8) broadcast against X (...,3): either one pose for all
-        points (tracker.py:150) or one pose per leading batch entry (tsdf_refine.py:864)."""
-        poses = self.data.reshape(-1, 8).contiguous()
+        """s*R*X + t.  self.data (...,8) against X (...,3): the pose batch shape, trailing size-1 dimensions dropped,
+        must be a prefix of X.shape[:-1]; each pose acts on the points under its index.  So one pose for all points
+        (tracker.py:150) and (N,1) poses against (N,P,3) (tsdf_refine.py:864) both pass; anything else raises."""
+        batch = tuple(self.data.shape[:-1])
+        while batch and batch[-1] == 1:
+            batch = batch[:-1]
+        if batch != tuple(X.shape[:len(batch)]) or X.dim() < len(batch) + 1 or X.shape[-1] != 3:
+            raise RuntimeError(f"Sim3.act: poses of shape {tuple(self.data.shape[:-1])} do not lead points of shape "
+                               f"{tuple(X.shape[:-1])}")
+        poses = self.data.reshape(-1, 8).contiguous().float()
         Xc = X.contiguous().float()
         pts = Xc.reshape(-1, 3)
         Y = torch.empty_like(pts)
@@ -103,8 +112,6 @@ class Sim3:
         if npose == 1:
             rc = _m.lib().mslam_sim3_act(_m.ptr(poses), _m.ptr(pts), _m.ptr(Y), 1, pts.shape[0], 1, _m.stream_ptr())
         else:
-            if pts.shape[0] % npose != 0:
-                raise RuntimeError(f"Sim3.act: {npose} poses do not divide {pts.shape[0]} points")
             rc = _m.lib().mslam_sim3_act(_m.ptr(poses), _m.ptr(pts), _m.ptr(Y), npose, pts.shape[0] // npose, 0,
                                          _m.stream_ptr())
         _m.check(rc, "Sim3.act")

@@ -5,8 +5,9 @@ d(ray, dist)/dP or d(u, v, log z)/dP times dP/dxi = [I, -[P]x, P], A = robust J,
 expanded rows.  numpy / scipy only; nothing here touches the device.  Pinned on its own in tests/test_tracker_ref_cpu.py
 (golden normal equations, finite differences of the cost, float32 baselines)."""
 import numpy as np
-import scipy.linalg
-from scipy.spatial.transform import Rotation
+
+# the float64 Sim3 group has one statement, tests/sim3_ref.py; this module's users keep finding it here
+from sim3_ref import sim3_exp, sim3_from_matrix, sim3_generator, sim3_log, sim3_matrix, sim3_retr  # noqa: F401
 
 CHUNK = 65536
 
@@ -38,49 +39,6 @@ def roundtrip_tol(tau):
     tau = np.asarray(tau, np.float64)
     sigma = max(abs(tau[6]), 1e-6)
     return 5e-7 * max(1.0, np.linalg.norm(tau)) + 2.0 ** -23 * np.linalg.norm(tau[:3]) / sigma
-
-
-# ---- Sim3 in float64 --------------------------------------------------------------------------------------------------
-def sim3_matrix(T):
-    """4x4 similarity [[s R, t], [0, 1]] of a pose [t(3), q(xyzw), s]."""
-    T = np.asarray(T, np.float64)
-    M = np.eye(4)
-    M[:3, :3] = T[7] * Rotation.from_quat(T[3:7]).as_matrix()
-    M[:3, 3] = T[:3]
-    return M
-
-
-def sim3_from_matrix(M):
-    s = np.cbrt(np.linalg.det(M[:3, :3]))
-    q = Rotation.from_matrix(M[:3, :3] / s).as_quat()
-    return np.concatenate([M[:3, 3], q, [s]])
-
-
-def sim3_generator(xi):
-    xi = np.asarray(xi, np.float64)
-    G = np.zeros((4, 4))
-    p = xi[3:6]
-    G[:3, :3] = np.array([[0, -p[2], p[1]], [p[2], 0, -p[0]], [-p[1], p[0], 0]]) + xi[6] * np.eye(3)
-    G[:3, 3] = xi[:3]
-    return G
-
-
-def sim3_exp(xi):
-    """Pose [t, q, s] of exp(xi), xi = [tau(3), phi(3), sigma]."""
-    return sim3_from_matrix(scipy.linalg.expm(sim3_generator(xi)))
-
-
-def sim3_retr(xi, T):
-    """exp(xi) * T."""
-    return sim3_from_matrix(scipy.linalg.expm(sim3_generator(xi)) @ sim3_matrix(T))
-
-
-def sim3_log(T1, T0):
-    """The xi with exp(xi) * T0 = T1, in float64: matrix logarithm of M(T1) M(T0)^-1."""
-    G = np.real(scipy.linalg.logm(sim3_matrix(T1) @ np.linalg.inv(sim3_matrix(T0))))
-    A = G[:3, :3]
-    W = 0.5 * (A - A.T)
-    return np.array([G[0, 3], G[1, 3], G[2, 3], W[2, 1], W[0, 2], W[1, 0], np.trace(A) / 3.0])
 
 
 # ---- one GN step --------------------------------------------------------------------------------------------------------
