@@ -752,6 +752,40 @@ int mslam_cloud_normals(const float* points, int num_points, const int32_t* neig
                         int viewpoint_stride, float* normals, float* curvature, int32_t* count, double* moments,
                         void* stream);
 
+/* Cloud views: the z-buffer splat of a cloud into pinhole views and the observed part of a cloud (no counterpart in the
+ * reference, DESIGN.md "Cloud views"; the definition is tests/cloudview_numpy.py; csrc/cloud_view.hip).  A view is a
+ * pose f32[8] (Sim3 [t,q,s], world from camera), the pinhole fx, fy, cx, cy and an image of h x w, h w num_views < 2^31.
+ * All in f64 on the f32 inputs: v = p - t, X = R(q)^T v, r = |v|, u = fx X0 / X2 + cx, v = fy X1 / X2 + cy; p is IN the
+ * view when its coordinates are finite, X2 > 0, -0.5 <= u < w - 0.5, -0.5 <= v < h - 0.5 and near <= r <= far (world
+ * units); its pixel is (floor(u + 0.5), floor(v + 0.5)).
+ *   mslam_cloud_view_splat    zbuf u64[num_views,h,w], set to all ones (empty) here, on the stream, and then, per view,
+ *                             lowered at every pixel of the square |dx|, |dy| <= rho around the pixel of every point in
+ *                             view, clipped to the image, to the minimum of (bits of f32(r)) << 32 | index: the nearest
+ *                             f32 range wins, then the lowest index; the same bytes on every call.  rho = radius, or with
+ *                             point_size >= 0 (a world-unit diameter; negative: none) min(max_radius, max(radius,
+ *                             floor(0.5 point_size max(fx, fy) / X2))), the min taken in f64.  0 <= radius <= max_radius
+ *                             <= MSLAM_CLOUD_VIEW_MAX_RADIUS.  counters (NULL outside measurements): u64[2], the
+ *                             footprint pixels visited and the atomics issued are ADDED to it.
+ *   mslam_cloud_view_resolve  per pixel of zbuf: hit u8 (not empty), index i32 (-1 on a miss), range f32 = f32(f64(r32) /
+ *                             s) for the view's scale s, so that range * ray is the camera-frame point (0 on a miss);
+ *                             with colors u8[num_points,3], rgb u8[num_views,h,w,3], the winner's colour, 0 on a miss
+ *                             (NULL together).
+ *   mslam_cloud_view_visible  seen u8[num_queries]: set to 1 where, for some view, the query is in the view and its own
+ *                             pixel is empty or f64(f32(r_query)) <= f64(r32 of the pixel) (1 + rel_tol) + tol.  `seen`
+ *                             is the caller's: it is never cleared, and a query that is already marked is not looked at.
+ * Bad arguments (a negative size, radius > max_radius, max_radius > 8, h w num_views >= 2^31, near > far, a negative
+ * tolerance) return MSLAM_EINVAL and nothing is written. */
+#define MSLAM_CLOUD_VIEW_MAX_RADIUS 8
+int mslam_cloud_view_splat(const float* points, int num_points, const float* poses, int num_views, double fx, double fy,
+                           double cx, double cy, int h, int w, double near, double far, int radius, double point_size,
+                           int max_radius, uint64_t* zbuf, uint64_t* counters, void* stream);
+int mslam_cloud_view_resolve(const uint64_t* zbuf, const float* poses, int num_views, int h, int w,
+                             const uint8_t* colors, int num_points, float* range, int32_t* index, uint8_t* hit,
+                             uint8_t* rgb, void* stream);
+int mslam_cloud_view_visible(const float* queries, int num_queries, const uint64_t* zbuf, const float* poses,
+                             int num_views, double fx, double fy, double cx, double cy, int h, int w, double near,
+                             double far, double tol, double rel_tol, uint8_t* seen, void* stream);
+
 /* Mesh textures: keyframe images baked into a per-face atlas, and the shading of a ray cast (no counterpart in the
  * reference, DESIGN.md "Mesh textures"; the definition is tests/texture_numpy.py).  The atlas is a pure function of
  * (F, texels = R >= 4): face f is half f & 1 of cell f >> 1, a cell is R + 1 texels wide and R high, the cells lie

@@ -508,7 +508,8 @@ class SlamSystem:
         return points, color, cloud_normals(points, normals, viewpoint=viewpoint)[0]
 
     def evaluate_cloud(self, gt_points, threshold=None, voxel=None, align=None, init=None, gt_positions=None,
-                       align_kw=None, index=None, conf_threshold=None, outliers=None, normals=None):
+                       align_kw=None, index=None, conf_threshold=None, outliers=None, normals=None, observed=False,
+                       gt_K=None):
         """Quality of the map's point cloud (self.keyframe_cloud(conf_threshold)) against a ground-truth cloud gt_points
         f32[N,3] (a numpy array or a device tensor; a laser scan needs no faces): the dict of tsdf.compare_clouds
         (DESIGN.md "Point clouds").  `threshold` and `voxel` default to the global TSDF's voxel size (the config's when
@@ -516,7 +517,13 @@ class SlamSystem:
         cell; voxel=0 scores the raw clouds.  `align`, `init` ("trajectory" with `gt_positions` for
         self.align_trajectory), `align_kw` and `index` (None or True) as in evaluate_mesh, with tsdf.align_clouds in the
         place of align_meshes.  `outliers`: a dict for tsdf.cloud_outliers, applied to the map's raw cloud first
-        (keyframe_cloud); `normals`: k, for compare_clouds' normal-consistency figures."""
+        (keyframe_cloud); `normals`: k, for compare_clouds' normal-consistency figures.
+
+        `observed=True`: only the part of the ground truth that some keyframe sees, the thinned ground-truth cloud itself
+        the occluder, enters completion, recall, fscore and chamfer (compare_clouds(observed=...), DESIGN.md "Cloud
+        views"): the cameras are the keyframes' T_WC, moved by the alignment, with the pinhole `gt_K` (3,3) or else the
+        system's calibration at the keyframes' image size.  Without either it raises: the ray-image camera model has no
+        projection.  A dict instead of True overrides entries of compare_clouds' `observed` (point_size, tol, ...)."""
         from mast3r_slam.tsdf import compare_clouds
 
         vs = float(self.tsdf_manager.volume.voxel_size if self.tsdf_manager is not None
@@ -530,7 +537,77 @@ class SlamSystem:
             kw["index"] = index
         if normals is not None:
             kw["normals"] = normals
+        if observed is not False and observed is not None:
+            K, poses, hw = self._keyframe_pinholes("SlamSystem.evaluate_cloud", gt_K, "observed=True")
+            kw["observed"] = dict(dict(poses=poses, K=K, hw=hw, frame="pred"),
+                                  **(observed if isinstance(observed, dict) else {}))
         return compare_clouds(points, gt, threshold=threshold, voxel=voxel if voxel > 0.0 else None, **kw)
+
+    def _keyframe_pinholes(self, what, gt_K, asked):
+        """(K, the keyframes' poses [n,8], (h, w) of the newest keyframe) for the cloud views; K is `gt_K` or else the
+        system's calibration.  Raises without a pinhole and without a keyframe."""
+        K = gt_K if gt_K is not None else self.K
+        n_kf = len(self.keyframes)
+        if K is None:
+            raise ValueError(f"{what}: {asked} needs a pinhole camera, gt_K or the system's calibration: the ray-image "
+                             "camera model has no projection")
+        if n_kf == 0:
+            raise RuntimeError(f"{what}: {asked} needs at least one keyframe")
+        poses = torch.stack([self.keyframes[i].T_WC.data.reshape(8) for i in range(n_kf)])
+        hw = tuple(int(x) for x in self.keyframes[n_kf - 1].img_shape.reshape(-1)[:2].tolist())
+        return K, poses, hw
+
+    def evaluate_cloud_depth(self, gt_points, point_size=None, align=None, near=0.05, far=10.0, gt_K=None):
+        """ "Depth L1" against a laser scan: for every keyframe, the view of the global TSDF (TSDFVolume.render) against
+        the z-buffer splat of the ground-truth cloud gt_points f32[N,3] (tsdf.render_cloud; a numpy array or a device
+        tensor) from the same camera through the same pinhole - `gt_K` (3,3) or else the system's calibration; without
+        either it raises, a splat needs a projection.  `point_size`: the world-unit diameter of a ground-truth point,
+        default twice the TSDF's voxel size (times the alignment's scale).  `align`, `near`, `far` and the returned
+        dict - depth_l1, depth_l1_median, both_hit_share, n_pixels - as in evaluate_depth, with the same handling of
+        scale.  Drains the backend first."""
+        what = "SlamSystem.evaluate_cloud_depth"
+        if self.tsdf_manager is None:
+            raise RuntimeError(f"{what}: the global TSDF is disabled (tsdf_global.enabled = False)")
+        from mast3r_slam.tsdf import render_cloud
+        from mast3r_slam.tsdf.mesh_raycast import compose_sim3
+
+        self.drain()
+        K, poses, _ = self._keyframe_pinholes(what, gt_K, "a cloud view")
+        gt = torch.as_tensor(gt_points, dtype=torch.float32).to(self.device).reshape(-1, 3).contiguous()
+        T = None if align is None else torch.as_tensor(getattr(align, "data", align)).detach().double().cpu().reshape(8)
+        a_scale = 1.0 if T is None else float(T[7])
+        if point_size is None:
+            point_size = 2.0 * float(self.tsdf_manager.volume.voxel_size) * a_scale
+        diffs, n_pixels = [], 0
+        for i in range(len(self.keyframes)):
+            kf = self.keyframes[i]
+            hw = tuple(int(x) for x in kf.img_shape.reshape(-1)[:2].tolist())
+            pose = kf.T_WC.data.detach().reshape(8)
+            moved = pose.double().cpu() if T is None else compose_sim3(T, pose.double().cpu().reshape(1, 8))[0]
+            r_map, _, hit_map = self.tsdf_manager.render(pose, near=near / a_scale, far=far / a_scale, K=K, hw=hw)[:3]
+            r_gt, _, hit_gt = render_cloud(gt, moved, K, hw, near=near, far=far, point_size=point_size)
+            both = hit_map & hit_gt
+            diffs.append((r_map.double() - r_gt.double()).abs()[both] * float(moved[7]))
+            n_pixels += hw[0] * hw[1]
+        d = torch.sort(torch.cat(diffs))[0]
+        m = int(d.numel())
+        l1, med = (float("nan"),) * 2 if m == 0 else torch.stack((d.sum() / m, 0.5 * (d[(m - 1) // 2] + d[m // 2]))).tolist()
+        return dict(depth_l1=l1, depth_l1_median=med, both_hit_share=m / n_pixels, n_pixels=n_pixels)
+
+    def render_cloud_view(self, pose=None, **kw):
+        """The map's own cloud seen from a camera: tsdf.render_cloud of self.keyframe_cloud() with its colours ->
+        (range f32[h,w], index i32[h,w], hit bool[h,w], rgb u8[h,w,3]).  `pose=None`: the newest keyframe's pose.
+        `kw`: render_cloud's K, hw, near, far, radius, point_size, max_radius, and keyframe_cloud's conf_threshold and
+        voxel; K and hw default to the system's calibration and the newest keyframe's image size, and without a pinhole
+        it raises."""
+        what = "SlamSystem.render_cloud_view"
+        from mast3r_slam.tsdf import render_cloud
+
+        cloud_kw = {k: kw.pop(k) for k in ("conf_threshold", "voxel") if k in kw}
+        points, colors = self.keyframe_cloud(**cloud_kw)                     # drains the backend
+        K, poses, hw = self._keyframe_pinholes(what, kw.pop("K", None), "a cloud view")
+        pose = poses[-1] if pose is None else torch.as_tensor(getattr(pose, "data", pose)).reshape(-1)    # one view
+        return render_cloud(points, pose, K, kw.pop("hw", None) or hw, colors=colors, **kw)
 
     def evaluate_depth(self, gt_vertices, gt_faces, align=None, near=0.05, far=10.0, index=None):
         """The "Depth L1" figure of dense-SLAM evaluations: for every keyframe, the view of the global TSDF

@@ -2,7 +2,8 @@
 trimmed point-to-point ICP and the accuracy / completion / precision / recall / F-score / Chamfer figures between two
 clouds - what scores the product's own output (evaluate.save_reconstruction's cloud) against a scan without faces.
 Below them the k nearest neighbours under a total order, and what stands on them: normals, the statistical and the
-radius outlier rule, the normal-consistency figures of compare_clouds.
+radius outlier rule, the normal-consistency figures of compare_clouds.  The views of a cloud and the observed part that
+compare_clouds(observed=...) scores are cloud_view.py's.
 
 No counterpart in the reference.  The kernels are csrc/cloud.hip and csrc/cloud_knn.hip (DESIGN.md "Point clouds"); the
 numpy statements of the same definitions are tests/cloud_numpy.py and tests/cloud_knn_numpy.py.  A cloud is points f32[N,3]; a point is valid when its three coordinates are
@@ -267,7 +268,7 @@ def _direction(queries, points, index, threshold, max_dist, scan=None):
 
 
 def compare_clouds(pred, gt, threshold=0.05, voxel=None, max_dist=None, align=None, align_kw=None, index=None,
-                   normals=None):
+                   normals=None, observed=None):
     """Quality of the cloud `pred` against the ground-truth cloud `gt` (f32[N,3] device tensors, one frame): the figure
     set of compare_meshes, from the points themselves.  Returns Python numbers: accuracy / accuracy_median /
     accuracy_rmse (every valid pred point to its nearest gt point: mean, median, root mean square), completion /
@@ -292,7 +293,17 @@ def compare_clouds(pred, gt, threshold=0.05, voxel=None, max_dist=None, align=No
     `normals`: None, or k - cloud_normals(., k) of both clouds after thinning and alignment, and the dict gains
     normal_consistency_accuracy / normal_consistency_completion (the mean of |n_query . n_nearest| over a direction's
     pairs within `max_dist` whose two normals are non-zero; NaN without one), normal_consistency (their mean) and
-    n_normal_pairs (the pairs of both directions)."""
+    n_normal_pairs (the pairs of both directions).
+
+    `observed`: None - every ground-truth point counts; a dict with `poses` (n Sim3s, world from camera), `K` (3,3),
+    `hw` and optionally `near`, `far`, `tol`, `rel_tol`, `radius`, `point_size`, `max_radius` (cloud_view.
+    observed_cloud_points) and `frame` - only the ground-truth points that some camera sees, the thinned ground-truth
+    cloud itself the occluder, enter completion, recall, fscore, chamfer and the completion half of the normal
+    consistency (DESIGN.md "Cloud views"); n_gt counts them.  `frame`: "gt" (default) - the poses lie in the ground
+    truth's frame; "pred" - in pred's, and the alignment transform moves them first.  `point_size` defaults to
+    2 `voxel` (after thinning the spacing is about one voxel and a cell's diagonal is below two); without `voxel`,
+    `point_size` and `radius` it raises.  The dict gains gt_observed_share (of the valid ground-truth points) and
+    n_gt_observed; ValueError when no point is observed (one more host read).  Accuracy and precision do not change."""
     what = "compare_clouds"
     if normals is not None:
         normals = _k_arg(normals, what, "normals")
@@ -315,18 +326,28 @@ def compare_clouds(pred, gt, threshold=0.05, voxel=None, max_dist=None, align=No
     if T is not None:
         pred = transform_cloud(pred, T)
     p_index = CloudIndex(pred) if g_index is not None else None
+    gt_all, seen = gt, None
+    if observed is not None:
+        from .cloud_view import _observed_cloud
+
+        seen = _observed_cloud(what, gt, observed, T, voxel)
+        n_all = _valid(gt).sum()
+        gt = gt[seen].contiguous()
+        n_obs, n_all = int(gt.shape[0]), int(n_all)                              # a host read
+        if n_obs == 0:
+            raise ValueError(f"{what}: no ground-truth point is observed by the given cameras")
     if normals is None:
-        figures = _direction(pred, gt, g_index, threshold, limit) + _direction(gt, pred, p_index, threshold, limit)
+        figures = _direction(pred, gt_all, g_index, threshold, limit) + _direction(gt, pred, p_index, threshold, limit)
         consistency = []
     else:
         # the normals' own k-NN is always indexed: the same bits as the plain scan, and not quadratic
         n_pred_, n_gt_ = (cloud_normals(c, normals, index=ix if ix is not None else True)[0]
-                          for c, ix in ((pred, p_index), (gt, g_index)))
-        acc_scan, comp_scan = _distance2(pred, gt, g_index), _distance2(gt, pred, p_index)
-        figures = (_direction(pred, gt, g_index, threshold, limit, acc_scan)
+                          for c, ix in ((pred, p_index), (gt_all, g_index)))
+        acc_scan, comp_scan = _distance2(pred, gt_all, g_index), _distance2(gt, pred, p_index)
+        figures = (_direction(pred, gt_all, g_index, threshold, limit, acc_scan)
                    + _direction(gt, pred, p_index, threshold, limit, comp_scan))
         consistency = (_normal_consistency(acc_scan, n_pred_, n_gt_, limit)
-                       + _normal_consistency(comp_scan, n_gt_, n_pred_, limit))
+                       + _normal_consistency(comp_scan, n_gt_ if seen is None else n_gt_[seen], n_pred_, limit))
     (acc, acc_med, acc_rms, prec, acc_out, n_pred, comp, comp_med, comp_rms, rec, comp_out,
      n_gt, *consistency) = torch.stack(figures + consistency).tolist()       # the one host read of the figures
     if n_pred == 0 or n_gt == 0:
@@ -338,6 +359,8 @@ def compare_clouds(pred, gt, threshold=0.05, voxel=None, max_dist=None, align=No
                completion_outliers=int(comp_out))
     if alignment is not None:
         out["alignment"] = alignment
+    if observed is not None:
+        out.update(gt_observed_share=n_obs / n_all, n_gt_observed=n_obs)
     if normals is not None:
         nc_acc, pairs_acc, nc_comp, pairs_comp = consistency
         out.update(normal_consistency_accuracy=nc_acc, normal_consistency_completion=nc_comp,
