@@ -15,17 +15,12 @@
 // footprint loop issues one 64-bit no-return atomic minimum per pixel it has to lower, and none where the pixel already
 // holds a key that is not above its own (see cv_splat_kernel).  No LDS, no returned atomic, no compare-and-swap loop.
 #include "common.h"
+#include "view.h"
 
 namespace mslam {
 
 constexpr int kCvBlock = 256;
 constexpr unsigned long long kCvEmpty = ~0ull;
-
-struct CvCamera {
-  double fx, fy, cx, cy;
-  int h, w;
-  double near, far;
-};
 
 struct CvProjection {
   bool in_view;
@@ -33,39 +28,27 @@ struct CvProjection {
   double r, z;
 };
 
-// A point against one view: v = p - o, X = rotate(conj q, v) grouped as raycast_numpy.rotate groups it, r = |v|,
-// u = fx X0 / X2 + cx, v = fy X1 / X2 + cy; in view when X2 > 0, the pixel lies in the image (centres at integers) and
-// near <= r <= far.  Every comparison is false on a NaN, and a point with a non-finite coordinate is in no view.
+// A cloud point against one view (view.h view_project, with its grouping of sums): a point with a non-finite coordinate
+// is in no view, and the pixel is the nearest centre.
 __device__ __forceinline__ CvProjection cv_project(const float* __restrict__ p3, const float* __restrict__ pose8,
-                                                   const CvCamera& c) {
+                                                   const ViewCamera& c) {
   CvProjection out;
-  const double p0 = (double)p3[0], p1 = (double)p3[1], p2 = (double)p3[2];
-  const double v0 = p0 - (double)pose8[0], v1 = p1 - (double)pose8[1], v2 = p2 - (double)pose8[2];
-  const double q0 = -(double)pose8[3], q1 = -(double)pose8[4], q2 = -(double)pose8[5], q3 = (double)pose8[6];
-  const double u0 = 2.0 * (q1 * v2 - q2 * v1);
-  const double u1 = 2.0 * (q2 * v0 - q0 * v2);
-  const double u2 = 2.0 * (q0 * v1 - q1 * v0);
-  const double X0 = (v0 + q3 * u0) + (q1 * u2 - q2 * u1);
-  const double X1 = (v1 + q3 * u1) + (q2 * u0 - q0 * u2);
-  const double X2 = (v2 + q3 * u2) + (q0 * u1 - q1 * u0);
-  const double r = sqrt((v0 * v0 + v1 * v1) + v2 * v2);
-  const double u = c.fx * X0 / X2 + c.cx;
-  const double v = c.fy * X1 / X2 + c.cy;
-  const bool finite = fabs(p0) < INFINITY && fabs(p1) < INFINITY && fabs(p2) < INFINITY;
-  out.in_view = finite && X2 > 0.0 && u >= -0.5 && u < (double)c.w - 0.5 && v >= -0.5 && v < (double)c.h - 0.5 &&
-                r >= c.near && r <= c.far;
+  const double p[3] = {(double)p3[0], (double)p3[1], (double)p3[2]};
+  const ViewProjection pr = view_project(p, pose8, c);
+  const bool finite = fabs(p[0]) < INFINITY && fabs(p[1]) < INFINITY && fabs(p[2]) < INFINITY;
+  out.in_view = finite && pr.in_view;
   // in view, u + 0.5 lies in [0, w): the min is a guard against an index outside the image and changes no value
-  out.px = out.in_view ? min((int)floor(u + 0.5), c.w - 1) : 0;
-  out.py = out.in_view ? min((int)floor(v + 0.5), c.h - 1) : 0;
-  out.r = r;
-  out.z = X2;
+  out.px = out.in_view ? min((int)floor(pr.u + 0.5), c.w - 1) : 0;
+  out.py = out.in_view ? min((int)floor(pr.v + 0.5), c.h - 1) : 0;
+  out.r = pr.r;
+  out.z = pr.z;
   return out;
 }
 
 // kCount: a measurement build of the same loop; counters[0] += footprint pixels visited, counters[1] += atomics issued.
 template <bool kCount>
 __global__ __launch_bounds__(kCvBlock) void cv_splat_kernel(const float* __restrict__ points, int n,
-                                                            const float* __restrict__ poses, CvCamera cam, int radius,
+                                                            const float* __restrict__ poses, ViewCamera cam, int radius,
                                                             double half_size_f, int max_radius,
                                                             unsigned long long* __restrict__ zbuf,
                                                             unsigned long long* __restrict__ counters) {
@@ -146,7 +129,7 @@ __global__ __launch_bounds__(kCvBlock) void cv_resolve_kernel(const unsigned lon
 // of this one) has marked leaves at once; `seen` is never cleared here.
 __global__ __launch_bounds__(kCvBlock) void cv_visible_kernel(const float* __restrict__ queries, int m,
                                                               const unsigned long long* __restrict__ zbuf,
-                                                              const float* __restrict__ poses, CvCamera cam, double tol,
+                                                              const float* __restrict__ poses, ViewCamera cam, double tol,
                                                               double rel_tol, uint8_t* __restrict__ seen) {
   const long long i = (long long)blockIdx.x * kCvBlock + threadIdx.x;
   const int view = blockIdx.y;
@@ -163,30 +146,18 @@ __global__ __launch_bounds__(kCvBlock) void cv_visible_kernel(const float* __res
 
 using namespace mslam;
 
-static bool cv_finite(double x) { return x - x == 0.0; }
-
-// the checks the three entry points share; MSLAM_OK or MSLAM_EINVAL with the error text set
-static int cv_check_views(const char* what, int num_views, double fx, double fy, double cx, double cy, int h, int w,
-                          double near, double far) {
-  MSLAM_REQUIRE(num_views >= 0 && h >= 0 && w >= 0, "%s: negative size", what);
-  MSLAM_REQUIRE((int64_t)h * w < (1ll << 31) && (int64_t)h * w * num_views < (1ll << 31) && num_views <= 65535,
-                "%s: %d views of %d x %d pixels are outside the int32 index range", what, num_views, h, w);
-  MSLAM_REQUIRE(cv_finite(fx) && cv_finite(fy) && cv_finite(cx) && cv_finite(cy), "%s: non-finite intrinsics", what);
-  MSLAM_REQUIRE(near <= far, "%s: near must not exceed far", what);
-  return MSLAM_OK;
-}
-
 extern "C" int mslam_cloud_view_splat(const float* points, int num_points, const float* poses, int num_views, double fx,
                                       double fy, double cx, double cy, int h, int w, double near, double far,
                                       int radius, double point_size, int max_radius, uint64_t* zbuf, uint64_t* counters,
                                       void* stream) {
   const char* what = "cloud_view_splat";
   MSLAM_REQUIRE(num_points >= 0, "%s: negative size", what);
-  if (int rc = cv_check_views(what, num_views, fx, fy, cx, cy, h, w, near, far)) return rc;
+  const double K4[4] = {fx, fy, cx, cy};
+  if (int rc = view_check(what, num_views, h, w, K4, near, far, false)) return rc;
   MSLAM_REQUIRE(0 <= radius && radius <= max_radius && max_radius <= MSLAM_CLOUD_VIEW_MAX_RADIUS,
                 "%s: need 0 <= radius <= max_radius <= %d, got %d and %d", what, MSLAM_CLOUD_VIEW_MAX_RADIUS, radius,
                 max_radius);
-  MSLAM_REQUIRE(point_size < 0.0 || cv_finite(point_size), "%s: point_size must be finite (negative: none)", what);
+  MSLAM_REQUIRE(point_size < 0.0 || view_finite(point_size), "%s: point_size must be finite (negative: none)", what);
   const size_t pixels = (size_t)num_views * h * w;
   if (pixels == 0) return MSLAM_OK;
   MSLAM_REQUIRE(zbuf && poses && (points || num_points == 0), "%s: null pointer", what);
@@ -194,7 +165,7 @@ extern "C" int mslam_cloud_view_splat(const float* points, int num_points, const
                          "cloud_view_splat memset"))
     return rc;
   if (num_points == 0) return MSLAM_OK;
-  const CvCamera cam = {fx, fy, cx, cy, h, w, near, far};
+  const ViewCamera cam = {fx, fy, cx, cy, h, w, near, far};
   const double half_size_f = point_size < 0.0 ? -1.0 : 0.5 * point_size * (fx > fy ? fx : fy);
   const dim3 grid(blocks_for(num_points, kCvBlock), (unsigned)num_views);
   hipLaunchKernelGGL(counters ? cv_splat_kernel<true> : cv_splat_kernel<false>, grid, dim3(kCvBlock), 0,
@@ -209,7 +180,7 @@ extern "C" int mslam_cloud_view_resolve(const uint64_t* zbuf, const float* poses
                                         uint8_t* hit, uint8_t* rgb, void* stream) {
   const char* what = "cloud_view_resolve";
   MSLAM_REQUIRE(num_points >= 0, "%s: negative size", what);
-  if (int rc = cv_check_views(what, num_views, 1.0, 1.0, 0.0, 0.0, h, w, 0.0, 0.0)) return rc;
+  if (int rc = view_check(what, num_views, h, w, nullptr, 0.0, 0.0, false)) return rc;
   // the colours of an empty cloud may be a null pointer: nothing is read from them
   MSLAM_REQUIRE(rgb ? (colors || num_points == 0) : !colors, "%s: colors and rgb go together", what);
   const int64_t total = (int64_t)num_views * h * w;
@@ -228,11 +199,12 @@ extern "C" int mslam_cloud_view_visible(const float* queries, int num_queries, c
                                         void* stream) {
   const char* what = "cloud_view_visible";
   MSLAM_REQUIRE(num_queries >= 0, "%s: negative size", what);
-  if (int rc = cv_check_views(what, num_views, fx, fy, cx, cy, h, w, near, far)) return rc;
+  const double K4[4] = {fx, fy, cx, cy};
+  if (int rc = view_check(what, num_views, h, w, K4, near, far, false)) return rc;
   MSLAM_REQUIRE(tol >= 0.0 && rel_tol >= 0.0, "%s: tol and rel_tol must be >= 0", what);
   if (num_queries == 0 || (size_t)num_views * h * w == 0) return MSLAM_OK;
   MSLAM_REQUIRE(queries && zbuf && poses && seen, "%s: null pointer", what);
-  const CvCamera cam = {fx, fy, cx, cy, h, w, near, far};
+  const ViewCamera cam = {fx, fy, cx, cy, h, w, near, far};
   const dim3 grid(blocks_for(num_queries, kCvBlock), (unsigned)num_views);
   hipLaunchKernelGGL(cv_visible_kernel, grid, dim3(kCvBlock), 0, (hipStream_t)stream, queries, num_queries,
                      (const unsigned long long*)zbuf, poses, cam, tol, rel_tol, seen);

@@ -37,6 +37,7 @@
 // the same faces, no wider: a face whose three sheared vertices are collinear with the origin to the last bit.
 // Nothing is written except the outputs (and, when asked for, the per-wave skip counts).
 #include "mesh_tri.h"
+#include "view.h"
 
 namespace mslam {
 
@@ -48,11 +49,7 @@ struct RcRay {
   int perm;              // 2 kz + (d[kz] < 0), -1 for a lane without a castable ray
 };
 
-template <int K>
-__device__ __forceinline__ double rc_pick(double a0, double a1, double a2, int k) {
-  if (K >= 0) return K == 0 ? a0 : (K == 1 ? a1 : a2);
-  return k == 0 ? a0 : (k == 1 ? a1 : a2);
-}
+static_assert(kMdBlock == kViewBlock, "the cast's blocks are the view's");
 
 // The faces of the staged tile against this lane's ray; KX, KY, KZ >= 0: the wave's common permutation, -1: the lane's.
 // kIndexed: the face's original index comes from its slot (md_stage) and a tie on t goes to the lowest.
@@ -119,9 +116,9 @@ __global__ __launch_bounds__(kMdBlock) void rc_kernel(const float* __restrict__ 
                                                       double* __restrict__ t64) {
   __shared__ double s_tri[kMdTile * kMdTriDoubles];
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  // h = 1: a list, 256 consecutive rays per block; otherwise 16x16 pixels per block, 8x8 per wave
-  const long long px = h == 1 ? (long long)blockIdx.x * kMdBlock + tid : blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
-  const int py = h == 1 ? 0 : blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+  long long px;
+  int py;
+  view_pixel(h, px, py);
   const bool has = px < w && py < h;
   const size_t i = (size_t)py * w + (size_t)px;
 
@@ -132,35 +129,15 @@ __global__ __launch_bounds__(kMdBlock) void rc_kernel(const float* __restrict__ 
 #pragma unroll
   for (int a = 0; a < 3; a++) r.o[a] = r.d[a] = r.po[a] = 0.0;
   if (has) {
-    const double q[4] = {(double)pose8[3], (double)pose8[4], (double)pose8[5], (double)pose8[6]};
-    const double c[3] = {(double)rays[3 * i], (double)rays[3 * i + 1], (double)rays[3 * i + 2]};
-    const double u0 = 2.0 * (q[1] * c[2] - q[2] * c[1]);
-    const double u1 = 2.0 * (q[2] * c[0] - q[0] * c[2]);
-    const double u2 = 2.0 * (q[0] * c[1] - q[1] * c[0]);
-    r.d[0] = (c[0] + q[3] * u0) + (q[1] * u2 - q[2] * u1);
-    r.d[1] = (c[1] + q[3] * u1) + (q[2] * u0 - q[0] * u2);
-    r.d[2] = (c[2] + q[3] * u2) + (q[0] * u1 - q[1] * u0);
-#pragma unroll
-    for (int a = 0; a < 3; a++) r.o[a] = (double)pose8[a];
-    const double a0 = fabs(r.d[0]), a1 = fabs(r.d[1]), a2 = fabs(r.d[2]);
-    // a zero or non-finite direction misses
-    if (a0 < INFINITY && a1 < INFINITY && a2 < INFINITY && (a0 > 0.0 || a1 > 0.0 || a2 > 0.0)) {
-      int kz = a1 > a0 ? 1 : 0;
-      if (a2 > (kz ? a1 : a0)) kz = 2;
-      int kx = kz == 2 ? 0 : kz + 1, ky = kx == 2 ? 0 : kx + 1;
-      const double dz = rc_pick<-1>(r.d[0], r.d[1], r.d[2], kz);
-      if (dz < 0.0) {
-        const int s = kx;
-        kx = ky, ky = s;
-      }
-      r.kx = kx, r.ky = ky, r.kz = kz;
-      r.sx = rc_pick<-1>(r.d[0], r.d[1], r.d[2], kx) / dz;
-      r.sy = rc_pick<-1>(r.d[0], r.d[1], r.d[2], ky) / dz;
-      r.sz = 1.0 / dz;
-      r.po[0] = rc_pick<-1>(r.o[0], r.o[1], r.o[2], kx);
-      r.po[1] = rc_pick<-1>(r.o[0], r.o[1], r.o[2], ky);
-      r.po[2] = rc_pick<-1>(r.o[0], r.o[1], r.o[2], kz);
-      r.perm = 2 * kz + (dz < 0.0 ? 1 : 0);
+    view_ray(rays, i, pose8, r.o, r.d);
+    const ViewShear s = view_shear(r.d);
+    if (s.perm >= 0) {                    // a zero or non-finite direction misses
+      r.kx = s.kx, r.ky = s.ky, r.kz = s.kz;
+      r.sx = s.sx, r.sy = s.sy, r.sz = s.sz;
+      r.po[0] = rc_pick<-1>(r.o[0], r.o[1], r.o[2], s.kx);
+      r.po[1] = rc_pick<-1>(r.o[0], r.o[1], r.o[2], s.ky);
+      r.po[2] = rc_pick<-1>(r.o[0], r.o[1], r.o[2], s.kz);
+      r.perm = s.perm;
     }
   }
   const bool casts = r.perm >= 0;
@@ -245,11 +222,6 @@ __global__ __launch_bounds__(kMdBlock) void rc_kernel(const float* __restrict__ 
 
 using namespace mslam;
 
-// h = 1: a list, 256 rays per block; otherwise 16x16 pixels per block
-static dim3 rc_grid(int h, int w) {
-  return h == 1 ? dim3(blocks_for(w, kMdBlock)) : dim3((unsigned)((w + 15) / 16), (unsigned)((h + 15) / 16));
-}
-
 extern "C" size_t mslam_mesh_raycast_workspace_bytes(int num_faces) {
   return num_faces > 0 ? md_box_bytes(num_faces) : 0;
 }
@@ -278,7 +250,7 @@ static int rc_cast_impl(const char* what, bool indexed, const float* rays, int h
   if ((indexed || cull) && box_bytes < need)
     return md_too_small(what, indexed ? "index" : "workspace", box_bytes, need);
   const double* gbox = indexed && levels == 2 && num_faces > 0 ? md_index_gbox(box, num_faces) : nullptr;
-  hipLaunchKernelGGL(indexed ? rc_kernel<true> : rc_kernel<false>, rc_grid(h, w), dim3(kMdBlock), 0,
+  hipLaunchKernelGGL(indexed ? rc_kernel<true> : rc_kernel<false>, view_grid(h, w), dim3(kMdBlock), 0,
                      (hipStream_t)stream, rays, h, w, pose8, vertices, faces, num_faces, num_vertices, near, far, cull,
                      (const double*)box, order, gbox, skip_counts, range, normal, hit, face, t64);
   return md_launched(what);
@@ -288,9 +260,8 @@ extern "C" int mslam_mesh_raycast(const float* rays, int h, int w, const float* 
                                   const int32_t* faces, int num_faces, int num_vertices, double near, double far,
                                   int skip, const void* workspace, size_t workspace_bytes, float* range, float* normal,
                                   uint8_t* hit, int32_t* face, double* t64, void* stream) {
-  MSLAM_REQUIRE(h >= 0 && w >= 0 && (int64_t)h * w < (1ll << 31), "mesh_raycast: bad image size");
+  if (int rc = view_check("mesh_raycast", 1, h, w, nullptr, near, far, false)) return rc;
   MSLAM_REQUIRE(num_faces >= 0 && num_vertices >= 0, "mesh_raycast: negative size");
-  MSLAM_REQUIRE(near <= far, "mesh_raycast: near must not exceed far");
   if (h == 0 || w == 0) return MSLAM_OK;
   MSLAM_REQUIRE(rays && pose8 && range && normal && hit, "mesh_raycast: null pointer");
   MSLAM_REQUIRE(num_faces == 0 || (faces && (vertices || num_vertices == 0)), "mesh_raycast: null pointer");
@@ -302,7 +273,7 @@ extern "C" int mslam_mesh_raycast(const float* rays, int h, int w, const float* 
 
 extern "C" int mslam_mesh_raycast_blocks(int h, int w) {
   if (h <= 0 || w <= 0) return 0;
-  const dim3 grid = rc_grid(h, w);
+  const dim3 grid = view_grid(h, w);
   return (int)(grid.x * grid.y);
 }
 
@@ -311,9 +282,8 @@ extern "C" int mslam_mesh_raycast_indexed(const float* rays, int h, int w, const
                                           double far, const int32_t* order, const void* index, size_t index_bytes,
                                           int levels, int32_t* skip_counts, float* range, float* normal, uint8_t* hit,
                                           int32_t* face, double* t64, void* stream) {
-  MSLAM_REQUIRE(h >= 0 && w >= 0 && (int64_t)h * w < (1ll << 31), "mesh_raycast_indexed: bad image size");
+  if (int rc = view_check("mesh_raycast_indexed", 1, h, w, nullptr, near, far, false)) return rc;
   MSLAM_REQUIRE(num_faces >= 0 && num_vertices >= 0, "mesh_raycast_indexed: negative size");
-  MSLAM_REQUIRE(near <= far, "mesh_raycast_indexed: near must not exceed far");
   MSLAM_REQUIRE(levels == 1 || levels == 2, "mesh_raycast_indexed: levels must be 1 (tiles) or 2 (tiles and groups)");
   if (h == 0 || w == 0) return MSLAM_OK;
   MSLAM_REQUIRE(rays && pose8 && range && normal && hit, "mesh_raycast_indexed: null pointer");

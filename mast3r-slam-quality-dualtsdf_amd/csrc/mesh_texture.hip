@@ -17,10 +17,12 @@
 //   tx_resolve_kernel     once: sums -> colour, or the fallback
 // Nothing is written except the outputs.
 #include "mesh_tri.h"
+#include "view.h"
 
 namespace mslam {
 
 constexpr int kTxBlock = 256;
+static_assert(kMdBlock == kViewBlock, "the shade's blocks are the view's");
 
 struct TxAtlas {
   int nf, R, cols, W;     // faces, texels per cell, cells per row, atlas width (R + 1) cols
@@ -114,7 +116,7 @@ __global__ __launch_bounds__(kTxBlock) void tx_rays_kernel(Atlas at, int n, cons
   int R, li, lj, idx[3];
   const int f = tx_texel(at, i, &R, &li, &lj);
   if (f >= 0 && tx_face(faces, f, nv, idx)) {
-    double b[3], A[3], B[3], C[3], p[3], v[3];
+    double b[3], A[3], B[3], C[3], p[3];
     tx_bary(R, li, lj, b);
 #pragma unroll
     for (int k = 0; k < 3; k++) {
@@ -122,29 +124,20 @@ __global__ __launch_bounds__(kTxBlock) void tx_rays_kernel(Atlas at, int n, cons
       B[k] = (double)vert[3 * (size_t)idx[1] + k];
       C[k] = (double)vert[3 * (size_t)idx[2] + k];
       p[k] = (b[0] * A[k] + b[1] * B[k]) + b[2] * C[k];
-      v[k] = p[k] - (double)pose8[k];
     }
     const double abx = B[0] - A[0], aby = B[1] - A[1], abz = B[2] - A[2];
     const double acx = C[0] - A[0], acy = C[1] - A[1], acz = C[2] - A[2];
     double nx = aby * acz - abz * acy, ny = abz * acx - abx * acz, nz = abx * acy - aby * acx;
     const double len = sqrt((nx * nx + ny * ny) + nz * nz);
     nx = nx / len, ny = ny / len, nz = nz / len;
-    // the conjugate quaternion: camera from world
-    const double q0 = -(double)pose8[3], q1 = -(double)pose8[4], q2 = -(double)pose8[5], q3 = (double)pose8[6];
-    const double u0 = 2.0 * (q1 * v[2] - q2 * v[1]);
-    const double u1 = 2.0 * (q2 * v[0] - q0 * v[2]);
-    const double u2 = 2.0 * (q0 * v[1] - q1 * v[0]);
-    const double X = (v[0] + q3 * u0) + (q1 * u2 - q2 * u1);
-    const double Y = (v[1] + q3 * u1) + (q2 * u0 - q0 * u2);
-    const double Z = (v[2] + q3 * u2) + (q0 * u1 - q1 * u0);
-    const double rr = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
-    const double pu = fx * X / Z + cx, pv = fy * Y / Z + cy;
-    const double c = -((nx * v[0] + ny * v[1]) + nz * v[2]) / rr;
+    const ViewCamera cam = {fx, fy, cx, cy, h, w, near, far};
+    const ViewProjection pr = view_project(p, pose8, cam);
+    const double* v = pr.v3;
+    const double c = -((nx * v[0] + ny * v[1]) + nz * v[2]) / pr.r;
     const bool finite_n = fabs(nx) < INFINITY && fabs(ny) < INFINITY && fabs(nz) < INFINITY;   // false on a NaN
-    if (finite_n && Z > 0.0 && pu >= -0.5 && pu < (double)w - 0.5 && pv >= -0.5 && pv < (double)h - 0.5 &&
-        rr >= near && rr <= far && c >= cos_min && c > 0.0) {
-      d[0] = (float)(v[0] / rr), d[1] = (float)(v[1] / rr), d[2] = (float)(v[2] / rr);
-      r = rr, cs = c, u = pu, vv = pv;
+    if (finite_n && pr.in_view && c >= cos_min && c > 0.0) {
+      d[0] = (float)(v[0] / pr.r), d[1] = (float)(v[1] / pr.r), d[2] = (float)(v[2] / pr.r);
+      r = pr.r, cs = c, u = pr.u, vv = pr.v;
     }
   }
   dir[3 * (size_t)i] = d[0], dir[3 * (size_t)i + 1] = d[1], dir[3 * (size_t)i + 2] = d[2];
@@ -220,10 +213,6 @@ __global__ __launch_bounds__(kTxBlock) void tx_resolve_kernel(Atlas at, int n, c
   atlas[3 * (size_t)i] = out[0], atlas[3 * (size_t)i + 1] = out[1], atlas[3 * (size_t)i + 2] = out[2];
 }
 
-__device__ __forceinline__ double tx_pick(double a0, double a1, double a2, int k) {
-  return k == 0 ? a0 : (k == 1 ? a1 : a2);
-}
-
 // The colour of every hit pixel of a ray cast: steps 1-4 of the intersection (mesh_raycast.hip) for the one face hit,
 // the same operations in the same order, then (U, V, W) / det as the barycentrics of a, b, c.  The pixel-to-thread map
 // is the cast's: 8x8 pixels per wave, h = 1 a plain list.
@@ -236,42 +225,27 @@ __global__ __launch_bounds__(kMdBlock) void tx_shade_kernel(const int32_t* __res
                                                             const float* __restrict__ atlas, int R, int cols,
                                                             const int32_t* __restrict__ face_cell, int aH, int aW,
                                                             float* __restrict__ rgb) {
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-  const long long px = h == 1 ? (long long)blockIdx.x * kMdBlock + tid : blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
-  const int py = h == 1 ? 0 : blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
+  long long px;
+  int py;
+  view_pixel(h, px, py);
   if (!(px < w && py < h)) return;
   const size_t i = (size_t)py * w + (size_t)px;
   float out[3] = {0.0f, 0.0f, 0.0f};
   const int f = face[i];
   int idx[3];
   if ((unsigned)f < (unsigned)nf && tx_face(faces, f, nv, idx)) {
-    const double q[4] = {(double)pose8[3], (double)pose8[4], (double)pose8[5], (double)pose8[6]};
-    const double c[3] = {(double)rays[3 * i], (double)rays[3 * i + 1], (double)rays[3 * i + 2]};
-    const double u0 = 2.0 * (q[1] * c[2] - q[2] * c[1]);
-    const double u1 = 2.0 * (q[2] * c[0] - q[0] * c[2]);
-    const double u2 = 2.0 * (q[0] * c[1] - q[1] * c[0]);
-    const double d0 = (c[0] + q[3] * u0) + (q[1] * u2 - q[2] * u1);
-    const double d1 = (c[1] + q[3] * u1) + (q[2] * u0 - q[0] * u2);
-    const double d2 = (c[2] + q[3] * u2) + (q[0] * u1 - q[1] * u0);
-    const double a0 = fabs(d0), a1 = fabs(d1), a2 = fabs(d2);
-    int kz = a1 > a0 ? 1 : 0;
-    if (a2 > (kz ? a1 : a0)) kz = 2;
-    int kx = kz == 2 ? 0 : kz + 1, ky = kx == 2 ? 0 : kx + 1;
-    const double dz = tx_pick(d0, d1, d2, kz);
-    if (dz < 0.0) {
-      const int s = kx;
-      kx = ky, ky = s;
-    }
-    const double sx = tx_pick(d0, d1, d2, kx) / dz, sy = tx_pick(d0, d1, d2, ky) / dz;
+    double o[3], d[3];
+    view_ray(rays, i, pose8, o, d);
+    const ViewShear s = view_shear(d);      // only pixels with a hit face come here; castability is not asked again
     double x[3], y[3];
 #pragma unroll
     for (int v = 0; v < 3; v++) {
-      const double q0 = (double)vert[3 * (size_t)idx[v]] - (double)pose8[0];
-      const double q1 = (double)vert[3 * (size_t)idx[v] + 1] - (double)pose8[1];
-      const double q2 = (double)vert[3 * (size_t)idx[v] + 2] - (double)pose8[2];
-      const double qz = tx_pick(q0, q1, q2, kz);
-      x[v] = tx_pick(q0, q1, q2, kx) - sx * qz;
-      y[v] = tx_pick(q0, q1, q2, ky) - sy * qz;
+      const double q0 = (double)vert[3 * (size_t)idx[v]] - o[0];
+      const double q1 = (double)vert[3 * (size_t)idx[v] + 1] - o[1];
+      const double q2 = (double)vert[3 * (size_t)idx[v] + 2] - o[2];
+      const double qz = rc_pick<-1>(q0, q1, q2, s.kz);
+      x[v] = rc_pick<-1>(q0, q1, q2, s.kx) - s.sx * qz;
+      y[v] = rc_pick<-1>(q0, q1, q2, s.ky) - s.sy * qz;
     }
     const double U = x[2] * y[1] - y[2] * x[1];
     const double V = x[0] * y[2] - y[0] * x[2];
@@ -580,7 +554,8 @@ extern "C" int mslam_mesh_texture_rays(const float* vertices, const int32_t* fac
   if (!tx_atlas_arg("mesh_texture_rays", num_faces, texels, cols, rows, &at, &n)) return MSLAM_EINVAL;
   MSLAM_REQUIRE(num_vertices >= 0, "mesh_texture_rays: negative size");
   MSLAM_REQUIRE(h >= 2 && w >= 2, "mesh_texture_rays: an image must be at least 2x2, got %dx%d", h, w);
-  MSLAM_REQUIRE(near <= far && cos_min == cos_min, "mesh_texture_rays: near must not exceed far, cos_min not be NaN");
+  if (int rc = view_check("mesh_texture_rays", 1, h, w, nullptr, near, far, false)) return rc;
+  MSLAM_REQUIRE(cos_min == cos_min, "mesh_texture_rays: cos_min must not be NaN");
   if (n == 0) return MSLAM_OK;
   MSLAM_REQUIRE(faces && pose8 && dir && r && cos && uv && (vertices || num_vertices == 0),
                 "mesh_texture_rays: null pointer");
@@ -594,8 +569,8 @@ extern "C" int mslam_mesh_texture_accumulate(const double* t64, const double* r,
                                              const float* image, int h, int w, const float* pose8, double tol, int n,
                                              double* sums, int32_t* views, void* stream) {
   MSLAM_REQUIRE(n >= 0, "mesh_texture_accumulate: negative size");
-  MSLAM_REQUIRE(h >= 2 && w >= 2 && (int64_t)h * w < (1ll << 31),
-                "mesh_texture_accumulate: an image must be at least 2x2 and within int32, got %dx%d", h, w);
+  MSLAM_REQUIRE(h >= 2 && w >= 2, "mesh_texture_accumulate: an image must be at least 2x2, got %dx%d", h, w);
+  if (int rc = view_check("mesh_texture_accumulate", 1, h, w, nullptr, 0.0, 0.0, false)) return rc;
   MSLAM_REQUIRE(tol == tol, "mesh_texture_accumulate: tol is NaN");
   if (n == 0) return MSLAM_OK;
   MSLAM_REQUIRE(t64 && r && cos && uv && image && pose8 && sums && views, "mesh_texture_accumulate: null pointer");
@@ -624,7 +599,7 @@ extern "C" int mslam_mesh_shade(const int32_t* face, const float* rays, int h, i
                                 const float* vertices, const int32_t* faces, int num_faces, int num_vertices,
                                 const float* colors, const float* atlas, int texels, int cols, int rows, float* rgb,
                                 void* stream) {
-  MSLAM_REQUIRE(h >= 0 && w >= 0 && (int64_t)h * w < (1ll << 31), "mesh_shade: bad image size");
+  if (int rc = view_check("mesh_shade", 1, h, w, nullptr, 0.0, 0.0, false)) return rc;
   MSLAM_REQUIRE(num_faces >= 0 && num_vertices >= 0, "mesh_shade: negative size");
   MSLAM_REQUIRE((colors != nullptr) != (atlas != nullptr), "mesh_shade: give either colors or an atlas");
   if (atlas) {
@@ -635,9 +610,8 @@ extern "C" int mslam_mesh_shade(const int32_t* face, const float* rays, int h, i
   if (h == 0 || w == 0) return MSLAM_OK;
   MSLAM_REQUIRE(face && rays && pose8 && rgb, "mesh_shade: null pointer");
   MSLAM_REQUIRE(num_faces == 0 || (faces && (vertices || num_vertices == 0)), "mesh_shade: null pointer");
-  const dim3 grid = h == 1 ? dim3(blocks_for(w, kMdBlock)) : dim3((unsigned)((w + 15) / 16), (unsigned)((h + 15) / 16));
-  hipLaunchKernelGGL(tx_shade_kernel, grid, dim3(kMdBlock), 0, (hipStream_t)stream, face, rays, h, w, pose8, vertices,
-                     faces, num_faces, num_vertices, colors, atlas, texels, cols, (const int32_t*)nullptr, 0,
+  hipLaunchKernelGGL(tx_shade_kernel, view_grid(h, w), dim3(kMdBlock), 0, (hipStream_t)stream, face, rays, h, w, pose8,
+                     vertices, faces, num_faces, num_vertices, colors, atlas, texels, cols, (const int32_t*)nullptr, 0,
                      atlas ? cols * (texels + 1) : 0, rgb);
   MSLAM_LAUNCH_CHECK("mesh_shade");
   return MSLAM_OK;
@@ -717,8 +691,8 @@ extern "C" int mslam_mesh_texture_rays_sized(const float* vertices, const int32_
   if (!tx_sized_arg("mesh_texture_rays_sized", owner, face_cell, num_faces, H, W, &at, &n)) return MSLAM_EINVAL;
   MSLAM_REQUIRE(num_vertices >= 0, "mesh_texture_rays_sized: negative size");
   MSLAM_REQUIRE(h >= 2 && w >= 2, "mesh_texture_rays_sized: an image must be at least 2x2, got %dx%d", h, w);
-  MSLAM_REQUIRE(near <= far && cos_min == cos_min,
-                "mesh_texture_rays_sized: near must not exceed far, cos_min not be NaN");
+  if (int rc = view_check("mesh_texture_rays_sized", 1, h, w, nullptr, near, far, false)) return rc;
+  MSLAM_REQUIRE(cos_min == cos_min, "mesh_texture_rays_sized: cos_min must not be NaN");
   if (n == 0) return MSLAM_OK;
   MSLAM_REQUIRE(faces && pose8 && dir && r && cos && uv && (vertices || num_vertices == 0),
                 "mesh_texture_rays_sized: null pointer");
@@ -748,16 +722,15 @@ extern "C" int mslam_mesh_shade_sized(const int32_t* face, const float* rays, in
                                       const float* vertices, const int32_t* faces, int num_faces, int num_vertices,
                                       const float* atlas, const int32_t* face_cell, int H, int W, float* rgb,
                                       void* stream) {
-  MSLAM_REQUIRE(h >= 0 && w >= 0 && (int64_t)h * w < (1ll << 31), "mesh_shade_sized: bad image size");
+  if (int rc = view_check("mesh_shade_sized", 1, h, w, nullptr, 0.0, 0.0, false)) return rc;
   MSLAM_REQUIRE(num_faces >= 0 && num_vertices >= 0, "mesh_shade_sized: negative size");
   MSLAM_REQUIRE(H >= 0 && W >= 0 && (int64_t)H * W < (1ll << 31), "mesh_shade_sized: bad atlas size %d x %d", H, W);
   MSLAM_REQUIRE(num_faces == 0 || (atlas && face_cell), "mesh_shade_sized: null atlas or face_cell");
   if (h == 0 || w == 0) return MSLAM_OK;
   MSLAM_REQUIRE(face && rays && pose8 && rgb, "mesh_shade_sized: null pointer");
   MSLAM_REQUIRE(num_faces == 0 || (faces && (vertices || num_vertices == 0)), "mesh_shade_sized: null pointer");
-  const dim3 grid = h == 1 ? dim3(blocks_for(w, kMdBlock)) : dim3((unsigned)((w + 15) / 16), (unsigned)((h + 15) / 16));
-  hipLaunchKernelGGL(tx_shade_kernel, grid, dim3(kMdBlock), 0, (hipStream_t)stream, face, rays, h, w, pose8, vertices,
-                     faces, num_faces, num_vertices, (const float*)nullptr, atlas, 0, 0, face_cell, H, W, rgb);
+  hipLaunchKernelGGL(tx_shade_kernel, view_grid(h, w), dim3(kMdBlock), 0, (hipStream_t)stream, face, rays, h, w, pose8,
+                     vertices, faces, num_faces, num_vertices, (const float*)nullptr, atlas, 0, 0, face_cell, H, W, rgb);
   MSLAM_LAUNCH_CHECK("mesh_shade_sized");
   return MSLAM_OK;
 }

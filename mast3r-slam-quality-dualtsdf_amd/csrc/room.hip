@@ -4,6 +4,7 @@
 // interface: it stands in for what a trained network would output (mast3r_slam/synthetic_gpu.py::RoomGeometryModel),
 // so that the rest of the loop works on meaningful geometry.  Same formulas as RoomRenderer.pair (torch), fused.
 #include "common.h"
+#include "view.h"
 
 namespace mslam {
 
@@ -33,20 +34,11 @@ __device__ __forceinline__ Pose room_pose(double k, int n_frames) {
   return P;
 }
 
-__device__ __forceinline__ void qrot(const double* q, const double* X, double* Y) {
-  const double u0 = 2.0 * (q[1] * X[2] - q[2] * X[1]);
-  const double u1 = 2.0 * (q[2] * X[0] - q[0] * X[2]);
-  const double u2 = 2.0 * (q[0] * X[1] - q[1] * X[0]);
-  Y[0] = X[0] + q[3] * u0 + (q[1] * u2 - q[2] * u1);
-  Y[1] = X[1] + q[3] * u1 + (q[2] * u0 - q[0] * u2);
-  Y[2] = X[2] + q[3] * u2 + (q[0] * u1 - q[1] * u0);
-}
-
 // camera-frame point of pixel (u, v) of the view at pose P: ray (x, y, 1) scaled to the inside of the 6 x 4 x 3 m box
 __device__ __forceinline__ void room_point(const Pose& P, double x, double y, double* Xc, double* Xw) {
   const double d[3] = {x, y, 1.0};
   double dw[3];
-  qrot(P.q, d, dw);
+  view_rotate(P.q, d, dw);
   const double half[3] = {3.0, 2.0, 1.5};
   double t = INFINITY;
 #pragma unroll
@@ -85,7 +77,7 @@ __global__ __launch_bounds__(256) void room_pair_kernel(const float* __restrict_
   const double qi_inv[4] = {-Pi.q[0], -Pi.q[1], -Pi.q[2], Pi.q[3]};
   const double dlt[3] = {Pw_j[0] - Pi.t[0], Pw_j[1] - Pi.t[1], Pw_j[2] - Pi.t[2]};
   double Xj_i[3];
-  qrot(qi_inv, dlt, Xj_i);
+  view_rotate(qi_inv, dlt, Xj_i);
   const double* Xs[2] = {Xi_i, Xj_i};
   const double* Pws[2] = {Pw_i, Pw_j};
   float* Xo[2] = {X1, X2};

@@ -21,6 +21,7 @@
 //             sample_color().
 #include "common.h"
 #include "tsdf_walk.h"
+#include "view.h"
 
 namespace mslam {
 
@@ -149,7 +150,7 @@ __global__ __launch_bounds__(256) void color_sample_kernel(void* base, uint64_t 
   size_t i;
   if (image_w > 0) {     // the points are the pixels of an image with rows of image_w
     int px, py;
-    pixel_tile(px, py);
+    view_pixel(px, py);
     if (px >= image_w || py >= n / image_w) return;
     i = (size_t)py * image_w + px;
   } else {
@@ -271,7 +272,7 @@ extern "C" int mslam_tsdf_color_sample(void* table, uint64_t capacity, const voi
   MSLAM_REQUIRE(voxel_size > 0.0, "tsdf_color_sample: voxel_size must be positive");
   MSLAM_REQUIRE(image_w >= 0 && (image_w == 0 || n % image_w == 0), "tsdf_color_sample: %d points are not rows of %d",
                 n, image_w);
-  const dim3 grid = image_w > 0 ? dim3(blocks_for(image_w, 16), blocks_for(n / image_w, 16))
+  const dim3 grid = image_w > 0 ? view_tile_grid(n / image_w, image_w)
                                 : dim3(blocks_for(n, 256));
   hipLaunchKernelGGL(color_sample_kernel, grid, dim3(256), 0, (hipStream_t)stream, table, capacity,
                      (const unsigned long long*)color, points, n, image_w, voxel_size, default_r, default_g, default_b,

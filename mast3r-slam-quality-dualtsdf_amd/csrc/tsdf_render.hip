@@ -19,6 +19,7 @@
 // Nothing here writes the table.
 #include "common.h"
 #include "tsdf_table.h"
+#include "view.h"
 
 namespace mslam {
 
@@ -146,25 +147,14 @@ __global__ __launch_bounds__(256) void render_kernel(void* base, uint64_t cap, c
                                                      float* __restrict__ normal, uint8_t* __restrict__ hit) {
   const TsdfTable t = table_carve(base, cap);
   int px, py;
-  pixel_tile(px, py);
+  view_pixel(px, py);
   if (px >= w || py >= h) return;
   const size_t i = (size_t)py * w + px;
 
   Ray r;
   r.near = near; r.step = step; r.vs = vs;
-  const double q[4] = {(double)pose8[3], (double)pose8[4], (double)pose8[5], (double)pose8[6]};
   const double scale = (double)pose8[7];
-  const double c[3] = {(double)rays[3 * i], (double)rays[3 * i + 1], (double)rays[3 * i + 2]};
-  {
-    const double u0 = 2.0 * (q[1] * c[2] - q[2] * c[1]);
-    const double u1 = 2.0 * (q[2] * c[0] - q[0] * c[2]);
-    const double u2 = 2.0 * (q[0] * c[1] - q[1] * c[0]);
-    r.d[0] = (c[0] + q[3] * u0) + (q[1] * u2 - q[2] * u1);
-    r.d[1] = (c[1] + q[3] * u1) + (q[2] * u0 - q[0] * u2);
-    r.d[2] = (c[2] + q[3] * u2) + (q[0] * u1 - q[1] * u0);
-  }
-#pragma unroll
-  for (int a = 0; a < 3; a++) r.o[a] = (double)pose8[a];
+  view_ray(rays, i, pose8, r.o, r.d);
 
   // kmax: the last k with near + k * step <= far (the host bounds (far - near) / step by kMaxSamples)
   int kmax = (int)floor((far - near) / step);
@@ -254,15 +244,15 @@ extern "C" int mslam_tsdf_render(void* table, uint64_t capacity, const float* ra
                                  double voxel_size, double min_weight, double level, double near, double far,
                                  double step, int skip, const void* workspace, size_t workspace_bytes, float* range,
                                  float* normal, uint8_t* hit, void* stream) {
-  MSLAM_REQUIRE(h >= 0 && w >= 0 && (int64_t)h * w < (1ll << 31), "tsdf_render: bad image size");
+  if (int rc = view_check("tsdf_render", 1, h, w, nullptr, near, far, true)) return rc;   // the march divides by the span
   if (h == 0 || w == 0) return MSLAM_OK;
   MSLAM_REQUIRE(table && rays && pose8 && workspace && range && normal && hit, "tsdf_render: null pointer");
   MSLAM_REQUIRE(table_cap_ok(capacity), "tsdf_render: bad capacity");
-  MSLAM_REQUIRE(voxel_size > 0.0 && step > 0.0 && far > near && far - near < INFINITY, "tsdf_render: bad march");
+  MSLAM_REQUIRE(voxel_size > 0.0 && step > 0.0, "tsdf_render: bad march");
   MSLAM_REQUIRE((far - near) / step < (double)kMaxSamples, "tsdf_render: more than 2^30 samples per ray");
   const BlockSet B = blocks_carve(const_cast<void*>(workspace), capacity);
   MSLAM_REQUIRE(workspace_bytes >= B.bytes, "tsdf_render: workspace needs %zu bytes", B.bytes);
-  hipLaunchKernelGGL(render_kernel, dim3(blocks_for(w, 16), blocks_for(h, 16)), dim3(256), 0,
+  hipLaunchKernelGGL(render_kernel, view_tile_grid(h, w), dim3(kViewBlock), 0,
                      (hipStream_t)stream, table, capacity, rays, h, w, pose8, voxel_size, min_weight, level, near, far,
                      step, skip, B, range, normal, hit);
   MSLAM_LAUNCH_CHECK("tsdf_render");

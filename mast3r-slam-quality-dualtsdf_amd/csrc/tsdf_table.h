@@ -1,6 +1,5 @@
 // The global-TSDF voxel hash and every rule of reading it, each stated once: layout and capacity rule, keys, the bounded
-// probe, what a valid voxel is, the sample lattice with its corner order and trilinear blend, and the pixel tile of the
-// image-shaped kernels.  Used by csrc/tsdf_global.hip (integrate / query / pose), tsdf_color.hip (colour fuse and
+// probe, what a valid voxel is, and the sample lattice with its corner order and trilinear blend.  Used by csrc/tsdf_global.hip (integrate / query / pose), tsdf_color.hip (colour fuse and
 // sample), tsdf_render.hip (ray cast), tsdf_mesh.hip (mesh extraction, loading), tsdf_walk.h (the ray walk of a fused
 // point) and cloud.hip (world_to_key).
 #pragma once
@@ -188,14 +187,6 @@ __device__ __forceinline__ double trilerp(const double (&v)[8], const double (&f
   const double c00 = lerp(v[0], v[1], f[0]), c10 = lerp(v[2], v[3], f[0]);
   const double c01 = lerp(v[4], v[5], f[0]), c11 = lerp(v[6], v[7], f[0]);
   return lerp(lerp(c00, c10, f[1]), lerp(c01, c11, f[1]), f[2]);
-}
-
-// Image-shaped launches: 16x16 pixels per 256-thread block, 8x8 per wave (2x2 waves), so that a wave's rays or points
-// probe neighbouring voxels.  The grid is blocks_for(w, 16) x blocks_for(h, 16).
-__device__ __forceinline__ void pixel_tile(int& px, int& py) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  px = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
-  py = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
 }
 
 }  // namespace mslam

@@ -14,22 +14,15 @@ import torch
 import mslam_hip as _m
 
 from ._mesh_args import _points_arg
-from .mesh_raycast import _poses_arg
+from ._view_args import _hw_arg, _K_arg, _poses_arg, _range_arg, compose_sim3
 
 MAX_RADIUS = _m.header_constants()["MSLAM_CLOUD_VIEW_MAX_RADIUS"]
 
 
 def _view_args(what, K, hw, near, far, radius, point_size, max_radius):
-    """((fx, fy, cx, cy), h, w, near, far, radius, point_size (-1.0: none), max_radius), checked."""
-    K = np.asarray(torch.as_tensor(K).detach().cpu(), np.float64)
-    if K.shape != (3, 3) or not np.isfinite(K).all():
-        raise ValueError(f"{what}: K must be a finite (3,3) pinhole matrix, got shape {K.shape}")
-    if hw is None or len(hw) != 2 or min(int(x) for x in hw) < 1:
-        raise ValueError(f"{what}: hw must be (h, w) with h, w >= 1, got {hw!r}")
-    h, w = (int(x) for x in hw)
-    near, far = float(near), float(far)
-    if not near <= far:
-        raise ValueError(f"{what}: near must not exceed far, got {near} and {far}")
+    """((fx, fy, cx, cy), h, w, near, far, radius, point_size (-1.0: none), max_radius), checked: the camera by
+    _view_args.py, the footprint of a point here."""
+    k4, (h, w), (near, far) = _K_arg(K, what), _hw_arg(hw, what), _range_arg(near, far, what, strict=False)
     for name, v in (("radius", radius), ("max_radius", max_radius)):
         if isinstance(v, bool) or int(v) != v:
             raise ValueError(f"{what}: {name} must be an integer, got {v!r}")
@@ -40,7 +33,7 @@ def _view_args(what, K, hw, near, far, radius, point_size, max_radius):
     if point_size is not None and not (float(point_size) >= 0.0 and math.isfinite(float(point_size))):
         raise ValueError(f"{what}: point_size must be None or a finite world-unit diameter >= 0, got {point_size!r}")
     size = -1.0 if point_size is None else float(point_size)
-    return (float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])), h, w, near, far, radius, size, max_radius
+    return k4, h, w, near, far, radius, size, max_radius
 
 
 def _check_pixels(what, V, h, w):
@@ -158,8 +151,6 @@ _OBSERVED_KEYS = {"poses", "K", "hw", "near", "far", "tol", "rel_tol", "radius",
 def _observed_cloud(what, gt, observed, T, voxel):
     """bool[n]: the points of the (thinned) ground-truth cloud that the cameras of compare_clouds' `observed` see, the
     cloud itself the occluder; T: the alignment transform or None."""
-    from .mesh_raycast import compose_sim3
-
     spec = dict(observed)
     if set(spec) - _OBSERVED_KEYS or not {"poses", "K", "hw"} <= set(spec):
         raise ValueError(f"{what}: observed needs poses, K and hw (and takes near, far, tol, rel_tol, radius, "

@@ -13,6 +13,7 @@ import torch
 
 import mslam_hip as _m
 
+from ._view_args import _hw_arg, _K_arg, _pose_arg, _range_arg, hit_points, pinhole_rays  # noqa: F401 (re-exported)
 from .mesh_chain import chain_options, run_chain
 
 
@@ -460,47 +461,14 @@ def _sample_color(table, capacity, color, pts, image_w, voxel_size, default_colo
     return rgb.reshape(shape + (3,)), cnt.reshape(shape)
 
 
-def hit_points(pose, rays, rng):
-    """World points f32[h,w,3] of a view's range image: o + (double)range * s * d in f64, d the ray directions as the
-    render kernel forms them (r + w u + q x u, u = 2 q x r, on the f32 pose and rays), rounded to f32 once."""
-    p = pose.double()
-    q, r = p[3:7], rays.double()
-    u0 = 2.0 * (q[1] * r[..., 2] - q[2] * r[..., 1])
-    u1 = 2.0 * (q[2] * r[..., 0] - q[0] * r[..., 2])
-    u2 = 2.0 * (q[0] * r[..., 1] - q[1] * r[..., 0])
-    d = torch.stack(((r[..., 0] + q[3] * u0) + (q[1] * u2 - q[2] * u1),
-                     (r[..., 1] + q[3] * u1) + (q[2] * u0 - q[0] * u2),
-                     (r[..., 2] + q[3] * u2) + (q[0] * u1 - q[1] * u0)), -1)
-    return (p[:3] + (rng.double() * p[7]).unsqueeze(-1) * d).float().contiguous()
-
-
-def pinhole_rays(K, hw, device="cuda"):
-    """Unit camera-frame rays f32[h,w,3] of a pinhole camera: ((u - cx) / fx, (v - cy) / fy, 1) normalised, pixel
-    centres at integer (u, v) (synthetic.pixel_rays)."""
-    h, w = (int(x) for x in hw)
-    K = torch.as_tensor(K).detach().to(device="cpu", dtype=torch.float64).reshape(3, 3)
-    u = torch.arange(w, dtype=torch.float64).view(1, w).expand(h, w)
-    v = torch.arange(h, dtype=torch.float64).view(h, 1).expand(h, w)
-    r = torch.stack(((u - K[0, 2]) / K[0, 0], (v - K[1, 2]) / K[1, 1], torch.ones(h, w, dtype=torch.float64)), -1)
-    return (r / r.norm(dim=-1, keepdim=True)).to(device=device, dtype=torch.float32).contiguous()
-
-
 def _render_args(pose, rays, K, hw, near, far, step, voxel_size, device):
     """Checked (pose f32[8], rays f32[h,w,3], step) on `device`."""
-    if isinstance(pose, np.ndarray):
-        pose = torch.from_numpy(np.ascontiguousarray(pose))
-    pose = getattr(pose, "data", pose)        # a lietorch Sim3 carries its (1,8) tensor in .data
-    pose = torch.as_tensor(pose)
-    if pose.numel() != 8:
-        raise ValueError(f"render: pose must hold 8 values [t, q, s], got shape {tuple(pose.shape)}")
-    pose = pose.detach().to(device=device, dtype=torch.float32).reshape(8).contiguous()
+    pose = _pose_arg(pose, "render", device)
     if (rays is None) == (K is None):
         raise ValueError("render: give either rays (h,w,3) or K with hw")
     if rays is None:
-        if hw is None or len(hw) != 2 or min(int(x) for x in hw) < 1:
-            raise ValueError("render: K needs hw = (h, w)")
-        if tuple(torch.as_tensor(K).shape) != (3, 3):
-            raise ValueError("render: K must be (3,3)")
+        hw = _hw_arg(hw, "render")
+        _K_arg(K, "render")
         rays = pinhole_rays(K, hw, device)
     else:
         if isinstance(rays, np.ndarray):
@@ -513,8 +481,7 @@ def _render_args(pose, rays, K, hw, near, far, step, voxel_size, device):
     step = 0.5 * float(voxel_size) if step is None else float(step)
     if not step > 0.0:
         raise ValueError("render: step must be positive")
-    if not float(far) > float(near) or not np.isfinite(float(far) - float(near)):
-        raise ValueError("render: far must be greater than near")
+    _range_arg(near, far, "render", strict=True)
     return pose, rays, step
 
 

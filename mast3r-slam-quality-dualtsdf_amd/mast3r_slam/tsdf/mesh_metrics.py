@@ -140,7 +140,8 @@ def compare_meshes(pred, gt, n_samples=200_000, threshold=0.05, seed=0, skip=Tru
 
 def _observed_samples(g_pts, gt, observed, T, skip, index=None):
     """bool[n]: the ground-truth samples the cameras of `observed` see; T: the alignment transform or None."""
-    from .mesh_raycast import _poses_arg, compose_sim3, observed_points
+    from ._view_args import _poses_arg, compose_sim3
+    from .mesh_raycast import observed_points
 
     spec = dict(observed)
     unknown = set(spec) - {"poses", "K", "hw", "near", "far", "tol", "frame"}

@@ -4,12 +4,12 @@ which mesh_metrics.compare_meshes(observed=...) keeps when it scores completion 
 
 No counterpart in the reference.  The kernel is csrc/mesh_raycast.hip (DESIGN.md "Mesh ray casting"); the numpy
 statement of the same definitions is tests/raycast_numpy.py.  Valid faces are those of mesh_metrics."""
-import numpy as np
 import torch
 
 import mslam_hip as _m
 
 from ._mesh_args import _mesh_arg, _pair, _points_arg
+from ._view_args import _eye, _hw_arg, _K_arg, _poses_arg, compose_sim3, rotate  # noqa: F401 (re-exported)
 from .global_volume import _render_args
 from .mesh_index import MeshIndex, _index_arg
 
@@ -74,40 +74,6 @@ def render_mesh(mesh, pose, rays=None, K=None, hw=None, near=0.05, far=10.0, ski
     return out + (fc.view(h, w),) if return_face else out
 
 
-def _rotate(q, r):
-    u0 = 2.0 * (q[1] * r[:, 2] - q[2] * r[:, 1])
-    u1 = 2.0 * (q[2] * r[:, 0] - q[0] * r[:, 2])
-    u2 = 2.0 * (q[0] * r[:, 1] - q[1] * r[:, 0])
-    return torch.stack(((r[:, 0] + q[3] * u0) + (q[1] * u2 - q[2] * u1),
-                        (r[:, 1] + q[3] * u1) + (q[2] * u0 - q[0] * u2),
-                        (r[:, 2] + q[3] * u2) + (q[0] * u1 - q[1] * u0)), -1)
-
-
-def _poses_arg(poses, what):
-    """f32[n,8] on the host, from a tensor, an array or a sequence of Sim3s (lietorch Sim3s included)."""
-    if not torch.is_tensor(poses) and not isinstance(poses, np.ndarray):
-        poses = [p if isinstance(p, np.ndarray) else getattr(p, "data", p) for p in poses]
-        poses = torch.stack([torch.as_tensor(p).detach().reshape(8).to("cpu", torch.float64) for p in poses]) \
-            if len(poses) else torch.zeros((0, 8), dtype=torch.float64)
-    poses = torch.as_tensor(poses).detach().to("cpu")
-    if poses.numel() % 8 != 0:
-        raise ValueError(f"{what}: poses must be (n,8) Sim3s [t, q, s], got shape {tuple(poses.shape)}")
-    return poses.reshape(-1, 8)
-
-
-def compose_sim3(T, poses):
-    """T o pose for poses f64[n,8] and one Sim3 T (8 numbers), in f64 on the host: the cameras of a map moved into the
-    frame an alignment leads to."""
-    T = torch.as_tensor(T, dtype=torch.float64).detach().to("cpu").reshape(8)
-    p = poses.to(torch.float64)
-    a, b = T[3:7], p[:, 3:7]
-    q = torch.stack((a[3] * b[:, 0] + a[0] * b[:, 3] + a[1] * b[:, 2] - a[2] * b[:, 1],
-                     a[3] * b[:, 1] - a[0] * b[:, 2] + a[1] * b[:, 3] + a[2] * b[:, 0],
-                     a[3] * b[:, 2] + a[0] * b[:, 1] - a[1] * b[:, 0] + a[2] * b[:, 3],
-                     a[3] * b[:, 3] - a[0] * b[:, 0] - a[1] * b[:, 1] - a[2] * b[:, 2]), -1)
-    return torch.cat((T[7] * _rotate(a, p[:, :3]) + T[:3], q, (T[7] * p[:, 7]).unsqueeze(-1)), -1)
-
-
 def observed_points(points, mesh, poses, K, hw, near=0.05, far=10.0, tol=0.01, skip=True, compact_every=4, index=None,
                     sort_queries=True):
     """bool[n] device tensor: which of the points f32[n,3] some pinhole camera sees.  A point p is observed when, for
@@ -132,8 +98,8 @@ def observed_points(points, mesh, poses, K, hw, near=0.05, far=10.0, tol=0.01, s
                                caster.index, False)
         return torch.empty_like(seen).index_copy_(0, perm, seen)
     poses = _poses_arg(poses, "observed_points").to(torch.float32)
-    Kd = torch.as_tensor(np.asarray(torch.as_tensor(K).detach().cpu(), np.float64)).reshape(3, 3).tolist()
-    h, w = (int(x) for x in hw)
+    fx, fy, cx, cy = _K_arg(K, "observed_points")
+    h, w = _hw_arg(hw, "observed_points")
     near, far, tol = float(near), float(far), float(tol)
     seen = torch.zeros(points.shape[0], dtype=torch.bool, device=dev)
     alive = torch.arange(points.shape[0], device=dev)
@@ -145,10 +111,10 @@ def observed_points(points, mesh, poses, K, hw, near=0.05, far=10.0, tol=0.01, s
             break
         p64 = pose.to(dev).double()
         v = P[alive] - p64[:3]
-        X = _rotate(torch.stack((-p64[3], -p64[4], -p64[5], p64[6])), v)
+        X = rotate(torch.stack((-p64[3], -p64[4], -p64[5], p64[6])), v)
         r = torch.sqrt((v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2])
-        u = Kd[0][0] * X[:, 0] / X[:, 2] + Kd[0][2]
-        vv = Kd[1][1] * X[:, 1] / X[:, 2] + Kd[1][2]
+        u = fx * X[:, 0] / X[:, 2] + cx
+        vv = fy * X[:, 1] / X[:, 2] + cy
         in_view = ((X[:, 2] > 0.0) & (u >= -0.5) & (u < w - 0.5) & (vv >= -0.5) & (vv < h - 0.5) & (r >= near) &
                    (r <= far) & ~seen[alive])
         idx = torch.nonzero(in_view).reshape(-1)
@@ -156,7 +122,6 @@ def observed_points(points, mesh, poses, K, hw, near=0.05, far=10.0, tol=0.01, s
         if m == 0:
             continue
         dirs = (v[idx] / r[idx].unsqueeze(-1)).float().contiguous()
-        eye = torch.cat((pose[:3], pose.new_tensor([0.0, 0.0, 0.0, 1.0, 1.0]))).to(dev).contiguous()
-        t64 = caster.cast(dirs, 1, m, eye, 0.0, float("inf"), t64=True)[4]
+        t64 = caster.cast(dirs, 1, m, _eye(pose).to(dev), 0.0, float("inf"), t64=True)[4]
         seen[alive[idx[t64 >= r[idx] - tol]]] = True
     return seen

@@ -16,8 +16,9 @@ import torch
 import mslam_hip as _m
 
 from ._mesh_args import _pair
+from ._view_args import _eye, _K_arg, _poses_arg, _range_arg
 from .global_volume import _render_args
-from .mesh_raycast import _Caster, _poses_arg
+from .mesh_raycast import _Caster
 
 
 def atlas_layout(num_faces, texels):
@@ -127,13 +128,6 @@ class MeshTexture:
         return torch.stack(out, 1).float() if F else torch.zeros((0, 3, 2), dtype=torch.float32, device=f.device)
 
 
-def _K_arg(K, what):
-    K = np.asarray(torch.as_tensor(K).detach().cpu(), np.float64)
-    if K.shape != (3, 3):
-        raise ValueError(f"{what}: K must be (3,3), got {K.shape}")
-    return float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
-
-
 def _colors_arg(colors, V, device, what, name="colors"):
     if not torch.is_tensor(colors):
         raise TypeError(f"{what}: {name} must be a device tensor")
@@ -179,8 +173,7 @@ class _Baker:
         """The occlusion rays of the last `rays` from the pose's origin, as observed_points casts them -> t64."""
         if self.n == 0:
             return torch.empty(0, dtype=torch.float64, device=self.c.device)
-        eye = torch.cat((pose[:3], pose.new_tensor([0.0, 0.0, 0.0, 1.0, 1.0]))).contiguous()
-        return self.c.cast(self.dir, 1, self.n, eye, 0.0, float("inf"), t64=True)[4]
+        return self.c.cast(self.dir, 1, self.n, _eye(pose), 0.0, float("inf"), t64=True)[4]
 
     def accumulate(self, t64, image, pose, tol):
         h, w = int(image.shape[0]), int(image.shape[1])
@@ -329,8 +322,9 @@ def bake_texture(mesh, images, poses, K, texels=8, near=0.05, far=10.0, tol=0.01
             raise ValueError(f"{what}: images and the mesh are on different devices")
         images = images.to(dev)
     K4 = _K_arg(K, what)
-    if not float(far) >= float(near) or not float(tol) == float(tol) or not float(cos_min) == float(cos_min):
-        raise ValueError(f"{what}: near must not exceed far, tol and cos_min must be numbers")
+    near, far = _range_arg(near, far, what, strict=False)
+    if not float(tol) == float(tol) or not float(cos_min) == float(cos_min):
+        raise ValueError(f"{what}: tol and cos_min must be numbers")
     with torch.cuda.device(dev):
         if density is None:
             bk = _Baker(caster, texels)

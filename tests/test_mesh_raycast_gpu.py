@@ -109,6 +109,32 @@ def test_image_tiles(device, hw, pose):
     assert len(view) == 3 and np.array_equal(view[0].cpu().numpy().reshape(-1), want[0])
 
 
+def test_image_and_list_share_one_pixel_map(device):
+    """The pixel-to-thread map has two forms (16x16 tiles; h = 1: a list of 256 per block) and the cast and the shade
+    each use it: a 17x9 view - two blocks of tiles, partial waves - of 130 faces - two face tiles - cast as an image and
+    as the list of the same 153 rays gives the same bytes, and so does the colour view."""
+    from mast3r_slam.tsdf import render_mesh_color
+
+    h, w = 17, 9
+    V, F = tile_mesh(130)
+    K = np.array([[0.6 * w, 0, 0.5 * w], [0, 0.6 * w, 0.5 * h], [0, 0, 1.0]])
+    d = synthetic.pixel_rays(h, w, K)
+    rays = (d / np.linalg.norm(d, axis=-1, keepdims=True)).astype(np.float32)
+    for skip in (0, 1):
+        image = _raw_cast(device, rays, h, w, BACK, V, F, skip)
+        _same_bytes(image, _raw_cast(device, rays, 1, h * w, BACK, V, F, skip))
+    assert 0 < image["hit"].sum() < h * w
+    _parity(image, R.render(BACK, rays, V, F, NEAR, FAR))
+    mesh = (_dev(device, V, np.float32), _dev(device, F, np.int32))
+    colors = _dev(device, np.random.default_rng(5).uniform(0.0, 1.0, (len(V), 3)), np.float32)
+    as_image = render_mesh_color(mesh, BACK, colors=colors, rays=rays, near=NEAR, far=FAR)
+    as_list = render_mesh_color(mesh, BACK, colors=colors, rays=rays.reshape(1, h * w, 3), near=NEAR, far=FAR)
+    for a, b in zip(_host(as_image), _host(as_list)):
+        assert a.dtype == b.dtype and a.tobytes() == b.tobytes()
+    assert np.array_equal(as_image[2].cpu().numpy().reshape(-1), image["hit"].astype(bool))
+    assert (as_image[3][as_image[2]] > 0.0).any() and not as_image[3][~as_image[2]].any()
+
+
 def _both(device, rays, h, w, pose, V, F, **kw):
     plain = _raw_cast(device, rays, h, w, pose, V, F, 0, **kw)
     _same_bytes(plain, _raw_cast(device, rays, h, w, pose, V, F, 1, **kw))
