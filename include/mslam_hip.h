@@ -752,6 +752,50 @@ int mslam_cloud_normals(const float* points, int num_points, const int32_t* neig
                         int viewpoint_stride, float* normals, float* curvature, int32_t* count, double* moments,
                         void* stream);
 
+/* Point-to-plane ICP for clouds and meshes: one fused step and a Gauss-Newton solve on Sim3 per iteration (no
+ * counterpart in the reference, DESIGN.md "Point-to-plane ICP"; the definition is tests/icp_plane_numpy.py;
+ * csrc/icp_plane.hip).  The state block and its init and read are mslam_mesh_align_init / _init_indexed / _read; all
+ * arithmetic is f64 on the f32 inputs; every sum is reduced in mslam_mesh_align_step's fixed order without atomics.
+ * A step moves src f32[n,3] by the state (moved, rounded once to f32), finds each moved sample's nearest primitive
+ * (dist2, nearest: the bits of mslam_cloud_distance / mslam_mesh_distance on `moved`; closest f64[n,3], may be NULL:
+ * the nearest point, or the closest point of the nearest face, NaN without one), takes the target's normal there (the
+ * given normals f32[N,3] of a cloud as they are; a face's ((b - a) x (c - a)) normalised in f64) and accumulates, about
+ * o = moved[0] with a = q - o, e = q - c, the plane row r = n . e, J = [n, a x n, n . a] and, with point_weight > 0, the
+ * three point rows r_d = e_d, J_d = [u_d, a x u_d, a_d] weighted by point_weight.  A pair counts when it has a
+ * neighbour, dist2 <= trim^2 and a finite non-zero normal; with point_weight > 0 a pair without a normal counts with
+ * its point rows alone.  The solve scales H = sum J^T J to unit diagonal, factors it by Cholesky, solves H xi = -g for
+ * xi = (tau, omega, sigma) (with_scale = 0: without sigma) and composes x -> o + e^sigma R(omega) (x - o) + tau onto
+ * the state.  MSLAM_MESH_ALIGN_DEGENERATE, the state left as it was: fewer pairs than unknowns, a zero or non-finite
+ * diagonal entry, a pivot of the scaled matrix <= 2^-40, a non-finite xi or scale.
+ *   log_row    f64[MSLAM_ICP_PLANE_LOG_DOUBLES]: the pairs that count, sqrt((sum r^2 + point_weight sum dist2) / sum w)
+ *              (+inf without a pair), the scale after the solve, the status, the point rmse sqrt(sum dist2 / sum w),
+ *              normal_spread - the smallest eigenvalue of H's 3 x 3 translation block over sum w, 0 when some
+ *              translation is not constrained - then the MSLAM_ICP_PLANE_SUMS sums: count, sum w, sum r^2, sum dist2,
+ *              g (7), the upper triangle of H row by row (28).
+ *   workspace  mslam_icp_plane_workspace_bytes(n, F): F faces' tile boxes (mslam_mesh_align_init writes them; 0 for a
+ *              cloud and for the indexed form) and one partial per block of 256 samples.
+ *   mslam_icp_plane_step_cloud         order NULL: the plain scan; else `index` is mslam_cloud_index_boxes' workspace
+ *                                      and levels as in mslam_cloud_distance.  The same bits in the three forms.
+ *   mslam_icp_plane_step_mesh          `nearest` is read first as a warm start, as in mslam_mesh_align_step.
+ *   mslam_icp_plane_step_mesh_indexed  over a mesh index, as mslam_mesh_align_step_indexed. */
+#define MSLAM_ICP_PLANE_SUMS 39
+#define MSLAM_ICP_PLANE_LOG_DOUBLES 45
+size_t mslam_icp_plane_workspace_bytes(int n, int num_faces);
+int mslam_icp_plane_step_cloud(const float* src, int n, const float* points, const float* normals, int num_points,
+                               const int32_t* order, const void* index, size_t index_bytes, int levels, double trim,
+                               double point_weight, int with_scale, void* workspace, size_t workspace_bytes,
+                               void* state, int32_t* nearest, float* moved, double* dist2, double* closest,
+                               double* log_row, void* stream);
+int mslam_icp_plane_step_mesh(const float* src, int n, const float* vertices, const int32_t* faces, int num_faces,
+                              int num_vertices, double trim, double point_weight, int with_scale, void* workspace,
+                              size_t workspace_bytes, void* state, int32_t* nearest, float* moved, double* dist2,
+                              double* closest, double* log_row, void* stream);
+int mslam_icp_plane_step_mesh_indexed(const float* src, int n, const float* vertices, const int32_t* faces,
+                                      int num_faces, int num_vertices, const int32_t* order, const void* index,
+                                      size_t index_bytes, double trim, double point_weight, int with_scale,
+                                      void* workspace, size_t workspace_bytes, void* state, int32_t* nearest,
+                                      float* moved, double* dist2, double* closest, double* log_row, void* stream);
+
 /* Cloud views: the z-buffer splat of a cloud into pinhole views and the observed part of a cloud (no counterpart in the
  * reference, DESIGN.md "Cloud views"; the definition is tests/cloudview_numpy.py; csrc/cloud_view.hip).  A view is a
  * pose f32[8] (Sim3 [t,q,s], world from camera), the pinhole fx, fy, cx, cy and an image of h x w, h w num_views < 2^31.

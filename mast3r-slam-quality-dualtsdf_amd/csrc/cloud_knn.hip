@@ -39,9 +39,10 @@
 // No atomics, no waiting between blocks, every loop bounded by a tile count or k.
 //
 // NORMALS.  kn_normals_kernel, one thread per point: centroid and covariance of the point's neighbour row in list
-// order, the eigenvectors by cyclic Jacobi (ma_jacobi4 of mesh_align.hip restated for 3 x 3, unrolled with constant
-// indices), the column of the smallest eigenvalue, its sign from a viewpoint or the largest component.
+// order, the eigenvectors by cyclic Jacobi (kn_jacobi3 of jacobi3.h), the column of the smallest eigenvalue, its sign
+// from a viewpoint or the largest component.
 #include "cloud_point.h"
+#include "jacobi3.h"
 
 namespace mslam {
 
@@ -132,33 +133,6 @@ __global__ __launch_bounds__(kMdBlock) void kn_kernel(const float* __restrict__ 
   if (skipped && (tid & (kWave - 1)) == 0) skipped[4 * (size_t)blockIdx.x + tid / kWave] = n_skipped;
 }
 
-// One rotation of the cyclic Jacobi sweep on the pair (P, Q): ma_jacobi4's, with constant indices
-template <int P, int Q>
-__device__ __forceinline__ void kn_rotate(double (&A)[3][3], double (&V)[3][3]) {
-  if (A[P][Q] == 0.0) return;
-  const double theta = (A[Q][Q] - A[P][P]) / (2.0 * A[P][Q]);
-  const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-  const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
-#pragma unroll
-  for (int r = 0; r < 3; r++) {                              // A <- A J
-    const double akp = A[r][P], akq = A[r][Q];
-    A[r][P] = cs * akp - sn * akq;
-    A[r][Q] = sn * akp + cs * akq;
-  }
-#pragma unroll
-  for (int r = 0; r < 3; r++) {                              // A <- J^T A
-    const double apk = A[P][r], aqk = A[Q][r];
-    A[P][r] = cs * apk - sn * aqk;
-    A[Q][r] = sn * apk + cs * aqk;
-  }
-#pragma unroll
-  for (int r = 0; r < 3; r++) {                              // V <- V J
-    const double vkp = V[r][P], vkq = V[r][Q];
-    V[r][P] = cs * vkp - sn * vkq;
-    V[r][Q] = sn * vkp + cs * vkq;
-  }
-}
-
 // One point per thread.  moments (may be null): f64[N,15] - the centroid, the covariance xx xy xz yy yz zz (zeros for
 // a point without a neighbour), the three diagonal entries after the sweeps and the oriented normal before its rounding
 // to f32 - what the tests compare with the statement.
@@ -204,21 +178,7 @@ __global__ __launch_bounds__(256) void kn_normals_kernel(const float* __restrict
 
   double A[3][3] = {{xx, xy, xz}, {xy, yy, yz}, {xz, yz, zz}};
   double V[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
-  for (int sweep = 0; sweep < 16; sweep++) {
-    double off = 0.0, diag = 0.0;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-#pragma unroll
-      for (int b = 0; b < 3; b++) {
-        if (a == b) diag += A[a][b] * A[a][b];
-        else off += A[a][b] * A[a][b];
-      }
-    }
-    if (!(off > 0x1p-104 * diag)) break;                     // off-diagonal norm below 2^-52 of the diagonal's
-    kn_rotate<0, 1>(A, V);
-    kn_rotate<0, 2>(A, V);
-    kn_rotate<1, 2>(A, V);
-  }
+  kn_jacobi3(A, V);
   const double l0 = A[0][0], l1 = A[1][1], l2 = A[2][2];
   int lo = 0;
   double lmin = l0;

@@ -14,7 +14,7 @@
 // from md_dist2(q_i, face nearest_prev[i]) when that face exists and is valid, so a block stages its home tile only
 // when one of its lanes has no such face.  The _indexed entries run the same step over the tiles of a mesh index
 // (mesh_index.hip); the warm start is by original face index and does not change.
-#include "mesh_tri.h"
+#include "mesh_align.h"
 
 namespace mslam {
 
@@ -22,20 +22,6 @@ constexpr int kMaSums = 19;        // count, sum w, sum w p (3), sum w c (3), su
 constexpr int kMaLog = MSLAM_MESH_ALIGN_LOG_DOUBLES;
 static_assert(MSLAM_MESH_ALIGN_STATE_BYTES == 9 * sizeof(double), "eight doubles, then the status in a slot of its own");
 static_assert(kMaLog >= 4 + kMaSums, "a log row holds four figures and the sums");
-
-// row-major rotation of the unit quaternion q = (x, y, z, w)
-__host__ __device__ __forceinline__ void ma_quat_to_mat(const double* q, double* R) {
-  const double x = q[0], y = q[1], z = q[2], w = q[3];
-  R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - z * w);       R[2] = 2.0 * (x * z + y * w);
-  R[3] = 2.0 * (x * y + z * w);       R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - x * w);
-  R[6] = 2.0 * (x * z - y * w);       R[7] = 2.0 * (y * z + x * w);       R[8] = 1.0 - 2.0 * (x * x + y * y);
-}
-
-// y = s * (R p) + t
-__host__ __device__ __forceinline__ void ma_act(const double* R, const double* t, double s, const double* p, double* y) {
-#pragma unroll
-  for (int d = 0; d < 3; d++) y[d] = s * ((R[3 * d] * p[0] + R[3 * d + 1] * p[1]) + R[3 * d + 2] * p[2]) + t[d];
-}
 
 // The moment terms of one pair about the origins op (source side) and oc (target side), weight w; `in` false: zeros.
 __device__ __forceinline__ void ma_terms(bool in, double w, const double* p, const double* c, const double* op,
@@ -56,20 +42,6 @@ __device__ __forceinline__ void ma_terms(bool in, double w, const double* p, con
   }
   v[17] = w * md_dot(a[0], a[1], a[2], a[0], a[1], a[2]);
   v[18] = w * d2;
-}
-
-// Block sum of v in a fixed order -> partial[kMaSums * block + k].  s_part: 4 * kMaSums doubles of LDS.
-__device__ __forceinline__ void ma_block_reduce(double* v, double* s_part, double* __restrict__ partial) {
-  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid / kWave;
-#pragma unroll
-  for (int k = 0; k < kMaSums; k++) {
-    const double x = wave_sum(v[k]);
-    if (lane == 0) s_part[wave * kMaSums + k] = x;
-  }
-  __syncthreads();
-  if (tid < kMaSums)
-    partial[kMaSums * (size_t)blockIdx.x + tid] =
-        ((s_part[tid] + s_part[kMaSums + tid]) + s_part[2 * kMaSums + tid]) + s_part[3 * kMaSums + tid];
 }
 
 // count: also write, per wave, how many tiles it did not scan to skipped[4 * block + wave] (the timing tool's figure).
@@ -148,7 +120,7 @@ __global__ __launch_bounds__(kMdBlock) void ma_step_kernel(const float* __restri
   // 4., 5. the moments about (p_0, T_k p_0), reduced in a fixed order
   double v[kMaSums];
   ma_terms(inlier, 1.0, p, c, op, oc, best, v);
-  ma_block_reduce(v, s_part, partial);
+  ma_block_reduce<kMaSums>(v, s_part, partial);
 }
 
 // Explicit pairs src[i] -> dst[i] with optional weights >= 0 (a pair of weight 0 does not count); the moments about
@@ -171,7 +143,7 @@ __global__ __launch_bounds__(kMdBlock) void ma_pairs_kernel(const float* __restr
   const double rx = c[0] - p[0], ry = c[1] - p[1], rz = c[2] - p[2];
   double v[kMaSums];
   ma_terms(has && w > 0.0, w, p, c, op, oc, md_dot(rx, ry, rz, rx, ry, rz), v);
-  ma_block_reduce(v, s_part, partial);
+  ma_block_reduce<kMaSums>(v, s_part, partial);
 }
 
 // Largest eigenvalue's unit eigenvector of the symmetric 4x4 A (destroyed) by cyclic Jacobi; one thread.

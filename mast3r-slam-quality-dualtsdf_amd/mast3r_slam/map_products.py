@@ -112,7 +112,8 @@ class MapProducts:
         `align=None`: the ground truth lies in the map's frame.  A Sim3 or "icp": compare_meshes(align=...) moves the
         mesh into the ground truth's frame first (DESIGN.md "Mesh alignment"); `init` is where ICP starts - a Sim3, or
         "trajectory" with `gt_positions` (K x 3, one row per keyframe) for self.align_trajectory(gt_positions);
-        `align_kw`: further arguments of tsdf.align_meshes.
+        `align_kw`: further arguments of tsdf.align_meshes, dict(metric="plane", point_weight=0.05) among them (DESIGN.md
+        "Point-to-plane ICP").
 
         `observed=True`: only the part of the ground truth that some keyframe sees enters completion, recall, fscore and
         chamfer (compare_meshes(observed=...), DESIGN.md "Mesh ray casting"): the cameras are the keyframes' T_WC, moved

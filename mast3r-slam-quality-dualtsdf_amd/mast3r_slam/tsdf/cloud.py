@@ -18,7 +18,7 @@ import mslam_hip as _m
 
 from ._mesh_args import _points_arg, _sim3_arg
 from .mesh_align import (DEGENERATE, LOG_DOUBLES, OK, STATE_BYTES, _alignment_arg, _icp_args, _icp_run,
-                         _read_state)
+                         _metric_arg, _plane_run, _read_state)
 from .mesh_index import _index_arg, _sorted_scan, _SpatialIndex
 from .mesh_metrics import _fscore_chamfer
 
@@ -169,10 +169,54 @@ def stride_sample(points, n_samples):
     return points[idx].contiguous(), idx
 
 
+def _align_clouds_plane(what, src, gt, init, trims, with_scale, tol, max_iters, check_every, index, normals,
+                        point_weight, trace):
+    """align_clouds with metric="plane" on the checked arguments: the normals, the state, and mesh_align._plane_run
+    over mslam_icp_plane_step_cloud."""
+    n, N, dev = int(src.shape[0]), int(gt.shape[0]), src.device
+    if torch.is_tensor(normals):
+        if tuple(normals.shape) != (N, 3):
+            raise ValueError(f"{what}: normals must be gt's, ({N},3), got {tuple(normals.shape)}")
+        _m.require_dtype(normals, torch.float32, "normals")
+        _m.ptr(normals)
+        if normals.device != dev:
+            raise ValueError(f"{what}: normals and gt are on different devices")
+        normals = normals.contiguous()
+    else:
+        k = _k_arg(normals, what, "normals")
+        normals = (cloud_normals(gt, k, index=index if index is not None else True)[0] if N
+                   else torch.zeros((0, 3), dtype=torch.float32, device=dev))
+    T0 = None if init is None else _sim3_arg(init, what, dev, torch.float32)
+    L, st = _m.lib(), _m.stream_ptr()
+    ws_bytes = int(L.mslam_icp_plane_workspace_bytes(n, 0))
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    state = torch.empty(STATE_BYTES, dtype=torch.uint8, device=dev)
+    _m.check(L.mslam_mesh_align_init_indexed(_m.ptr(T0), _m.ptr(state), st), "mesh_align_init_indexed")
+    order, iws, iws_bytes = (0, 0, 0) if index is None else (_m.ptr(index.order), _m.ptr(index.ws), index.ws_bytes)
+
+    def launch(it, nearest, moved, dist2, closest, log_row):
+        _m.check(L.mslam_icp_plane_step_cloud(_m.ptr(src), n, _m.ptr(gt), _m.ptr(normals), N, order, iws, iws_bytes, 2,
+                                              trims[it], point_weight, 1 if with_scale else 0, _m.ptr(ws), ws_bytes,
+                                              _m.ptr(state), _m.ptr(nearest), _m.ptr(moved), _m.ptr(dist2), closest,
+                                              log_row, st), "icp_plane_step_cloud")
+
+    return _plane_run(src, state, launch, max_iters, check_every, tol, trace)
+
+
 def align_clouds(pred, gt, init=None, n_samples=20000, max_iters=50, trim=math.inf, with_scale=True, tol=1e-6,
-                 check_every=5, index=None, _trace=None):
+                 check_every=5, index=None, metric="point", normals=16, point_weight=0.0, _trace=None):
     """Trimmed point-to-point ICP of the cloud `pred` onto the cloud `gt` (f32[N,3] device tensors): the Sim3 T with
     T(pred) ~ gt.  The arguments, the returned dict and the stop rule are align_meshes' (mesh_align._icp_args, _icp_run).
+
+    `metric`: "point" - what follows; "plane" - the point-to-plane metric (DESIGN.md "Point-to-plane ICP"): one fused
+    launch per iteration moves the sample, finds the nearest neighbours (the same scan, the same bits) and accumulates
+    n . (q - c) with the neighbour's normal n, and a second one solves for a small Sim3 and composes it onto T.
+    `normals`: a k - cloud_normals(gt, k) once before the loop - or gt's normals f32[N,3] themselves; a pair whose
+    neighbour has a zero or non-finite normal does not count.  The metric constrains nothing ALONG a surface: where few
+    normals face some direction (normal_spread near 0) the sample slides, and `point_weight` > 0 (0.05 is a mild tie;
+    "plane" only) adds the three point residuals with that weight, under which a pair without a normal counts too.  The
+    dict then gains point_rmse (the RMSE of the distances; `rmse` is that of the minimised residual) and normal_spread,
+    both of the last iteration.  `init` is rounded to f32 there, as in align_meshes.
 
     The source sample is stride_sample(pred, n_samples), drawn once.  Every iteration moves it by the current T (f64,
     rounded once to f32), finds each moved point's nearest neighbour in gt (cloud_distance; `index`: None, True or a
@@ -189,6 +233,7 @@ def align_clouds(pred, gt, init=None, n_samples=20000, max_iters=50, trim=math.i
     rmse, scale after the solve, status)."""
     what = "align_clouds"
     max_iters, check_every, trims = _icp_args(what, max_iters, check_every, tol, trim)
+    plane, point_weight = _metric_arg(what, metric, point_weight)
     if int(n_samples) < 1:
         raise ValueError(f"{what}: n_samples must be >= 1, got {n_samples}")
     pred = _points_arg(pred, "pred", what)
@@ -199,6 +244,9 @@ def align_clouds(pred, gt, init=None, n_samples=20000, max_iters=50, trim=math.i
     dev = pred.device
     src = stride_sample(pred, n_samples)[0]
     n = int(src.shape[0])
+    if plane:
+        return _align_clouds_plane(what, src, gt, init, trims, with_scale, tol, max_iters, check_every, index, normals,
+                                   point_weight, _trace)
     T = torch.tensor([0, 0, 0, 0, 0, 0, 1, 1], dtype=torch.float64, device=dev)
     if init is not None:
         T = _sim3_arg(init, what, dev, torch.float64).clone()
@@ -283,7 +331,8 @@ def compare_clouds(pred, gt, threshold=0.05, voxel=None, max_dist=None, align=No
     counted in accuracy_outliers / completion_outliers; they still count against precision and recall.
 
     `align`: None - the clouds are taken as they are; a Sim3 - pred is moved by it first (transform_cloud); "icp" - by
-    align_clouds(pred, gt, **align_kw) (a local method: pass align_kw=dict(init=...) beyond a modest offset).  With
+    align_clouds(pred, gt, **align_kw) (a local method: pass align_kw=dict(init=...) beyond a modest offset;
+    align_kw=dict(metric="plane", point_weight=0.05) is the point-to-plane metric with a mild point tie).  With
     alignment the dict gains `alignment`: T (8 floats), rmse and iterations (None for a given Sim3).
 
     `index`: None - plain scans, every pair is measured; True - a CloudIndex of each cloud is built; a CloudIndex of

@@ -123,6 +123,49 @@ def _icp_run(step, log, max_iters, check_every, tol):
     return it + 1, converged, hist
 
 
+PLANE_LOG_DOUBLES = _m.header_constants()["MSLAM_ICP_PLANE_LOG_DOUBLES"]
+
+
+def _metric_arg(what, metric, point_weight):
+    """(plane, point_weight) of align_meshes' and align_clouds' `metric` and `point_weight`, checked."""
+    if metric not in ("point", "plane"):
+        raise ValueError(f"{what}: metric must be 'point' or 'plane', got {metric!r}")
+    w = float(point_weight)
+    if not (w >= 0.0 and math.isfinite(w)):
+        raise ValueError(f"{what}: point_weight must be finite and >= 0, got {point_weight}")
+    if metric == "point" and w != 0.0:
+        raise ValueError(f"{what}: point_weight goes with metric='plane' only")
+    return metric == "plane", w
+
+
+def _plane_run(src, state, launch, max_iters, check_every, tol, trace):
+    """The loop of metric="plane" (csrc/icp_plane.hip; DESIGN.md "Point-to-plane ICP") over an initialised state block
+    -> the dict align_meshes and align_clouds return.  launch(it, nearest, moved, dist2, closest, log_row) runs the
+    fused step of iteration `it`; `closest` is 0 unless traced.  Beside _icp_run's reads there is one more at the end,
+    the last row's point rmse and normal_spread."""
+    n, dev = int(src.shape[0]), src.device
+    log = torch.zeros((max_iters, PLANE_LOG_DOUBLES), dtype=torch.float64, device=dev)
+    nearest = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    moved = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    dist2 = torch.empty(n, dtype=torch.float64, device=dev)
+
+    def step(it):
+        if trace is None:
+            launch(it, nearest, moved, dist2, 0, _m.ptr(log[it]))
+            return
+        T_before = _read_state(state)[0]
+        closest = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        launch(it, nearest, moved, dist2, _m.ptr(closest), _m.ptr(log[it]))
+        T, _, status = _read_state(state)
+        trace.append(dict(T_before=T_before, moved=moved.clone(), dist2=dist2.clone(), nearest=nearest.clone(),
+                          closest=closest, log=log[it].clone(), T=T, status=status))
+
+    iterations, converged, hist = _icp_run(step, log, max_iters, check_every, tol)
+    point_rmse, spread = log[iterations - 1, 4:6].tolist()
+    return dict(T=_read_state(state)[0], iterations=iterations, converged=converged, rmse=float(hist[-1, 1]),
+                inliers=int(hist[-1, 0]), history=hist, point_rmse=point_rmse, normal_spread=spread)
+
+
 def _alignment_arg(what, align, align_kw, icp):
     """compare_meshes' and compare_clouds' `align` -> (T, alignment): (None, None) for None; a Sim3 itself; for "icp"
     the T of icp(**align_kw), align_meshes or align_clouds bound to the pair.  alignment: the dict the figures gain."""
@@ -140,7 +183,7 @@ def _alignment_arg(what, align, align_kw, icp):
 
 
 def align_meshes(pred, gt, init=None, n_samples=20000, max_iters=50, trim=math.inf, with_scale=True, seed=0, tol=1e-6,
-                 check_every=5, index=None):
+                 check_every=5, index=None, metric="point", point_weight=0.0, _trace=None):
     """Trimmed point-to-mesh ICP of the mesh `pred` onto the mesh `gt` (both (vertices f32[V,3], faces i32[F,3]) device
     tensors or extract_mesh tuples): the Sim3 T with T(pred) ~ gt.
 
@@ -155,6 +198,14 @@ def align_meshes(pred, gt, init=None, n_samples=20000, max_iters=50, trim=math.i
     `index`: None, True or a MeshIndex of `gt`: the scan runs over its Morton-ordered tiles and group boxes instead of
     the tiles of gt's face order, warm start unchanged; same transform and log, bit for bit (DESIGN.md "Mesh index").
 
+    `metric`: "point" - the above; "plane" - the point-to-plane metric with a Gauss-Newton solve (DESIGN.md
+    "Point-to-plane ICP"): each pair contributes n . (q - c), n the plane of the nearest face, and the solve composes a
+    small Sim3 onto T; on planar scenes it needs a tenth of the iterations.  It constrains nothing ALONG a surface, so a
+    scene whose faces leave a direction free slides; `point_weight` > 0 (0.05 is a mild tie; "plane" only) adds the
+    three point residuals q - c with that weight.  The dict then gains point_rmse (the RMSE of |q - c|; `rmse` is that
+    of the minimised residual) and normal_spread (the smallest eigenvalue of the summed n n^T - with point_weight, plus
+    point_weight I - over the pairs; near 0: some translation is free), both of the last iteration.
+
     ICP is a LOCAL method: it needs `init` (a Sim3, default the identity) for anything beyond a modest offset.  On a
     partial room, a numpy prototype recovered 8 degrees / 15 cm / scale 0.9 and failed at 15 degrees / 0.3 m / scale
     0.8, where the samples slid along a wall.  SlamSystem.align_trajectory gives an `init` from camera centres.
@@ -164,6 +215,7 @@ def align_meshes(pred, gt, init=None, n_samples=20000, max_iters=50, trim=math.i
     f64[iterations, 4]: inliers, rmse, scale after the solve, status)."""
     what = "align_meshes"
     max_iters, check_every, trims = _icp_args(what, max_iters, check_every, tol, trim)
+    plane, point_weight = _metric_arg(what, metric, point_weight)
     index = _index_arg(MeshIndex, index, what, *_pair(gt, "gt"))
     pv, pf, pV, pF = _mesh_arg(*_pair(pred, "pred"), True, what)
     gv, gf, gV, gF = _mesh_arg(*_pair(gt, "gt"), True, what)
@@ -174,18 +226,37 @@ def align_meshes(pred, gt, init=None, n_samples=20000, max_iters=50, trim=math.i
     n = int(src.shape[0])
     T0 = None if init is None else _sim3_arg(init, what, dev, torch.float32)
     L, st = _m.lib(), _m.stream_ptr()
-    ws_bytes = int(L.mslam_mesh_align_workspace_bytes(n, gF if index is None else 0, 0))
+    boxed = gF if index is None else 0
+    ws_bytes = int(L.mslam_icp_plane_workspace_bytes(n, boxed) if plane
+                   else L.mslam_mesh_align_workspace_bytes(n, boxed, 0))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     state = torch.empty(STATE_BYTES, dtype=torch.uint8, device=dev)
-    log = torch.zeros((max_iters, LOG_DOUBLES), dtype=torch.float64, device=dev)
-    nearest = torch.full((n,), -1, dtype=torch.int32, device=dev)
-    moved = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    dist2 = torch.empty(n, dtype=torch.float64, device=dev)
     if index is None:
         _m.check(L.mslam_mesh_align_init(_m.ptr(T0), _m.ptr(gv), _m.ptr(gf), gF, gV, _m.ptr(ws), ws_bytes,
                                          _m.ptr(state), st), "mesh_align_init")
     else:
         _m.check(L.mslam_mesh_align_init_indexed(_m.ptr(T0), _m.ptr(state), st), "mesh_align_init_indexed")
+
+    def plane_step(it, nearest, moved, dist2, closest, log_row):
+        if index is None:
+            _m.check(L.mslam_icp_plane_step_mesh(_m.ptr(src), n, _m.ptr(gv), _m.ptr(gf), gF, gV, trims[it], point_weight,
+                                                 1 if with_scale else 0, _m.ptr(ws), ws_bytes, _m.ptr(state),
+                                                 _m.ptr(nearest), _m.ptr(moved), _m.ptr(dist2), closest, log_row, st),
+                     "icp_plane_step_mesh")
+        else:
+            _m.check(L.mslam_icp_plane_step_mesh_indexed(_m.ptr(src), n, _m.ptr(gv), _m.ptr(gf), gF, gV,
+                                                         _m.ptr(index.order), _m.ptr(index.ws), index.ws_bytes,
+                                                         trims[it], point_weight, 1 if with_scale else 0, _m.ptr(ws),
+                                                         ws_bytes, _m.ptr(state), _m.ptr(nearest), _m.ptr(moved),
+                                                         _m.ptr(dist2), closest, log_row, st),
+                     "icp_plane_step_mesh_indexed")
+
+    if plane:
+        return _plane_run(src, state, plane_step, max_iters, check_every, tol, _trace)
+    log = torch.zeros((max_iters, LOG_DOUBLES), dtype=torch.float64, device=dev)
+    nearest = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    moved = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    dist2 = torch.empty(n, dtype=torch.float64, device=dev)
 
     def step(it):
         if index is None:
@@ -199,6 +270,8 @@ def align_meshes(pred, gt, init=None, n_samples=20000, max_iters=50, trim=math.i
                                                      1 if with_scale else 0, 0, _m.ptr(ws), ws_bytes, _m.ptr(state),
                                                      _m.ptr(nearest), _m.ptr(moved), _m.ptr(dist2), 0,
                                                      _m.ptr(log[it]), st), "mesh_align_step_indexed")
+        if _trace is not None:
+            _trace.append(dict(moved=moved.clone(), dist2=dist2.clone(), nearest=nearest.clone(), log=log[it].clone()))
 
     iterations, converged, hist = _icp_run(step, log, max_iters, check_every, tol)
     return dict(T=_read_state(state)[0], iterations=iterations, converged=converged, rmse=float(hist[-1, 1]),

@@ -89,7 +89,7 @@ def compare_meshes(pred, gt, n_samples=200_000, threshold=0.05, seed=0, skip=Tru
 
     `align`: None - the meshes are taken as they are; a Sim3 ([t(3), q(xyzw), s], 8 numbers) - pred is moved by it first
     (transform_mesh); "icp" - pred is moved by align_meshes(pred, gt, **align_kw) first (a local method: pass
-    align_kw=dict(init=...) for more than a modest offset).  With alignment the dict gains `alignment`: T (a list of 8
+    align_kw=dict(init=...) for more than a modest offset; dict(metric="plane") is the point-to-plane metric).  With alignment the dict gains `alignment`: T (a list of 8
     floats), rmse and iterations (None for a given Sim3).
 
     `observed`: None - every ground-truth sample counts; a dict with `poses` (n Sim3s, world from camera), `K` (3,3),
