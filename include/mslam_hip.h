@@ -752,6 +752,41 @@ int mslam_cloud_normals(const float* points, int num_points, const int32_t* neig
                         int viewpoint_stride, float* normals, float* curvature, int32_t* count, double* moments,
                         void* stream);
 
+/* Cloud clusters: the points within a radius and density clustering, DBSCAN (no counterpart in the reference, DESIGN.md
+ * "Cloud clusters"; the definition is tests/cloud_cluster_numpy.py; csrc/cloud_cluster.hip).  d2 is
+ * mslam_cloud_distance's sum, the same bits for (i, j) and (j, i); "within" is d2 <= eps2, eps2 >= 0 an f64 taken as it
+ * is (+inf: everything).  order, index, index_bytes, levels and skip_counts as mslam_cloud_distance: order NULL is the
+ * plain scan; with an index a tile or group whose box lies beyond eps2 is not scanned; the same bytes in the three forms.
+ *   mslam_cloud_radius_count     count i32[n]: the valid points of the cloud within eps2 of each query (a point of the
+ *                                cloud counts itself and its duplicates; not capped); 0 for a query with a non-finite
+ *                                coordinate.  No atomics.
+ *   mslam_cloud_cluster_init     parent i32[N]: parent[v] = v.
+ *   mslam_cloud_cluster_link     the cloud in itself; row q of n stands for point self[q] (self i32[n]; NULL: the
+ *                                identity; an entry outside [0, N) is skipped, never followed).  core u8[N] (only read):
+ *                                the caller's valid && count >= min_points.  parent i32[N], in and out, touched only
+ *                                through atomics: a core row i unites (i, j) for every core j < i within eps2, in a
+ *                                lock-free union-find with parent[v] <= v that never waits.  A row that is not core keeps
+ *                                the core point smallest under the total order (d2, index) among those within eps2.
+ *                                anchor i32[n] / anchor_dist2 f64[n]: (the row's own point, 0) for a core row, (that core
+ *                                point, its d2) for a border row, (-1, +inf) for noise, an invalid point or a skipped row.
+ *   mslam_cloud_cluster_flatten  parent[v] = its root, the smallest index of its tree, in a launch of its own; after the
+ *                                link of every point that is the smallest core index of v's cluster (v itself for a
+ *                                point that is not core), whatever order the atomics landed in.
+ *   mslam_cloud_cluster_labels   with anchor i32[N] in point order: label_root i32[N] = root[anchor[i]], -1 where the
+ *                                anchor is outside [0, N); is_cluster_root u8[N] = core[v] && root[v] == v.  Numbering
+ *                                the roots and the sizes are the caller's integer work. */
+int mslam_cloud_radius_count(const float* queries, int n, const float* points, int num_points, double eps2,
+                             const int32_t* order, const void* index, size_t index_bytes, int levels,
+                             int32_t* skip_counts, int32_t* count, void* stream);
+int mslam_cloud_cluster_init(int num_points, int32_t* parent, void* stream);
+int mslam_cloud_cluster_link(const float* points, int num_points, const int32_t* self, int n, double eps2,
+                             const uint8_t* core, const int32_t* order, const void* index, size_t index_bytes,
+                             int levels, int32_t* skip_counts, int32_t* parent, int32_t* anchor, double* anchor_dist2,
+                             void* stream);
+int mslam_cloud_cluster_flatten(int num_points, int32_t* parent, void* stream);
+int mslam_cloud_cluster_labels(const int32_t* root, const uint8_t* core, const int32_t* anchor, int num_points,
+                               int32_t* label_root, uint8_t* is_cluster_root, void* stream);
+
 /* Point-to-plane ICP for clouds and meshes: one fused step and a Gauss-Newton solve on Sim3 per iteration (no
  * counterpart in the reference, DESIGN.md "Point-to-plane ICP"; the definition is tests/icp_plane_numpy.py;
  * csrc/icp_plane.hip).  The state block and its init and read are mslam_mesh_align_init / _init_indexed / _read; all

@@ -26,36 +26,11 @@
 // everything parent[v] has ever held.  When the hook kernel has ended, no pair is pending, the parent links alone span
 // each component, every tree's root is its smallest index, and flatten reads it.
 #include "mesh_topo.h"
+#include "union_find.h"
 
 namespace mslam {
 
-#define CC_RELAXED __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
-
-// Root of v as far as this thread can see; halves the path on the way.  v strictly decreases in every round.
-__device__ __forceinline__ int cc_find(int32_t* parent, int v) {
-  int p = __hip_atomic_load(parent + v, CC_RELAXED);
-  while (p < v) {
-    const int gp = __hip_atomic_load(parent + p, CC_RELAXED);
-    if (gp >= p) return p;
-    atomicMin(parent + v, gp);
-    v = gp;
-    p = __hip_atomic_load(parent + v, CC_RELAXED);
-  }
-  return v;
-}
-
-// Links the larger root below the smaller.  max(a, b) strictly decreases in every round.
-__device__ __forceinline__ void cc_unite(int32_t* parent, int a, int b) {
-  a = cc_find(parent, a);
-  b = cc_find(parent, b);
-  while (a != b) {
-    const int hi = a > b ? a : b, lo = a > b ? b : a;
-    const int old = atomicMin(parent + hi, lo);
-    if (old == hi) return;            // hi was a root and now hangs below lo
-    a = cc_find(parent, old);         // old < hi: hi was no root any more; (old, lo) still has to be united
-    b = cc_find(parent, lo);
-  }
-}
+// cc_find, cc_unite and CC_RELAXED: union_find.h, shared with cloud_cluster.hip
 
 __global__ __launch_bounds__(256) void cc_init_kernel(int nv, int32_t* __restrict__ root) {
   const int v = blockIdx.x * 256 + threadIdx.x;

@@ -3,7 +3,8 @@ trimmed point-to-point ICP and the accuracy / completion / precision / recall / 
 clouds - what scores the product's own output (evaluate.save_reconstruction's cloud) against a scan without faces.
 Below them the k nearest neighbours under a total order, and what stands on them: normals, the statistical and the
 radius outlier rule, the normal-consistency figures of compare_clouds.  The views of a cloud and the observed part that
-compare_clouds(observed=...) scores are cloud_view.py's.
+compare_clouds(observed=...) scores are cloud_view.py's; the count within a radius and the density clusters are
+cloud_cluster.py's.
 
 No counterpart in the reference.  The kernels are csrc/cloud.hip and csrc/cloud_knn.hip (DESIGN.md "Point clouds"); the
 numpy statements of the same definitions are tests/cloud_numpy.py and tests/cloud_knn_numpy.py.  A cloud is points f32[N,3]; a point is valid when its three coordinates are
