@@ -128,20 +128,14 @@ extern "C" int mslam_cloud_distance(const float* queries, int n, const float* po
                                     const int32_t* order, const void* index, size_t index_bytes, int levels,
                                     int32_t* skip_counts, double* dist2, int32_t* nearest, void* stream) {
   MSLAM_REQUIRE(n >= 0 && num_points >= 0, "cloud_distance: negative size");
-  MSLAM_REQUIRE(levels == 1 || levels == 2, "cloud_distance: levels must be 1 (tiles) or 2 (tiles and groups)");
+  if (int rc = md_levels_arg("cloud_distance", levels)) return rc;
   if (n == 0) return MSLAM_OK;
   MSLAM_REQUIRE(queries && dist2 && nearest, "cloud_distance: null pointer");
   MSLAM_REQUIRE(num_points == 0 || points, "cloud_distance: null pointer");
-  const bool indexed = order != nullptr && num_points > 0;
-  if (indexed) {
-    MSLAM_REQUIRE(index, "cloud_distance: an order needs its index");
-    if (index_bytes < md_index_bytes(num_points))
-      return md_too_small("cloud_distance", "index", index_bytes, md_index_bytes(num_points));
-  }
-  const double* box = indexed ? (const double*)index : nullptr;
-  const double* gbox = indexed && levels == 2 ? md_index_gbox(index, num_points) : nullptr;
-  hipLaunchKernelGGL(indexed ? cd_distance_kernel<true> : cd_distance_kernel<false>, dim3(blocks_for(n, kMdBlock)),
-                     dim3(kMdBlock), 0, (hipStream_t)stream, queries, n, points, num_points, order, box, gbox,
+  MdIndexArg ix;
+  if (int rc = md_index_arg("cloud_distance", num_points, order, index, index_bytes, levels, &ix)) return rc;
+  hipLaunchKernelGGL(ix.order ? cd_distance_kernel<true> : cd_distance_kernel<false>, dim3(blocks_for(n, kMdBlock)),
+                     dim3(kMdBlock), 0, (hipStream_t)stream, queries, n, points, num_points, ix.order, ix.box, ix.gbox,
                      skip_counts, dist2, nearest);
   MSLAM_LAUNCH_CHECK("cloud_distance");
   return MSLAM_OK;

@@ -171,25 +171,6 @@ __global__ __launch_bounds__(256) void cl_labels_kernel(const int32_t* __restric
   is_cluster_root[i] = core[i] && root[i] == i ? 1 : 0;
 }
 
-// The checks both scans share; *box / *gbox from the index (null for the plain scan)
-static int cl_index_arg(const char* what, int num_points, const int32_t* order, const void* index, size_t index_bytes,
-                        int levels, const double** box, const double** gbox) {
-  *box = *gbox = nullptr;
-  if (levels != 1 && levels != 2) {
-    set_error("%s: levels must be 1 (tiles) or 2 (tiles and groups)", what);
-    return MSLAM_EINVAL;
-  }
-  if (order == nullptr || num_points == 0) return MSLAM_OK;
-  if (!index) {
-    set_error("%s: an order needs its index", what);
-    return MSLAM_EINVAL;
-  }
-  if (index_bytes < md_index_bytes(num_points)) return md_too_small(what, "index", index_bytes, md_index_bytes(num_points));
-  *box = (const double*)index;
-  if (levels == 2) *gbox = md_index_gbox(index, num_points);
-  return MSLAM_OK;
-}
-
 }  // namespace mslam
 
 using namespace mslam;
@@ -199,15 +180,14 @@ extern "C" int mslam_cloud_radius_count(const float* queries, int n, const float
                                         int32_t* skip_counts, int32_t* count, void* stream) {
   MSLAM_REQUIRE(n >= 0 && num_points >= 0, "cloud_radius_count: negative size");
   MSLAM_REQUIRE(eps2 >= 0.0, "cloud_radius_count: eps2 must be >= 0, got %g", eps2);
-  const double *box, *gbox;
-  const int rc = cl_index_arg("cloud_radius_count", num_points, order, index, index_bytes, levels, &box, &gbox);
-  if (rc) return rc;
+  MdIndexArg ix;
+  if (int rc = md_index_arg("cloud_radius_count", num_points, order, index, index_bytes, levels, &ix)) return rc;
   if (n == 0) return MSLAM_OK;
   MSLAM_REQUIRE(queries && count, "cloud_radius_count: null pointer");
   MSLAM_REQUIRE(num_points == 0 || points, "cloud_radius_count: null pointer");
-  const auto kernel = box ? cl_count_kernel<true> : cl_count_kernel<false>;
+  const auto kernel = ix.order ? cl_count_kernel<true> : cl_count_kernel<false>;
   hipLaunchKernelGGL(kernel, dim3(blocks_for(n, kMdBlock)), dim3(kMdBlock), 0, (hipStream_t)stream, queries, n, points,
-                     num_points, eps2, order, box, gbox, skip_counts, count);
+                     num_points, eps2, ix.order, ix.box, ix.gbox, skip_counts, count);
   MSLAM_LAUNCH_CHECK("cloud_radius_count");
   return MSLAM_OK;
 }
@@ -228,15 +208,14 @@ extern "C" int mslam_cloud_cluster_link(const float* points, int num_points, con
                                         int32_t* anchor, double* anchor_dist2, void* stream) {
   MSLAM_REQUIRE(n >= 0 && num_points >= 0, "cloud_cluster_link: negative size");
   MSLAM_REQUIRE(eps2 >= 0.0, "cloud_cluster_link: eps2 must be >= 0, got %g", eps2);
-  const double *box, *gbox;
-  const int rc = cl_index_arg("cloud_cluster_link", num_points, order, index, index_bytes, levels, &box, &gbox);
-  if (rc) return rc;
+  MdIndexArg ix;
+  if (int rc = md_index_arg("cloud_cluster_link", num_points, order, index, index_bytes, levels, &ix)) return rc;
   if (n == 0) return MSLAM_OK;
   MSLAM_REQUIRE(anchor && anchor_dist2, "cloud_cluster_link: null pointer");
   MSLAM_REQUIRE(num_points == 0 || (points && core && parent), "cloud_cluster_link: null pointer");
-  const auto kernel = box ? cl_link_kernel<true> : cl_link_kernel<false>;
+  const auto kernel = ix.order ? cl_link_kernel<true> : cl_link_kernel<false>;
   hipLaunchKernelGGL(kernel, dim3(blocks_for(n, kMdBlock)), dim3(kMdBlock), 0, (hipStream_t)stream, points, num_points,
-                     self, n, eps2, core, order, box, gbox, skip_counts, parent, anchor, anchor_dist2);
+                     self, n, eps2, core, ix.order, ix.box, ix.gbox, skip_counts, parent, anchor, anchor_dist2);
   MSLAM_LAUNCH_CHECK("cloud_cluster_link");
   return MSLAM_OK;
 }

@@ -226,25 +226,19 @@ extern "C" int mslam_cloud_knn(const float* queries, int n, const float* points,
                                int levels, int32_t* skip_counts, double* dist2, int32_t* neighbors, void* stream) {
   MSLAM_REQUIRE(n >= 0 && num_points >= 0, "cloud_knn: negative size");
   MSLAM_REQUIRE(k >= 1 && k <= kKnMaxK, "cloud_knn: k must be in [1, %d], got %d", kKnMaxK, k);
-  MSLAM_REQUIRE(levels == 1 || levels == 2, "cloud_knn: levels must be 1 (tiles) or 2 (tiles and groups)");
+  if (int rc = md_levels_arg("cloud_knn", levels)) return rc;
   if (n == 0) return MSLAM_OK;
   MSLAM_REQUIRE(queries && dist2 && neighbors, "cloud_knn: null pointer");
   MSLAM_REQUIRE(num_points == 0 || points, "cloud_knn: null pointer");
-  const bool indexed = order != nullptr && num_points > 0;
-  if (indexed) {
-    MSLAM_REQUIRE(index, "cloud_knn: an order needs its index");
-    if (index_bytes < md_index_bytes(num_points))
-      return md_too_small("cloud_knn", "index", index_bytes, md_index_bytes(num_points));
-  }
-  const double* box = indexed ? (const double*)index : nullptr;
-  const double* gbox = indexed && levels == 2 ? md_index_gbox(index, num_points) : nullptr;
+  MdIndexArg ix;
+  if (int rc = md_index_arg("cloud_knn", num_points, order, index, index_bytes, levels, &ix)) return rc;
   // the smallest capacity that holds k, plain or indexed
   static const decltype(&kn_kernel<8, false>) kernels[3][2] = {{kn_kernel<8, false>, kn_kernel<8, true>},
                                                                  {kn_kernel<16, false>, kn_kernel<16, true>},
                                                                  {kn_kernel<32, false>, kn_kernel<32, true>}};
-  const auto kernel = kernels[k <= 8 ? 0 : k <= 16 ? 1 : 2][indexed];
+  const auto kernel = kernels[k <= 8 ? 0 : k <= 16 ? 1 : 2][ix.order != nullptr];
   hipLaunchKernelGGL(kernel, dim3(blocks_for(n, kMdBlock)), dim3(kMdBlock), 0, (hipStream_t)stream, queries, n, points,
-                     num_points, k, exclude, order, box, gbox, skip_counts, dist2, neighbors);
+                     num_points, k, exclude, ix.order, ix.box, ix.gbox, skip_counts, dist2, neighbors);
   MSLAM_LAUNCH_CHECK("cloud_knn");
   return MSLAM_OK;
 }

@@ -347,13 +347,10 @@ static int ip_step(const char* what, const float* src, int n, const typename Pri
 
 using namespace mslam;
 
-// the checks every step shares, in the style of ma_step
-#define IP_REQUIRE_STEP(what, sizes_ok)                                                                          \
-  MSLAM_REQUIRE(sizes_ok, what ": negative size");                                                               \
-  MSLAM_REQUIRE(trim >= 0.0, what ": trim must be >= 0 (+inf keeps every pair)");                                \
-  MSLAM_REQUIRE(point_weight >= 0.0 && point_weight < INFINITY, what ": point_weight must be finite and >= 0"); \
-  MSLAM_REQUIRE(state && log_row, what ": null pointer");                                                        \
-  MSLAM_REQUIRE(n == 0 || (src && nearest && moved && dist2 && workspace), what ": null pointer")
+// the checks every step shares: mesh_align.h's, and the weight
+#define IP_REQUIRE_STEP(what, sizes_ok) \
+  MA_REQUIRE_STEP(what, sizes_ok);      \
+  MSLAM_REQUIRE(point_weight >= 0.0 && point_weight < INFINITY, what ": point_weight must be finite and >= 0")
 
 extern "C" size_t mslam_icp_plane_workspace_bytes(int n, int num_faces) {
   if (n < 0 || num_faces < 0) return 0;
@@ -367,20 +364,15 @@ extern "C" int mslam_icp_plane_step_cloud(const float* src, int n, const float* 
                                           float* moved, double* dist2, double* closest, double* log_row,
                                           void* stream) {
   IP_REQUIRE_STEP("icp_plane_step_cloud", n >= 0 && num_points >= 0);
-  MSLAM_REQUIRE(levels == 1 || levels == 2, "icp_plane_step_cloud: levels must be 1 (tiles) or 2 (tiles and groups)");
+  if (int rc = md_levels_arg("icp_plane_step_cloud", levels)) return rc;
   MSLAM_REQUIRE(num_points == 0 || (points && normals), "icp_plane_step_cloud: null pointer");
   if (workspace_bytes < ip_partial_bytes(n))
     return md_too_small("icp_plane_step_cloud", "workspace", workspace_bytes, ip_partial_bytes(n));
-  const bool indexed = order != nullptr && num_points > 0;
-  if (indexed) {
-    MSLAM_REQUIRE(index, "icp_plane_step_cloud: an order needs its index");
-    if (index_bytes < md_index_bytes(num_points))
-      return md_too_small("icp_plane_step_cloud", "index", index_bytes, md_index_bytes(num_points));
-  }
-  return ip_step<MdPoint>("icp_plane_step_cloud", src, n, {points, num_points}, normals, indexed ? 1 : 0,
-                          indexed ? (const double*)index : nullptr, indexed ? order : nullptr,
-                          indexed && levels == 2 ? md_index_gbox(index, num_points) : nullptr, trim, point_weight,
-                          with_scale, (double*)workspace, state, nearest, moved, dist2, closest, log_row, stream);
+  MdIndexArg ix;
+  if (int rc = md_index_arg("icp_plane_step_cloud", num_points, order, index, index_bytes, levels, &ix)) return rc;
+  return ip_step<MdPoint>("icp_plane_step_cloud", src, n, {points, num_points}, normals, ix.order ? 1 : 0, ix.box,
+                          ix.order, ix.gbox, trim, point_weight, with_scale, (double*)workspace, state, nearest, moved,
+                          dist2, closest, log_row, stream);
 }
 
 extern "C" int mslam_icp_plane_step_mesh(const float* src, int n, const float* vertices, const int32_t* faces,
@@ -411,10 +403,10 @@ extern "C" int mslam_icp_plane_step_mesh_indexed(const float* src, int n, const 
                 "icp_plane_step_mesh_indexed: null pointer");
   if (workspace_bytes < ip_partial_bytes(n))
     return md_too_small("icp_plane_step_mesh_indexed", "workspace", workspace_bytes, ip_partial_bytes(n));
-  if (index_bytes < md_index_bytes(num_faces))
-    return md_too_small("icp_plane_step_mesh_indexed", "index", index_bytes, md_index_bytes(num_faces));
+  MdIndexArg ix;
+  if (int rc = md_index_arg("icp_plane_step_mesh_indexed", num_faces, order, index, index_bytes, 2, &ix)) return rc;
+  // `order` itself, also over no faces: it selects the indexed kernel
   return ip_step<MdTri>("icp_plane_step_mesh_indexed", src, n, {vertices, faces, num_faces, num_vertices}, nullptr,
-                        num_faces > 0 ? 1 : 0, (const double*)index, order,
-                        num_faces > 0 ? md_index_gbox(index, num_faces) : nullptr, trim, point_weight, with_scale,
+                        num_faces > 0 ? 1 : 0, ix.box, order, ix.gbox, trim, point_weight, with_scale,
                         (double*)workspace, state, nearest, moved, dist2, closest, log_row, stream);
 }

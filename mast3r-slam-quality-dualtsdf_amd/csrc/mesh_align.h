@@ -1,8 +1,16 @@
 // What the two ICP steps share (mesh_align.hip: point-to-mesh with the closed-form solve; icp_plane.hip: point-to-plane
 // with the Gauss-Newton solve): the rotation of the state's quaternion, the action of the state on a point, and the
-// block reduce in the fixed order both document.  f64, uncontracted.
+// block reduce in the fixed order both document (f64, uncontracted), and the argument checks of their entry points.
 #pragma once
 #include "mesh_tri.h"
+
+// The checks every step's entry point shares, on its own parameters src, n, trim, workspace, state, nearest, moved,
+// dist2 and log_row; sizes_ok: its sizes are >= 0
+#define MA_REQUIRE_STEP(what, sizes_ok)                                                \
+  MSLAM_REQUIRE(sizes_ok, what ": negative size");                                     \
+  MSLAM_REQUIRE(trim >= 0.0, what ": trim must be >= 0 (+inf keeps every pair)");      \
+  MSLAM_REQUIRE(state && log_row, what ": null pointer");                              \
+  MSLAM_REQUIRE(n == 0 || (src && nearest && moved && dist2 && workspace), what ": null pointer")
 
 namespace mslam {
 

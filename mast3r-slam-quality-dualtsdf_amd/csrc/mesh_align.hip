@@ -337,17 +337,16 @@ static int ma_step(const char* what, const float* src, int n, const float* verti
   const size_t box_bytes = indexed ? 0 : md_box_bytes(num_faces), part_bytes = ma_partial_bytes(n);
   const size_t need = box_bytes + part_bytes + (count_skips ? md_count_bytes(n) : 0);
   if (workspace_bytes < need) return md_too_small(what, "workspace", workspace_bytes, need);
-  if (indexed && index_bytes < md_index_bytes(num_faces))
-    return md_too_small(what, "index", index_bytes, md_index_bytes(num_faces));
+  MdIndexArg ix;
+  if (int rc = md_index_arg(what, num_faces, order, index, index_bytes, 2, &ix)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const unsigned nblocks = blocks_for(n, kMdBlock);
   double* partial = (double*)((char*)workspace + box_bytes);
   int32_t* skipped = count_skips ? (int32_t*)((char*)workspace + box_bytes + part_bytes) : nullptr;
   if (n > 0 && indexed)
     hipLaunchKernelGGL(ma_step_kernel<true>, dim3(nblocks), dim3(kMdBlock), 0, s, src, n, vertices, faces, num_faces,
-                       num_vertices, (const double*)state, num_faces > 0 ? 1 : 0, (const double*)index, order,
-                       num_faces > 0 ? md_index_gbox(index, num_faces) : (const double*)nullptr, trim * trim, skipped,
-                       nearest, moved, dist2, closest, partial);
+                       num_vertices, (const double*)state, num_faces > 0 ? 1 : 0, ix.box, order, ix.gbox, trim * trim,
+                       skipped, nearest, moved, dist2, closest, partial);
   else if (n > 0)
     hipLaunchKernelGGL(ma_step_kernel<false>, dim3(nblocks), dim3(kMdBlock), 0, s, src, n, vertices, faces, num_faces,
                        num_vertices, (const double*)state, num_faces > kMdTile ? 1 : 0, (const double*)workspace,
@@ -362,10 +361,7 @@ extern "C" int mslam_mesh_align_step(const float* src, int n, const float* verti
                                      int num_faces, int num_vertices, double trim, int with_scale, int count_skips,
                                      void* workspace, size_t workspace_bytes, void* state, int32_t* nearest,
                                      float* moved, double* dist2, double* closest, double* log_row, void* stream) {
-  MSLAM_REQUIRE(n >= 0 && num_faces >= 0 && num_vertices >= 0, "mesh_align_step: negative size");
-  MSLAM_REQUIRE(trim >= 0.0, "mesh_align_step: trim must be >= 0 (+inf keeps every pair)");
-  MSLAM_REQUIRE(state && log_row, "mesh_align_step: null pointer");
-  MSLAM_REQUIRE(n == 0 || (src && nearest && moved && dist2 && workspace), "mesh_align_step: null pointer");
+  MA_REQUIRE_STEP("mesh_align_step", n >= 0 && num_faces >= 0 && num_vertices >= 0);
   MSLAM_REQUIRE(num_faces == 0 || (faces && workspace && (vertices || num_vertices == 0)),
                 "mesh_align_step: null pointer");
   return ma_step("mesh_align_step", src, n, vertices, faces, num_faces, num_vertices, nullptr, nullptr, 0, trim,
@@ -386,10 +382,8 @@ extern "C" int mslam_mesh_align_step_indexed(const float* src, int n, const floa
                                              void* workspace, size_t workspace_bytes, void* state, int32_t* nearest,
                                              float* moved, double* dist2, double* closest, double* log_row,
                                              void* stream) {
-  MSLAM_REQUIRE(n >= 0 && num_faces >= 0 && num_vertices >= 0, "mesh_align_step_indexed: negative size");
-  MSLAM_REQUIRE(trim >= 0.0, "mesh_align_step_indexed: trim must be >= 0 (+inf keeps every pair)");
-  MSLAM_REQUIRE(state && log_row && order, "mesh_align_step_indexed: null pointer");
-  MSLAM_REQUIRE(n == 0 || (src && nearest && moved && dist2 && workspace), "mesh_align_step_indexed: null pointer");
+  MA_REQUIRE_STEP("mesh_align_step_indexed", n >= 0 && num_faces >= 0 && num_vertices >= 0);
+  MSLAM_REQUIRE(order, "mesh_align_step_indexed: null pointer");
   MSLAM_REQUIRE(num_faces == 0 || (faces && index && (vertices || num_vertices == 0)),
                 "mesh_align_step_indexed: null pointer");
   return ma_step("mesh_align_step_indexed", src, n, vertices, faces, num_faces, num_vertices, order, index,

@@ -131,10 +131,9 @@ static int md_distance_impl(const char* what, bool indexed, const float* points,
                             int levels, int32_t* skip_counts, double* dist2, int32_t* nearest, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   int cull = num_faces > 0 && (indexed || skip);
-  const double* box = (const double*)(indexed ? index : workspace);
+  MdIndexArg ix = {nullptr, (const double*)workspace, nullptr};
   if (indexed) {
-    if (index_bytes < md_index_bytes(num_faces))
-      return md_too_small(what, "index", index_bytes, md_index_bytes(num_faces));
+    if (int rc = md_index_arg(what, num_faces, order, index, index_bytes, levels, &ix)) return rc;
   } else if (cull) {
     const size_t box_bytes = md_box_bytes(num_faces), count_bytes = skip == 2 ? md_count_bytes(n) : 0;
     if (workspace_bytes < box_bytes + count_bytes)
@@ -149,10 +148,9 @@ static int md_distance_impl(const char* what, bool indexed, const float* points,
       cull = 0, skip_counts = nullptr;
     }
   }
-  const double* gbox = indexed && levels == 2 && num_faces > 0 ? md_index_gbox(index, num_faces) : nullptr;
   hipLaunchKernelGGL(indexed ? md_distance_kernel<true> : md_distance_kernel<false>, dim3(blocks_for(n, kMdBlock)),
-                     dim3(kMdBlock), 0, s, points, n, vertices, faces, num_faces, num_vertices, cull, box, order, gbox,
-                     skip_counts, dist2, nearest);
+                     dim3(kMdBlock), 0, s, points, n, vertices, faces, num_faces, num_vertices, cull, ix.box, ix.order,
+                     ix.gbox, skip_counts, dist2, nearest);
   return md_launched(what);
 }
 
@@ -174,7 +172,7 @@ extern "C" int mslam_mesh_distance_indexed(const float* points, int n, const flo
                                            size_t index_bytes, int levels, int32_t* skip_counts, double* dist2,
                                            int32_t* nearest, void* stream) {
   MSLAM_REQUIRE(n >= 0 && num_faces >= 0 && num_vertices >= 0, "mesh_distance_indexed: negative size");
-  MSLAM_REQUIRE(levels == 1 || levels == 2, "mesh_distance_indexed: levels must be 1 (tiles) or 2 (tiles and groups)");
+  if (int rc = md_levels_arg("mesh_distance_indexed", levels)) return rc;
   if (n == 0) return MSLAM_OK;
   MSLAM_REQUIRE(points && dist2 && nearest, "mesh_distance_indexed: null pointer");
   MSLAM_REQUIRE(num_faces == 0 || (faces && order && index && (vertices || num_vertices == 0)),

@@ -246,13 +246,15 @@ static int rc_cast_impl(const char* what, bool indexed, const float* rays, int h
                         double far, int cull, const void* box, size_t box_bytes, const int32_t* order, int levels,
                         int32_t* skip_counts, float* range, float* normal, uint8_t* hit, int32_t* face, double* t64,
                         void* stream) {
-  const size_t need = indexed ? md_index_bytes(num_faces) : md_box_bytes(num_faces);
-  if ((indexed || cull) && box_bytes < need)
-    return md_too_small(what, indexed ? "index" : "workspace", box_bytes, need);
-  const double* gbox = indexed && levels == 2 && num_faces > 0 ? md_index_gbox(box, num_faces) : nullptr;
+  MdIndexArg ix = {nullptr, (const double*)box, nullptr};
+  if (indexed) {
+    if (int rc = md_index_arg(what, num_faces, order, box, box_bytes, levels, &ix)) return rc;
+  } else if (cull && box_bytes < md_box_bytes(num_faces)) {
+    return md_too_small(what, "workspace", box_bytes, md_box_bytes(num_faces));
+  }
   hipLaunchKernelGGL(indexed ? rc_kernel<true> : rc_kernel<false>, view_grid(h, w), dim3(kMdBlock), 0,
                      (hipStream_t)stream, rays, h, w, pose8, vertices, faces, num_faces, num_vertices, near, far, cull,
-                     (const double*)box, order, gbox, skip_counts, range, normal, hit, face, t64);
+                     ix.box, ix.order, ix.gbox, skip_counts, range, normal, hit, face, t64);
   return md_launched(what);
 }
 
@@ -284,7 +286,7 @@ extern "C" int mslam_mesh_raycast_indexed(const float* rays, int h, int w, const
                                           int32_t* face, double* t64, void* stream) {
   if (int rc = view_check("mesh_raycast_indexed", 1, h, w, nullptr, near, far, false)) return rc;
   MSLAM_REQUIRE(num_faces >= 0 && num_vertices >= 0, "mesh_raycast_indexed: negative size");
-  MSLAM_REQUIRE(levels == 1 || levels == 2, "mesh_raycast_indexed: levels must be 1 (tiles) or 2 (tiles and groups)");
+  if (int rc = md_levels_arg("mesh_raycast_indexed", levels)) return rc;
   if (h == 0 || w == 0) return MSLAM_OK;
   MSLAM_REQUIRE(rays && pose8 && range && normal && hit, "mesh_raycast_indexed: null pointer");
   MSLAM_REQUIRE(num_faces == 0 || (faces && order && index && (vertices || num_vertices == 0)),

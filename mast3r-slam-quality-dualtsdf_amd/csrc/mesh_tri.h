@@ -3,7 +3,8 @@
 // distance from a point to a box, the home-tile search md_home_tile, md_scan, the one culled nearest-element scan that
 // md_distance_kernel and ma_step_kernel call over triangles (MdTri) and cd_distance_kernel of cloud.hip over points
 // (MdPoint), md_walk, the same block-wide walk over groups and tiles keeping what a policy object says (kn_kernel of
-// cloud_knn.hip: the k best), and the index builder md_build_index.  Semantics in DESIGN.md "Mesh quality";
+// cloud_knn.hip: the k best), the index builder md_build_index, and md_index_arg, the host checks of an index handed
+// to an entry point.  Semantics in DESIGN.md "Mesh quality";
 // tests/meshdist_numpy.py states the same definitions, operation by operation, in numpy.  Everything is f64 on the f32
 // inputs and the build has -ffp-contract=off, so a * b + c below is two roundings, as in numpy.
 //
@@ -470,6 +471,37 @@ inline void md_launch_boxes(const typename Prim::Src src, const int32_t* order, 
 inline int md_too_small(const char* what, const char* thing, size_t have, size_t need) {
   set_error("%s: %s of %zu bytes, %zu needed", what, thing, have, need);
   return MSLAM_ENOMEM;
+}
+
+// The `levels` of entry point `what`; an entry point that tests it ahead of its early return calls this by itself
+inline int md_levels_arg(const char* what, int levels) {
+  if (levels == 1 || levels == 2) return MSLAM_OK;
+  set_error("%s: levels must be 1 (tiles) or 2 (tiles and groups)", what);
+  return MSLAM_EINVAL;
+}
+
+// What the scans take of an index: all null for the plain scan; gbox null at `levels` 1
+struct MdIndexArg {
+  const int32_t* order;
+  const double *box, *gbox;
+};
+
+// The index argument (order, index, index_bytes, levels) of entry point `what` over a target of n elements -> *arg.
+// The plain scan (no order, or no element to index) asks nothing of `index`; an order needs its index, large enough.
+// Every entry point calls it where its own checks stand, so which degenerate calls it refuses is the entry point's
+// (tests/test_index_arg_gpu.py has the table).  An entry point without a `levels` parameter passes 2.
+inline int md_index_arg(const char* what, int n, const int32_t* order, const void* index, size_t index_bytes,
+                        int levels, MdIndexArg* arg) {
+  *arg = {nullptr, nullptr, nullptr};
+  if (int rc = md_levels_arg(what, levels)) return rc;
+  if (!order || n == 0) return MSLAM_OK;
+  if (!index) {
+    set_error("%s: an order needs its index", what);
+    return MSLAM_EINVAL;
+  }
+  if (index_bytes < md_index_bytes(n)) return md_too_small(what, "index", index_bytes, md_index_bytes(n));
+  *arg = {order, (const double*)index, levels == 2 ? md_index_gbox(index, n) : nullptr};
+  return MSLAM_OK;
 }
 
 // MSLAM_LAUNCH_CHECK for an entry point whose name is known at run time: the status to return after the launches

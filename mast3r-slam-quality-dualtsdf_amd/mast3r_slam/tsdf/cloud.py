@@ -19,8 +19,8 @@ import mslam_hip as _m
 
 from ._mesh_args import _points_arg, _sim3_arg
 from .mesh_align import (DEGENERATE, LOG_DOUBLES, OK, STATE_BYTES, _alignment_arg, _icp_args, _icp_run,
-                         _metric_arg, _plane_run, _read_state)
-from .mesh_index import _index_arg, _sorted_scan, _SpatialIndex
+                         _icp_setup, _metric_arg, _read_state, _state_run)
+from .mesh_index import _NEAREST, _index_arg, _index_ops, _sorted_scan, _SpatialIndex
 from .mesh_metrics import _fscore_chamfer
 
 _NONE = torch.iinfo(torch.int64).max
@@ -66,15 +66,12 @@ class CloudIndex(_SpatialIndex):
 def _distance2(queries, points, index=None, sort_queries=True, levels=2):
     """(dist2 f64[n], nearest i32[n]) of the checked arguments."""
     n, N = int(queries.shape[0]), int(points.shape[0])
-    # without an index: no order, no boxes, and levels 1, which the plain scan does not read
-    order, ws, ws_bytes, levels = (0, 0, 0, 1) if index is None else (_m.ptr(index.order), _m.ptr(index.ws),
-                                                                      index.ws_bytes, levels)
 
     def scan(q, dist2, nearest):
-        _m.check(_m.lib().mslam_cloud_distance(_m.ptr(q), n, _m.ptr(points), N, order, ws, ws_bytes, levels, 0,
+        _m.check(_m.lib().mslam_cloud_distance(_m.ptr(q), n, _m.ptr(points), N, *_index_ops(index, levels), 0,
                                                _m.ptr(dist2), _m.ptr(nearest), _m.stream_ptr()), "cloud_distance")
 
-    return _sorted_scan(queries, index, sort_queries, scan)
+    return _sorted_scan(queries, index, sort_queries, _NEAREST, scan)
 
 
 def cloud_distance(queries, points, index=None, sort_queries=True):
@@ -172,7 +169,7 @@ def stride_sample(points, n_samples):
 
 def _align_clouds_plane(what, src, gt, init, trims, with_scale, tol, max_iters, check_every, index, normals,
                         point_weight, trace):
-    """align_clouds with metric="plane" on the checked arguments: the normals, the state, and mesh_align._plane_run
+    """align_clouds with metric="plane" on the checked arguments: the normals, the state, and mesh_align._state_run
     over mslam_icp_plane_step_cloud."""
     n, N, dev = int(src.shape[0]), int(gt.shape[0]), src.device
     if torch.is_tensor(normals):
@@ -190,18 +187,15 @@ def _align_clouds_plane(what, src, gt, init, trims, with_scale, tol, max_iters, 
     T0 = None if init is None else _sim3_arg(init, what, dev, torch.float32)
     L, st = _m.lib(), _m.stream_ptr()
     ws_bytes = int(L.mslam_icp_plane_workspace_bytes(n, 0))
-    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
-    state = torch.empty(STATE_BYTES, dtype=torch.uint8, device=dev)
-    _m.check(L.mslam_mesh_align_init_indexed(_m.ptr(T0), _m.ptr(state), st), "mesh_align_init_indexed")
-    order, iws, iws_bytes = (0, 0, 0) if index is None else (_m.ptr(index.order), _m.ptr(index.ws), index.ws_bytes)
+    ws, state = _icp_setup(dev, ws_bytes, T0)
 
     def launch(it, nearest, moved, dist2, closest, log_row):
-        _m.check(L.mslam_icp_plane_step_cloud(_m.ptr(src), n, _m.ptr(gt), _m.ptr(normals), N, order, iws, iws_bytes, 2,
+        _m.check(L.mslam_icp_plane_step_cloud(_m.ptr(src), n, _m.ptr(gt), _m.ptr(normals), N, *_index_ops(index),
                                               trims[it], point_weight, 1 if with_scale else 0, _m.ptr(ws), ws_bytes,
                                               _m.ptr(state), _m.ptr(nearest), _m.ptr(moved), _m.ptr(dist2), closest,
                                               log_row, st), "icp_plane_step_cloud")
 
-    return _plane_run(src, state, launch, max_iters, check_every, tol, trace)
+    return _state_run(src, state, launch, True, max_iters, check_every, tol, trace)
 
 
 def align_clouds(pred, gt, init=None, n_samples=20000, max_iters=50, trim=math.inf, with_scale=True, tol=1e-6,
@@ -432,19 +426,13 @@ def _k_arg(k, what, name="k"):
 
 def _knn2(queries, points, k, index=None, sort_queries=True, exclude=None, levels=2):
     """(dist2 f64[n,k], neighbors i32[n,k]) of the checked arguments; `exclude`: None or i32[n] on the device."""
-    n, N, dev = int(queries.shape[0]), int(points.shape[0]), queries.device
-    order, ws, ws_bytes, levels = (0, 0, 0, 1) if index is None else (_m.ptr(index.order), _m.ptr(index.ws),
-                                                                      index.ws_bytes, levels)
-    dist2 = torch.empty((n, k), dtype=torch.float64, device=dev)
-    neighbors = torch.empty((n, k), dtype=torch.int32, device=dev)
-    perm = index.query_order(queries) if index is not None and sort_queries and n > 1 else None
-    q = queries if perm is None else queries[perm].contiguous()
-    ex = exclude if perm is None or exclude is None else exclude[perm].contiguous()
-    _m.check(_m.lib().mslam_cloud_knn(_m.ptr(q), n, _m.ptr(points), N, k, _m.ptr(ex), order, ws, ws_bytes, levels, 0,
-                                      _m.ptr(dist2), _m.ptr(neighbors), _m.stream_ptr()), "cloud_knn")
-    if perm is None:
-        return dist2, neighbors
-    return torch.empty_like(dist2).index_copy_(0, perm, dist2), torch.empty_like(neighbors).index_copy_(0, perm, neighbors)
+    n, N = int(queries.shape[0]), int(points.shape[0])
+
+    def scan(q, ex, dist2, neighbors):
+        _m.check(_m.lib().mslam_cloud_knn(_m.ptr(q), n, _m.ptr(points), N, k, _m.ptr(ex), *_index_ops(index, levels), 0,
+                                          _m.ptr(dist2), _m.ptr(neighbors), _m.stream_ptr()), "cloud_knn")
+
+    return _sorted_scan(queries, index, sort_queries, ((torch.float64, (k,)), (torch.int32, (k,))), scan, (exclude,))
 
 
 def _self(points):

@@ -15,25 +15,18 @@ import mslam_hip as _m
 
 from ._mesh_args import _points_arg
 from .cloud import CloudIndex, _colors_arg, _valid
-from .mesh_index import _index_arg
-
-
-def _index_ops(index, levels=2):
-    """(order, index, index_bytes, levels) of the C entry points; without an index the plain scan."""
-    if index is None:
-        return 0, 0, 0, 1
-    return _m.ptr(index.order), _m.ptr(index.ws), index.ws_bytes, levels
+from .mesh_index import _index_arg, _index_ops, _sorted_scan
 
 
 def _radius_count(queries, points, eps2, index=None, sort_queries=True, levels=2):
     """count i32[n] of the checked arguments."""
-    n, N, dev = int(queries.shape[0]), int(points.shape[0]), queries.device
-    count = torch.empty(n, dtype=torch.int32, device=dev)
-    perm = index.query_order(queries) if index is not None and sort_queries and n > 1 else None
-    q = queries if perm is None else queries[perm].contiguous()
-    _m.check(_m.lib().mslam_cloud_radius_count(_m.ptr(q), n, _m.ptr(points), N, eps2, *_index_ops(index, levels), 0,
-                                               _m.ptr(count), _m.stream_ptr()), "cloud_radius_count")
-    return count if perm is None else torch.empty_like(count).index_copy_(0, perm, count)
+    n, N = int(queries.shape[0]), int(points.shape[0])
+
+    def scan(q, count):
+        _m.check(_m.lib().mslam_cloud_radius_count(_m.ptr(q), n, _m.ptr(points), N, eps2, *_index_ops(index, levels), 0,
+                                                   _m.ptr(count), _m.stream_ptr()), "cloud_radius_count")
+
+    return _sorted_scan(queries, index, sort_queries, ((torch.int32, ()),), scan)[0]
 
 
 def cloud_radius_count(queries, points, radius, index=None, sort_queries=True):

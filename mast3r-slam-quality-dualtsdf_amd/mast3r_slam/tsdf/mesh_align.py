@@ -13,7 +13,7 @@ import torch
 import mslam_hip as _m
 
 from ._mesh_args import _mesh_arg, _pair, _points_arg, _sample, _sim3_arg
-from .mesh_index import MeshIndex, _index_arg
+from .mesh_index import MeshIndex, _index_arg, _index_ops
 
 STATE_BYTES, LOG_DOUBLES, OK, DEGENERATE = (_m.header_constants()["MSLAM_MESH_ALIGN_" + k] for k in (
     "STATE_BYTES", "LOG_DOUBLES", "OK", "DEGENERATE"))
@@ -138,20 +138,39 @@ def _metric_arg(what, metric, point_weight):
     return metric == "plane", w
 
 
-def _plane_run(src, state, launch, max_iters, check_every, tol, trace):
-    """The loop of metric="plane" (csrc/icp_plane.hip; DESIGN.md "Point-to-plane ICP") over an initialised state block
-    -> the dict align_meshes and align_clouds return.  launch(it, nearest, moved, dist2, closest, log_row) runs the
-    fused step of iteration `it`; `closest` is 0 unless traced.  Beside _icp_run's reads there is one more at the end,
-    the last row's point rmse and normal_spread."""
+def _icp_setup(dev, ws_bytes, T0, boxed=None):
+    """(ws, state) of a loop over a state block: the workspace, and the state set to T0 f32[8] (None: the identity).
+    `boxed`: the (vertices, faces, F, V) of a target mesh scanned without an index - the boxes of its tiles are built at
+    the head of the workspace."""
+    L, st = _m.lib(), _m.stream_ptr()
+    ws = torch.empty(max(ws_bytes, 8), dtype=torch.uint8, device=dev)
+    state = torch.empty(STATE_BYTES, dtype=torch.uint8, device=dev)
+    if boxed is None:
+        _m.check(L.mslam_mesh_align_init_indexed(_m.ptr(T0), _m.ptr(state), st), "mesh_align_init_indexed")
+    else:
+        gv, gf, gF, gV = boxed
+        _m.check(L.mslam_mesh_align_init(_m.ptr(T0), _m.ptr(gv), _m.ptr(gf), gF, gV, _m.ptr(ws), ws_bytes,
+                                         _m.ptr(state), st), "mesh_align_init")
+    return ws, state
+
+
+def _state_run(src, state, launch, plane, max_iters, check_every, tol, trace):
+    """The loop of both metrics over an initialised state block (csrc/mesh_align.hip, csrc/icp_plane.hip) -> the dict
+    align_meshes and align_clouds return.  launch(it, nearest, moved, dist2, closest, log_row) runs the step of
+    iteration `it`; `closest` is 0 unless the plane metric is traced.  `plane`: the log rows are the plane metric's, and
+    beside _icp_run's reads there is one more at the end, the last row's point rmse and normal_spread."""
     n, dev = int(src.shape[0]), src.device
-    log = torch.zeros((max_iters, PLANE_LOG_DOUBLES), dtype=torch.float64, device=dev)
+    log = torch.zeros((max_iters, PLANE_LOG_DOUBLES if plane else LOG_DOUBLES), dtype=torch.float64, device=dev)
     nearest = torch.full((n,), -1, dtype=torch.int32, device=dev)
     moved = torch.empty((n, 3), dtype=torch.float32, device=dev)
     dist2 = torch.empty(n, dtype=torch.float64, device=dev)
 
     def step(it):
-        if trace is None:
+        if trace is None or not plane:
             launch(it, nearest, moved, dist2, 0, _m.ptr(log[it]))
+            if trace is not None:
+                trace.append(dict(moved=moved.clone(), dist2=dist2.clone(), nearest=nearest.clone(),
+                                  log=log[it].clone()))
             return
         T_before = _read_state(state)[0]
         closest = torch.empty((n, 3), dtype=torch.float64, device=dev)
@@ -161,9 +180,11 @@ def _plane_run(src, state, launch, max_iters, check_every, tol, trace):
                           closest=closest, log=log[it].clone(), T=T, status=status))
 
     iterations, converged, hist = _icp_run(step, log, max_iters, check_every, tol)
-    point_rmse, spread = log[iterations - 1, 4:6].tolist()
-    return dict(T=_read_state(state)[0], iterations=iterations, converged=converged, rmse=float(hist[-1, 1]),
-                inliers=int(hist[-1, 0]), history=hist, point_rmse=point_rmse, normal_spread=spread)
+    res = dict(T=_read_state(state)[0], iterations=iterations, converged=converged, rmse=float(hist[-1, 1]),
+               inliers=int(hist[-1, 0]), history=hist)
+    if plane:
+        res["point_rmse"], res["normal_spread"] = log[iterations - 1, 4:6].tolist()
+    return res
 
 
 def _alignment_arg(what, align, align_kw, icp):
@@ -229,50 +250,17 @@ def align_meshes(pred, gt, init=None, n_samples=20000, max_iters=50, trim=math.i
     boxed = gF if index is None else 0
     ws_bytes = int(L.mslam_icp_plane_workspace_bytes(n, boxed) if plane
                    else L.mslam_mesh_align_workspace_bytes(n, boxed, 0))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    state = torch.empty(STATE_BYTES, dtype=torch.uint8, device=dev)
-    if index is None:
-        _m.check(L.mslam_mesh_align_init(_m.ptr(T0), _m.ptr(gv), _m.ptr(gf), gF, gV, _m.ptr(ws), ws_bytes,
-                                         _m.ptr(state), st), "mesh_align_init")
-    else:
-        _m.check(L.mslam_mesh_align_init_indexed(_m.ptr(T0), _m.ptr(state), st), "mesh_align_init_indexed")
+    ws, state = _icp_setup(dev, ws_bytes, T0, (gv, gf, gF, gV) if index is None else None)
+    # mslam_{mesh_align_step, icp_plane_step_mesh}[_indexed]: the sample and the mesh, with an index its three operands,
+    # then the metric's own arguments, then what every step takes
+    name = ("icp_plane_step_mesh" if plane else "mesh_align_step") + ("" if index is None else "_indexed")
+    step_fn = getattr(L, "mslam_" + name)
+    target = (_m.ptr(src), n, _m.ptr(gv), _m.ptr(gf), gF, gV) + (() if index is None else _index_ops(index)[:3])
+    scale = 1 if with_scale else 0
 
-    def plane_step(it, nearest, moved, dist2, closest, log_row):
-        if index is None:
-            _m.check(L.mslam_icp_plane_step_mesh(_m.ptr(src), n, _m.ptr(gv), _m.ptr(gf), gF, gV, trims[it], point_weight,
-                                                 1 if with_scale else 0, _m.ptr(ws), ws_bytes, _m.ptr(state),
-                                                 _m.ptr(nearest), _m.ptr(moved), _m.ptr(dist2), closest, log_row, st),
-                     "icp_plane_step_mesh")
-        else:
-            _m.check(L.mslam_icp_plane_step_mesh_indexed(_m.ptr(src), n, _m.ptr(gv), _m.ptr(gf), gF, gV,
-                                                         _m.ptr(index.order), _m.ptr(index.ws), index.ws_bytes,
-                                                         trims[it], point_weight, 1 if with_scale else 0, _m.ptr(ws),
-                                                         ws_bytes, _m.ptr(state), _m.ptr(nearest), _m.ptr(moved),
-                                                         _m.ptr(dist2), closest, log_row, st),
-                     "icp_plane_step_mesh_indexed")
+    def launch(it, nearest, moved, dist2, closest, log_row):
+        metric = (trims[it], point_weight, scale) if plane else (trims[it], scale, 0)       # 0: no skip counts
+        _m.check(step_fn(*target, *metric, _m.ptr(ws), ws_bytes, _m.ptr(state), _m.ptr(nearest), _m.ptr(moved),
+                         _m.ptr(dist2), closest, log_row, st), name)
 
-    if plane:
-        return _plane_run(src, state, plane_step, max_iters, check_every, tol, _trace)
-    log = torch.zeros((max_iters, LOG_DOUBLES), dtype=torch.float64, device=dev)
-    nearest = torch.full((n,), -1, dtype=torch.int32, device=dev)
-    moved = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    dist2 = torch.empty(n, dtype=torch.float64, device=dev)
-
-    def step(it):
-        if index is None:
-            _m.check(L.mslam_mesh_align_step(_m.ptr(src), n, _m.ptr(gv), _m.ptr(gf), gF, gV, trims[it],
-                                             1 if with_scale else 0, 0, _m.ptr(ws), ws_bytes, _m.ptr(state),
-                                             _m.ptr(nearest), _m.ptr(moved), _m.ptr(dist2), 0, _m.ptr(log[it]), st),
-                     "mesh_align_step")
-        else:
-            _m.check(L.mslam_mesh_align_step_indexed(_m.ptr(src), n, _m.ptr(gv), _m.ptr(gf), gF, gV,
-                                                     _m.ptr(index.order), _m.ptr(index.ws), index.ws_bytes, trims[it],
-                                                     1 if with_scale else 0, 0, _m.ptr(ws), ws_bytes, _m.ptr(state),
-                                                     _m.ptr(nearest), _m.ptr(moved), _m.ptr(dist2), 0,
-                                                     _m.ptr(log[it]), st), "mesh_align_step_indexed")
-        if _trace is not None:
-            _trace.append(dict(moved=moved.clone(), dist2=dist2.clone(), nearest=nearest.clone(), log=log[it].clone()))
-
-    iterations, converged, hist = _icp_run(step, log, max_iters, check_every, tol)
-    return dict(T=_read_state(state)[0], iterations=iterations, converged=converged, rmse=float(hist[-1, 1]),
-                inliers=int(hist[-1, 0]), history=hist)
+    return _state_run(src, state, launch, plane, max_iters, check_every, tol, _trace)

@@ -92,15 +92,27 @@ def _index_arg(cls, index, what, *tensors):
     return index.check(*tensors, what)
 
 
-def _sorted_scan(queries, index, sort_queries, scan):
-    """(dist2 f64[n], nearest i32[n]) from scan(q, dist2, nearest), the call that fills them for the queries q f32[n,3].
-    With an index and `sort_queries`, q is the queries in the order of their Morton keys and the results are scattered
-    back."""
+def _index_ops(index, levels=2):
+    """The operands (order, index, index_bytes, levels) of a C entry point that takes an index; without one the plain
+    scan: no order, no boxes, and levels 1, which it does not read.  An entry point without `levels` takes [:3]."""
+    if index is None:
+        return 0, 0, 0, 1
+    return _m.ptr(index.order), _m.ptr(index.ws), index.ws_bytes, levels
+
+
+_NEAREST = ((torch.float64, ()), (torch.int32, ()))     # a nearest-element scan's outputs: dist2 f64[n], nearest i32[n]
+
+
+def _sorted_scan(queries, index, sort_queries, outputs, scan, extras=()):
+    """The tensors of `outputs`, a (dtype, trailing shape) each - (torch.int32, (k,)) is i32[n,k] - from
+    scan(q, *extras, *outs), the call that fills them for the queries q f32[n,3].  With an index, `sort_queries` and more
+    than one query, q is the queries in the order of their Morton keys, `extras` (per-query tensors or None) go with
+    them, and the results are scattered back."""
     n, dev = int(queries.shape[0]), queries.device
-    dist2 = torch.empty(n, dtype=torch.float64, device=dev)
-    nearest = torch.empty(n, dtype=torch.int32, device=dev)
+    outs = [torch.empty((n, *tail), dtype=dtype, device=dev) for dtype, tail in outputs]
     perm = index.query_order(queries) if index is not None and sort_queries and n > 1 else None
-    scan(queries if perm is None else queries[perm].contiguous(), dist2, nearest)
     if perm is None:
-        return dist2, nearest
-    return torch.empty_like(dist2).index_copy_(0, perm, dist2), torch.empty_like(nearest).index_copy_(0, perm, nearest)
+        scan(queries, *extras, *outs)
+        return tuple(outs)
+    scan(queries[perm].contiguous(), *(None if e is None else e[perm].contiguous() for e in extras), *outs)
+    return tuple(torch.empty_like(o).index_copy_(0, perm, o) for o in outs)

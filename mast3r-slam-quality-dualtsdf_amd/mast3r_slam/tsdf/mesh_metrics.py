@@ -14,7 +14,7 @@ import mslam_hip as _m
 
 from ._mesh_args import _areas, _mesh_arg, _pair, _points_arg, _sample
 from .mesh_align import _alignment_arg, align_meshes, transform_mesh
-from .mesh_index import MeshIndex, _index_arg, _sorted_scan
+from .mesh_index import _NEAREST, MeshIndex, _index_arg, _index_ops, _sorted_scan
 
 
 def face_areas(vertices, faces, _validate=True):
@@ -42,15 +42,14 @@ def _distance2(points, vertices, faces, V, F, skip, index=None, sort_queries=Tru
     def scan(pts, dist2, nearest):
         if index is not None:
             _m.check(L.mslam_mesh_distance_indexed(_m.ptr(pts), n, _m.ptr(vertices), _m.ptr(faces), F, V,
-                                                   _m.ptr(index.order), _m.ptr(index.ws), index.ws_bytes, 2, 0,
-                                                   _m.ptr(dist2), _m.ptr(nearest), _m.stream_ptr()),
-                     "mesh_distance_indexed")
+                                                   *_index_ops(index), 0, _m.ptr(dist2), _m.ptr(nearest),
+                                                   _m.stream_ptr()), "mesh_distance_indexed")
         else:
             _m.check(L.mslam_mesh_distance(_m.ptr(pts), n, _m.ptr(vertices), _m.ptr(faces), F, V, 1 if ws_bytes else 0,
                                            _m.ptr(ws), ws_bytes, _m.ptr(dist2), _m.ptr(nearest), _m.stream_ptr()),
                      "mesh_distance")
 
-    return _sorted_scan(points, index, sort_queries, scan)
+    return _sorted_scan(points, index, sort_queries, _NEAREST, scan)
 
 
 def _fscore_chamfer(precision, recall, accuracy, completion):

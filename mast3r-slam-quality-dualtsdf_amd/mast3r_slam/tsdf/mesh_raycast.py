@@ -11,7 +11,7 @@ import mslam_hip as _m
 from ._mesh_args import _mesh_arg, _pair, _points_arg
 from ._view_args import _eye, _hw_arg, _K_arg, _poses_arg, compose_sim3, rotate  # noqa: F401 (re-exported)
 from .global_volume import _render_args
-from .mesh_index import MeshIndex, _index_arg
+from .mesh_index import MeshIndex, _index_arg, _index_ops
 
 
 class _Caster:
@@ -39,12 +39,11 @@ class _Caster:
         fc = torch.empty(n, dtype=torch.int32, device=dev) if face else None
         t = torch.empty(n, dtype=torch.float64, device=dev) if t64 else None
         if self.index is not None:
-            ix = self.index
             _m.check(_m.lib().mslam_mesh_raycast_indexed(_m.ptr(rays), h, w, _m.ptr(pose), _m.ptr(self.v),
                                                          _m.ptr(self.f), self.F, self.V, float(near), float(far),
-                                                         _m.ptr(ix.order), _m.ptr(ix.ws), ix.ws_bytes, 2, 0,
-                                                         _m.ptr(rng), _m.ptr(nrm), _m.ptr(hit), _m.ptr(fc), _m.ptr(t),
-                                                         _m.stream_ptr()), "mesh_raycast_indexed")
+                                                         *_index_ops(self.index), 0, _m.ptr(rng), _m.ptr(nrm),
+                                                         _m.ptr(hit), _m.ptr(fc), _m.ptr(t), _m.stream_ptr()),
+                     "mesh_raycast_indexed")
             return rng, nrm, hit, fc, t
         _m.check(_m.lib().mslam_mesh_raycast(_m.ptr(rays), h, w, _m.ptr(pose), _m.ptr(self.v), _m.ptr(self.f), self.F,
                                              self.V, float(near), float(far), 1 if self.ws_bytes else 0,

@@ -24,6 +24,7 @@ import mslam_hip as _m
 from mast3r_slam import synthetic
 from mast3r_slam.config import config
 from mast3r_slam.tsdf import CloudIndex, cloud_clusters, downsample_cloud
+from mast3r_slam.tsdf.mesh_index import _index_ops
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--cloud", type=int, default=2_000_000)
@@ -54,10 +55,6 @@ def room_points(n):
     return torch.cat(out)[:n].to(dev).contiguous()
 
 
-def index_ops(ix):
-    return (0, 0, 0, 1) if ix is None else (_m.ptr(ix.order), _m.ptr(ix.ws), ix.ws_bytes, 2)
-
-
 def run(label, cloud, eps, min_points):
     N = int(cloud.shape[0])
     eps2 = float(eps) * float(eps)
@@ -71,7 +68,7 @@ def run(label, cloud, eps, min_points):
     print(f"{label}: N={N} ({ntiles} tiles, {(ntiles + 31) // 32} groups) eps={eps} min_points={min_points}", flush=True)
 
     def radius_count(q, out, ix_, sk):
-        _m.check(L.mslam_cloud_radius_count(_m.ptr(q), int(q.shape[0]), _m.ptr(cloud), N, eps2, *index_ops(ix_),
+        _m.check(L.mslam_cloud_radius_count(_m.ptr(q), int(q.shape[0]), _m.ptr(cloud), N, eps2, *_index_ops(ix_),
                                             _m.ptr(sk), _m.ptr(out), st), "cloud_radius_count")
 
     radius_count(rows, count, ix, skips)
@@ -99,7 +96,7 @@ def run(label, cloud, eps, min_points):
         _m.check(L.mslam_cloud_cluster_init(N, _m.ptr(parent), st), "cloud_cluster_init")
 
     def link():
-        _m.check(L.mslam_cloud_cluster_link(_m.ptr(cloud), N, _m.ptr(order), N, eps2, _m.ptr(core), *index_ops(ix),
+        _m.check(L.mslam_cloud_cluster_link(_m.ptr(cloud), N, _m.ptr(order), N, eps2, _m.ptr(core), *_index_ops(ix),
                                             _m.ptr(skips), _m.ptr(parent), _m.ptr(anchor), _m.ptr(dist2), st),
                  "cloud_cluster_link")
 
@@ -123,7 +120,7 @@ def run(label, cloud, eps, min_points):
     nb = torch.empty((N, k), dtype=torch.int32, device=dev)
 
     def knn():
-        _m.check(L.mslam_cloud_knn(_m.ptr(rows), N, _m.ptr(cloud), N, k, 0, *index_ops(ix), _m.ptr(skips), _m.ptr(d2),
+        _m.check(L.mslam_cloud_knn(_m.ptr(rows), N, _m.ptr(cloud), N, k, 0, *_index_ops(ix), _m.ptr(skips), _m.ptr(d2),
                                    _m.ptr(nb), st), "cloud_knn")
 
     knn()
