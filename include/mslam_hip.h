@@ -787,6 +787,74 @@ int mslam_cloud_cluster_flatten(int num_points, int32_t* parent, void* stream);
 int mslam_cloud_cluster_labels(const int32_t* root, const uint8_t* core, const int32_t* anchor, int num_points,
                                int32_t* label_root, uint8_t* is_cluster_root, void* stream);
 
+/* Cloud planes: which planes a cloud consists of, by sequential RANSAC (no counterpart in the reference, DESIGN.md
+ * "Cloud planes"; the definition is tests/cloud_planes_numpy.py; csrc/cloud_planes.hip).  f64 on the f32 inputs, one
+ * multiply or add at a time; integer counts; no float atomics; the same bytes on every call.  A point SUPPORTS the plane
+ * (n, d) when |((nx px + ny py) + nz pz) + d| <= tol and, with normals f32[N,3] (may be NULL), its normal m is finite
+ * and not zero and |(nx mx + ny my) + nz mz| >= cos_angle.  One round finds one plane; nothing is read back between
+ * rounds.  state i32[MSLAM_CLOUD_PLANES_STATE]: M (the remaining list's length), planes_found, done, the chosen
+ * hypothesis, its count, and whether the refit has stopped; every stage but the compaction returns at once when done is
+ * set.  fit f64[MSLAM_CLOUD_PLANES_FIT]: the current plane (4), the origin (3, one spare), the
+ * MSLAM_CLOUD_PLANES_SUMS sums of its supporters (count, q, q q^T as xx xy xz yy yz zz, r^2; q = p - origin), the
+ * refit's candidate (4) and its scratch.  num_remaining: the length of the buffer `remaining`, an upper bound of M.
+ *   mslam_cloud_planes_remaining  remaining i32[N]: the indices of the valid points (finite coordinates) with
+ *                                 labels[i] < 0, ascending, by a stable scan; block_offsets i32[ceil(N / 256)] is its
+ *                                 scratch.  state: M, and done when M < max(3, min_points).
+ *   mslam_cloud_planes_draw       hypotheses f64[H,4], triples i32[H,3]: hypothesis h of `round` takes the points
+ *                                 remaining[draw(seed, round, h, j)], j = 0, 1, 2, draw = mix(mix(mix(seed) ^ ((round <<
+ *                                 32) | h)) ^ j) mod M with mix SplitMix64's finaliser; n = (p1 - p0) x (p2 - p0) over
+ *                                 its length sqrt((nx nx + ny ny) + nz nz), d = -((nx p0x + ny p0y) + nz p0z).  A void
+ *                                 hypothesis (two equal draws, a length not finite and > 0, M = 0) is four NaNs.
+ *   mslam_cloud_planes_count      count i32[H]: the supporters of each hypothesis among the remaining points.
+ *   mslam_cloud_planes_select     the largest count, the lowest h on ties, into state; a count below min_points (or
+ *                                 below 1) sets done; else fit holds the hypothesis and its origin, the point
+ *                                 triples[h][0].
+ *   mslam_cloud_planes_refit      `iterations` times: a candidate from the sums of the plane's supporters (the
+ *                                 eigenvector of the smallest eigenvalue of their covariance, d at the centroid)
+ *                                 replaces the plane unless the fit is degenerate (fewer than 3 supporters, a middle
+ *                                 eigenvalue <= 2^-40 of the largest) or the candidate has fewer supporters, which ends
+ *                                 the refit.  partial f64[MSLAM_CLOUD_PLANES_SUMS ceil(num_remaining / 256)] is its
+ *                                 scratch.  fit ends with the plane and the sums of its supporters.
+ *   mslam_cloud_planes_label      the supporters of fit's plane get the label planes_found; planes
+ *                                 f64[max_planes, MSLAM_CLOUD_PLANES_ROW] gains the row n (3), d, count, sum r^2, the
+ *                                 centroid (3), the eigenvalues of the supporters' covariance (3), sqrt(sum r^2 / count); n and d negated
+ *                                 together when the viewpoint f32[3] lies on the negative side or, with viewpoint NULL,
+ *                                 when n's component of largest magnitude (lowest axis on ties) is negative; then
+ *                                 planes_found grows by one.
+ *   mslam_cloud_planes            the whole call: state and labels (-1) are initialised, then max_planes rounds are
+ *                                 enqueued.  workspace: mslam_cloud_planes_workspace_bytes(N, H) bytes, 16-byte aligned.
+ * Bad arguments (a null or misaligned pointer, H outside [1, MSLAM_CLOUD_PLANES_MAX_HYPOTHESES], max_planes outside
+ * [1, MSLAM_CLOUD_PLANES_MAX_PLANES], tol not finite and > 0, cos_angle outside [0, 1], min_points < 1) return
+ * MSLAM_EINVAL, a workspace that is too small MSLAM_ENOMEM, and nothing is written. */
+#define MSLAM_CLOUD_PLANES_MAX_HYPOTHESES 1024
+#define MSLAM_CLOUD_PLANES_MAX_PLANES 64
+#define MSLAM_CLOUD_PLANES_STATE 8
+#define MSLAM_CLOUD_PLANES_FIT 40
+#define MSLAM_CLOUD_PLANES_SUMS 11
+#define MSLAM_CLOUD_PLANES_ROW 13
+int mslam_cloud_planes_remaining(const float* points, int num_points, const int32_t* labels, int min_points,
+                                 int32_t* block_offsets, int32_t* remaining, int32_t* state, void* stream);
+int mslam_cloud_planes_draw(const float* points, int num_points, const int32_t* remaining, int num_remaining,
+                            const int32_t* state, uint64_t seed, int round, int num_hypotheses, double* hypotheses,
+                            int32_t* triples, void* stream);
+int mslam_cloud_planes_count(const float* points, const float* normals, int num_points, const int32_t* remaining,
+                             int num_remaining, const int32_t* state, const double* hypotheses, int num_hypotheses,
+                             double tol, double cos_angle, int32_t* count, void* stream);
+int mslam_cloud_planes_select(const int32_t* count, int num_hypotheses, int min_points, const float* points,
+                              int num_points, const double* hypotheses, const int32_t* triples, int32_t* state,
+                              double* fit, void* stream);
+int mslam_cloud_planes_refit(const float* points, const float* normals, int num_points, const int32_t* remaining,
+                             int num_remaining, double tol, double cos_angle, int iterations, double* partial,
+                             int32_t* state, double* fit, void* stream);
+int mslam_cloud_planes_label(const float* points, const float* normals, int num_points, const int32_t* remaining,
+                             int num_remaining, double tol, double cos_angle, const float* viewpoint, const double* fit,
+                             int max_planes, int32_t* state, int32_t* labels, double* planes, void* stream);
+size_t mslam_cloud_planes_workspace_bytes(int num_points, int num_hypotheses);
+int mslam_cloud_planes(const float* points, const float* normals, int num_points, double tol, double cos_angle,
+                       int max_planes, int min_points, int num_hypotheses, int refit_iterations, uint64_t seed,
+                       const float* viewpoint, void* workspace, size_t workspace_bytes, int32_t* labels, double* planes,
+                       int32_t* state, void* stream);
+
 /* Point-to-plane ICP for clouds and meshes: one fused step and a Gauss-Newton solve on Sim3 per iteration (no
  * counterpart in the reference, DESIGN.md "Point-to-plane ICP"; the definition is tests/icp_plane_numpy.py;
  * csrc/icp_plane.hip).  The state block and its init and read are mslam_mesh_align_init / _init_indexed / _read; all

@@ -278,6 +278,12 @@ def save_cloud_metrics(savedir, filename, metrics):
     return save_mesh_metrics(savedir, filename, metrics)
 
 
+def save_plane_metrics(savedir, filename, figures):
+    """The dict of tsdf.plane_figures / SlamSystem.evaluate_planarity as JSON with sorted keys, in the form of
+    save_mesh_metrics.  Returns the path."""
+    return save_mesh_metrics(savedir, filename, figures)
+
+
 def trajectory_ate(est_xyz, gt_xyz, with_scale=True, device="cuda:0"):
     """Absolute trajectory error of the positions est_xyz (K x 3) against gt_xyz (K x 3), numpy arrays or tensors, after
     the best similarity (tsdf.fit_sim3 on `device`; `with_scale=False`: the best rigid motion) -> (rmse, T): the root

@@ -244,6 +244,28 @@ class MapProducts:
                                   **(observed if isinstance(observed, dict) else {}))
         return compare_clouds(points, gt, threshold=threshold, voxel=voxel if voxel > 0.0 else None, **kw)
 
+    def cloud_planes(self, conf_threshold=None, voxel=None, outliers=None, **planes_kw):
+        """The planes of the map's point cloud: tsdf.cloud_planes on self.keyframe_cloud(conf_threshold, voxel,
+        outliers=outliers) -> (points f32[N,3], the dict of tsdf.cloud_planes).  `tol` defaults to the global TSDF's
+        voxel size (the config's when the global TSDF is off); every other keyword is cloud_planes' (DESIGN.md "Cloud
+        planes")."""
+        from mast3r_slam.tsdf import cloud_planes
+
+        points, _ = self.keyframe_cloud(conf_threshold, voxel, colors=False, outliers=outliers)
+        if "tol" not in planes_kw:
+            planes_kw["tol"] = float(self.tsdf_manager.volume.voxel_size if self.tsdf_manager is not None
+                                     else config["tsdf_global"]["voxel_size"])
+        return points, cloud_planes(points, **planes_kw)
+
+    def evaluate_planarity(self, conf_threshold=None, voxel=None, outliers=None, **planes_kw):
+        """Quality figures of the map that need no ground truth: tsdf.plane_figures of self.cloud_planes(...) - the
+        share of the cloud that lies on planes, the rmse of those points about their planes, the number of planes, and
+        how far the planes stand from parallel or square to each other, in degrees.  Python floats."""
+        from mast3r_slam.tsdf import plane_figures
+
+        points, result = self.cloud_planes(conf_threshold, voxel, outliers, **planes_kw)
+        return plane_figures(result, points)
+
     def evaluate_cloud_depth(self, gt_points, point_size=None, align=None, near=0.05, far=10.0, gt_K=None):
         """ "Depth L1" against a laser scan: for every keyframe, the view of the global TSDF (TSDFVolume.render) against
         the z-buffer splat of the ground-truth cloud gt_points f32[N,3] (tsdf.render_cloud; a numpy array or a device
