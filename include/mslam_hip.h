@@ -787,6 +787,43 @@ int mslam_cloud_cluster_flatten(int num_points, int32_t* parent, void* stream);
 int mslam_cloud_cluster_labels(const int32_t* root, const uint8_t* core, const int32_t* anchor, int num_points,
                                int32_t* label_root, uint8_t* is_cluster_root, void* stream);
 
+/* Cloud smoothing: one step of the moving-least-squares projection in its plane form (no counterpart in the reference,
+ * DESIGN.md "Cloud smoothing"; the definition is tests/cloud_mls_numpy.py; csrc/cloud_mls.hip).  All f64 on the f32
+ * inputs, one multiply or add at a time.  d2 is mslam_cloud_distance's sum; a valid point q of the cloud JOINS query p
+ * when d2 <= h2 (h2 finite and > 0) and, with normals, passes the gate.  inv = 1 / h2, u = 1 - d2 inv, w = u u (a
+ * neighbour at d2 == h2 counts with weight 0), r = q - p; per joining neighbour, in the order of the walk: S0 += w; wx =
+ * w rx, S1x += wx, Sxx += wx rx, Sxy += wx ry, Sxz += wx rz; wy = w ry, S1y += wy, Syy += wy ry, Syz += wy rz; wz = w rz,
+ * S1z += wz, Szz += wz rz; count += 1.  Then m = S1 / S0, C = S2 / S0 - m m^T entry by entry (zeros unless S0 > 0), its
+ * eigenvectors by cyclic Jacobi, the unit eigenvector n of the smallest eigenvalue with its component of largest
+ * magnitude positive, t = (nx mx + ny my) + nz mz and
+ *   out_points     f32[n,3] = (float)(p + (strength t) n), strength in [0, 1].  A query STAYS - its input bits are
+ *                  copied, NaN payloads included - when a coordinate is not finite, when count < min_points (>= 1),
+ *                  when count < 3 or when the fit is degenerate (a middle eigenvalue <= 2^-40 of the largest).
+ *                  out_points may alias neither queries nor points.
+ *   out_normals    f32[n,3] = n, (0, 0, 0) for a query that stays;  out_curvature f32[n] = max(l_min, 0) / (l0 + l1 +
+ *                  l2), NaN for a query that stays;  out_count i32[n] = count in every case (0 for an invalid query), not
+ *                  capped.
+ *   the gate       query_normals f32[n,3] and point_normals f32[N,3], both or neither (NULL may also stand for the one
+ *                  that has no rows): neighbour j joins only when
+ *                  fabs((ax bx + ay by) + az bz) >= cos_gate (in [0, 1]), a the query's normal and b point_normals[j].
+ *                  A query whose normal is (0, 0, 0) or not finite is not gated; a neighbour's normal that is not
+ *                  finite counts as (0, 0, 0), which fails every cos_gate > 0.
+ *   moments        (may be NULL, for tests) f64[n, MSLAM_CLOUD_MLS_MOMENTS]: S0, S1 (3), S2 as xx xy xz yy yz zz, the
+ *                  three diagonal entries after the sweeps, the signed unit normal before its rounding (zeros when the
+ *                  query stays), t (0 when it stays) and one spare word, 0.
+ * order, index, index_bytes, levels and skip_counts as mslam_cloud_radius_count.  THE ORDER OF THE SUMS IS THE WALK'S:
+ * ascending point index with order NULL, order[0], order[1], ... with an index.  Levels 1 and 2 give the same bytes (a
+ * skipped tile holds only points with d2 > h2, which add nothing); the plain and the indexed form differ by rounding,
+ * since f64 sums depend on their order.  No atomics.  Bad arguments (a negative size, h2 not finite and > 0, min_points
+ * < 1, strength or cos_gate outside [0, 1], one normal pointer without the other, a null output with n > 0) return
+ * MSLAM_EINVAL and nothing is written; n == 0 returns MSLAM_OK after these checks; num_points == 0: every query stays. */
+#define MSLAM_CLOUD_MLS_MOMENTS 18
+int mslam_cloud_mls_step(const float* queries, int n, const float* points, int num_points, double h2, int min_points,
+                         double strength, const float* query_normals, const float* point_normals, double cos_gate,
+                         const int32_t* order, const void* index, size_t index_bytes, int levels, int32_t* skip_counts,
+                         float* out_points, float* out_normals, float* out_curvature, int32_t* out_count,
+                         double* moments, void* stream);
+
 /* Cloud planes: which planes a cloud consists of, by sequential RANSAC (no counterpart in the reference, DESIGN.md
  * "Cloud planes"; the definition is tests/cloud_planes_numpy.py; csrc/cloud_planes.hip).  f64 on the f32 inputs, one
  * multiply or add at a time; integer counts; no float atomics; the same bytes on every call.  A point SUPPORTS the plane

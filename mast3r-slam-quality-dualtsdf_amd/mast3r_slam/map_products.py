@@ -142,7 +142,8 @@ class MapProducts:
         return compare_meshes(mesh, (gt_vertices, gt_faces), n_samples=n_samples, threshold=threshold,
                               _validate_pred=False, **kw)
 
-    def keyframe_cloud(self, conf_threshold=None, voxel=None, colors=True, outliers=None, normals=None, clusters=None):
+    def keyframe_cloud(self, conf_threshold=None, voxel=None, colors=True, outliers=None, normals=None, clusters=None,
+                       smooth=None):
         """The map as a point cloud at this point of the run, on the device: what evaluate.save_reconstruction gathers -
         for every keyframe the world points T_WC.act(X_canon) (with calibration: X_canon constrained to the pixel rays
         first) of the pixels whose average confidence is > `conf_threshold` (default tracking.C_conf of the config), in
@@ -154,7 +155,10 @@ class MapProducts:
         (after thinning: the keyframe of the cell's lowest-index member).  `clusters`: a dict of keyword arguments for
         tsdf.filter_cloud_clusters (eps, min_points, min_cluster_points, keep_largest, keep_noise), applied after
         `voxel` and `outliers` and before `normals`: whole clusters leave the cloud - the small dense blobs in the air
-        that have neighbours enough for the point-wise rules.  With all three None the pair is what it was."""
+        that have neighbours enough for the point-wise rules.  `smooth`: a dict of keyword arguments for
+        tsdf.smooth_cloud (radius, which is required; iterations, min_points, strength, edge_angle), applied after
+        `voxel`, `outliers` and `clusters` and before `normals`: the points that are left move onto the local planes of
+        the cloud, their colours and order stay.  With all four None the pair is what it was."""
         from mast3r_slam.geometry import constrain_points_to_ray
 
         self.drain()
@@ -176,13 +180,14 @@ class MapProducts:
         points = torch.cat(pts).contiguous() if pts else torch.zeros((0, 3), dtype=torch.float32, device=self.device)
         color = (torch.cat(cols).contiguous() if cols else torch.zeros((0, 3), dtype=torch.uint8,
                                                                         device=self.device)) if colors else None
-        if outliers is None and normals is None and clusters is None:
+        if outliers is None and normals is None and clusters is None and smooth is None:
             if voxel is not None:
                 from mast3r_slam.tsdf import downsample_cloud
 
                 points, color, _ = downsample_cloud(points, voxel, color)
             return points, color
-        from mast3r_slam.tsdf import cloud_normals, downsample_cloud, filter_cloud, filter_cloud_clusters
+        from mast3r_slam.tsdf import (cloud_normals, downsample_cloud, filter_cloud, filter_cloud_clusters,
+                                      smooth_cloud)
 
         # the keyframe of every point, carried through the thinning and the filter
         kf_of = (torch.cat([torch.full((int(p.shape[0]),), i, dtype=torch.int64, device=self.device)
@@ -200,6 +205,10 @@ class MapProducts:
             points, color, kept = filter_cloud_clusters(points, color, **dict(clusters))
             if normals is not None:
                 kf_of = kf_of[kept]
+        if smooth is not None:
+            if "radius" not in smooth:
+                raise ValueError("SlamSystem.keyframe_cloud: smooth needs a radius")
+            points, color, _ = smooth_cloud(points, colors=color, **dict(smooth))
         if normals is None:
             return points, color
         centres = (torch.stack([c for _, c in source]) if source else
@@ -209,7 +218,7 @@ class MapProducts:
 
     def evaluate_cloud(self, gt_points, threshold=None, voxel=None, align=None, init=None, gt_positions=None,
                        align_kw=None, index=None, conf_threshold=None, outliers=None, normals=None, observed=False,
-                       gt_K=None, clusters=None):
+                       gt_K=None, clusters=None, smooth=None):
         """Quality of the map's point cloud (self.keyframe_cloud(conf_threshold)) against a ground-truth cloud gt_points
         f32[N,3] (a numpy array or a device tensor; a laser scan needs no faces): the dict of tsdf.compare_clouds
         (DESIGN.md "Point clouds").  `threshold` and `voxel` default to the global TSDF's voxel size (the config's when
@@ -217,8 +226,8 @@ class MapProducts:
         cell; voxel=0 scores the raw clouds.  `align`, `init` ("trajectory" with `gt_positions` for
         self.align_trajectory), `align_kw` and `index` (None or True) as in evaluate_mesh, with tsdf.align_clouds in the
         place of align_meshes.  `outliers`: a dict for tsdf.cloud_outliers, applied to the map's raw cloud first
-        (keyframe_cloud), and `clusters` a dict for tsdf.filter_cloud_clusters, applied after it; `normals`: k, for
-        compare_clouds' normal-consistency figures.
+        (keyframe_cloud), `clusters` a dict for tsdf.filter_cloud_clusters, applied after it, and `smooth` a dict for
+        tsdf.smooth_cloud, applied last; `normals`: k, for compare_clouds' normal-consistency figures.
 
         `observed=True`: only the part of the ground truth that some keyframe sees, the thinned ground-truth cloud itself
         the occluder, enters completion, recall, fscore and chamfer (compare_clouds(observed=...), DESIGN.md "Cloud
@@ -232,7 +241,8 @@ class MapProducts:
         threshold = vs if threshold is None else float(threshold)
         voxel = vs if voxel is None else float(voxel)
         kw = self._alignment_kw("SlamSystem.evaluate_cloud", align, init, gt_positions, align_kw)
-        points, _ = self.keyframe_cloud(conf_threshold, colors=False, outliers=outliers, clusters=clusters)
+        points, _ = self.keyframe_cloud(conf_threshold, colors=False, outliers=outliers, clusters=clusters,
+                                        smooth=smooth)
         gt = torch.as_tensor(gt_points, dtype=torch.float32).to(points.device).reshape(-1, 3).contiguous()
         if index is not None and index is not False:
             kw["index"] = index
@@ -244,14 +254,14 @@ class MapProducts:
                                   **(observed if isinstance(observed, dict) else {}))
         return compare_clouds(points, gt, threshold=threshold, voxel=voxel if voxel > 0.0 else None, **kw)
 
-    def cloud_planes(self, conf_threshold=None, voxel=None, outliers=None, **planes_kw):
+    def cloud_planes(self, conf_threshold=None, voxel=None, outliers=None, smooth=None, **planes_kw):
         """The planes of the map's point cloud: tsdf.cloud_planes on self.keyframe_cloud(conf_threshold, voxel,
-        outliers=outliers) -> (points f32[N,3], the dict of tsdf.cloud_planes).  `tol` defaults to the global TSDF's
+        outliers=outliers, smooth=smooth) -> (points f32[N,3], the dict of tsdf.cloud_planes).  `tol` defaults to the global TSDF's
         voxel size (the config's when the global TSDF is off); every other keyword is cloud_planes' (DESIGN.md "Cloud
         planes")."""
         from mast3r_slam.tsdf import cloud_planes
 
-        points, _ = self.keyframe_cloud(conf_threshold, voxel, colors=False, outliers=outliers)
+        points, _ = self.keyframe_cloud(conf_threshold, voxel, colors=False, outliers=outliers, smooth=smooth)
         if "tol" not in planes_kw:
             planes_kw["tol"] = float(self.tsdf_manager.volume.voxel_size if self.tsdf_manager is not None
                                      else config["tsdf_global"]["voxel_size"])

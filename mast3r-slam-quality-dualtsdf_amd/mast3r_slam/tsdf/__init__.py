@@ -14,6 +14,7 @@ from .cloud import (CloudIndex, align_clouds, cloud_distance, cloud_knn, cloud_n
                     compare_clouds, downsample_cloud, filter_cloud, transform_cloud)
 from .cloud_cluster import cloud_clusters, cloud_radius_count, filter_cloud_clusters  # noqa: F401
 from .cloud_planes import cloud_planes, plane_figures  # noqa: F401
+from .cloud_smooth import cloud_mls, smooth_cloud  # noqa: F401
 from .cloud_view import observed_cloud_points, render_cloud  # noqa: F401
 from .image_metrics import image_metrics  # noqa: F401
 from .tsdf_optimizer import TSDFPoseOptimizer  # noqa: F401
